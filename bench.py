@@ -13,8 +13,15 @@ Default workload = BASELINE.json configs[3], the largest single-GPU
 configuration: 2 x 250 Mbp, 1 % SNP, -m 20 (n = 5*10^8, 32-bit index).
 `--L 5000000` gives configs[1] (2 x 5 Mbp), `--L 5000000 --genomes 10` configs[2].
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the line (the judged kernel's
+roofline rides on the timed steps' own launches).  `--full` adds everything else: the
+full-size property and golden checks of the last step, the per-kernel breakdown and the
+node's copy peak (runs of their own), the companion legs (level pipeline, indel workload,
+stream), the divided run of `--gpus N`, the CPU baselines and the CPU/GPU parity sample.
+`--dump-outputs DIR` writes what the last timed step computed as DIR/*.npy (see dump_outputs).
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment re-executes itself under
 torch.distributed.run with N ranks (one process per GPU); under a launcher whose
@@ -545,6 +552,41 @@ def anchor_set(l, off, pos):
     return sorted((int(l[k]), tuple(int(x) for x in pos[off[k]:off[k + 1]])) for k in range(len(l)))
 
 
+DUMP_ANCHORS = 1 << 19      # anchors written at most (a seeded sample of a larger set)
+DUMP_POSITIONS = 1 << 21    # their member positions at most
+DUMP_TEXT = 1 << 22         # final-text bytes written at most (a seeded sample of a longer text)
+
+
+def dump_outputs(path, res, T=None, seed=1234):
+    """--dump-outputs DIR: what the last timed step handed its caller -- the anchors of align_builtin (lengths, members, positions)
+    and the lower-cased final text -- as float64 / float32 .npy files, about 40 MB at most.  Anchors are taken in their canonical order
+    (by the first member's position, reveal_amd/check.py anchor_stream), so two builds that find the same set write the same files;
+    larger sets and texts are sampled at indices drawn from a fixed seed.  anchors_summary covers the whole set and text."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    l, off, pos = (np.asarray(a, dtype=np.int64) for a in res["anchors"])
+    na = len(l)
+    cnt = np.diff(off)
+    order = np.argsort(pos[off[:-1]], kind="stable") if na else np.zeros(0, dtype=np.int64)
+    rng = np.random.default_rng(seed)
+    pick = order if na <= DUMP_ANCHORS else order[np.unique(rng.integers(0, na, DUMP_ANCHORS))]
+    pick = pick[:int(np.searchsorted(np.cumsum(cnt[pick]), DUMP_POSITIONS, side="right"))]
+    c = cnt[pick]
+    within = np.arange(int(c.sum()), dtype=np.int64) - np.repeat(np.cumsum(c) - c, c)
+    out = {"anchors_length": l[pick].astype(np.float64), "anchors_members": c.astype(np.float64),
+           "anchors_positions": pos[np.repeat(off[:-1][pick], c) + within].astype(np.float64)}
+    # whole set: count, total length, total members, sum of positions, anchored bp, levels [, lower-case bytes of the final text]
+    summary = [na, int(l.sum()), int(cnt.sum()), int(pos.sum()), int(res["stats"]["anchored_bp"]), int(res["stats"]["levels"])]
+    if T is not None:      # (the sampled positions follow from the seed and the text's length alone)
+        T = np.asarray(T, dtype=np.uint8)
+        at = np.arange(len(T), dtype=np.int64) if len(T) <= DUMP_TEXT else np.unique(rng.integers(0, len(T), DUMP_TEXT))
+        out["final_text"] = T[at].astype(np.float32)
+        summary.append(int(np.count_nonzero((T >= ord("a")) & (T <= ord("z")))))
+    out["anchors_summary"] = np.asarray(summary, dtype=np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -588,6 +630,11 @@ def main():
     ap.add_argument("--jobs", type=int, default=1,
                     help="independent alignments per rank, run concurrently (one index handle, HIP stream and host thread each): "
                          "config 5's 20 independent 5-genome jobs on 8 GPUs (reveal/align.py:45-53); the default 1 is the metric's config")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: full-size checks, per-kernel breakdown, copy peak, companion legs, the divided run "
+                         "of --gpus N, CPU baselines and parity (a plain run times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (anchors, final text) as DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
 
     if args.class_one:
@@ -651,7 +698,8 @@ def main():
     elif mode == "auto":      # both in one invocation: throughput (weak) and the interval-split curve (strong)
         # (two samples: the anchor cascade finishes the run on rank 0 before there is a frontier to hand out -- rv_align_builtin_until returns 0 --,
         #  so the divided leg is not run: the line says "speedup 1.0, nothing to divide".  --mode divide still runs it.)
-        modes = ["per-rank"] + (["divide"] if big and args.genomes > 2 else [])
+        # (the divided leg is a figure beside the headline: --full only)
+        modes = ["per-rank"] + (["divide"] if big and args.genomes > 2 and args.full else [])
     else:
         modes = [mode]
     jobs = max(1, args.jobs) if "per-rank" in modes else 1
@@ -724,7 +772,7 @@ def main():
             last = step(divide)
         barrier()
         elapsed = time.perf_counter() - t0
-        if rank == 0 and not divide and not args.no_check and len(modes) > 1:
+        if rank == 0 and not divide and (not args.no_check or args.dump_outputs) and len(modes) > 1:
             last["T_after"] = idx.array("T")      # (the divided run of the same invocation works on the same handle afterwards)
         prof = (idx_div if divide else idx).prof(enable=False)
         for ix in extra:      # the judged kernel over all jobs (launches that overlap other jobs' kernels share the GPU with them)
@@ -740,9 +788,17 @@ def main():
     primary = modes[0]
     divide = primary == "divide"
     tmax, last, prof = runs[primary]
+    if rank == 0 and args.dump_outputs:
+        T_last = None
+        if not divide:
+            T_last = last.get("T_after")
+            if T_last is None:
+                T_last = idx.array("T")
+        dump_outputs(args.dump_outputs, last, T_last)
+        del T_last
     # full-size properties of the last timed step's result (reveal_amd/check.py), before the breakdown steps run again
-    properties = full_size = None
-    if rank == 0 and not args.no_check:
+    properties = full_size = grec = None
+    if rank == 0 and args.full and not args.no_check:
         T0 = np.frombuffer(b"$".join(flat(seqs)) + b"$", dtype=np.uint8)
         nsep = np.asarray(sample_seps(seqs), dtype=np.int64)
         if divide:      # (a divided run lower-cases each share on its own rank: rebuild the text from the merged anchors)
@@ -770,7 +826,7 @@ def main():
             properties["divide_same_anchor_set_as_rank0_alone"] = anchor_set(*dl["anchors"]) == anchor_set(*last["anchors"])
         del T0
     breakdown = roofline_other = None
-    if rank == 0 and not divide:
+    if rank == 0 and not divide and args.full:
         idx.prof(enable=True, reset=True)
         for _ in range(2):
             idx.construct()
@@ -803,10 +859,12 @@ def main():
                         break
                 except Exception:
                     pass
-        try:
-            read_gbs, copy_gbs = _lib.measure_bandwidth(1 << 30, 10)      # the node's practical ceiling (streaming kernels, 1 GiB)
-        except Exception:
-            read_gbs = copy_gbs = None
+        read_gbs = copy_gbs = None
+        if args.full:
+            try:
+                read_gbs, copy_gbs = _lib.measure_bandwidth(1 << 30, 10)      # the node's practical ceiling (streaming kernels, 1 GiB)
+            except Exception:
+                read_gbs = copy_gbs = None
         st = last["stats"]
         if divide:
             sharding = "one alignment divided over %d ranks (frontier hand-off after the top levels, no collective), ranks per share %s" % (world, last.get("shares"))
@@ -883,9 +941,10 @@ def main():
                              "speedup_vs_rank0_alone": (tmax / args.steps) / (dt / args.steps),
                              "note": None if any(dl.get("shares") or [0]) else "nothing was handed out: the anchor cascade finished this two-sample run on rank 0 "
                                      "before there was a frontier to divide (rv_align_builtin_until); inputs with more than two samples are divided"}
-        out["parity"] = {"full_size": full_size if full_size is not None else
-                         "no CPU digests for this configuration in tests/golden/fullsize.json (oracle/gen_fullsize_golden.py writes them)"}
-        if world == 1 and not args.no_extra and not divide and jobs == 1:
+        if args.full:
+            out["parity"] = {"full_size": full_size if full_size is not None else
+                             "no CPU digests for this configuration in tests/golden/fullsize.json (oracle/gen_fullsize_golden.py writes them)"}
+        if world == 1 and args.full and not args.no_extra and not divide and jobs == 1:
             # ---- companion figures, outside the timed region (what the headline does not show) ----
             # (1) the same workload through the LEVEL PIPELINE: scan / pick / label + split / bubble_sort of every level, reveal.c:731-1338 step by
             # step -- what index.align(mumpicker, graphalign) callers, rc = 1 and traced runs get; the headline's two-sample recursion
@@ -938,7 +997,7 @@ def main():
                     "properties": check.recursion_properties(iT0, iT1, ir["anchors"], insep, args.minl)["all"],
                     "golden": check.compare_with_golden(irec, anchors=ir["anchors"], T_final=iT1) if irec is not None else None}
                 del iidx, iseqs, iT0, iT1
-        if world == 1 and not args.no_extra and not divide and jobs == 1 and args.L * args.genomes >= 100_000_000:
+        if world == 1 and args.full and not args.no_extra and not divide and jobs == 1 and args.L * args.genomes >= 100_000_000:
             # (3) north_star's target volume as a sustained stream: 20 inputs of this size (10 Gbp at the default workload) through `--config stream` in a
             # process of its own -- host assembly, host->device copy, construct, recursion and result delivery of every input inside its timed region
             try:
@@ -953,7 +1012,7 @@ def main():
                                          "anchored inside the timed region, four inputs in flight (a handle, HIP stream and host thread each)"}
             except Exception as e:      # noqa: BLE001  (a companion figure: its failure must not lose the line)
                 out["stream"] = {"failed": repr(e)[:300]}
-        if world == 1 and not args.no_cpu:
+        if world == 1 and args.full and not args.no_cpu:
             # CPU legs and bit-exact parity on a stated sample: 2 x 20 Mbp (or the workload itself when it is not larger)
             cl = min(args.L, CPU_SAMPLE_L)
             same = cl == args.L
@@ -1001,7 +1060,7 @@ def main():
                                   "identical_final_text": gT == cb["result"]["T"]})
     else:
         out = None
-    if world > 1 and big and not args.no_extra and not divide and jobs == 1:
+    if world > 1 and big and args.full and not args.no_extra and not divide and jobs == 1:
         # north_star's target on a node: every rank its own queue of 20 inputs of this size (10 Gbp per rank at the default workload), host assembly and
         # host->device copies inside the timed region -- `--config stream` run by all ranks right here (its barriers and max-over-ranks timing are its own)
         import copy

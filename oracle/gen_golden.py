@@ -34,12 +34,16 @@ def sha(a):
 
 
 def load(name):
-    """a fixture is either a tests/golden/<name>.fa.gz copy of a reference test file or a literal sequence"""
+    """a fixture is either a tests/golden/<name>.fa.gz copy of a reference test file (or its byte ranges <name>.fa.gz.part1, .part2, ...
+    where the file is larger than a committed file may be) or a literal sequence"""
     p = os.path.join(GOLD, name + ".fa.gz")
-    if os.path.exists(p):
+    parts = [p] if os.path.exists(p) else []
+    while not os.path.exists(p) and os.path.exists("%s.part%d" % (p, len(parts) + 1)):
+        parts.append("%s.part%d" % (p, len(parts) + 1))
+    if parts:
         tmp = os.path.join("/tmp", "golden_" + name + ".fa")
-        with gzip.open(p, "rt") as f, open(tmp, "w") as g:
-            g.write(f.read())
+        with open(tmp, "w") as g:
+            g.write(gzip.decompress(b"".join(open(q, "rb").read() for q in parts)).decode())
         return tmp
     return name
 

@@ -1,5 +1,5 @@
 """Host-side pieces of round 4 (no GPU): the indel generator against a literal restatement of the reference simulator's loop
-(utils/simulate.py:17-77), the canonical anchor stream / digests of reveal_amd/check.py, the golden look-up, bench.py's contig helpers."""
+(utils/simulate.py:17-77), the canonical anchor stream / digests of reveal_amd/check.py, the golden look-up, bench.py's contig helpers and its output dump."""
 import importlib.util
 import os
 
@@ -97,3 +97,43 @@ def test_bench_contig_helpers():
     seps = bench.sample_seps(cut)
     assert len(seps) == 1 and T[seps[0]:seps[0] + 1] == b"$" and seps[0] == sum(len(c) + 1 for c in cut[0]) - 1
     assert bench.sample_seps(seqs) == [len(seqs[0])]
+
+
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the anchors in canonical order whatever order the library returned them in, a seeded sample of a larger
+    set within its caps, float64 / float32 files, and a summary of the whole set and text"""
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rng = np.random.default_rng(5)
+    na = 3000
+    first = np.sort(rng.choice(100_000, na, replace=False))
+    l = rng.integers(20, 60, na).astype(np.uint32)
+    cnt = rng.integers(2, 4, na)
+    off = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
+    pos = np.concatenate([first[k] + 100_001 * np.arange(cnt[k]) for k in range(na)]).astype(np.int64)
+    T = rng.integers(65, 123, 400_000).astype(np.uint8)
+    stats = {"anchored_bp": 123, "levels": 4}
+    perm = rng.permutation(na)      # the same set in another order
+    pos2 = np.concatenate([pos[off[k]:off[k + 1]] for k in perm])
+    off2 = np.concatenate([[0], np.cumsum(cnt[perm])]).astype(np.int64)
+    monkeypatch.setattr(bench, "DUMP_ANCHORS", 1000)
+    monkeypatch.setattr(bench, "DUMP_POSITIONS", 2000)
+    monkeypatch.setattr(bench, "DUMP_TEXT", 50_000)
+    bench.dump_outputs(str(tmp_path / "a"), {"anchors": (l, off, pos), "stats": stats}, T)
+    bench.dump_outputs(str(tmp_path / "b"), {"anchors": (l[perm], off2, pos2), "stats": stats}, T)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["anchors_length.npy", "anchors_members.npy", "anchors_positions.npy", "anchors_summary.npy", "final_text.npy"]
+    A = {n: np.load(tmp_path / "a" / n) for n in names}
+    for n in names:
+        assert np.array_equal(A[n], np.load(tmp_path / "b" / n)), n
+        assert A[n].dtype in (np.float64, np.float32)
+    m, p = A["anchors_members.npy"].astype(np.int64), A["anchors_positions.npy"].astype(np.int64)
+    assert 0 < len(m) <= 1000 and len(p) == m.sum() <= 2000 and len(A["anchors_length.npy"]) == len(m)
+    heads = p[np.cumsum(m) - m]
+    assert np.all(np.diff(heads) > 0)
+    k = np.searchsorted(first, heads)      # every written anchor is one of the set, members and length included
+    assert np.array_equal(first[k], heads) and np.array_equal(cnt[k], m) and np.array_equal(l[k].astype(np.float64), A["anchors_length.npy"])
+    assert 0 < len(A["final_text.npy"]) <= 50_000 and set(np.unique(A["final_text.npy"])) <= set(range(65, 123))
+    s = A["anchors_summary.npy"]
+    assert s.tolist() == [na, int(l.sum()), int(cnt.sum()), int(pos.sum()), 123, 4, int(np.count_nonzero(T >= ord("a")))]
