@@ -188,9 +188,8 @@ struct Align {
     DBuf dDec, dErr, dTab0;
     bool next_dev_ok = false, cur_dev_ok = false, early_done = false, early_bubble = false, use_leaf = false;
     int64_t par_min_cur = RV_BUBBLE_PAR_N;
-    const sa_t *d_next_nodes = nullptr; const uint8_t *d_next_flags = nullptr; const int *d_next_tsub2 = nullptr;
+    const sa_t *d_next_nodes = nullptr; const uint8_t *d_next_flags = nullptr;
     std::vector<sa_t> next_nodes; std::vector<uint8_t> next_flags;
-    RvLabelTabs e_lt; RvSplitArgs e_sa;
     bool leaf_pending[RV_LEVEL_BUFS + 1] = {};   // a leaf launch may still be reading level buffer k
     size_t leaf_anchor_cap = 0, leaf_trace_cap = 0;
     std::vector<uint8_t> leaf_done;   // per sub of the current level: handed to the leaf kernel
@@ -206,7 +205,7 @@ struct Align {
     std::vector<int64_t> mpre, sub_start, woff, toff, next_ss;
     const int64_t *d_next_ss = nullptr;      // device copy of the next level's sub-index starts (inside dTab)
     const int *d_next_want = nullptr;        // ... and of its sub-indices' sample counts
-    const int *d_next_tsub = nullptr;        // ... and its tile -> sub-index table (more than two samples)
+    const int *d_next_tsub = nullptr;        // ... and its tile -> sub-index table (more than two samples, or a level the device can decide)
     std::vector<int> next_tsub;
     std::vector<u32> pick_l; std::vector<sa_t> pick_pos;
     std::vector<u32> child_base, child_n;
@@ -220,7 +219,7 @@ struct Align {
     bool trace_on = false;
     std::vector<rv_trace> trace;
     rv_align_stats st{};
-    double lg[8] = {0}, lgx[8] = {0};          // RV_LEVEL_LOG: host time stamps inside the current level
+    double lg[8] = {0}, lgx[8] = {0}, lg_t0 = 0;   // RV_LEVEL_LOG: host time stamps inside the current level's commit, counted from lg_t0
     // rv_align_builtin split into set-up / levels / collection, so that a frontier can be handed to other devices in between
     int leaf_flip = 0;
     bool leaf_launch_due = false, hook_early = false;   // the level's leaf launch waits until the level's scan / split kernels are queued
@@ -465,9 +464,6 @@ int rv_run_multi_scan(rv_index *h, const sa_t *SA, const lcp_t *LCP, const uint8
 
 extern "C" {
 
-static int early_split(rv_index *h);
-static int early_split_multi(rv_index *h);
-
 /* the leaf kernel of the current level (roots prepared by builtin_levels) on its own stream */
 static int leaf_launch(rv_index *h) {
     Align *a = h->al;
@@ -506,146 +502,123 @@ static int leaf_launch(rv_index *h) {
     return 0;
 }
 
-/* called by the pair scan once its kernels and the picker's are queued, before the host waits for the picks */
-static int level_hook(rv_index *h) {
+/* ---- steps of a level's split and bubble, shared by the early split (tables built on the device) and rv_frontier_commit (tables
+ * built by the host) ---- */
+
+// which of the level buffers in rotation the split of the current level writes
+static int next_buf(const Align *a) { return a->level == 0 ? 0 : (a->cur + 1) % RV_LEVEL_BUFS; }
+
+// the buffers the split of a level of m ranks writes: label bytes, tile counters, m_out ranks of the next level's arrays
+static int split_reserve(rv_index *h, int nxt, int64_t m, int64_t m_out) {
     Align *a = h->al;
-    if (a->hook_early) RV_TRY(early_split(h));
-    if (a->leaf_launch_due) RV_TRY(leaf_launch(h));
+    RV_TRY(a->dD.reserve((size_t)m + 64));
+    RV_TRY(a->dTile.reserve((size_t)ceil_div(m, RV_SPLIT_TILE) * 3 * 5 * 4 + 64));
+    RV_TRY(a->lvSA[nxt].reserve((size_t)(m_out + 64) * sizeof(sa_t)));
+    RV_TRY(a->lvLCP[nxt].reserve((size_t)(m_out + 64) * sizeof(lcp_t)));
+    RV_TRY(a->lvBWT[nxt].reserve((size_t)m_out + 64));
     return 0;
 }
 
-/* The split of the current level (reveal.c:1005-1252 without lower-casing and bubble_sort), queued right behind the picker
- * kernels with decisions taken on the device (rv_decide.hip): it runs while the host receives the picks and rebuilds the
- * same decisions for its own bookkeeping.  rv_frontier_commit then finds it done. */
-static int early_split(rv_index *h) {
+// a leaf launch of an earlier level may still be reading level buffer `slot` (RV_LEVEL_BUFS = the main arrays): the main stream goes on behind it
+static int leaf_wait(rv_index *h, int slot) {
     Align *a = h->al;
-    hipStream_t q = h->ws.stream;
-    const Level &lv = a->lv;
-    const int ns = lv.size();
-    const int64_t m = lv.m, ntiles = ceil_div(m, RV_SPLIT_TILE);
-    const int nxt = (a->level == 0) ? 0 : (a->cur + 1) % RV_LEVEL_BUFS;
-    RV_TRY(a->dD.reserve((size_t)m + 64));
-    RV_TRY(a->dTile.reserve((size_t)ntiles * 3 * 5 * 4 + 64));
-    RV_TRY(a->lvSA[nxt].reserve((size_t)(m + 64) * sizeof(sa_t)));
-    RV_TRY(a->lvLCP[nxt].reserve((size_t)(m + 64) * sizeof(lcp_t)));
-    RV_TRY(a->lvBWT[nxt].reserve((size_t)m + 64));
-    // a leaf launch of an earlier level may still be reading the buffer the split writes (ping-pong)
-    if (a->leaf_pending[nxt]) { RV_HIP(hipStreamWaitEvent(q, a->ev_leaf[nxt], 0)); a->leaf_pending[nxt] = false; }
-    const size_t S = (size_t)ns;
-    size_t bytes = 0;
-    auto take = [&](size_t b) { const size_t o = (bytes + 15) & ~(size_t)15; bytes = o + b; return o; };
-    const size_t o_cb = take(4 * S * sizeof(sa_t)), o_ce = take(4 * S * sizeof(sa_t)), o_cc = take(4 * S), o_ctf = take((S + 1) * 4);
-    const size_t o_mb = take(2 * S * sizeof(sa_t)), o_me = take(2 * S * sizeof(sa_t)), o_mtf = take((S + 1) * 4);
-    const size_t o_cn = take(3 * S * 4), o_cbase = take(3 * S * 4), o_soff = take(3 * S * 4), o_exp = take(16), o_tot = take(16);
-    const size_t o_cf = take((S + 1) * 4), o_mf = take((S + 1) * 4), o_clo = take(2 * S * sizeof(sa_t)), o_chi = take(2 * S * sizeof(sa_t)), o_mp = take(2 * S * sizeof(sa_t));
-    const size_t o_kid = take(S * sizeof(RvBubbleDesc));
-    RV_TRY(a->dDec.reserve(bytes + 64));
-    uint8_t *db = a->dDec.as<uint8_t>();
-    RvDecideArgs d;
-    d.nsubs = ns; d.lcap = h->maxlcp;
-    d.nodes = a->d_next_nodes; d.flags = a->d_next_flags; d.picks = h->hscan.as<RvPairRec>();
-    d.ctab_first = (int *)(db + o_ctf); d.mtab_first = (int *)(db + o_mtf);
-    d.cb = (sa_t *)(db + o_cb); d.ce = (sa_t *)(db + o_ce); d.cc = db + o_cc; d.mb = (sa_t *)(db + o_mb); d.me = (sa_t *)(db + o_me);
-    d.child_n = (u32 *)(db + o_cn); d.child_base = (u32 *)(db + o_cbase); d.sub_off = (u32 *)(db + o_soff); d.expect_total = (u32 *)(db + o_exp);
-    d.cut_first = (int *)(db + o_cf); d.mend_first = (int *)(db + o_mf);
-    d.cut_lo = (sa_t *)(db + o_clo); d.cut_hi = (sa_t *)(db + o_chi); d.mend_pos = (sa_t *)(db + o_mp);
-    d.err = a->dErr.as<u32>();
-    d.ovf_cap = (u32)std::min<size_t>(h->ws.misc[4].cap / sizeof(RvPairRec), 0xffffffffu);      // (the scan's overflow buffer)
-    d.kid = (RvBubbleDesc *)(db + o_kid);
-    RV_TRY(rv_decide_launch(h->ws, d));
-    RvLabelTabs &lt = a->e_lt;
-    lt.sub_start = a->d_next_ss; lt.nsubs = ns; lt.tile_sub = a->d_next_tsub2;
-    lt.ctab_first = d.ctab_first; lt.cbegin = d.cb; lt.cend = d.ce; lt.ccls = d.cc;
-    lt.mtab_first = d.mtab_first; lt.mbegin = d.mb; lt.mend = d.me; lt.nmatch = 2 * ns;
-    RvSplitArgs &sa = a->e_sa;
+    if (a->leaf_pending[slot]) { RV_HIP(hipStreamWaitEvent(h->ws.stream, a->ev_leaf[slot], 0)); a->leaf_pending[slot] = false; }
+    return 0;
+}
+
+// where the tables of a level's split lie on the device: carved from dDec and filled by the decide kernel (early split), or inside the
+// host's upload to dTab (commit)
+struct SplitTabs {
+    const int64_t *sub_start; const int *tile_sub;
+    int *ctab_first, *mtab_first, *cut_first, *mend_first;
+    sa_t *cb, *ce, *mb, *me, *cut_lo, *cut_hi, *mend_pos; uint8_t *cc;
+    u32 *child_n, *child_base, *sub_off, *expect_total, *total;
+    int nmatch;
+};
+
+// the arguments of the current level's label / split kernels (outputs: level buffer nxt); tmin_out and mend_all are the caller's
+static void split_args(rv_index *h, const SplitTabs &t, int nxt, RvLabelTabs &lt, RvSplitArgs &sa) {
+    Align *a = h->al;
+    const int ns = a->lv.size();
+    const int64_t ntiles = ceil_div(a->lv.m, RV_SPLIT_TILE);
+    lt.sub_start = t.sub_start; lt.nsubs = ns; lt.tile_sub = t.tile_sub;
+    lt.ctab_first = t.ctab_first; lt.cbegin = t.cb; lt.cend = t.ce; lt.ccls = t.cc;
+    lt.mtab_first = t.mtab_first; lt.mbegin = t.mb; lt.mend = t.me; lt.nmatch = t.nmatch;
     u32 *tiles = a->dTile.as<u32>();
     sa.ntiles = ntiles;
     sa.tile_cnt = tiles; sa.tile_has = tiles + 3 * ntiles; sa.tile_post = tiles + 6 * ntiles;
     sa.tile_G = tiles + 9 * ntiles; sa.tile_carry = tiles + 12 * ntiles;
-    sa.total = (u32 *)(db + o_tot);
+    sa.total = t.total;
     sa.sub_start = lt.sub_start; sa.nsubs = ns; sa.tile_sub = lt.tile_sub;
-    sa.child_base = d.child_base; sa.child_n = d.child_n; sa.sub_off = d.sub_off; sa.expect_total = d.expect_total;
-    sa.cut_first = d.cut_first; sa.cut_lo = d.cut_lo; sa.cut_hi = d.cut_hi;
-    sa.mend_first = d.mend_first; sa.mend_pos = d.mend_pos;
+    sa.child_base = t.child_base; sa.child_n = t.child_n; sa.sub_off = t.sub_off; sa.expect_total = t.expect_total;
+    sa.cut_first = t.cut_first; sa.cut_lo = t.cut_lo; sa.cut_hi = t.cut_hi;
+    sa.mend_first = t.mend_first; sa.mend_pos = t.mend_pos;
     sa.SA_out = a->lvSA[nxt].as<sa_t>(); sa.LCP_out = a->lvLCP[nxt].as<lcp_t>(); sa.BWT_out = a->lvBWT[nxt].as<uint8_t>(); sa.SAi = h->dSAi.as<sa_t>();
-    sa.err = a->dErr.as<u32>();
-    {   // tile bounds for the data-parallel bubble rounds: only a level that can still have a child above their threshold needs them
-        int64_t big0 = 0;
-        for (int s2 = 0; s2 < ns; s2++) big0 = std::max<int64_t>(big0, lv.n[(size_t)s2]);
-        sa.tmin_out = nullptr;
-        if (big0 > a->par_min_cur) {
-            RV_TRY(a->dTmin.reserve((size_t)(m / RV_SPLIT_TILE + 2) * 4));      // (the next level is not larger than this one)
-            RV_HIP(hipMemsetAsync(a->dTmin.p, 0xFF, (size_t)(m / RV_SPLIT_TILE + 2) * 4, q));
-            sa.tmin_out = a->dTmin.as<u32>();
-        }
-    }
-    int id = h->prof.begin(q, RV_K_SPLIT, (double)m * (2 * (sizeof(sa_t) + sizeof(lcp_t) + 2)) + (double)m * (sizeof(sa_t) + sizeof(lcp_t) + 1));
-    RV_TRY(rv_split_launch(h->ws, cur_sa(h), cur_lcp(h), a->dD.as<uint8_t>(), cur_bwt(h), m, lt, sa, 1));
-    h->prof.end(q, id);
-    a->early_done = true;
-    // Few sub-indices (above a few thousand the LDS kernels on their own stream are the better choice): lower-casing and the bubble of every leading child the rounds
-    // do not take follow at once, too -- the whole level except those rounds is then queued before the host has seen the picks.
-    a->early_bubble = false;
-    int64_t biggest = 0;
-    for (int s2 = 0; s2 < ns; s2++) biggest = std::max<int64_t>(biggest, lv.n[(size_t)s2]);
-    // (a level that still has a sub-index above the rounds' threshold keeps the host-built mix of rounds and joined children)
-    // (ns > 4096 through the size-class launches below: tried at 2 x 250 Mbp, 304 against 300 ms -- five launches over every
-    // descriptor cost more GPU time than the hidden host time is worth; RV_EARLY_BUBBLE_MANY=1 switches it on)
-    if (biggest <= a->par_min_cur && !h->ws.opt.bubble_lds_always && !h->ws.opt.no_early_bubble && (ns <= 4096 || h->ws.opt.early_bubble_many)) {
-        RV_TRY(rv_lower_ranges_launch(h->ws, h->dT.as<uint8_t>(), d.mb, d.me, 2 * ns));
-        {
-            const void *before = a->dFlag.p;
-            RV_TRY(a->dFlag.reserve((size_t)m + 64));
-            if (!a->flag_clean || a->dFlag.p != before) { RV_HIP(hipMemsetAsync(a->dFlag.p, 0, a->dFlag.cap, q)); a->flag_clean = true; }
-        }
-        RvBubbleArgs ba;
-        memset(&ba, 0, sizeof ba);
-        ba.flag = a->dFlag.as<uint8_t>();
-        ba.SA = sa.SA_out; ba.LCP = sa.LCP_out; ba.BWT = sa.BWT_out; ba.SAi = sa.SAi; ba.cut_lo = d.cut_lo; ba.cut_hi = d.cut_hi; ba.err = a->dErr.as<u32>();
-        id = h->prof.begin(q, RV_K_BUBBLE, 0.0);
-        if (ns <= 4096) {
-            RV_TRY(rv_bubble_children_dev_launch(h->ws, ba, d.kid, ns, a->par_min_cur));
-        } else {
-            // thousands of sub-indices (the deep levels of large inputs): the size-class kernels, LDS-resident ones included, each on
-            // its own stream -- the host-built launches of rv_frontier_commit, minus the wait for the host's tables
-            if (!a->bub_stream) {
-                RV_HIP(rv_stream_get(&a->bub_stream));
-                RV_HIP(rv_stream_get(&a->bub_stream2));
-                RV_HIP(hipEventCreateWithFlags(&a->ev_fork, hipEventDisableTiming));
-                RV_HIP(hipEventCreateWithFlags(&a->ev_join, hipEventDisableTiming));
-                RV_HIP(hipEventCreateWithFlags(&a->ev_join2, hipEventDisableTiming));
-            }
-            RV_HIP(hipEventRecord(a->ev_fork, q));
-            RV_HIP(hipStreamWaitEvent(a->bub_stream, a->ev_fork, 0));
-            RV_HIP(hipStreamWaitEvent(a->bub_stream2, a->ev_fork, 0));
-            Workspace wl, wk; wl.stream = a->bub_stream; wk.stream = a->bub_stream2;
-            RV_TRY(rv_bubble_children_dev_classes_launch(wl, wk, ba, d.kid, ns, a->par_min_cur));
-            RV_HIP(hipEventRecord(a->ev_join, a->bub_stream));
-            RV_HIP(hipEventRecord(a->ev_join2, a->bub_stream2));
-            RV_HIP(hipStreamWaitEvent(q, a->ev_join, 0));
-            RV_HIP(hipStreamWaitEvent(q, a->ev_join2, 0));
-        }
-        h->prof.end(q, id);
-        a->early_bubble = true;
-    }
+    sa.err = a->dErr.as<u32>();      // persistent for the alignment: an early split runs before the commit's upload exists
+}
+
+// tile bounds for the data-parallel bubble rounds (the split's scatter lowers them): preset for the level being written
+static int tmin_preset(rv_index *h, RvSplitArgs &sa) {
+    Align *a = h->al;
+    const size_t bytes = (size_t)(a->lv.m / RV_SPLIT_TILE + 2) * 4;      // (the next level is not larger than this one)
+    RV_TRY(a->dTmin.reserve(bytes));
+    RV_HIP(hipMemsetAsync(a->dTmin.p, 0xFF, bytes, h->ws.stream));
+    sa.tmin_out = a->dTmin.as<u32>();
     return 0;
 }
 
-/* The same for more than two samples: decisions of the built-in callbacks on the device (rv_decide.hip, k_decide_multi) right behind
- * the multi-sample picker, then the level's split -- it runs while the host receives the picks and rebuilds the same decisions
- * for its own bookkeeping (thousands of sub-indices per level with ten samples: 30 of 163 ms at 10 x 5 Mbp with no kernel running). */
-static int early_split_multi(rv_index *h) {
+// one flag byte per rank for the bubble kernels.  Every bubble kernel leaves the flag bytes it set at zero again: one memset per
+// alignment (and per reallocation) instead of per level
+static int bubble_flags(rv_index *h, int64_t ranks) {
+    Align *a = h->al;
+    const void *before = a->dFlag.p;
+    RV_TRY(a->dFlag.reserve((size_t)ranks + 64));
+    if (!a->flag_clean || a->dFlag.p != before) { RV_HIP(hipMemsetAsync(a->dFlag.p, 0, a->dFlag.cap, h->ws.stream)); a->flag_clean = true; }
+    return 0;
+}
+
+// Independent groups of a level's bubble work go to streams of their own beside the main one -- LDS-resident kernels to bub_stream,
+// one-workgroup kernels to bub_stream2: a kernel boundary on one stream is a barrier, so the level's bubble time is the longest
+// group, not their sum.  Fork: the side streams start behind what the main stream holds now (streams and events are made on first use).
+static int bubble_fork(rv_index *h, bool record, bool lds_side, bool kid_side) {
+    Align *a = h->al;
+    if (!a->bub_stream) {
+        RV_HIP(rv_stream_get(&a->bub_stream));
+        RV_HIP(rv_stream_get(&a->bub_stream2));
+        RV_HIP(hipEventCreateWithFlags(&a->ev_fork, hipEventDisableTiming));
+        RV_HIP(hipEventCreateWithFlags(&a->ev_join, hipEventDisableTiming));
+        RV_HIP(hipEventCreateWithFlags(&a->ev_join2, hipEventDisableTiming));
+    }
+    if (record) RV_HIP(hipEventRecord(a->ev_fork, h->ws.stream));
+    if (lds_side) RV_HIP(hipStreamWaitEvent(a->bub_stream, a->ev_fork, 0));
+    if (kid_side) RV_HIP(hipStreamWaitEvent(a->bub_stream2, a->ev_fork, 0));
+    return 0;
+}
+// Join: the main stream goes on behind what the side streams hold now.
+static int bubble_join(rv_index *h, bool lds_side, bool kid_side) {
+    Align *a = h->al;
+    if (lds_side) RV_HIP(hipEventRecord(a->ev_join, a->bub_stream));
+    if (kid_side) RV_HIP(hipEventRecord(a->ev_join2, a->bub_stream2));
+    if (kid_side) RV_HIP(hipStreamWaitEvent(h->ws.stream, a->ev_join2, 0));
+    if (lds_side) RV_HIP(hipStreamWaitEvent(h->ws.stream, a->ev_join, 0));
+    return 0;
+}
+
+/* The split of the current level (reveal.c:1005-1252 without lower-casing and bubble_sort), queued right behind the picker
+ * kernels with decisions taken on the device (rv_decide.hip: k_decide for two samples, k_decide_multi -- the built-in callbacks'
+ * decisions -- for more): it runs while the host receives the picks and rebuilds the same decisions for its own bookkeeping
+ * (thousands of sub-indices per level with ten samples: 30 of 163 ms at 10 x 5 Mbp with no kernel running).  rv_frontier_commit
+ * then finds it done. */
+static int early_split(rv_index *h) {
     Align *a = h->al;
     hipStream_t q = h->ws.stream;
     const Level &lv = a->lv;
-    const int ns = lv.size(), W = h->nsamples;
-    const int64_t m = lv.m, ntiles = ceil_div(m, RV_SPLIT_TILE);
-    const int nxt = (a->level == 0) ? 0 : (a->cur + 1) % RV_LEVEL_BUFS;
-    RV_TRY(a->dD.reserve((size_t)m + 64));
-    RV_TRY(a->dTile.reserve((size_t)ntiles * 3 * 5 * 4 + 64));
-    RV_TRY(a->lvSA[nxt].reserve((size_t)(m + 64) * sizeof(sa_t)));
-    RV_TRY(a->lvLCP[nxt].reserve((size_t)(m + 64) * sizeof(lcp_t)));
-    RV_TRY(a->lvBWT[nxt].reserve((size_t)m + 64));
+    const int ns = lv.size(), W = a->multi ? h->nsamples : 2;
+    const int64_t m = lv.m;
+    const int nxt = next_buf(a);
+    RV_TRY(split_reserve(h, nxt, m, m));
+    RV_TRY(leaf_wait(h, nxt));      // (ping-pong; more than two samples: no leaf launches, nothing pending)
+    // fixed strides per sub-index: 2 W class intervals, W matched ranges, W cut windows, W "behind the match" positions (rv_decide.h)
     const size_t S = (size_t)ns;
     size_t bytes = 0;
     auto take = [&](size_t b) { const size_t o = (bytes + 15) & ~(size_t)15; bytes = o + b; return o; };
@@ -656,87 +629,90 @@ static int early_split_multi(rv_index *h) {
     const size_t o_kid = take(S * sizeof(RvBubbleDesc));
     RV_TRY(a->dDec.reserve(bytes + 64));
     uint8_t *db = a->dDec.as<uint8_t>();
-    RvDecideMultiArgs d;
-    d.kid = (RvBubbleDesc *)(db + o_kid);
-    d.nsubs = ns; d.W = W; d.minl = a->minl; d.minn = a->minn; d.lcap = h->maxlcp;
-    d.nodes = a->d_next_nodes; d.want = a->d_next_want;
-    // the picker's device buffers (rv_run_multi_pick, rv_api.hip)
-    d.pick_l = h->ws.misc[13].as<u32>(); d.pick_pos = h->ws.misc[7].as<sa_t>();
-    d.cand_count = h->ws.misc[1].as<u32>() + RV_MULTI_REGIONS * 64;
-    d.cand_cap = (u32)std::min<size_t>(h->ws.misc[8].cap / RV_MULTI_CAND_BYTES / RV_MULTI_REGIONS, 0xffffffffu);
-    d.ctab_first = (int *)(db + o_ctf); d.mtab_first = (int *)(db + o_mtf); d.cut_first = (int *)(db + o_cf); d.mend_first = (int *)(db + o_mf);
-    d.cb = (sa_t *)(db + o_cb); d.ce = (sa_t *)(db + o_ce); d.cc = db + o_cc; d.mb = (sa_t *)(db + o_mb); d.me = (sa_t *)(db + o_me);
-    d.cut_lo = (sa_t *)(db + o_clo); d.cut_hi = (sa_t *)(db + o_chi); d.mend_pos = (sa_t *)(db + o_mp);
-    d.child_n = (u32 *)(db + o_cn); d.child_base = (u32 *)(db + o_cbase); d.sub_off = (u32 *)(db + o_soff); d.expect_total = (u32 *)(db + o_exp);
-    d.err = a->dErr.as<u32>();
-    RV_TRY(rv_decide_multi_launch(h->ws, d));
-    RvLabelTabs &lt = a->e_lt;
-    lt.sub_start = a->d_next_ss; lt.nsubs = ns; lt.tile_sub = a->d_next_tsub;
-    lt.ctab_first = d.ctab_first; lt.cbegin = d.cb; lt.cend = d.ce; lt.ccls = d.cc;
-    lt.mtab_first = d.mtab_first; lt.mbegin = d.mb; lt.mend = d.me; lt.nmatch = W * ns;
-    RvSplitArgs &sa = a->e_sa;
-    u32 *tiles = a->dTile.as<u32>();
-    sa.ntiles = ntiles;
-    sa.tile_cnt = tiles; sa.tile_has = tiles + 3 * ntiles; sa.tile_post = tiles + 6 * ntiles;
-    sa.tile_G = tiles + 9 * ntiles; sa.tile_carry = tiles + 12 * ntiles;
-    sa.total = (u32 *)(db + o_tot);
-    sa.sub_start = lt.sub_start; sa.nsubs = ns; sa.tile_sub = lt.tile_sub;
-    sa.child_base = d.child_base; sa.child_n = d.child_n; sa.sub_off = d.sub_off; sa.expect_total = d.expect_total;
-    sa.cut_first = d.cut_first; sa.cut_lo = d.cut_lo; sa.cut_hi = d.cut_hi;
-    sa.mend_first = d.mend_first; sa.mend_pos = d.mend_pos; sa.mend_all = 0;
-    sa.SA_out = a->lvSA[nxt].as<sa_t>(); sa.LCP_out = a->lvLCP[nxt].as<lcp_t>(); sa.BWT_out = a->lvBWT[nxt].as<uint8_t>(); sa.SAi = h->dSAi.as<sa_t>();
-    sa.err = a->dErr.as<u32>();
-    {   // tile bounds for the data-parallel bubble rounds (see early_split)
-        int64_t big0 = 0;
-        for (int s2 = 0; s2 < ns; s2++) big0 = std::max<int64_t>(big0, lv.n[(size_t)s2]);
-        sa.tmin_out = nullptr;
-        if (big0 > a->par_min_cur) {
-            RV_TRY(a->dTmin.reserve((size_t)(m / RV_SPLIT_TILE + 2) * 4));
-            RV_HIP(hipMemsetAsync(a->dTmin.p, 0xFF, (size_t)(m / RV_SPLIT_TILE + 2) * 4, q));
-            sa.tmin_out = a->dTmin.as<u32>();
-        }
+    SplitTabs t;
+    t.sub_start = a->d_next_ss; t.tile_sub = a->d_next_tsub;
+    t.ctab_first = (int *)(db + o_ctf); t.mtab_first = (int *)(db + o_mtf); t.cut_first = (int *)(db + o_cf); t.mend_first = (int *)(db + o_mf);
+    t.cb = (sa_t *)(db + o_cb); t.ce = (sa_t *)(db + o_ce); t.cc = db + o_cc; t.mb = (sa_t *)(db + o_mb); t.me = (sa_t *)(db + o_me);
+    t.cut_lo = (sa_t *)(db + o_clo); t.cut_hi = (sa_t *)(db + o_chi); t.mend_pos = (sa_t *)(db + o_mp);
+    t.child_n = (u32 *)(db + o_cn); t.child_base = (u32 *)(db + o_cbase); t.sub_off = (u32 *)(db + o_soff); t.expect_total = (u32 *)(db + o_exp);
+    t.total = (u32 *)(db + o_tot);
+    t.nmatch = W * ns;
+    RvBubbleDesc *kid = (RvBubbleDesc *)(db + o_kid);
+    auto outputs = [&](auto &d) {      // what both decide kernels write
+        d.nsubs = ns; d.lcap = h->maxlcp;
+        d.ctab_first = t.ctab_first; d.mtab_first = t.mtab_first; d.cut_first = t.cut_first; d.mend_first = t.mend_first;
+        d.cb = t.cb; d.ce = t.ce; d.cc = t.cc; d.mb = t.mb; d.me = t.me;
+        d.cut_lo = t.cut_lo; d.cut_hi = t.cut_hi; d.mend_pos = t.mend_pos;
+        d.child_n = t.child_n; d.child_base = t.child_base; d.sub_off = t.sub_off; d.expect_total = t.expect_total;
+        d.err = a->dErr.as<u32>();
+        d.kid = kid;
+    };
+    if (a->multi) {
+        RvDecideMultiArgs d;
+        outputs(d);
+        d.W = W; d.minl = a->minl; d.minn = a->minn;
+        d.nodes = a->d_next_nodes; d.want = a->d_next_want;
+        // the picker's device buffers (rv_run_multi_pick, rv_api.hip)
+        d.pick_l = h->ws.misc[13].as<u32>(); d.pick_pos = h->ws.misc[7].as<sa_t>();
+        d.cand_count = h->ws.misc[1].as<u32>() + RV_MULTI_REGIONS * 64;
+        d.cand_cap = (u32)std::min<size_t>(h->ws.misc[8].cap / RV_MULTI_CAND_BYTES / RV_MULTI_REGIONS, 0xffffffffu);
+        RV_TRY(rv_decide_multi_launch(h->ws, d));
+    } else {
+        RvDecideArgs d;
+        outputs(d);
+        d.nodes = a->d_next_nodes; d.flags = a->d_next_flags; d.picks = h->hscan.as<RvPairRec>();
+        d.ovf_cap = (u32)std::min<size_t>(h->ws.misc[4].cap / sizeof(RvPairRec), 0xffffffffu);      // (the scan's overflow buffer)
+        RV_TRY(rv_decide_launch(h->ws, d));
     }
+    RvLabelTabs lt; RvSplitArgs sa;
+    split_args(h, t, nxt, lt, sa);
+    int64_t biggest = 0;
+    for (int s2 = 0; s2 < ns; s2++) biggest = std::max<int64_t>(biggest, lv.n[(size_t)s2]);
+    // (tile bounds: only a level that can still have a child above the rounds' threshold needs them)
+    if (biggest > a->par_min_cur) RV_TRY(tmin_preset(h, sa));
     int id = h->prof.begin(q, RV_K_SPLIT, (double)m * (2 * (sizeof(sa_t) + sizeof(lcp_t) + 2)) + (double)m * (sizeof(sa_t) + sizeof(lcp_t) + 1));
     RV_TRY(rv_split_launch(h->ws, cur_sa(h), cur_lcp(h), a->dD.as<uint8_t>(), cur_bwt(h), m, lt, sa, 1));
     h->prof.end(q, id);
     a->early_done = true;
+    // No sub-index above the rounds' threshold: lower-casing and the bubble of every leading child follow at once, from the device-built
+    // descriptors -- the whole level is queued before the host has seen the picks.  (A level that still has a sub-index above the
+    // threshold keeps the host-built mix of rounds and joined children.)
+    // Two samples, more than 4096 sub-indices: left to the commit.  Tried at 2 x 250 Mbp through the size-class launches below, 304
+    // against 300 ms -- five launches over every descriptor cost more GPU time than the hidden host time is worth; RV_EARLY_BUBBLE_MANY=1
+    // switches it on.
     a->early_bubble = false;
-    // No sub-index above the rounds' threshold: lower-casing and the bubble of every leading child follow at once, from the
-    // device-built descriptors (all size classes: LDS kernels and one-workgroup kernels on their own streams, as the host-built
-    // launches of rv_frontier_commit) -- the whole level is queued before the host has seen the picks.
-    int64_t biggest = 0;
-    for (int s2 = 0; s2 < ns; s2++) biggest = std::max<int64_t>(biggest, lv.n[(size_t)s2]);
-    if (biggest <= a->par_min_cur && !h->ws.opt.no_early_bubble) {
-        RV_TRY(rv_lower_ranges_launch(h->ws, h->dT.as<uint8_t>(), d.mb, d.me, W * ns));
-        {
-            const void *before = a->dFlag.p;
-            RV_TRY(a->dFlag.reserve((size_t)m + 64));
-            if (!a->flag_clean || a->dFlag.p != before) { RV_HIP(hipMemsetAsync(a->dFlag.p, 0, a->dFlag.cap, q)); a->flag_clean = true; }
-        }
+    const bool all_classes = a->multi || ns > 4096;
+    if (biggest <= a->par_min_cur && !h->ws.opt.no_early_bubble &&
+        (a->multi || (!h->ws.opt.bubble_lds_always && (!all_classes || h->ws.opt.early_bubble_many)))) {
+        RV_TRY(rv_lower_ranges_launch(h->ws, h->dT.as<uint8_t>(), t.mb, t.me, W * ns));
+        RV_TRY(bubble_flags(h, m));
         RvBubbleArgs ba;
         memset(&ba, 0, sizeof ba);
         ba.flag = a->dFlag.as<uint8_t>();
-        ba.SA = sa.SA_out; ba.LCP = sa.LCP_out; ba.BWT = sa.BWT_out; ba.SAi = sa.SAi; ba.cut_lo = d.cut_lo; ba.cut_hi = d.cut_hi; ba.err = a->dErr.as<u32>();
-        if (!a->bub_stream) {
-            RV_HIP(rv_stream_get(&a->bub_stream));
-            RV_HIP(rv_stream_get(&a->bub_stream2));
-            RV_HIP(hipEventCreateWithFlags(&a->ev_fork, hipEventDisableTiming));
-            RV_HIP(hipEventCreateWithFlags(&a->ev_join, hipEventDisableTiming));
-            RV_HIP(hipEventCreateWithFlags(&a->ev_join2, hipEventDisableTiming));
-        }
+        ba.SA = sa.SA_out; ba.LCP = sa.LCP_out; ba.BWT = sa.BWT_out; ba.SAi = sa.SAi; ba.cut_lo = t.cut_lo; ba.cut_hi = t.cut_hi; ba.err = a->dErr.as<u32>();
         id = h->prof.begin(q, RV_K_BUBBLE, 0.0);
-        RV_HIP(hipEventRecord(a->ev_fork, q));
-        RV_HIP(hipStreamWaitEvent(a->bub_stream, a->ev_fork, 0));
-        RV_HIP(hipStreamWaitEvent(a->bub_stream2, a->ev_fork, 0));
-        Workspace wl, wk; wl.stream = a->bub_stream; wk.stream = a->bub_stream2;
-        RV_TRY(rv_bubble_children_dev_classes_launch(wl, wk, ba, d.kid, ns, a->par_min_cur));
-        RV_HIP(hipEventRecord(a->ev_join, a->bub_stream));
-        RV_HIP(hipEventRecord(a->ev_join2, a->bub_stream2));
-        RV_HIP(hipStreamWaitEvent(q, a->ev_join, 0));
-        RV_HIP(hipStreamWaitEvent(q, a->ev_join2, 0));
+        if (!all_classes) {
+            // few sub-indices of two samples (above a few thousand the LDS kernels on their own stream are the better choice): one launch on the main stream
+            RV_TRY(rv_bubble_children_dev_launch(h->ws, ba, kid, ns, a->par_min_cur));
+        } else {
+            // all size classes, LDS-resident kernels included, each on its own stream -- the host-built launches of rv_frontier_commit,
+            // minus the wait for the host's tables
+            RV_TRY(bubble_fork(h, true, true, true));
+            Workspace wl, wk; wl.stream = a->bub_stream; wk.stream = a->bub_stream2;
+            RV_TRY(rv_bubble_children_dev_classes_launch(wl, wk, ba, kid, ns, a->par_min_cur));
+            RV_TRY(bubble_join(h, true, true));
+        }
         h->prof.end(q, id);
         a->early_bubble = true;
     }
+    return 0;
+}
+
+/* called by the pair scan once its kernels and the picker's are queued, before the host waits for the picks */
+static int level_hook(rv_index *h) {
+    Align *a = h->al;
+    if (a->hook_early) RV_TRY(early_split(h));
+    if (a->leaf_launch_due) RV_TRY(leaf_launch(h));
     return 0;
 }
 
@@ -816,7 +792,7 @@ int rv_frontier_scan(rv_index *h) {
             d_ps = (const int64_t *)(buf.as<uint8_t>() + o1);
         }
         RV_TRY(rv_run_pair_scan(h, cur_sa(h), cur_lcp(h), cur_bwt(h), a->lv.m, a->minl, a->recs, a->dErr.as<u32>(), &err, d_ss, ns, level_hook, early || a->leaf_launch_due,
-                                (d_ss && a->cur_dev_ok) ? a->d_next_tsub2 : nullptr, d_ps, ns, a->presel));
+                                (d_ss && a->cur_dev_ok) ? a->d_next_tsub : nullptr, d_ps, ns, a->presel));
         if (a->presel_on && !a->full_only) a->presel_d2h += (int64_t)a->recs.size();
         RV_TRY(report_dev_err(err));
         int si = 0;
@@ -835,7 +811,7 @@ int rv_frontier_scan(rv_index *h) {
             const bool early = a->cur_dev_ok && !h->ws.opt.no_early_split;
             bool redo = false;
             RV_TRY(rv_run_multi_pick(h, cur_sa(h), cur_lcp(h), cur_bwt(h), a->lv.m, a->minl, a->minn, a->d_next_ss, a->d_next_want, ns, a->d_next_tsub, a->pick_l, a->pick_pos,
-                                     early ? early_split_multi : nullptr, &redo));
+                                     early ? early_split : nullptr, &redo));
             if (redo) a->early_done = false;      // (the early split saw an overflowed candidate list and decided nothing: the commit splits again)
             a->ml.clear(); a->mn.clear(); a->moff.assign(1, 0); a->mso.clear(); a->mpos.clear();
             const int W = h->nsamples;
@@ -1072,6 +1048,23 @@ int rv_sub_split(rv_index *h, int s, uint32_t l, int nsp, const int64_t *sp,
     return 0;
 }
 
+// A two-sample sub-index' one or two intervals, slotted by the first separator: out = (a0, a1, b0, b1), the interval of sample 0 and of
+// sample 1 (an absent one stays empty).  false: the sub-index does not fit the two-interval model (no interval or more than two, two of
+// one sample, one that begins at the separator).
+static bool pair_intervals(const rv_index *h, const Level &lv, int s, int64_t out[4]) {
+    out[0] = out[1] = out[2] = out[3] = 0;
+    const int64_t nf = lv.node_first[(size_t)s], nn = lv.node_first[(size_t)s + 1] - nf, sep = h->nsep[0];
+    if (nn < 1 || nn > 2) return false;
+    for (int64_t k = 0; k < nn; k++) {
+        const RvIntv iv = lv.nodes[(size_t)(nf + k)];
+        if (iv.begin == sep) return false;
+        int64_t *o = out + (iv.begin < sep ? 0 : 2);
+        if (o[0] < o[1]) return false;
+        o[0] = iv.begin; o[1] = iv.end;
+    }
+    return true;
+}
+
 // Tables the scan and the device-side decisions of a level need; the commit in front of the level ships them with its own
 // upload (a frontier import ships them itself): sub-index starts, and
 //  - more than two samples: tile -> sub-index table (the multi-sample picker looks sub-indices up per candidate)
@@ -1103,17 +1096,10 @@ static void prep_level_tables(rv_index *h, const Level &nx, int64_t m_next, bool
         }
     } else if (a->next_dev_ok) {
         a->next_nodes.assign((size_t)nsn * 4, 0); a->next_flags.assign((size_t)nsn, 0);
-        const int64_t sep = h->nsep[0];
         for (int s2 = 0; s2 < nsn && a->next_dev_ok; s2++) {
-            const int64_t nf = nx.node_first[(size_t)s2], nn = nx.node_first[(size_t)s2 + 1] - nf;
-            if (nn < 1 || nn > 2) { a->next_dev_ok = false; break; }
-            sa_t *nd = a->next_nodes.data() + (size_t)s2 * 4;
-            for (int64_t k = 0; k < nn; k++) {
-                const RvIntv iv = nx.nodes[(size_t)(nf + k)];
-                if (iv.begin < sep) { if (nd[0] < nd[1]) a->next_dev_ok = false; nd[0] = (sa_t)iv.begin; nd[1] = (sa_t)iv.end; }
-                else if (iv.begin > sep) { if (nd[2] < nd[3]) a->next_dev_ok = false; nd[2] = (sa_t)iv.begin; nd[3] = (sa_t)iv.end; }
-                else a->next_dev_ok = false;
-            }
+            int64_t ab[4];
+            a->next_dev_ok = pair_intervals(h, nx, s2, ab);
+            for (int k = 0; k < 4; k++) a->next_nodes[(size_t)s2 * 4 + k] = (sa_t)ab[k];
             // the leaf kernel takes every sub-index of at most RV_LEAF_N ranks here (same rule as builtin_levels)
             a->next_flags[(size_t)s2] = (a->use_leaf && nx.n[(size_t)s2] <= RV_LEAF_N) ? 1 : 0;
         }
@@ -1121,9 +1107,9 @@ static void prep_level_tables(rv_index *h, const Level &nx, int64_t m_next, bool
     a->next_tsub.clear();
     if ((a->multi || a->next_dev_ok) && !tsub_on_device) {
         const int64_t ntn = ceil_div(m_next, RV_SPLIT_TILE);
-        a->next_tsub.resize((size_t)ntn);
+        a->next_tsub.assign((size_t)ntn, 0);
         int s2 = 0;
-        for (int64_t t = 0; t < ntn; t++) {
+        for (int64_t t = 0; t < ntn && nsn > 1; t++) {      // (one sub-index, level 0 of a run: all zero already)
             const int64_t r = t * RV_SPLIT_TILE;
             while (s2 + 1 < nsn && a->next_ss[(size_t)s2 + 1] <= r) s2++;
             a->next_tsub[(size_t)t] = s2;
@@ -1131,43 +1117,59 @@ static void prep_level_tables(rv_index *h, const Level &nx, int64_t m_next, bool
     }
 }
 
-/* reveal.c:1005-1252 for every decided sub-index; children -> next frontier */
-int rv_frontier_commit(rv_index *h, int32_t *children) {
-    RV_TRY(need_align(h));
+// Publish the tables prep_level_tables made (want: the sample counts of the level's sub-indices): packed behind whatever the caller has
+// begun in the staging buffer, the lot shipped to dst in one upload, the d_next_* pointers set.
+static int publish_next_tables(rv_index *h, DBuf &dst, const std::vector<int32_t> &want, bool plain_copy) {
     Align *a = h->al;
-    RV_HIP(hipSetDevice(h->device));
-    hipStream_t q = h->ws.stream;
-    const double t0 = now_s();
+    Packer &pk = a->pk;
+    const size_t o_ss = pk.addv(a->next_ss), o_want = pk.addv(want), o_tsub = pk.addv(a->next_tsub);
+    size_t o_nodes = 0, o_flags = 0;
+    if (a->next_dev_ok) { o_nodes = pk.addv(a->next_nodes); o_flags = pk.addv(a->next_flags); }
+    RV_TRY(dst.reserve(pk.size() + 64));
+    a->lgx[3] = now_s() - a->lg_t0;     // offsets packed (RV_LEVEL_LOG prints a commit's)
+    // (pinned staging: a queued copy kernel reads it.  No pinned memory to be had, or RV_TABLES_MEMCPY in a commit: the runtime's copy)
+    if (pk.pageable || plain_copy) RV_HIP(hipMemcpyAsync(dst.p, pk.data(), pk.size(), hipMemcpyHostToDevice, h->ws.stream));
+    else { pk.grow(pk.size() + 16); RV_TRY(rv_h2d_copy(h->ws, pk.data(), dst.p, pk.size())); }
+    const uint8_t *tb = dst.as<uint8_t>();
+    a->d_next_ss = (const int64_t *)(tb + o_ss); a->d_next_want = (const int *)(tb + o_want); a->d_next_tsub = (const int *)(tb + o_tsub);
+    a->d_next_nodes = (const sa_t *)(tb + o_nodes); a->d_next_flags = tb + o_flags;
+    return 0;
+}
+
+/* ---- rv_frontier_commit (reveal.c:1005-1252 for every decided sub-index; children -> next frontier), stage by stage ---- */
+// what the stages hand on: the bubble plan of the level and where each table lies in the upload
+struct Commit {
+    bool split_tabs, lower_tabs;       // the split is still to be launched, from the tables built here; ... and so is the lower-casing of the matched ranges
+    int64_t par_min;                   // leading children above this many ranks take the data-parallel bubble rounds (RV_BUBBLE_PAR_MIN: test hook)
+    bool any_par = false; int64_t window_sum = 0;
+    int64_t m_next = 0; int nxt = 0;
+    std::vector<int> round_first;
+    std::vector<uint8_t> round_seq;    // some window of the round exceeds what the parallel path takes: also launch the sequential kernels
+    int lds_count[3] = {0, 0, 0};
+    size_t o_tsub, o_cb, o_ce, o_cc, o_mb, o_me, o_mpre, o_ctf, o_mtf, o_ss, o_cbase, o_cn, o_cf, o_clo, o_chi, o_desc, o_woff, o_toff, o_mf, o_mp;
+    size_t o_ks, o_kb, o_kl, o_suboff, o_expect, o_total, o_bcnt, o_mcnt, o_gcnt, o_bstate;
+};
+
+// per-sub tables, next level layout, child bookkeeping (reveal.c:1136-1207)
+static int commit_tables(rv_index *h, int32_t *children, Commit &cm) {
+    Align *a = h->al;
     const Level &lv = a->lv;
     Level &nx = a->nx;
     const Decisions &dc = a->dec;
     const int ns = lv.size();
-    if (children) for (int k = 0; k < 3 * ns; k++) children[k] = -1;
-    a->scanned = false;
-    nx.clear();
-    if (dc.size() == 0) { a->lv.clear(); a->dec.reset(0); return 0; }
-
-    // ---- per-sub tables, next level layout, child bookkeeping (reveal.c:1136-1207) ----------------
     a->cb.clear(); a->ce.clear(); a->cc.clear(); a->mb.clear(); a->me.clear(); a->mpre.assign(1, 0);
     a->ctab_first.assign((size_t)ns + 1, 0); a->mtab_first.assign((size_t)ns + 1, 0);
     a->cut_first.assign((size_t)ns + 1, 0); a->mend_first.assign((size_t)ns + 1, 0);
     a->cut_lo.clear(); a->cut_hi.clear(); a->mend_pos.clear(); a->split_subs.clear();
     a->child_base.assign((size_t)ns * 3, 0); a->child_n.assign((size_t)ns * 3, 0);
     a->sub_start.resize((size_t)ns + 1);
-    for (auto &r : a->rounds) r.clear();
-    a->kids_small.clear(); a->kids_big.clear(); a->kids_lds.clear();
-    const int64_t lds_n = h->ws.opt.bubble_no_lds ? 0 : RV_BUBBLE_LDS_N;
     int64_t running = 0;
     const int64_t lcap = (int64_t)h->maxlcp;
-    // leading children above this many ranks take the data-parallel bubble rounds (RV_BUBBLE_PAR_MIN: test hook)
-    const int64_t par_min = (h->ws.opt.bubble_par_min >= 0 ? h->ws.opt.bubble_par_min : bubble_par_default(a->multi));
+    const int64_t par_min = cm.par_min;
     struct Ent { int64_t b, e; uint8_t c; };
     std::vector<Ent> ent;
     a->kid_tmp.clear();
-    bool any_par = false;
-    int64_t window_sum = 0;
-    const bool split_tabs = !a->early_done;       // the split is still to be launched, from the tables built here
-    const bool lower_tabs = !a->early_bubble;     // ... and so is the lower-casing of the matched ranges
+    const bool split_tabs = cm.split_tabs, lower_tabs = cm.lower_tabs;
     for (int s = 0; s < ns; s++) {
         a->sub_start[(size_t)s] = lv.off[(size_t)s];
         a->ctab_first[(size_t)s] = (int)a->cb.size(); a->mtab_first[(size_t)s] = (int)a->mb.size();
@@ -1247,15 +1249,29 @@ int rv_frontier_commit(rv_index *h, int32_t *children) {
             for (int q = c0; q < c1; q++) { any = any || a->cut_lo[(size_t)q] < a->cut_hi[(size_t)q]; wsum += (int64_t)a->cut_hi[(size_t)q] - (int64_t)a->cut_lo[(size_t)q]; }
             if (any) {
                 a->kid_tmp.push_back({lead_off, lead_n, c0, c1, m0, wsum});
-                if (lead_n > par_min) any_par = true;
-                window_sum += wsum;
+                if (lead_n > par_min) cm.any_par = true;
+                cm.window_sum += wsum;
             }
         }
     }
+    a->sub_start[(size_t)ns] = lv.m;
+    a->ctab_first[(size_t)ns] = (int)a->cb.size(); a->mtab_first[(size_t)ns] = (int)a->mb.size();
+    a->cut_first[(size_t)ns] = (int)a->cut_lo.size(); a->mend_first[(size_t)ns] = (int)a->mend_pos.size();
+    nx.m = cm.m_next = running;
+    if (cm.m_next >= ((int64_t)1 << 32)) { rv_set_error("level larger than 2^32 ranks not supported yet"); return -1; }
+    return 0;
+}
+
+// the bubble plan: which kernels take which leading child
+static void commit_bubble_plan(rv_index *h, Commit &cm) {
+    Align *a = h->al;
+    const int64_t par_min = cm.par_min, lds_n = h->ws.opt.bubble_no_lds ? 0 : RV_BUBBLE_LDS_N;
+    for (auto &r : a->rounds) r.clear();
+    a->kids_small.clear(); a->kids_big.clear(); a->kids_lds.clear();
     // Leading children above par_min ranks take the data-parallel rounds.  Once a level runs those rounds anyway, the small
     // children join them as long as there are few of them (measured: with thousands of small children per level the
     // one-workgroup-per-child kernel is the cheaper way, C3/C4): their kernel would only add its own latency in front.
-    const bool all_par = any_par && window_sum <= ((int64_t)1 << 20) && !h->ws.opt.bubble_no_join && !a->early_bubble;
+    const bool all_par = cm.any_par && cm.window_sum <= ((int64_t)1 << 20) && !h->ws.opt.bubble_no_join && !a->early_bubble;
     // The LDS kernels pay off by throughput (thousands of small children per level: many samples, or very large inputs).  A
     // few hundred small children ride along with the larger ones for free (measured on C2: 612 vs 597 Mbp/s).
     size_t lds_candidates = 0;
@@ -1278,32 +1294,32 @@ int rv_frontier_commit(rv_index *h, int32_t *children) {
             a->rounds[r].push_back(bd);
         }
     }
-    a->sub_start[(size_t)ns] = lv.m;
-    a->ctab_first[(size_t)ns] = (int)a->cb.size(); a->mtab_first[(size_t)ns] = (int)a->mb.size();
-    a->cut_first[(size_t)ns] = (int)a->cut_lo.size(); a->mend_first[(size_t)ns] = (int)a->mend_pos.size();
-    nx.m = running;
-    const int64_t m_next = running;
-    if (m_next >= ((int64_t)1 << 32)) { rv_set_error("level larger than 2^32 ranks not supported yet"); return -1; }
     a->descs.clear();
-    std::vector<int> round_first;
-    std::vector<uint8_t> round_seq;      // some window of the round exceeds what the parallel path takes: also launch the sequential kernels
     for (auto &r : a->rounds) {
-        round_first.push_back((int)a->descs.size());
+        cm.round_first.push_back((int)a->descs.size());
         bool seq = false;
         for (auto &x : r) seq = seq || (x.B - x.wlo) > RV_PB_CAP;
-        round_seq.push_back(seq ? 1 : 0);
+        cm.round_seq.push_back(seq ? 1 : 0);
         a->descs.insert(a->descs.end(), r.begin(), r.end());
     }
-    round_first.push_back((int)a->descs.size());
+    cm.round_first.push_back((int)a->descs.size());
     a->woff.assign(a->descs.size() + 1, 0);
     a->toff.assign(a->descs.size() + 1, 0);
     for (size_t k = 0; k < a->descs.size(); k++) {
         a->woff[k + 1] = a->woff[k] + (a->descs[k].B - a->descs[k].wlo);
         a->toff[k + 1] = a->toff[k] + ceil_div(a->descs[k].n, RV_SPLIT_TILE);
     }
+}
 
-    a->lg[0] = now_s() - t0;      // tables built
-    // ---- one upload for all the tables ---------------------------------------------------
+// one upload for all the tables, the next level's among them
+static int commit_upload(rv_index *h, Commit &cm) {
+    Align *a = h->al;
+    const Level &lv = a->lv;
+    const Level &nx = a->nx;
+    const int ns = lv.size();
+    const double t0 = a->lg_t0;
+    const bool split_tabs = cm.split_tabs;
+    const int64_t m_next = cm.m_next;
     const int64_t ntiles = ceil_div(lv.m, RV_SPLIT_TILE);
     a->tile_sub.resize(split_tabs ? (size_t)ntiles : 0);
     if (split_tabs) {
@@ -1317,34 +1333,29 @@ int rv_frontier_commit(rv_index *h, int32_t *children) {
     a->lgx[0] = now_s() - t0;     // tile -> sub-index table
     Packer &pk = a->pk;
     pk.clear();
-    const size_t o_tsub = pk.addv(a->tile_sub);
-    const size_t o_cb = pk.addv(a->cb), o_ce = pk.addv(a->ce), o_cc = pk.addv(a->cc), o_mb = pk.addv(a->mb), o_me = pk.addv(a->me), o_mpre = pk.addv(a->mpre);
+    cm.o_tsub = pk.addv(a->tile_sub);
+    cm.o_cb = pk.addv(a->cb), cm.o_ce = pk.addv(a->ce), cm.o_cc = pk.addv(a->cc), cm.o_mb = pk.addv(a->mb), cm.o_me = pk.addv(a->me), cm.o_mpre = pk.addv(a->mpre);
     // (tables only the split reads stay at home when it has run already: ~100 bytes per sub-index, 50000 sub-indices per level at 2 x 250 Mbp)
     static const std::vector<int> no_int; static const std::vector<u32> no_u32; static const std::vector<int64_t> no_i64;
-    const size_t o_ctf = pk.addv(split_tabs ? a->ctab_first : no_int), o_mtf = pk.addv(split_tabs ? a->mtab_first : no_int);
-    const size_t o_ss = pk.addv(split_tabs ? a->sub_start : no_i64), o_cbase = pk.addv(split_tabs ? a->child_base : no_u32), o_cn = pk.addv(split_tabs ? a->child_n : no_u32);
-    const size_t o_cf = pk.addv(split_tabs ? a->cut_first : no_int);
-    const size_t o_clo = pk.addv(a->cut_lo), o_chi = pk.addv(a->cut_hi);
-    const size_t o_desc = pk.addv(a->descs), o_woff = pk.addv(a->woff), o_toff = pk.addv(a->toff), o_mf = pk.addv(split_tabs ? a->mend_first : no_int), o_mp = pk.addv(a->mend_pos);
+    cm.o_ctf = pk.addv(split_tabs ? a->ctab_first : no_int), cm.o_mtf = pk.addv(split_tabs ? a->mtab_first : no_int);
+    cm.o_ss = pk.addv(split_tabs ? a->sub_start : no_i64), cm.o_cbase = pk.addv(split_tabs ? a->child_base : no_u32), cm.o_cn = pk.addv(split_tabs ? a->child_n : no_u32);
+    cm.o_cf = pk.addv(split_tabs ? a->cut_first : no_int);
+    cm.o_clo = pk.addv(a->cut_lo), cm.o_chi = pk.addv(a->cut_hi);
+    cm.o_desc = pk.addv(a->descs), cm.o_woff = pk.addv(a->woff), cm.o_toff = pk.addv(a->toff), cm.o_mf = pk.addv(split_tabs ? a->mend_first : no_int), cm.o_mp = pk.addv(a->mend_pos);
     // one launch instead of two when a level has few small children next to large ones (the kernels would run one after the
     // other on the stream; in a 1024-thread workgroup a small child simply finishes early)
     if (!a->kids_big.empty() && a->kids_small.size() <= 512 && !h->ws.opt.bubble_no_merge) { a->kids_big.insert(a->kids_big.end(), a->kids_small.begin(), a->kids_small.end()); a->kids_small.clear(); }
-    int lds_count[3] = {0, 0, 0};
     {   // LDS children by size class (stable: the order inside a class does not matter)
         auto cls = [](const RvBubbleDesc &x) { return x.n <= RV_BUBBLE_LDS_N0 ? 0 : x.n <= RV_BUBBLE_LDS_N1 ? 1 : 2; };
         std::stable_sort(a->kids_lds.begin(), a->kids_lds.end(), [&](const RvBubbleDesc &x, const RvBubbleDesc &y) { return cls(x) < cls(y); });
-        for (auto &x : a->kids_lds) lds_count[cls(x)]++;
+        for (auto &x : a->kids_lds) cm.lds_count[cls(x)]++;
         // few children: one launch with the largest configuration (occupancy does not matter, a launch does)
-        if (a->kids_lds.size() <= 512) { lds_count[2] = (int)a->kids_lds.size(); lds_count[0] = lds_count[1] = 0; }
+        if (a->kids_lds.size() <= 512) { cm.lds_count[2] = (int)a->kids_lds.size(); cm.lds_count[0] = cm.lds_count[1] = 0; }
     }
-    const size_t o_ks = pk.addv(a->kids_small), o_kb = pk.addv(a->kids_big), o_kl = pk.addv(a->kids_lds);
+    cm.o_ks = pk.addv(a->kids_small), cm.o_kb = pk.addv(a->kids_big), cm.o_kl = pk.addv(a->kids_lds);
     a->lgx[1] = now_s() - t0;     // packed
     prep_level_tables(h, nx, m_next, true);
     a->lgx[2] = now_s() - t0;     // tables of the next level
-    size_t o_ntsub = 0, o_nnodes = 0, o_nflags = 0, o_ntsub2 = 0;
-    if (a->multi) o_ntsub = pk.addv(a->next_tsub);
-    if (a->next_dev_ok) { o_nnodes = pk.addv(a->next_nodes); o_nflags = pk.addv(a->next_flags); o_ntsub2 = a->multi ? o_ntsub : pk.addv(a->next_tsub); }
-    const size_t o_nss = pk.addv(a->next_ss), o_nwant = pk.addv(nx.nsamples);
     a->sub_off_h.assign(split_tabs ? (size_t)ns * 3 : 0, 0);
     {   // SURVEY 8(a) A12 / reveal.c:666-727: bubble_sort looks at every rank of a leading child (4 B SA + 4 B LCP; the BWT byte travels with them here).
         // The spans of the class are opened where the kernels are queued (the early ones before the host knows the children's sizes): its bytes come from here.
@@ -1355,68 +1366,47 @@ int rv_frontier_commit(rv_index *h, int32_t *children) {
     u32 class_total[4] = {0, 0, 0, 0};
     if (split_tabs)
         for (int s = 0; s < ns; s++) for (int c = 0; c < 3; c++) { a->sub_off_h[(size_t)s * 3 + c] = a->child_base[(size_t)s * 3 + c] - class_total[c]; class_total[c] += a->child_n[(size_t)s * 3 + c]; }
-    const size_t o_suboff = pk.addv(a->sub_off_h), o_expect = pk.add(class_total, sizeof class_total), o_total = pk.reserve(16), o_bcnt = pk.reserve(a->descs.size() * 4 + 4), o_mcnt = pk.reserve(a->descs.size() * 4 + 4), o_gcnt = pk.reserve(16);
-    const size_t o_bstate = pk.reserve((a->descs.size() + 1) * sizeof(RvBubbleState));
-    RV_TRY(a->dTab.reserve(pk.size() + 64));
-    a->lgx[3] = now_s() - t0;     // offsets packed
-    if (pk.pageable || h->ws.opt.tables_memcpy) RV_HIP(hipMemcpyAsync(a->dTab.p, pk.data(), pk.size(), hipMemcpyHostToDevice, q));
-    else { pk.grow(pk.size() + 16); RV_TRY(rv_h2d_copy(h->ws, pk.data(), a->dTab.p, pk.size())); }
+    cm.o_suboff = pk.addv(a->sub_off_h), cm.o_expect = pk.add(class_total, sizeof class_total), cm.o_total = pk.reserve(16), cm.o_bcnt = pk.reserve(a->descs.size() * 4 + 4), cm.o_mcnt = pk.reserve(a->descs.size() * 4 + 4), cm.o_gcnt = pk.reserve(16);
+    cm.o_bstate = pk.reserve((a->descs.size() + 1) * sizeof(RvBubbleState));
+    RV_TRY(publish_next_tables(h, a->dTab, nx.nsamples, h->ws.opt.tables_memcpy != 0));
     a->lg[1] = now_s() - t0;      // upload issued
-    uint8_t *tb = a->dTab.as<uint8_t>();
-    a->d_next_ss = (const int64_t *)(tb + o_nss); a->d_next_want = (const int *)(tb + o_nwant); a->d_next_tsub = (const int *)(tb + o_ntsub);
-    a->d_next_nodes = (const sa_t *)(tb + o_nnodes); a->d_next_flags = tb + o_nflags; a->d_next_tsub2 = (const int *)(tb + o_ntsub2);
     if (a->multi || a->next_dev_ok) {      // the next level's tile -> sub-index table, from its sub-index starts (queued behind the upload)
         const int64_t ntn = ceil_div(m_next, RV_SPLIT_TILE);
         RV_TRY(a->dNextTsub.reserve((size_t)ntn * 4 + 64));
         RV_TRY(rv_tile_sub_launch(h->ws, a->d_next_ss, nx.size(), a->dNextTsub.as<int>(), ntn));
-        a->d_next_tsub = a->d_next_tsub2 = a->dNextTsub.as<int>();
+        a->d_next_tsub = a->dNextTsub.as<int>();
     }
-    RV_TRY(a->dD.reserve((size_t)lv.m + 64));
-    RV_TRY(a->dTile.reserve((size_t)ntiles * 3 * 5 * 4 + 64));
-    RV_TRY(a->dList.reserve((size_t)a->woff.back() * 4 + 64));
-    const int nxt = (a->level == 0) ? 0 : (a->cur + 1) % RV_LEVEL_BUFS;
-    RV_TRY(a->lvSA[nxt].reserve((size_t)(m_next + 64) * sizeof(sa_t)));
-    RV_TRY(a->lvLCP[nxt].reserve((size_t)(m_next + 64) * sizeof(lcp_t)));
-    RV_TRY(a->lvBWT[nxt].reserve((size_t)m_next + 64));
+    return 0;
+}
 
+// label / split of the level (unless it went out behind the picker already) and the lower-casing of the matched ranges
+static int commit_split(rv_index *h, const Commit &cm, RvSplitArgs &sa) {
+    Align *a = h->al;
+    hipStream_t q = h->ws.stream;
+    const Level &lv = a->lv;
+    const int nxt = cm.nxt;
+    uint8_t *tb = a->dTab.as<uint8_t>();
+    RV_TRY(split_reserve(h, nxt, lv.m, cm.m_next));
+    RV_TRY(a->dList.reserve((size_t)a->woff.back() * 4 + 64));
     // A leaf launch of an earlier level may still be reading the buffer this commit writes (ping-pong), and the long-move
     // path of this commit scribbled over the current (parent) buffer when that was its scratch: order after them.
-    {
-        const int cur_id = (a->level == 0) ? RV_LEVEL_BUFS : a->cur;            // RV_LEVEL_BUFS = the main arrays
-        (void)cur_id;
-        const int wait_ids[2] = {nxt, h->ws.opt.bubble_parent_scratch && !a->descs.empty() ? cur_id : -1};
-        for (int k = 0; k < 2; k++) {
-            const int id = wait_ids[k];
-            if (id < 0) continue;
-            const int slot = id;
-            if (a->leaf_pending[slot]) { RV_HIP(hipStreamWaitEvent(q, a->ev_leaf[slot], 0)); a->leaf_pending[slot] = false; }
-        }
-    }
+    RV_TRY(leaf_wait(h, nxt));
+    if (h->ws.opt.bubble_parent_scratch && !a->descs.empty()) RV_TRY(leaf_wait(h, a->level == 0 ? RV_LEVEL_BUFS : a->cur));
+    SplitTabs t;
+    t.sub_start = (const int64_t *)(tb + cm.o_ss); t.tile_sub = (const int *)(tb + cm.o_tsub);
+    t.ctab_first = (int *)(tb + cm.o_ctf); t.mtab_first = (int *)(tb + cm.o_mtf); t.cut_first = (int *)(tb + cm.o_cf); t.mend_first = (int *)(tb + cm.o_mf);
+    t.cb = (sa_t *)(tb + cm.o_cb); t.ce = (sa_t *)(tb + cm.o_ce); t.cc = tb + cm.o_cc; t.mb = (sa_t *)(tb + cm.o_mb); t.me = (sa_t *)(tb + cm.o_me);
+    t.cut_lo = (sa_t *)(tb + cm.o_clo); t.cut_hi = (sa_t *)(tb + cm.o_chi); t.mend_pos = (sa_t *)(tb + cm.o_mp);
+    t.child_n = (u32 *)(tb + cm.o_cn); t.child_base = (u32 *)(tb + cm.o_cbase); t.sub_off = (u32 *)(tb + cm.o_suboff); t.expect_total = (u32 *)(tb + cm.o_expect);
+    t.total = (u32 *)(tb + cm.o_total);
+    t.nmatch = (int)a->mb.size();
     RvLabelTabs lt;
-    lt.sub_start = (const int64_t *)(tb + o_ss); lt.nsubs = ns; lt.tile_sub = (const int *)(tb + o_tsub);
-    lt.ctab_first = (const int *)(tb + o_ctf); lt.cbegin = (const sa_t *)(tb + o_cb); lt.cend = (const sa_t *)(tb + o_ce); lt.ccls = tb + o_cc;
-    lt.mtab_first = (const int *)(tb + o_mtf); lt.mbegin = (const sa_t *)(tb + o_mb); lt.mend = (const sa_t *)(tb + o_me); lt.nmatch = (int)a->mb.size();
-    RvSplitArgs sa;
-    u32 *tiles = a->dTile.as<u32>();
-    sa.ntiles = ntiles;
-    sa.tile_cnt = tiles; sa.tile_has = tiles + 3 * ntiles; sa.tile_post = tiles + 6 * ntiles;
-    sa.tile_G = tiles + 9 * ntiles; sa.tile_carry = tiles + 12 * ntiles;
-    sa.total = (u32 *)(tb + o_total);
-    sa.sub_start = lt.sub_start; sa.nsubs = ns; sa.tile_sub = lt.tile_sub;
-    sa.child_base = (const u32 *)(tb + o_cbase); sa.child_n = (const u32 *)(tb + o_cn); sa.sub_off = (const u32 *)(tb + o_suboff); sa.expect_total = (const u32 *)(tb + o_expect);
-    sa.cut_first = (const int *)(tb + o_cf); sa.cut_lo = (const sa_t *)(tb + o_clo); sa.cut_hi = (const sa_t *)(tb + o_chi);
-    sa.mend_first = (const int *)(tb + o_mf); sa.mend_pos = (const sa_t *)(tb + o_mp);
-    sa.mend_all = dc.host_lists ? 1 : 0;
-    sa.SA_out = a->lvSA[nxt].as<sa_t>(); sa.LCP_out = a->lvLCP[nxt].as<lcp_t>(); sa.BWT_out = a->lvBWT[nxt].as<uint8_t>(); sa.SAi = h->dSAi.as<sa_t>();
-    sa.err = a->dErr.as<u32>();      // persistent for the alignment: an early split (rv_decide.hip) runs before this upload exists
+    split_args(h, t, nxt, lt, sa);
+    sa.mend_all = a->dec.host_lists ? 1 : 0;
     // (a level whose split went out behind the picker has its span there: none here, or its bytes would count twice)
-    int id = a->early_done ? -1 : h->prof.begin(q, RV_K_SPLIT, (double)lv.m * (2 * (sizeof(sa_t) + sizeof(lcp_t) + 2)) + (double)m_next * (sizeof(sa_t) + sizeof(lcp_t) + 1));
+    int id = a->early_done ? -1 : h->prof.begin(q, RV_K_SPLIT, (double)lv.m * (2 * (sizeof(sa_t) + sizeof(lcp_t) + 2)) + (double)cm.m_next * (sizeof(sa_t) + sizeof(lcp_t) + 1));
     if (!a->early_done) {     // (otherwise queued behind the picker already, with the same tables built on the device)
-        if (!a->descs.empty()) {      // tile bounds: the level has data-parallel bubble rounds
-            RV_TRY(a->dTmin.reserve((size_t)(lv.m / RV_SPLIT_TILE + 2) * 4));
-            RV_HIP(hipMemsetAsync(a->dTmin.p, 0xFF, (size_t)(lv.m / RV_SPLIT_TILE + 2) * 4, q));
-            sa.tmin_out = a->dTmin.as<u32>();
-        }
+        if (!a->descs.empty()) RV_TRY(tmin_preset(h, sa));      // tile bounds: the level has data-parallel bubble rounds
         RV_TRY(rv_split_launch(h->ws, cur_sa(h), cur_lcp(h), a->dD.as<uint8_t>(), cur_bwt(h), lv.m, lt, sa, (int)a->split_subs.size()));
     }
     h->prof.end(q, id);
@@ -1424,109 +1414,122 @@ int rv_frontier_commit(rv_index *h, int32_t *children) {
         // many short ranges (the deep levels: 10^5 matches of ~100 bases): a wave per range; few long ones: a thread per base, which looks
         // its range up by a binary search over the prefix sums (17 dependent loads per base at 10^5 ranges: 0.2 ms per level at C4)
         if (lt.nmatch > 256 && a->mpre.back() / lt.nmatch <= 512) RV_TRY(rv_lower_ranges_launch(h->ws, h->dT.as<uint8_t>(), lt.mbegin, lt.mend, lt.nmatch));
-        else RV_TRY(rv_lower_launch(h->ws, h->dT.as<uint8_t>(), lt.mbegin, lt.mend, (const int64_t *)(tb + o_mpre), lt.nmatch, a->mpre.back()));
+        else RV_TRY(rv_lower_launch(h->ws, h->dT.as<uint8_t>(), lt.mbegin, lt.mend, (const int64_t *)(tb + cm.o_mpre), lt.nmatch, a->mpre.back()));
     }
+    return 0;
+}
+
+// bubble_sort of the leading children (reveal.c:1250-1252, :666-727)
+static int commit_bubble(rv_index *h, const Commit &cm, const RvSplitArgs &sa) {
+    Align *a = h->al;
+    hipStream_t q = h->ws.stream;
+    uint8_t *tb = a->dTab.as<uint8_t>();
+    const int64_t m_next = cm.m_next;
+    if (a->descs.empty() && a->kids_small.empty() && a->kids_big.empty() && a->kids_lds.empty()) return 0;
+    RvBubbleArgs ba;
+    ba.desc = (const RvBubbleDesc *)(tb + cm.o_desc); ba.woff = (const int64_t *)(tb + cm.o_woff);
+    ba.cnt = (u32 *)(tb + cm.o_bcnt); ba.list = a->dList.as<u32>();
+    RV_TRY(bubble_flags(h, m_next));
+    ba.flag = a->dFlag.as<uint8_t>();
+    ba.SA = sa.SA_out; ba.LCP = sa.LCP_out; ba.BWT = sa.BWT_out; ba.SAi = sa.SAi; ba.cut_lo = sa.cut_lo; ba.cut_hi = sa.cut_hi; ba.err = sa.err;
+    ba.state = (RvBubbleState *)(tb + cm.o_bstate);
+    ba.dbg = nullptr;
+    if (h->ws.opt.level_log) { if (!a->dDbg.p) { RV_TRY(a->dDbg.reserve(64)); RV_HIP(hipMemsetAsync(a->dDbg.p, 0, 64, q)); } ba.dbg = a->dDbg.as<unsigned long long>(); }
+    // the parent level is dead once split has run (at level 0 these are the main SA/LCP/BWT, which the
+    // reference frees at this point, reveal.c:1279-1284): scratch for the grid-wide long moves
+    ba.scrSA = const_cast<sa_t *>(cur_sa(h)); ba.scrLCP = const_cast<lcp_t *>(cur_lcp(h)); ba.scrBWT = const_cast<uint8_t *>(cur_bwt(h));
+    if (!a->descs.empty() && !h->ws.opt.bubble_parent_scratch) {
+        // ... but this level's leaf launch (second stream, ~180 us) still reads them, and waiting for it left the main
+        // stream idle for ~40 us at every level that has both leaf sub-indices and data-parallel rounds: own scratch
+        // (9 B per rank of the next level; RV_BUBBLE_PARENT_SCRATCH=1 = the parent arrays and the wait, as before)
+        RV_TRY(a->scrSA.reserve((size_t)(m_next + 64) * sizeof(sa_t)));
+        RV_TRY(a->scrLCP.reserve((size_t)(m_next + 64) * sizeof(lcp_t)));
+        RV_TRY(a->scrBWT.reserve((size_t)m_next + 64));
+        ba.scrSA = a->scrSA.as<sa_t>(); ba.scrLCP = a->scrLCP.as<lcp_t>(); ba.scrBWT = a->scrBWT.as<uint8_t>();
+    }
+    if (!a->descs.empty()) {
+        const size_t W = (size_t)a->woff.back() + 16, TT = (size_t)a->toff.back() + 16;
+        RV_TRY(a->dPar.reserve(TT * 4 + W * (8 + 7 * 4 + sizeof(sa_t) + 2) + 256));
+        uint8_t *pb = a->dPar.as<uint8_t>();
+        ba.par.toff = (const int64_t *)(tb + cm.o_toff);
+        ba.par.mcnt = (u32 *)(tb + cm.o_mcnt);
+        ba.par.gcount = (u32 *)(tb + cm.o_gcnt);
+        ba.par.glist = (u64 *)pb; pb += W * 8;
+        ba.par.Qs = (sa_t *)pb; pb += W * sizeof(sa_t);
+        ba.par.tmin = a->dTmin.as<u32>(); pb += TT * 4;
+        ba.par.mrank = (u32 *)pb; pb += W * 4;
+        ba.par.msite = (u32 *)pb; pb += W * 4;
+        ba.par.R = (u32 *)pb; pb += W * 4;
+        ba.par.Qsite = (u32 *)pb; pb += W * 4;
+        ba.par.QF = (u32 *)pb; pb += W * 4;
+        ba.par.Qt = (u32 *)pb; pb += W * 4;
+        ba.par.Qlcp = (u32 *)pb; pb += W * 4;
+        ba.par.Qbw = pb; pb += W;
+        ba.par.Qlast = pb;
+        ba.par.tready = nullptr; ba.par.epoch = 0;
+        if (!h->ws.opt.pb_two_pass) {      // (test hook: copy-out + scatter as two kernels through the scratch arrays)
+            const size_t before = a->dPbReady.cap;
+            RV_TRY(a->dPbReady.reserve(TT * 4 + 64));
+            if (a->dPbReady.cap != before) RV_HIP(hipMemsetAsync(a->dPbReady.p, 0, a->dPbReady.cap, q));      // launch numbers start at 1
+            ba.par.tready = a->dPbReady.as<u32>();
+        }
+    }
+    const int id = h->prof.begin(q, RV_K_BUBBLE, 0.0);
+    // Three independent groups of work: children that fit into LDS, children replayed in one workgroup each, and the
+    // data-parallel rounds of the largest ones, which stay on the main stream; each extra group goes to a side stream (bubble_fork).
+    const bool have_kids = !a->kids_small.empty() || !a->kids_big.empty();
+    const int groups = (int)!a->kids_lds.empty() + (int)have_kids + (int)!a->descs.empty();
+    const bool lds_side = !a->kids_lds.empty() && groups > 1;
+    // (two samples, a few hundred children: the fork/join costs what it saves -- measured on C2)
+    const bool kid_side = have_kids && !a->descs.empty() && (a->multi || a->kids_small.size() + a->kids_big.size() > 1024);
+    RV_TRY(bubble_fork(h, groups > 1, lds_side, kid_side));
+    if (!a->kids_lds.empty()) {
+        Workspace lw; lw.stream = lds_side ? a->bub_stream : q;
+        RV_TRY(rv_bubble_children_lds_launch(lw, ba, (const RvBubbleDesc *)(tb + cm.o_kl), cm.lds_count));
+    }
+    if (have_kids) {
+        Workspace lw; lw.stream = kid_side ? a->bub_stream2 : q;
+        RV_TRY(rv_bubble_children_launch(lw, ba, (const RvBubbleDesc *)(tb + cm.o_ks), (int)a->kids_small.size(), (const RvBubbleDesc *)(tb + cm.o_kb), (int)a->kids_big.size()));
+    }
+    bool seq_before = false;      // an earlier round of this level ran the sequential kernels: the tile bounds have to be refreshed
+    for (size_t r = 0; r + 1 < cm.round_first.size(); r++) {
+        const int first = cm.round_first[r], count = cm.round_first[r + 1] - first;
+        ba.par.epoch = ++a->pb_epoch;
+        if (a->pb_epoch == 0xFFFFFFFFu) { a->pb_epoch = 0; RV_HIP(hipMemsetAsync(a->dPbReady.p, 0, a->dPbReady.cap, q)); }
+        RV_TRY(rv_bubble_par_round_launch(h->ws, ba, first, count, a->woff[(size_t)(first + count)] - a->woff[(size_t)first],
+                                          a->toff[(size_t)(first + count)] - a->toff[(size_t)first], seq_before));
+        if (cm.round_seq[r]) { RV_TRY(rv_bubble_seq_launch(h->ws, ba, first, count)); seq_before = true; }
+    }
+    RV_TRY(bubble_join(h, lds_side, kid_side));
+    h->prof.end(q, id);
+    return 0;
+}
+
+int rv_frontier_commit(rv_index *h, int32_t *children) {
+    RV_TRY(need_align(h));
+    Align *a = h->al;
+    RV_HIP(hipSetDevice(h->device));
+    hipStream_t q = h->ws.stream;
+    const double t0 = a->lg_t0 = now_s();
+    const int ns = a->lv.size();
+    if (children) for (int k = 0; k < 3 * ns; k++) children[k] = -1;
+    a->scanned = false;
+    a->nx.clear();
+    if (a->dec.size() == 0) { a->lv.clear(); a->dec.reset(0); return 0; }
+    Commit cm;
+    cm.split_tabs = !a->early_done; cm.lower_tabs = !a->early_bubble;
+    cm.par_min = (h->ws.opt.bubble_par_min >= 0 ? h->ws.opt.bubble_par_min : bubble_par_default(a->multi));
+    cm.nxt = next_buf(a);
+    RV_TRY(commit_tables(h, children, cm));
+    commit_bubble_plan(h, cm);
+    a->lg[0] = now_s() - t0;      // tables built
+    RV_TRY(commit_upload(h, cm));
+    RvSplitArgs sa;
+    RV_TRY(commit_split(h, cm, sa));
     const double t1 = now_s();
     a->lg[2] = t1 - t0;           // label/split/lower enqueued
-
-    // ---- bubble_sort rounds (reveal.c:1250-1252, :666-727) -----------------------------------
-    if (!a->descs.empty() || !a->kids_small.empty() || !a->kids_big.empty() || !a->kids_lds.empty()) {
-        RvBubbleArgs ba;
-        ba.desc = (const RvBubbleDesc *)(tb + o_desc); ba.woff = (const int64_t *)(tb + o_woff);
-        ba.cnt = (u32 *)(tb + o_bcnt); ba.list = a->dList.as<u32>();
-        {   // every bubble kernel leaves the flag bytes it set at zero again: one memset per alignment (and per reallocation) instead of per level
-            const void *before = a->dFlag.p;
-            RV_TRY(a->dFlag.reserve((size_t)m_next + 64));
-            if (!a->flag_clean || a->dFlag.p != before) { RV_HIP(hipMemsetAsync(a->dFlag.p, 0, a->dFlag.cap, q)); a->flag_clean = true; }
-        }
-        ba.flag = a->dFlag.as<uint8_t>();
-        ba.SA = sa.SA_out; ba.LCP = sa.LCP_out; ba.BWT = sa.BWT_out; ba.SAi = sa.SAi; ba.cut_lo = sa.cut_lo; ba.cut_hi = sa.cut_hi; ba.err = sa.err;
-        ba.state = (RvBubbleState *)(tb + o_bstate);
-        ba.dbg = nullptr;
-        if (h->ws.opt.level_log) { if (!a->dDbg.p) { RV_TRY(a->dDbg.reserve(64)); RV_HIP(hipMemsetAsync(a->dDbg.p, 0, 64, q)); } ba.dbg = a->dDbg.as<unsigned long long>(); }
-        // the parent level is dead once split has run (at level 0 these are the main SA/LCP/BWT, which the
-        // reference frees at this point, reveal.c:1279-1284): scratch for the grid-wide long moves
-        ba.scrSA = const_cast<sa_t *>(cur_sa(h)); ba.scrLCP = const_cast<lcp_t *>(cur_lcp(h)); ba.scrBWT = const_cast<uint8_t *>(cur_bwt(h));
-        if (!a->descs.empty() && !h->ws.opt.bubble_parent_scratch) {
-            // ... but this level's leaf launch (second stream, ~180 us) still reads them, and waiting for it left the main
-            // stream idle for ~40 us at every level that has both leaf sub-indices and data-parallel rounds: own scratch
-            // (9 B per rank of the next level; RV_BUBBLE_PARENT_SCRATCH=1 = the parent arrays and the wait, as before)
-            RV_TRY(a->scrSA.reserve((size_t)(m_next + 64) * sizeof(sa_t)));
-            RV_TRY(a->scrLCP.reserve((size_t)(m_next + 64) * sizeof(lcp_t)));
-            RV_TRY(a->scrBWT.reserve((size_t)m_next + 64));
-            ba.scrSA = a->scrSA.as<sa_t>(); ba.scrLCP = a->scrLCP.as<lcp_t>(); ba.scrBWT = a->scrBWT.as<uint8_t>();
-        }
-        if (!a->descs.empty()) {
-            const size_t W = (size_t)a->woff.back() + 16, TT = (size_t)a->toff.back() + 16;
-            RV_TRY(a->dPar.reserve(TT * 4 + W * (8 + 7 * 4 + sizeof(sa_t) + 2) + 256));
-            uint8_t *pb = a->dPar.as<uint8_t>();
-            ba.par.toff = (const int64_t *)(tb + o_toff);
-            ba.par.mcnt = (u32 *)(tb + o_mcnt);
-            ba.par.gcount = (u32 *)(tb + o_gcnt);
-            ba.par.glist = (u64 *)pb; pb += W * 8;
-            ba.par.Qs = (sa_t *)pb; pb += W * sizeof(sa_t);
-            ba.par.tmin = a->dTmin.as<u32>(); pb += TT * 4;
-            ba.par.mrank = (u32 *)pb; pb += W * 4;
-            ba.par.msite = (u32 *)pb; pb += W * 4;
-            ba.par.R = (u32 *)pb; pb += W * 4;
-            ba.par.Qsite = (u32 *)pb; pb += W * 4;
-            ba.par.QF = (u32 *)pb; pb += W * 4;
-            ba.par.Qt = (u32 *)pb; pb += W * 4;
-            ba.par.Qlcp = (u32 *)pb; pb += W * 4;
-            ba.par.Qbw = pb; pb += W;
-            ba.par.Qlast = pb;
-            ba.par.tready = nullptr; ba.par.epoch = 0;
-            if (!h->ws.opt.pb_two_pass) {      // (test hook: copy-out + scatter as two kernels through the scratch arrays)
-                const size_t before = a->dPbReady.cap;
-                RV_TRY(a->dPbReady.reserve(TT * 4 + 64));
-                if (a->dPbReady.cap != before) RV_HIP(hipMemsetAsync(a->dPbReady.p, 0, a->dPbReady.cap, q));      // launch numbers start at 1
-                ba.par.tready = a->dPbReady.as<u32>();
-            }
-        }
-        id = h->prof.begin(q, RV_K_BUBBLE, 0.0);
-        // Three independent groups of work: children that fit into LDS, children replayed in one workgroup each, and the
-        // data-parallel rounds of the largest ones.  A kernel boundary on one stream is a barrier, so each extra group goes
-        // to its own stream (fork / join by events): the level's bubble time is the longest group, not their sum.
-        bool forked = false, forked2 = false;
-        if (!a->bub_stream) {
-            RV_HIP(rv_stream_get(&a->bub_stream));
-            RV_HIP(rv_stream_get(&a->bub_stream2));
-            RV_HIP(hipEventCreateWithFlags(&a->ev_fork, hipEventDisableTiming));
-            RV_HIP(hipEventCreateWithFlags(&a->ev_join, hipEventDisableTiming));
-            RV_HIP(hipEventCreateWithFlags(&a->ev_join2, hipEventDisableTiming));
-        }
-        const bool have_kids = !a->kids_small.empty() || !a->kids_big.empty();
-        const int groups = (int)!a->kids_lds.empty() + (int)have_kids + (int)!a->descs.empty();
-        if (groups > 1) RV_HIP(hipEventRecord(a->ev_fork, q));
-        if (!a->kids_lds.empty()) {
-            const bool side = groups > 1;
-            Workspace lw; lw.stream = side ? a->bub_stream : q;
-            if (side) RV_HIP(hipStreamWaitEvent(a->bub_stream, a->ev_fork, 0));
-            RV_TRY(rv_bubble_children_lds_launch(lw, ba, (const RvBubbleDesc *)(tb + o_kl), lds_count));
-            if (side) { RV_HIP(hipEventRecord(a->ev_join, a->bub_stream)); forked = true; }
-        }
-        if (have_kids) {
-            // (two samples, a few hundred children: the fork/join costs what it saves -- measured on C2)
-            const bool side = !a->descs.empty() && (a->multi || a->kids_small.size() + a->kids_big.size() > 1024);      // the rounds stay on the main stream
-            Workspace lw; lw.stream = side ? a->bub_stream2 : q;
-            if (side) RV_HIP(hipStreamWaitEvent(a->bub_stream2, a->ev_fork, 0));
-            RV_TRY(rv_bubble_children_launch(lw, ba, (const RvBubbleDesc *)(tb + o_ks), (int)a->kids_small.size(), (const RvBubbleDesc *)(tb + o_kb), (int)a->kids_big.size()));
-            if (side) { RV_HIP(hipEventRecord(a->ev_join2, a->bub_stream2)); forked2 = true; }
-        }
-        bool seq_before = false;      // an earlier round of this level ran the sequential kernels: the tile bounds have to be refreshed
-        for (size_t r = 0; r + 1 < round_first.size(); r++) {
-            const int first = round_first[r], count = round_first[r + 1] - first;
-            ba.par.epoch = ++a->pb_epoch;
-            if (a->pb_epoch == 0xFFFFFFFFu) { a->pb_epoch = 0; RV_HIP(hipMemsetAsync(a->dPbReady.p, 0, a->dPbReady.cap, q)); }
-            RV_TRY(rv_bubble_par_round_launch(h->ws, ba, first, count, a->woff[(size_t)(first + count)] - a->woff[(size_t)first],
-                                              a->toff[(size_t)(first + count)] - a->toff[(size_t)first], seq_before));
-            if (round_seq[r]) { RV_TRY(rv_bubble_seq_launch(h->ws, ba, first, count)); seq_before = true; }
-        }
-        if (forked2) RV_HIP(hipStreamWaitEvent(q, a->ev_join2, 0));
-        if (forked) RV_HIP(hipStreamWaitEvent(q, a->ev_join, 0));
-        h->prof.end(q, id);
-    }
-    if (!a->multi && m_next > 1) {
+    RV_TRY(commit_bubble(h, cm, sa));
+    if (!a->multi && cm.m_next > 1) {
         a->d_err = a->dErr.as<u32>();      // pair mode: the next scan's single copy brings the error word along
     } else {
         u32 err = 0;
@@ -1537,7 +1540,7 @@ int rv_frontier_commit(rv_index *h, int32_t *children) {
 
     if (a->level == 0) h->main_arrays_freed = true;      /* reveal.c:1279-1284 */
     a->level++;
-    a->cur = nxt;
+    a->cur = cm.nxt;
     a->cur_dev_ok = a->next_dev_ok; a->early_done = false; a->early_bubble = false;
     std::swap(a->lv, a->nx);
     a->dec.reset(a->lv.size());
@@ -1606,27 +1609,12 @@ static int builtin_setup(rv_index *h, int minl, int minn) {
     a->use_leaf = use_leaf;
     // level 0 of an untraced two-sample run: ship the tables the device-side picker and decisions need (what a commit ships for
     // the levels after it), so the first level takes the same path as the others
-    if (!a->multi && a->full_only && !a->lv.nodes.empty() && a->lv.nodes.size() <= 2 && h->n < ((int64_t)1 << 32)) {
-        sa_t nd[4] = {0, 0, 0, 0};
-        bool ok = true;
-        for (const RvIntv &iv : a->lv.nodes) {
-            if (iv.begin < h->nsep[0]) { if (nd[0] < nd[1]) ok = false; nd[0] = (sa_t)iv.begin; nd[1] = (sa_t)iv.end; }
-            else if (iv.begin > h->nsep[0]) { if (nd[2] < nd[3]) ok = false; nd[2] = (sa_t)iv.begin; nd[3] = (sa_t)iv.end; }
-            else ok = false;
-        }
-        if (ok) {
-            Packer &pk = a->pk;
-            pk.clear();
-            const int64_t ss[2] = {0, h->n};
-            const uint8_t fl[16] = {(uint8_t)((use_leaf && h->n <= RV_LEAF_N) ? 1 : 0)};
-            a->next_tsub.assign((size_t)ceil_div(h->n, RV_SPLIT_TILE), 0);
-            const size_t o1 = pk.add(ss, sizeof ss), o2 = pk.add(nd, sizeof nd), o3 = pk.add(fl, sizeof fl), o4 = pk.addv(a->next_tsub);
-            RV_TRY(a->dTab0.reserve(pk.size() + 64));
-            if (pk.pageable) RV_HIP(hipMemcpyAsync(a->dTab0.p, pk.data(), pk.size(), hipMemcpyHostToDevice, h->ws.stream));
-            else { pk.grow(pk.size() + 16); RV_TRY(rv_h2d_copy(h->ws, pk.data(), a->dTab0.p, pk.size())); }
+    if (!a->multi && a->full_only && h->n < ((int64_t)1 << 32)) {
+        prep_level_tables(h, a->lv, h->n);
+        if (a->next_dev_ok) {
             // (the staging buffer is reused by the first commit, which comes after the host has waited for the first scan's result)
-            const uint8_t *t0b = a->dTab0.as<uint8_t>();
-            a->d_next_ss = (const int64_t *)(t0b + o1); a->d_next_nodes = (const sa_t *)(t0b + o2); a->d_next_flags = t0b + o3; a->d_next_tsub2 = (const int *)(t0b + o4);
+            a->pk.clear();
+            RV_TRY(publish_next_tables(h, a->dTab0, a->lv.nsamples, false));
             a->cur_dev_ok = true;
         }
     }
@@ -1776,18 +1764,10 @@ static int builtin_levels(rv_index *h, int stop_subs) {
             roots.clear();
             for (int s = 0; s < lv0.size(); s++) {
                 if (lv0.n[(size_t)s] > RV_LEAF_N) continue;
-                const int64_t nf = lv0.node_first[(size_t)s], nn = lv0.node_first[(size_t)s + 1] - nf;
-                if (nn < 1 || nn > 2) continue;
+                int64_t ab[4];
+                if (!pair_intervals(h, lv0, s, ab)) continue;
                 RvLeafRoot r; r.off = lv0.off[(size_t)s]; r.n = (int32_t)lv0.n[(size_t)s]; r.depth = lv0.depth[(size_t)s];
-                r.a0 = r.a1 = r.b0 = r.b1 = 0;
-                bool ok = true;
-                for (int64_t k = 0; k < nn && ok; k++) {
-                    const RvIntv iv = lv0.nodes[(size_t)(nf + k)];
-                    if (iv.begin < h->nsep[0]) { if (r.a0 < r.a1) ok = false; r.a0 = iv.begin; r.a1 = iv.end; }
-                    else if (iv.begin > h->nsep[0]) { if (r.b0 < r.b1) ok = false; r.b0 = iv.begin; r.b1 = iv.end; }
-                    else ok = false;
-                }
-                if (!ok) continue;
+                r.a0 = ab[0]; r.a1 = ab[1]; r.b0 = ab[2]; r.b1 = ab[3];
                 a->leaf_done[(size_t)s] = 1;
                 roots.push_back(r);
             }
@@ -2344,19 +2324,9 @@ static int install_frontier(rv_index *h, int level, int nsubs, const int64_t *me
     }
     // what the commit in front of a level ships for it
     prep_level_tables(h, lv, m);
-    Packer &pk = a->pk;
-    pk.clear();
-    const size_t o_ss = pk.addv(a->next_ss), o_want = pk.addv(lv.nsamples);
-    size_t o_tsub = 0, o_nodes = 0, o_flags = 0, o_tsub2 = 0;
-    if (a->multi) o_tsub = pk.addv(a->next_tsub);
-    if (a->next_dev_ok) { o_nodes = pk.addv(a->next_nodes); o_flags = pk.addv(a->next_flags); o_tsub2 = a->multi ? o_tsub : pk.addv(a->next_tsub); }
-    RV_TRY(a->dTab0.reserve(pk.size() + 64));
-    if (pk.pageable) RV_HIP(hipMemcpyAsync(a->dTab0.p, pk.data(), pk.size(), hipMemcpyHostToDevice, q));
-    else { pk.grow(pk.size() + 16); RV_TRY(rv_h2d_copy(h->ws, pk.data(), a->dTab0.p, pk.size())); }
+    a->pk.clear();
+    RV_TRY(publish_next_tables(h, a->dTab0, lv.nsamples, false));
     RV_HIP(hipStreamSynchronize(q));
-    const uint8_t *tb = a->dTab0.as<uint8_t>();
-    a->d_next_ss = (const int64_t *)(tb + o_ss); a->d_next_want = (const int *)(tb + o_want); a->d_next_tsub = (const int *)(tb + o_tsub);
-    a->d_next_nodes = (const sa_t *)(tb + o_nodes); a->d_next_flags = tb + o_flags; a->d_next_tsub2 = (const int *)(tb + o_tsub2);
     a->cur_dev_ok = a->next_dev_ok; a->early_done = false; a->early_bubble = false;
     a->scanned = false; a->d_err = nullptr;
     a->dec.reset(lv.size());
