@@ -111,7 +111,9 @@ int rv_fetch_mums(rv_index *h, uint32_t *l, int64_t *a, int64_t *b, int64_t cap)
 /* getmultimums / getmultimems (reveal.c:436-580 / 292-434) in CSR form, in the
  * reference's emission order; mems!=0 selects getmultimems.  Returns the match
  * count, *members the total member count; rv_fetch_multi copies
- * l[k], n[k], off[k..k+1], so[], pos[]. */
+ * l[k], n[k], off[k..k+1], so[], pos[].  so[] names a sample in 16 bits:
+ * getmultimems takes indices of 2 .. 65536 samples and refuses more (<0,
+ * rv_last_error). */
 int64_t rv_getmultimums(rv_index *h, int minlength, int minn, int mems, int64_t *members);
 int rv_fetch_multi(rv_index *h, uint32_t *l, int32_t *n, int64_t *off, uint16_t *so, int64_t *pos);
 

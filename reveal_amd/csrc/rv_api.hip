@@ -764,8 +764,9 @@ int rv_run_multi_scan(rv_index *h, const sa_t *SA, const lcp_t *LCP, const uint8
     if (ub_out) ub_out->clear();
     if (h->nsamples < 2) { rv_set_error("multi scan needs at least two samples"); return -1; }
     if (mems) {
-        /* reveal.c:292-434, a stack machine per run of LCP values of minl and more (rv_mems.hip).  The sample census of an interval is a 64-bit mask there. */
-        if (h->nsamples > 64) { rv_set_error("getmultimems: more than 64 samples not supported yet"); return -1; }
+        /* reveal.c:292-434, a stack machine per run of LCP values of minl and more (rv_mems.hip).  The sample census of an interval is a bit per sample there,
+           as many words as the index has samples for; the records name a sample in 16 bits, which is the one limit left. */
+        if (h->nsamples > RV_MEMS_MAX_SAMPLES) { rv_set_error("getmultimems: more than 65536 samples (a record names its sample in 16 bits)"); return -1; }
         if (m <= 1) return 0;
         hipStream_t q = h->ws.stream;
         DBuf &brec = h->ws.misc[13], &bso = h->ws.misc[6], &bpos = h->ws.misc[7];

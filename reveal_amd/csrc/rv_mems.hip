@@ -20,7 +20,18 @@
 //                        share an interval's members), started at the run's first rank; counts
 //   exclusive sums of the tiles' counts = where each tile's records and members go
 //   k_mems_runs<true>, k_mems_long<true>   the same again, writing
-// Exact by the same construction as before: tests/test_gpu_align.py getmultimems cases, the golden vectors, random inputs against the oracle.
+// The sample census of an interval (reveal.c:266-277 counts in int flag_so[nsamples]) is a bit per sample, as wide as the index needs.  Which form runs
+// follows from nsamples alone:
+//   a thread        CW = 1, 2 or 4 words of 64 bits in registers (up to 256 samples; the word is selected by an unrolled chain of compile-time
+//                   indices, so the words stay registers).  The forms of 2 and 4 words keep 32 stack entries per word instead of 24 (a run's
+//                   intervals nest deeper the more samples it has) and give a run up after 65 536 member visits.  Beyond 256 samples no thread
+//                   walks: every run is listed for the wavefront machine
+//   a wavefront     up to 64 samples: one ballot per sample and 64 members.  More: a bitmap in LDS; the lane whose atomic OR sets a sample's bit
+//                   is the first to meet that sample, one ballot per 64 members counts those lanes, and the words the interval touched are
+//                   cleared behind it.  The ring keeps the samples in 16 bits then (8 bits up to 64 samples: that form's LDS is what it was)
+// Exact by the same construction as before: tests/test_gpu_align.py getmultimems cases, the golden vectors, random inputs against the oracle;
+// more than 64 samples: tests/test_gpu_mems_wide.py.  Measurements and resource usage of every form: profiles/mems_wide.txt.
+#include <type_traits>
 #include "rv_common.h"
 #include "rv_scan.h"
 
@@ -31,8 +42,11 @@ constexpr int LCP_CHUNK = 2048;      // ranks staged per refill
 constexpr int RING = 2 * LCP_CHUNK;  // SA / sample / BWT of the current and the previous chunk stay in LDS: an interval ends right behind the scan position
 constexpr int ST_LDS = 4096;         // stack entries kept in LDS; deeper ones live in global memory
 constexpr int MR = 32;               // ranks per thread of k_mems_runs
-constexpr int ST_THREAD = 24;        // a thread's stack
+constexpr int ST_THREAD = 24;        // a thread's stack (one census word; 32 per word in the wide forms)
 constexpr int64_t RUN_MAX = 2048;    // ranks a thread follows a run for
+constexpr int64_t WORK_MAX = 32 * RUN_MAX;      // members a thread visits for a run of a wide index (what nests 32 deep over 2048 ranks)
+constexpr int CW_THREAD = 4;         // census words (64 samples each) a thread keeps: beyond, every run goes to the wavefront machine
+constexpr int BM_WORDS = RV_MEMS_MAX_SAMPLES / 32;      // the wavefront machine's census bitmap (32-bit words in LDS): a bit for every sample a record can name
 
 __device__ inline bool is_lower_c(uint8_t c) { return c >= 'a' && c <= 'z'; }
 
@@ -57,20 +71,41 @@ struct MemsArgs {
 
 // ---- a run per thread ----------------------------------------------------------------------------------------------------------------------------
 // the run whose first LCP value of minl and more stands at rank s (members from rank s - 1 on).  WRITE = false: counts its records and members;
-// true: writes them from (nrec, nmem) on.  -> false: too long or too deep for a thread (nothing counted, nothing written)
-template <bool WRITE>
+// true: writes them from (nrec, nmem) on.  -> false: too long or too deep for a thread (nothing counted, nothing written).
+// CW: 64-bit words of the sample census (nsamples <= 64 * CW).  CW > 1 also gives up on a run whose intervals hold more than WORK_MAX members
+// between them: a homopolymer closes an interval per rank, each a rank longer than the one before (one entry on the stack, 2 x 10^6 members in
+// 2048 ranks), and a member costs a binary search over the samples -- seconds in one thread, milliseconds in a wavefront
+template <bool WRITE, int CW>
 __device__ bool run_thread(const MemsArgs &A, int64_t s, unsigned long long &nrec, unsigned long long &nmem) {
-    u32 st_l[ST_THREAD]; int64_t st_b[ST_THREAD];
+    // the stack: 24 entries for one census word, as ever.  The intervals of a run nest as deep as a Cartesian tree over its samples is high (some
+    // 5 ln(nsamples) for samples that drift apart at random places: 25 at 100 samples), so the wide forms keep 32 entries per census word, the left
+    // bounds as 16-bit distances from the run's first member
+    constexpr int ST = CW == 1 ? ST_THREAD : 32 * CW;
+    using lb_t = typename std::conditional<CW == 1, int64_t, uint16_t>::type;
+    const int64_t lb0 = CW == 1 ? 0 : s - 1;
+    u32 st_l[ST]; lb_t st_b[ST];
     int depth = 0;
     const int nsep_n = A.nsamples - 1;
     unsigned long long r0 = nrec, m0 = nmem;
+    [[maybe_unused]] int64_t work = 0;
     auto close = [&](u32 l, int64_t lb, int64_t ub) -> bool {      // reveal.c:323-363 for an interval of minl and more; true = the reference's `continue`
         const int64_t cnt = ub - lb + 1;
         if (cnt < (int64_t)A.minn) return false;
-        u64 seen = 0; bool maximal = false;
+        if constexpr (CW > 1) { work += cnt; if (work > WORK_MAX) return false; }      // (the caller gives up)
+        u64 seen[CW]; bool maximal = false;
+#pragma unroll
+        for (int w = 0; w < CW; w++) seen[w] = 0;
         uint8_t ca = (uint8_t)(A.BWT[lb] & RV_BWT_CHAR);
         for (int64_t j = lb; j <= ub; j++) {
-            if (A.nsamples > 2) seen |= 1ull << sample_of_pos(A.nsep, nsep_n, A.SA[j]);
+            if (A.nsamples > 2) {
+                const int sx = sample_of_pos(A.nsep, nsep_n, A.SA[j]);
+                if constexpr (CW == 1) seen[0] |= 1ull << sx;
+                else {      // (seen[sx >> 6] would put the census into scratch memory: every index is a compile-time one)
+                    const u64 bit = 1ull << (sx & 63); const int wx = sx >> 6;
+#pragma unroll
+                    for (int w = 0; w < CW; w++) seen[w] |= w == wx ? bit : 0ull;
+                }
+            }
             if (j < ub) {
                 const uint8_t cb = (uint8_t)(A.BWT[j + 1] & RV_BWT_CHAR);      // '$' stands for "position 0" (SA == 0)
                 maximal |= (cb == '$') | (ca != cb) | (ca == 'N') | (ca == '$') | is_lower_c(ca);
@@ -78,7 +113,10 @@ __device__ bool run_thread(const MemsArgs &A, int64_t s, unsigned long long &nre
             }
         }
         if (!maximal) return false;
-        const int cc = A.nsamples == 2 ? 1 : __popcll(seen);      // two samples: flag_so[a == b]++ : exactly one counter is positive
+        int cc = __popcll(seen[0]);
+#pragma unroll
+        for (int w = 1; w < CW; w++) cc += __popcll(seen[w]);
+        if (A.nsamples == 2) cc = 1;                               // two samples: flag_so[a == b]++ : exactly one counter is positive
         if (cc < A.minn) return true;
         if (WRITE) {
             if (r0 < A.rec_cap) {
@@ -103,21 +141,29 @@ __device__ bool run_thread(const MemsArgs &A, int64_t s, unsigned long long &nre
         int64_t lb = i - 1;
         while (depth > 0 && v < st_l[depth - 1]) {            // reveal.c:322
             depth--;
-            const u32 i_lcp = st_l[depth]; const int64_t i_lb = st_b[depth];
+            const u32 i_lcp = st_l[depth]; const int64_t i_lb = (int64_t)st_b[depth] + lb0;
             if (close(i_lcp, i_lb, i - 1)) continue;          // the quirk: lb keeps its value
+            if constexpr (CW > 1) if (work > WORK_MAX) return false;
             lb = i_lb;
         }
         if (!open) break;                                     // (everything of minl and more has been popped: v is below all of it)
         if (depth == 0 || v > st_l[depth - 1]) {              // reveal.c:365-389
-            if (depth == ST_THREAD) return false;
-            st_l[depth] = v; st_b[depth] = lb; depth++;
+            if (depth == ST) return false;
+            st_l[depth] = v; st_b[depth] = (lb_t)(lb - lb0); depth++;
         }
     }
     nrec = r0; nmem = m0;
     return true;
 }
 
-template <bool WRITE>
+// CW = 0: more samples than a thread's census holds -- no run is walked here, all of them are listed
+template <bool WRITE, int CW>
+__device__ inline bool run_walk(const MemsArgs &A, int64_t s, unsigned long long &nrec, unsigned long long &nmem) {
+    if constexpr (CW == 0) return false;
+    else return run_thread<WRITE, CW>(A, s, nrec, nmem);
+}
+
+template <bool WRITE, int CW>
 __global__ __launch_bounds__(TB) void k_mems_runs(MemsArgs A) {
     const int64_t t = (int64_t)blockIdx.x * TB + threadIdx.x;
     if (t >= A.ntiles) return;
@@ -137,9 +183,9 @@ __global__ __launch_bounds__(TB) void k_mems_runs(MemsArgs A) {
                     A.long_rec[a] = nrec; A.long_mem[a] = nmem;
                     nrec += cr; nmem += cm;
                 } else {
-                    (void)run_thread<true>(A, i, nrec, nmem);
+                    (void)run_walk<true, CW>(A, i, nrec, nmem);
                 }
-            } else if (!run_thread<false>(A, i, nrec, nmem)) {
+            } else if (!run_walk<false, CW>(A, i, nrec, nmem)) {
                 const u32 x = (u32)atomicAdd(&A.out[3], 1ull);
                 if (x < A.long_cap) A.long_s[x] = i;
             }
@@ -150,15 +196,24 @@ __global__ __launch_bounds__(TB) void k_mems_runs(MemsArgs A) {
 }
 
 // ---- a run per wavefront: the machine of rounds 1-4, started at a run's first rank -------------------------------------------------------------
-template <bool WRITE>
+// WIDE: more than 64 samples (the census is the bitmap s_bm, the ring's samples are 16 bits: 12 KB of LDS on top of the narrow form's)
+template <bool WRITE, bool WIDE>
 __global__ __launch_bounds__(64) void k_mems_long(MemsArgs A) {
+    using so_t = typename std::conditional<WIDE, uint16_t, uint8_t>::type;
     __shared__ u32 s_lcp[LCP_CHUNK];
     __shared__ sa_t r_sa[RING];
-    __shared__ uint8_t r_so[RING], r_bw[RING];
+    __shared__ so_t r_so[RING];
+    __shared__ uint8_t r_bw[RING];
     __shared__ u32 st_lcp[ST_LDS];
     __shared__ int64_t st_lb[ST_LDS];
+    __shared__ u32 s_bm[WIDE ? BM_WORDS : 1];             // bit sx: sample sx is among the members of the interval being closed; all zero between intervals
     const int lane = threadIdx.x;
     const int nsep_n = A.nsamples - 1;
+    const int bmw = (A.nsamples + 31) >> 5;               // the words of s_bm in use
+    if constexpr (WIDE) {
+        for (int w = lane; w < bmw; w += 64) s_bm[w] = 0u;
+        __syncthreads();
+    }
     u32 *const g_lcp = A.g_lcp + (size_t)blockIdx.x * (size_t)A.g_cap;
     int64_t *const g_lb = A.g_lb + (size_t)blockIdx.x * (size_t)A.g_cap;
     for (u32 run = blockIdx.x; run < A.nlong; run += gridDim.x) {
@@ -176,6 +231,7 @@ __global__ __launch_bounds__(64) void k_mems_long(MemsArgs A) {
         if (cnt < (int64_t)A.minn) return false;
         // sample census (reveal.c:266-277) and left-maximality (:279-287), 64 members at a time
         u64 seen = 0; bool maximal = false;               // seen: wave-uniform mask of the samples met so far
+        int cc_w = 0;                                     // WIDE: samples met so far
         const bool in_lds = lb >= win_lo;
         for (int64_t j0 = lb; j0 <= ub; j0 += 64) {
             const int64_t j = j0 + lane;
@@ -188,11 +244,26 @@ __global__ __launch_bounds__(64) void k_mems_long(MemsArgs A) {
                 }
             }
             // one ballot per sample (a cross-lane OR of 64-bit masks is twelve LDS-crossbar shuffles: it was most of the kernel's time)
-            if (A.nsamples > 2)
+            if constexpr (WIDE) {
+                // nsamples ballots per 64 members would be most of the kernel here.  LDS atomics on one word are served one after the other, so of the
+                // lanes that hold a sample exactly one finds its bit clear: the first to meet it in this interval
+                bool first = false;
+                if (my >= 0) first = ((atomicOr(&s_bm[my >> 5], 1u << (my & 31)) >> (my & 31)) & 1u) == 0u;
+                cc_w += __popcll(__ballot(first));
+            } else if (A.nsamples > 2)
                 for (int sx = 0; sx < A.nsamples; sx++) if (__ballot(my == sx)) seen |= 1ull << sx;
         }
+        if constexpr (WIDE) {
+            // the bitmap is empty again before the next interval: the words this one touched, or all of them where that is fewer stores
+            // (one wavefront: its LDS accesses are served in program order)
+            if (in_lds && cnt < (int64_t)bmw) {
+                for (int64_t j = lb + lane; j <= ub; j += 64) s_bm[r_so[j & (RING - 1)] >> 5] = 0u;
+            } else {
+                for (int w = lane; w < bmw; w += 64) s_bm[w] = 0u;
+            }
+        }
         if (!__any(maximal)) return false;
-        const int cc = A.nsamples == 2 ? 1 : __popcll(seen);      // two samples: flag_so[a == b]++ : exactly one counter is positive
+        const int cc = WIDE ? cc_w : A.nsamples == 2 ? 1 : __popcll(seen);      // two samples: flag_so[a == b]++ : exactly one counter is positive
         if (cc < A.minn) return true;
         if (WRITE) {
             if (nrec < A.rec_cap && lane == 0) { A.rec_l[nrec] = l; A.rec_c[nrec] = cc; A.rec_first[nrec] = (int64_t)nmem; }
@@ -237,7 +308,7 @@ __global__ __launch_bounds__(64) void k_mems_long(MemsArgs A) {
                 const sa_t p = A.SA[r];
                 s_lcp[k] = (u32)A.LCP[r];
                 r_sa[r & (RING - 1)] = p; r_bw[r & (RING - 1)] = A.BWT[r] & RV_BWT_CHAR;
-                r_so[r & (RING - 1)] = (uint8_t)(A.nsamples > 2 ? sample_of_pos(A.nsep, nsep_n, p) : (p > sep0 ? 1 : 0));
+                r_so[r & (RING - 1)] = (so_t)(A.nsamples > 2 ? sample_of_pos(A.nsep, nsep_n, p) : (p > sep0 ? 1 : 0));
             } else s_lcp[k] = 0u;
         }
         __syncthreads();
@@ -299,6 +370,22 @@ int rv_multimems_launch(Workspace &ws, const sa_t *SA, const lcp_t *LCP, const u
     A.rec_l = rec_l; A.rec_c = rec_c; A.rec_first = rec_first; A.so = so; A.pos = pos;
     A.rec_cap = rec_cap; A.mem_cap = mem_cap; A.out = out;
     A.ntiles = ceil_div(n, MR);
+    if (nsamples > RV_MEMS_MAX_SAMPLES) { rv_set_error("getmultimems: more samples than a record's 16-bit sample field names"); return -1; }      // (s_bm holds no more)
+    // which forms run follows from the number of samples: census words of a thread (0 = none walks), bitmap or ballots for a wavefront
+    const int cw = nsamples <= 64 ? 1 : nsamples <= 128 ? 2 : nsamples <= 64 * CW_THREAD ? 4 : 0;
+    const bool wide = nsamples > 64;
+    auto launch_runs = [&](bool write, unsigned grid) {
+#define RV_MEMS_RUNS(W, C) hipLaunchKernelGGL((k_mems_runs<W, C>), dim3(grid), dim3(TB), 0, q, A)
+        if (write) { if (cw == 1) RV_MEMS_RUNS(true, 1); else if (cw == 2) RV_MEMS_RUNS(true, 2); else if (cw == 4) RV_MEMS_RUNS(true, 4); else RV_MEMS_RUNS(true, 0); }
+        else { if (cw == 1) RV_MEMS_RUNS(false, 1); else if (cw == 2) RV_MEMS_RUNS(false, 2); else if (cw == 4) RV_MEMS_RUNS(false, 4); else RV_MEMS_RUNS(false, 0); }
+#undef RV_MEMS_RUNS
+    };
+    auto launch_long = [&](bool write, unsigned lgrid) {
+#define RV_MEMS_LONG(W, X) hipLaunchKernelGGL((k_mems_long<W, X>), dim3(lgrid), dim3(64), 0, q, A)
+        if (write) { if (wide) RV_MEMS_LONG(true, true); else RV_MEMS_LONG(true, false); }
+        else { if (wide) RV_MEMS_LONG(false, true); else RV_MEMS_LONG(false, false); }
+#undef RV_MEMS_LONG
+    };
     DBuf &btile = ws.misc[16], &blong = ws.misc[17], &bst = ws.misc[11];
     RV_TRY(btile.reserve((size_t)(A.ntiles + 1) * 16 + 64));
     A.tile_rec = btile.as<u64>(); A.tile_mem = A.tile_rec + (A.ntiles + 1);
@@ -314,7 +401,7 @@ int rv_multimems_launch(Workspace &ws, const sa_t *SA, const lcp_t *LCP, const u
         A.long_s = blong.as<int64_t>(); A.long_rec = (u64 *)(A.long_s + A.long_cap); A.long_mem = A.long_rec + A.long_cap;
         RV_HIP(hipMemsetAsync(out, 0, 32, q));
         RV_HIP(hipMemsetAsync(A.tile_rec + A.ntiles, 0, 8, q)); RV_HIP(hipMemsetAsync(A.tile_mem + A.ntiles, 0, 8, q));
-        hipLaunchKernelGGL(k_mems_runs<false>, dim3(grid), dim3(TB), 0, q, A);
+        launch_runs(false, grid);
         RV_LAUNCH_CHECK();
         RV_TRY(rv_read_back(ws, res, out, sizeof res));
         if (res[3] <= A.long_cap) break;
@@ -333,7 +420,7 @@ int rv_multimems_launch(Workspace &ws, const sa_t *SA, const lcp_t *LCP, const u
         lgrid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(A.nlong, 1024), ((int64_t)1 << 24) / A.g_cap));
         RV_TRY(bst.reserve((size_t)lgrid * (size_t)A.g_cap * 12 + 64));
         A.g_lb = bst.as<int64_t>(); A.g_lcp = (u32 *)(A.g_lb + (size_t)lgrid * (size_t)A.g_cap);
-        hipLaunchKernelGGL(k_mems_long<false>, dim3(lgrid), dim3(64), 0, q, A);
+        launch_long(false, lgrid);
         RV_LAUNCH_CHECK();
         hipLaunchKernelGGL(k_mems_add_long, dim3((unsigned)ceil_div((int64_t)A.nlong, TB)), dim3(TB), 0, q, A);
         RV_LAUNCH_CHECK();
@@ -345,10 +432,10 @@ int rv_multimems_launch(Workspace &ws, const sa_t *SA, const lcp_t *LCP, const u
     RV_TRY(rv_read_back(ws, res, out, 24));
     if (res[2]) return 0;                                             // (the caller reports it)
     if (res[0] > rec_cap || res[1] > mem_cap) return 0;               // (the caller grows its arrays and comes again)
-    hipLaunchKernelGGL(k_mems_runs<true>, dim3(grid), dim3(TB), 0, q, A);
+    launch_runs(true, grid);
     RV_LAUNCH_CHECK();
     if (A.nlong) {
-        hipLaunchKernelGGL(k_mems_long<true>, dim3(lgrid), dim3(64), 0, q, A);
+        launch_long(true, lgrid);
         RV_LAUNCH_CHECK();
     }
     return 0;

@@ -46,7 +46,9 @@ int rv_scan_multi_launch(Workspace &ws, const sa_t *SA, const lcp_t *LCP, int64_
                          int minl, int minn, RvMultiRec *rec, uint16_t *so, sa_t *pos, u32 rec_cap, u32 mem_cap, u32 *counters, uint4 *tiletab,
                          const int64_t *sub_start, const int *sub_want, int nsubs);   // sub_want != NULL: keep only matches with n == sub_want[sub of ub]
 
-// getmultimems (reveal.c:292-434) replayed by one wavefront (rv_mems.hip); counts beyond the capacities are still counted
+// getmultimems (reveal.c:292-434), a stack machine per run of LCP values of minl and more (rv_mems.hip); counts beyond the capacities are still counted.
+// Any number of samples a record's 16-bit sample field can name
+#define RV_MEMS_MAX_SAMPLES 65536
 int rv_multimems_launch(Workspace &ws, const sa_t *SA, const lcp_t *LCP, const uint8_t *BWT, int64_t n, const sa_t *nsep, int nsamples, int minl, int minn,
                         u32 maxlcp, u32 *rec_l, int32_t *rec_c, int64_t *rec_first, uint16_t *so, sa_t *pos,
                         unsigned long long rec_cap, unsigned long long mem_cap, unsigned long long *out);
