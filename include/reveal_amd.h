@@ -450,6 +450,39 @@ int rv_batch_add(rv_batch *b, rv_index *h);
 int rv_batch_run(rv_batch *b, int minl, int minn, int construct, rv_align_stats *stats, int *status);
 int rv_batch_info(const rv_batch *b, int64_t *out);      /* out[0] = joint level loops run so far, out[1] = jobs they served */
 void rv_batch_free(rv_batch *b);
+/* ---- many small alignments in one call ------------------------------------------------------------------------------------------------------------
+ * `reveal refine --method reveal_rem` calls the recursion once per bubble (reveal/refine.py:220-229): 10^4 .. 10^6 inputs of a few bases up to 10 kbp,
+ * each of which pays for a construct() and a level loop when it goes through a handle of its own.  Here the jobs of a call share their launches: the
+ * pair jobs of at most 2048 ranks (la + lb + 2) are laid out as ONE text (every first sequence, then every second one), their SA / LCP / BWT segments
+ * are built by one kernel per size class with the job's text in LDS (rv_many.hip), and the segments finish as a frontier of J roots in one launch of the
+ * leaf kernel.  Every other job -- more than two sequences (each a sample of its own), more than 2048 ranks -- runs the ordinary way inside the same
+ * call (construct + rv_align_builtin on one internal handle, rv_reset in between).  The built-in picker only (as rv_align_builtin).  A job's result is
+ * what rv_align_builtin gives a stand-alone index of its sequences, in that index' coordinates (text `s0$s1$..`).
+ *   rv_many_add     a job of k >= 2 non-empty sequences -> its id (0, 1, ..), < 0 on error (an empty sequence, k < 2, non-ASCII bytes)
+ *   rv_many_clear   forgets the jobs and results, keeps every allocation for the next batch
+ *   rv_many_run     runs every job; *total (may be NULL) = the sums of the runs' statistics.  A text beyond the 32-bit library's position limit (or
+ *                   RV_MANY_ROUND positions) is split into several rounds
+ *   rv_many_anchor_count -> anchors of all jobs; first[0 .. jobs] (may be NULL): job j owns the anchors first[j] .. first[j+1]; *members: all positions
+ *   rv_many_fetch   l[k], off[k .. k+1] -> pos[]: the layout and member order of rv_fetch_anchors
+ *   rv_many_text    the job's text after the run (lower-cased where aligned): sum of lengths + k bytes; returns that count
+ *   rv_many_info    out[0] jobs, out[1] jobs built and finished by the shared launches, out[2] jobs through the ordinary path, out[3] rounds,
+ *                   out[4] kernel launches of the shared part of the last run (index build, leaf kernel, lower-casing; copies not counted)
+ *   rv_many_option  RV_MANY_KEEP (test hook: keep SA / LCP of the shared-launch jobs for rv_many_arrays), RV_MANY_ROUND (positions per round),
+ *                   RV_MANY_WAVE_MAX (ranks up to which a wavefront builds a job, at most 512; above: a workgroup); any other name: rv_set_option on
+ *                   the internal handles
+ *   rv_many_arrays  test hook: which = RV_SA / RV_LCP of a shared-launch job in job-local positions, native element width; -2: not kept */
+typedef struct rv_many rv_many;
+rv_many *rv_many_new(int device);       /* NULL on failure */
+void rv_many_free(rv_many *m);
+int rv_many_option(rv_many *m, const char *name, int64_t value);
+int64_t rv_many_add(rv_many *m, const char *const *seqs, const int64_t *lens, int k);
+int rv_many_clear(rv_many *m);
+int rv_many_run(rv_many *m, int minl, int minn, rv_align_stats *total);
+int64_t rv_many_anchor_count(rv_many *m, int64_t *first, int64_t *members);
+int rv_many_fetch(rv_many *m, uint32_t *l, int64_t *off, int64_t *pos);
+int64_t rv_many_text(rv_many *m, int64_t job, char *out, int64_t cap);
+int rv_many_info(const rv_many *m, int64_t *out);
+int64_t rv_many_arrays(rv_many *m, int64_t job, int which, void *out, int64_t cap);
 /* ---- device memory for the frontier hand-off between processes ("child SA/LCP shipped once to the owner GPU, peer copy over
  * xGMI") -- what reveal_amd/shard.py's own transport uses instead of a tensor library: the owner packs the segments it hands out into buffers of its
  * device (rv_frontier_pack, on_device = 1) and exports them once (hipIpcGetMemHandle: 64 bytes that travel over any byte channel); a worker process

@@ -158,6 +158,17 @@ SYMBOLS = {
     "rv_graph_prune": (_I, [V, V]),
     "rv_graph_gfa": (_L, [V, V, _I, V, V, V]),
     "rv_graph_free": (None, [V]),
+    "rv_many_new": (V, [_I]),
+    "rv_many_free": (None, [V]),
+    "rv_many_option": (_I, [V, ctypes.c_char_p, _L]),
+    "rv_many_add": (_L, [V, V, V, _I]),
+    "rv_many_clear": (_I, [V]),
+    "rv_many_run": (_I, [V, _I, _I, ctypes.POINTER(RvAlignStats)]),
+    "rv_many_anchor_count": (_L, [V, V, c_i64p]),
+    "rv_many_fetch": (_I, [V, V, V, V]),
+    "rv_many_text": (_L, [V, _L, V, _L]),
+    "rv_many_info": (_I, [V, V]),
+    "rv_many_arrays": (_L, [V, _L, _I, V, _L]),
     "rv_test_exclusive_sum_u32": (_I, [V, V, _L]),
     "rv_test_inclusive_max_u32": (_I, [V, V, _L]),
     "rv_test_radix_sort": (_I, [V, V, _L, _I, _I]),

@@ -1,0 +1,570 @@
+// rv_many.hip -- many small pair alignments in one call (include/reveal_amd.h "many small alignments").
+//
+// `reveal refine --method reveal_rem` calls the recursion once per bubble (reveal/refine.py:220-229): 10^4 - 10^6 inputs of a few
+// bases up to 10 kbp.  Through a handle each of them pays for a construct() and a level loop -- dozens of launches and several
+// stream waits, whatever its size.  Here the pair jobs of at most RV_LEAF_N ranks share their launches:
+//   text     all first sequences, then all second sequences (a_0$a_1$..a_J-1$b_0$..b_J-1$): ONE nsep[0] separates the two samples
+//            of every job, so the leaf kernel, pair_intervals and the lower-casing work on it unchanged
+//   build    k_many_build: SA, LCP and the BWT byte of every job from a job-local copy of its text `a$b$` in LDS
+//   finish   the segments become a level-0 frontier of J roots of a handle that was never constructed (rv_frontier_import);
+//            every root is leaf-sized, so rv_align_builtin_resume is ONE leaf launch
+// Jobs the shared launches do not take (more than two sequences, more than RV_LEAF_N ranks) run the ordinary way -- construct() +
+// rv_align_builtin -- on one internal handle reused with rv_reset.
+//
+// k_many_build, per job (n = la + lb + 2 <= 2048 ranks, local positions in 16 bits):
+//   order    prefix doubling: first key = six text bytes (past the end: 0, so a suffix that is a prefix of another sorts first and
+//            suffixes that tie through a '$' come out in the stand-alone order), then keys (rank[i], rank[i + h]), h = 6, 12, 24 ..
+//            until every rank is its own; each round is one bitonic sort of (key << 16 | position) words in LDS -- alleles of one
+//            bubble tie for hundreds of characters, homopolymers within a sequence: <= 10 rounds at 2048 ranks
+//   LCP      text order with Kasai's carry (interface.c:97-114: stops at '$' / 'N'), eight bytes per step; a thread takes
+//            consecutive text positions, so its work is its share plus one LCP value, not share x LCP
+//   BWT      the character in front ('$' for local position 0), RV_BWT_SIDE for the suffixes of the second sequence
+// Size classes (DESIGN.md "Many small alignments" has the measurements): up to `wave_max` ranks (default 512) a wavefront per job,
+// four jobs per workgroup, no workgroup barrier; above, a workgroup of 256 threads per job.  Both hold 22.6 KB of LDS per workgroup:
+// seven workgroups per CU.
+#include "rv_index.h"
+#include "rv_leaf.h"
+#include <algorithm>
+#include <limits.h>
+#include <new>
+#include <stdexcept>
+
+namespace {
+
+constexpr int MT = 256;                    // threads per workgroup
+constexpr int CAP_L = RV_LEAF_N;           // ranks of the largest job a workgroup builds
+constexpr int CAP_S = 512;                 // ... a wavefront builds
+static_assert(CAP_L <= 2048, "local ranks are packed in 12 bits, positions in 16");
+
+struct ManyDevJob { int64_t abeg, bbeg, off; int32_t la, lb; };      // where the two sequences begin in the shared text, first rank of the segment
+
+#define MANY_WSYNC() do { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); __builtin_amdgcn_wave_barrier(); } while (0)
+
+__device__ inline u32 many_wave_incl_max(u32 v) {
+    const int lane = threadIdx.x & 63;
+#define MANY_STEP_(CTRL, RM, TAKE) { const u32 o = rv_dpp_u32<CTRL, RM>(v); v = ((TAKE) && o > v) ? o : v; }
+    RV_WAVE_SCAN_STEPS(MANY_STEP_)
+#undef MANY_STEP_
+    return v;
+}
+__device__ inline u32 many_lane_below(u32 x) { return (u32)__builtin_amdgcn_update_dpp(0, (int)x, 0x138 /* wave_shr:1 */, 0xf, 0xf, false); }
+// bit 7 of every byte of v that is zero (exact for the lowest such byte)
+__device__ inline u64 many_zero_bytes(u64 v) { return (v - 0x0101010101010101ull) & ~v & 0x8080808080808080ull; }
+
+// TPJ threads per job (64: a wavefront, synchronised by wave barriers; 256: the workgroup), CAP ranks at most
+template <int CAP, int TPJ>
+__global__ __launch_bounds__(MT) void k_many_build(const ManyDevJob *__restrict__ jobs, int njobs, const uint8_t *__restrict__ T, sa_t *__restrict__ SA,
+                                                   lcp_t *__restrict__ LCP, uint8_t *__restrict__ BWT, u32 *__restrict__ d_maxlcp, u32 *__restrict__ d_err) {
+    constexpr int JPB = MT / TPJ;          // jobs per workgroup
+    constexpr int PER = CAP / TPJ;         // consecutive ranks a thread names
+    __shared__ __attribute__((aligned(16))) u64 s_key[JPB][CAP];
+    __shared__ __attribute__((aligned(16))) uint8_t s_txt[JPB][CAP + 16];
+    __shared__ uint16_t s_rank[JPB][CAP];
+    __shared__ u32 s_part[JPB][4];
+    __shared__ int s_tied[JPB];
+    const int slot = (int)threadIdx.x / TPJ, t = (int)threadIdx.x % TPJ;
+    const int jn = (int)blockIdx.x * JPB + slot;
+    if (jn >= njobs) return;               // (a whole wavefront of the last workgroup; TPJ == 256: the grid is the job count)
+    const ManyDevJob J = jobs[jn];
+    const int la = J.la, n = J.la + J.lb + 2;
+    if (n > CAP || J.la < 1 || J.lb < 1) { if (t == 0) atomicOr(d_err, 1u); return; }
+    u64 *key = s_key[slot];
+    uint8_t *txt = s_txt[slot];
+    uint16_t *rank = s_rank[slot];
+#define MANY_SYNC() do { if (TPJ == 64) MANY_WSYNC(); else __syncthreads(); } while (0)
+    int N2 = 2;
+    while (N2 < n) N2 <<= 1;               // size of the sorting network (<= CAP)
+
+    for (int k = t; k < n + 16; k += TPJ) txt[k] = k <= la ? T[J.abeg + k] : (k < n ? T[J.bbeg + (k - la - 1)] : (uint8_t)0);
+    MANY_SYNC();
+    for (int p = t; p < N2; p += TPJ) {
+        u64 k = ~0ull;                     // (padding of the network: behind every suffix)
+        if (p < n) {
+            k = 0;
+#pragma unroll
+            for (int b = 0; b < 6; b++) k = (k << 8) | txt[p + b];
+            k = (k << 16) | (u64)p;
+        }
+        key[p] = k;
+    }
+    const int c = (N2 + TPJ - 1) / TPJ;    // ranks per thread when the order is read (<= PER)
+    int h = 6;
+    for (int round = 0;; round++) {
+        MANY_SYNC();
+        if (t == 0) s_tied[slot] = 0;
+        for (int k = 2; k <= N2; k <<= 1) {
+            for (int jj = k >> 1; jj > 0; jj >>= 1) {
+                for (int p = t; p < (N2 >> 1); p += TPJ) {
+                    const int i = ((p & ~(jj - 1)) << 1) | (p & (jj - 1)), q = i | jj;
+                    const u64 a = key[i], b = key[q];
+                    if ((a > b) == ((i & k) == 0)) { key[i] = b; key[q] = a; }
+                }
+                MANY_SYNC();
+            }
+        }
+        // a suffix' new rank = 1 + the first position of its run of equal keys: inclusive maximum over the run heads
+        u64 kv[PER];
+        u32 mine = 0; bool tie = false;
+        const int p0 = t * c;
+#pragma unroll
+        for (int e = 0; e < PER; e++) {
+            const int p = p0 + e;
+            kv[e] = 0;
+            if (e < c && p < n) {
+                kv[e] = key[p];
+                const bool head = p == 0 || (key[p - 1] >> 16) != (kv[e] >> 16);
+                if (head) mine = (u32)p + 1; else tie = true;
+            }
+        }
+        const u32 inc = many_wave_incl_max(mine);
+        u32 run = many_lane_below(inc);
+        if (TPJ > 64) {
+            const int wv = t >> 6;
+            if ((t & 63) == 63) s_part[slot][wv] = inc;
+            __syncthreads();
+            for (int w = 0; w < wv; w++) { const u32 o = s_part[slot][w]; run = o > run ? o : run; }
+        }
+#pragma unroll
+        for (int e = 0; e < PER; e++) {
+            const int p = p0 + e;
+            if (e < c && p < n) {
+                if (p == 0 || (key[p - 1] >> 16) != (kv[e] >> 16)) run = (u32)p + 1;
+                rank[(int)(kv[e] & 0xFFFFu)] = (uint16_t)run;
+            }
+        }
+        if (tie) s_tied[slot] = 1;
+        MANY_SYNC();
+        if (!s_tied[slot]) break;
+        if (round >= 16) { if (t == 0) atomicOr(d_err, 2u); return; }      // (cannot happen: h passes n after eleven rounds; a job is left by all its threads)
+        for (int p = t; p < n; p += TPJ) {      // (every thread read the order in front of the barrier above)
+            const u32 r1 = rank[p], r2 = p + h < n ? rank[p + h] : 0u;
+            key[p] = ((u64)((r1 << 12) | r2) << 16) | (u64)p;
+        }
+        h <<= 1;
+    }
+    // the order is final: rank[i] - 1 is the inverse.  SA and LCP in 16 bits over the sort's words
+    uint16_t *sa16 = (uint16_t *)key, *lcp16 = sa16 + CAP;
+    {
+        uint16_t mine16[PER];
+#pragma unroll
+        for (int e = 0; e < PER; e++) { const int p = t + e * TPJ; mine16[e] = p < n ? (uint16_t)(key[p] & 0xFFFFu) : (uint16_t)0; }
+        MANY_SYNC();
+#pragma unroll
+        for (int e = 0; e < PER; e++) { const int p = t + e * TPJ; if (p < n) sa16[p] = mine16[e]; }
+        MANY_SYNC();
+    }
+    u32 lmax = 0;
+    {
+        const int c2 = (n + TPJ - 1) / TPJ;
+        int hh = 0;
+        for (int i = t * c2; i < (t + 1) * c2 && i < n; i++) {
+            const int k = (int)rank[i] - 1;
+            if (k > 0) {
+                const int j = sa16[k - 1];
+                for (;;) {
+                    u64 a, b;
+                    __builtin_memcpy(&a, txt + i + hh, 8);
+                    __builtin_memcpy(&b, txt + j + hh, 8);
+                    const u64 x = a ^ b, z = many_zero_bytes(a ^ 0x2424242424242424ull) | many_zero_bytes(a ^ 0x4E4E4E4E4E4E4E4Eull);      // '$', 'N'
+                    const int m = x ? (int)(__builtin_ctzll(x) >> 3) : 8, s = z ? (int)(__builtin_ctzll(z) >> 3) : 8;
+                    const int step = m < s ? m : s;
+                    hh += step;
+                    if (step < 8) break;   // (the text ends with '$': no comparison runs past it)
+                }
+                lcp16[k] = (uint16_t)hh;
+                if ((u32)hh > lmax) lmax = (u32)hh;
+            } else lcp16[0] = 0;
+            if (hh > 0) hh--;
+        }
+    }
+    MANY_SYNC();
+    for (int p = t; p < n; p += TPJ) {
+        const int i = sa16[p];
+        SA[J.off + p] = (sa_t)(i <= la ? J.abeg + i : J.bbeg + (i - la - 1));
+        LCP[J.off + p] = (lcp_t)lcp16[p];
+        BWT[J.off + p] = (uint8_t)((i > 0 ? txt[i - 1] : (uint8_t)'$') | (i > la ? RV_BWT_SIDE : 0u));
+    }
+    lmax = (u32)rv_wave_max_u64((u64)lmax);
+    if ((threadIdx.x & 63) == 0 && lmax > __atomic_load_n(d_maxlcp, __ATOMIC_RELAXED)) atomicMax(d_maxlcp, lmax);
+#undef MANY_SYNC
+}
+
+struct ManyJob {
+    int k = 0;                             // sequences
+    size_t seq0 = 0;                       // first entry in lens / starts
+    int64_t ranks = 0;                     // sum of lengths + k
+    bool clean = true;                     // no NUL byte (the past-the-end character of the build)
+    bool shared = false;
+    int64_t text_off = 0;                  // final text in out_text (ranks bytes)
+    int64_t arr_off = -1;                  // RV_MANY_KEEP: SA / LCP in keep_sa / keep_lcp
+};
+struct ManyRec { int job; u32 l; int np; int64_t p0; };
+
+}  // namespace
+
+struct rv_many {
+    int device = 0;
+    rv_index *hs = nullptr, *ho = nullptr;      // the shared launches' handle (never constructed), the ordinary path's
+    std::vector<char> in;                       // the jobs' sequences back to back
+    std::vector<int64_t> lens, starts;
+    std::vector<ManyJob> jobs;
+    int64_t keep = 0, round_max = (int64_t)1 << 27, wave_max = CAP_S;
+    std::vector<std::pair<std::string, int64_t>> fwd;      // switches for the internal handles
+    // results of the last run
+    bool ran = false;
+    std::vector<int64_t> an_first, an_off, an_pos;
+    std::vector<u32> an_l;
+    std::vector<char> out_text;
+    std::vector<sa_t> keep_sa; std::vector<lcp_t> keep_lcp;
+    int64_t info[5] = {0, 0, 0, 0, 0};
+    DBuf dJobs, dSA, dLCP, dBWT, dCnt;
+    // scratch of a run
+    std::vector<ManyRec> recs; std::vector<int64_t> rpos;
+};
+
+namespace {
+
+int many_handle(rv_many *m, rv_index **h) {
+    if (*h) return 0;
+    *h = rv_new(m->device);
+    if (!*h) return -1;
+    for (auto &o : m->fwd) RV_TRY(rv_set_option(*h, o.first.c_str(), o.second));
+    return 0;
+}
+
+// anchors of the handle's last run -> records of `job`, or (job < 0) of the job whose first sequence holds the first member
+int many_collect(rv_many *m, rv_index *h, int job, const std::vector<int> &order, const std::vector<int64_t> &abeg, const std::vector<int64_t> &bbeg) {
+    int64_t members = 0;
+    const int64_t na = rv_anchor_count(h, &members);
+    if (na < 0) return -1;
+    std::vector<u32> l((size_t)std::max<int64_t>(na, 1));
+    std::vector<int64_t> off((size_t)na + 1, 0), pos((size_t)std::max<int64_t>(members, 1));
+    RV_TRY(rv_fetch_anchors(h, l.data(), off.data(), pos.data()));
+    for (int64_t k = 0; k < na; k++) {
+        ManyRec r; r.l = l[(size_t)k]; r.np = (int)(off[(size_t)k + 1] - off[(size_t)k]); r.p0 = (int64_t)m->rpos.size(); r.job = job;
+        const int64_t *p = pos.data() + off[(size_t)k];
+        if (job >= 0) {
+            for (int q = 0; q < r.np; q++) m->rpos.push_back(p[q]);
+        } else {
+            if (r.np != 2) { rv_set_error("rv_many_run: an anchor of %d members in a pair job", r.np); return -1; }
+            const size_t s = (size_t)(std::upper_bound(abeg.begin(), abeg.end(), p[0]) - abeg.begin()) - 1;
+            if (s >= order.size()) { rv_set_error("rv_many_run: an anchor outside the text"); return -1; }
+            const ManyJob &jb = m->jobs[(size_t)order[s]];
+            const int64_t la = m->lens[jb.seq0], lb = m->lens[jb.seq0 + 1];
+            const int64_t a = p[0] - abeg[s], b = p[1] - bbeg[s];
+            if (a < 0 || a + r.l > la || b < 0 || b + r.l > lb) { rv_set_error("rv_many_run: an anchor outside its job"); return -1; }
+            r.job = order[s];
+            m->rpos.push_back(a); m->rpos.push_back(b + la + 1);      // stand-alone coordinates of `a$b$`
+        }
+        m->recs.push_back(r);
+    }
+    return 0;
+}
+
+void many_add_stats(rv_align_stats *t, const rv_align_stats &s) {
+    if (!t) return;
+    t->steps += s.steps; t->splits += s.splits; t->anchored_bp += s.anchored_bp; t->levels += s.levels;
+    if (s.maxdepth > t->maxdepth) t->maxdepth = s.maxdepth;
+    t->scanned_ranks += s.scanned_ranks; t->t_scan += s.t_scan; t->t_host += s.t_host; t->t_split += s.t_split; t->t_bubble += s.t_bubble;
+}
+
+// one round of the shared launches: the jobs order[lo .. hi) (ascending size)
+int many_round(rv_many *m, const std::vector<int> &order, size_t lo, size_t hi, int minl, int minn, rv_align_stats *total) {
+    RV_TRY(many_handle(m, &m->hs));
+    rv_index *h = m->hs;
+    const size_t J = hi - lo;
+    RV_TRY(rv_reset(h));
+    // text: every first sequence, then every second one
+    std::vector<int> ord(order.begin() + (ptrdiff_t)lo, order.begin() + (ptrdiff_t)hi);
+    std::vector<int64_t> abeg(J), bbeg(J), la(J), lb(J);
+    int64_t ta = 0, tb = 0;
+    for (size_t s = 0; s < J; s++) {
+        const ManyJob &jb = m->jobs[(size_t)ord[s]];
+        la[s] = m->lens[jb.seq0]; lb[s] = m->lens[jb.seq0 + 1];
+        abeg[s] = ta; ta += la[s] + 1; bbeg[s] = tb; tb += lb[s] + 1;
+    }
+    std::vector<char> buf((size_t)std::max(ta, tb));
+    for (int side = 0; side < 2; side++) {
+        int64_t at = 0;
+        for (size_t s = 0; s < J; s++) {
+            const ManyJob &jb = m->jobs[(size_t)ord[s]];
+            const int64_t len = m->lens[jb.seq0 + (size_t)side];
+            memcpy(buf.data() + at, m->in.data() + m->starts[jb.seq0 + (size_t)side], (size_t)len);
+            buf[(size_t)(at + len)] = '$';
+            at += len + 1;
+        }
+        RV_TRY(rv_add_sample(h));
+        RV_TRY(rv_add_sequences(h, buf.data(), at, side == 0 ? la.data() : lb.data(), (int64_t)J));
+    }
+    for (size_t s = 0; s < J; s++) bbeg[s] += ta;
+    const int64_t n = ta + tb;
+    RV_TRY(rv_upload(h));
+    // jobs, segment offsets, frontier tables
+    std::vector<ManyDevJob> dj(J);
+    std::vector<int64_t> meta(6 * J), node_first(J + 1), nodes(4 * J);
+    int64_t off = 0;
+    size_t nsmall = 0;
+    for (size_t s = 0; s < J; s++) {
+        const int64_t r = la[s] + lb[s] + 2;
+        dj[s].abeg = abeg[s]; dj[s].bbeg = bbeg[s]; dj[s].off = off; dj[s].la = (int32_t)la[s]; dj[s].lb = (int32_t)lb[s];
+        int64_t *m6 = meta.data() + 6 * s;
+        m6[0] = off; m6[1] = r; m6[2] = 0; m6[3] = 2; m6[4] = 0; m6[5] = -1;
+        node_first[s] = (int64_t)(2 * s);
+        nodes[4 * s] = abeg[s]; nodes[4 * s + 1] = abeg[s] + la[s]; nodes[4 * s + 2] = bbeg[s]; nodes[4 * s + 3] = bbeg[s] + lb[s];
+        if (r <= m->wave_max && r <= CAP_S) nsmall = s + 1;      // (ascending sizes: the small class is a prefix)
+        off += r;
+    }
+    node_first[J] = (int64_t)(2 * J);
+    if (off != n) { rv_set_error("rv_many_run: the jobs' ranks do not add up to the text"); return -1; }
+    hipStream_t q = h->ws.stream;
+    RV_TRY(m->dJobs.reserve(J * sizeof(ManyDevJob)));
+    RV_TRY(m->dSA.reserve((size_t)(n + 64) * sizeof(sa_t)));
+    RV_TRY(m->dLCP.reserve((size_t)(n + 64) * sizeof(lcp_t)));
+    RV_TRY(m->dBWT.reserve((size_t)n + 64));
+    RV_TRY(m->dCnt.reserve(64));
+    RV_HIP(hipMemcpyAsync(m->dJobs.p, dj.data(), J * sizeof(ManyDevJob), hipMemcpyHostToDevice, q));
+    RV_HIP(hipMemsetAsync(m->dCnt.p, 0, 64, q));
+    u32 *d_max = m->dCnt.as<u32>(), *d_err = d_max + 1;
+    const ManyDevJob *djobs = m->dJobs.as<ManyDevJob>();
+    const uint8_t *dT = h->dT0.as<uint8_t>();
+    if (nsmall) {
+        hipLaunchKernelGGL((k_many_build<CAP_S, 64>), dim3((unsigned)ceil_div((int64_t)nsmall, MT / 64)), dim3(MT), 0, q, djobs, (int)nsmall, dT,
+                           m->dSA.as<sa_t>(), m->dLCP.as<lcp_t>(), m->dBWT.as<uint8_t>(), d_max, d_err);
+        RV_LAUNCH_CHECK();
+        m->info[4]++;
+    }
+    if (nsmall < J) {
+        hipLaunchKernelGGL((k_many_build<CAP_L, MT>), dim3((unsigned)(J - nsmall)), dim3(MT), 0, q, djobs + nsmall, (int)(J - nsmall), dT,
+                           m->dSA.as<sa_t>(), m->dLCP.as<lcp_t>(), m->dBWT.as<uint8_t>(), d_max, d_err);
+        RV_LAUNCH_CHECK();
+        m->info[4]++;
+    }
+    u32 cnt[2] = {0, 0};
+    RV_TRY(rv_read_back(h->ws, cnt, d_max, 8));
+    if (cnt[1]) { rv_set_error("rv_many_run: the index build refused a job (error bits %u)", cnt[1]); return -1; }
+    if (m->keep) {
+        // test hook: SA / LCP of every job in job-local positions
+        std::vector<sa_t> sa((size_t)n); std::vector<lcp_t> lc((size_t)n);
+        RV_HIP(hipMemcpy(sa.data(), m->dSA.p, (size_t)n * sizeof(sa_t), hipMemcpyDeviceToHost));
+        RV_HIP(hipMemcpy(lc.data(), m->dLCP.p, (size_t)n * sizeof(lcp_t), hipMemcpyDeviceToHost));
+        const size_t base = m->keep_sa.size();
+        m->keep_sa.resize(base + (size_t)n); m->keep_lcp.resize(base + (size_t)n);
+        for (size_t s = 0; s < J; s++) {
+            m->jobs[(size_t)ord[s]].arr_off = (int64_t)base + dj[s].off;
+            for (int64_t r = 0; r < la[s] + lb[s] + 2; r++) {
+                const int64_t p = (int64_t)sa[(size_t)(dj[s].off + r)];
+                m->keep_sa[base + (size_t)(dj[s].off + r)] = (sa_t)(p >= bbeg[s] ? p - bbeg[s] + la[s] + 1 : p - abeg[s]);
+                m->keep_lcp[base + (size_t)(dj[s].off + r)] = lc[(size_t)(dj[s].off + r)];
+            }
+        }
+    }
+    // the segments as a frontier of J roots; every root is leaf-sized: one leaf launch
+    RV_TRY(rv_frontier_import(h, minl, minn, cnt[0], 0, (int)J, meta.data(), node_first.data(), nodes.data(), n, m->dSA.p, m->dLCP.p, m->dBWT.p, 1));
+    rv_align_stats st;
+    memset(&st, 0, sizeof st);
+    RV_TRY(rv_align_builtin_resume(h, &st));
+    many_add_stats(total, st);
+    const size_t rec0 = m->recs.size();
+    RV_TRY(many_collect(m, h, -1, ord, abeg, bbeg));
+    m->info[4] += st.levels + (m->recs.size() > rec0 ? 2 : 0);      // leaf launches, and the two of the lower-casing when there are anchors
+    // final text of every job: a$b$
+    std::vector<char> txt((size_t)n);
+    RV_HIP(hipMemcpy(txt.data(), h->dT.p, (size_t)n, hipMemcpyDeviceToHost));
+    for (size_t s = 0; s < J; s++) {
+        ManyJob &jb = m->jobs[(size_t)ord[s]];
+        jb.text_off = (int64_t)m->out_text.size();
+        jb.shared = true;
+        m->out_text.insert(m->out_text.end(), txt.begin() + (ptrdiff_t)abeg[s], txt.begin() + (ptrdiff_t)(abeg[s] + la[s] + 1));
+        m->out_text.insert(m->out_text.end(), txt.begin() + (ptrdiff_t)bbeg[s], txt.begin() + (ptrdiff_t)(bbeg[s] + lb[s] + 1));
+    }
+    m->info[1] += (int64_t)J; m->info[3]++;
+    return 0;
+}
+
+// a job the shared launches do not take: construct() + rv_align_builtin on the reused handle, every sequence a sample
+int many_ordinary(rv_many *m, int job, int minl, int minn, rv_align_stats *total) {
+    RV_TRY(many_handle(m, &m->ho));
+    rv_index *h = m->ho;
+    ManyJob &jb = m->jobs[(size_t)job];
+    RV_TRY(rv_reset(h));
+    for (int s = 0; s < jb.k; s++) {
+        RV_TRY(rv_add_sample(h));
+        RV_TRY(rv_add_sequence(h, m->in.data() + m->starts[jb.seq0 + (size_t)s], m->lens[jb.seq0 + (size_t)s], nullptr, nullptr));
+    }
+    RV_TRY(rv_construct(h, 0, nullptr, nullptr, 0));
+    rv_align_stats st;
+    memset(&st, 0, sizeof st);
+    RV_TRY(rv_align_builtin(h, minl, minn, &st));
+    many_add_stats(total, st);
+    static const std::vector<int> none; static const std::vector<int64_t> none64;
+    RV_TRY(many_collect(m, h, job, none, none64, none64));
+    jb.text_off = (int64_t)m->out_text.size();
+    jb.shared = false;
+    m->out_text.resize(m->out_text.size() + (size_t)jb.ranks);
+    if (rv_get_array(h, RV_T, m->out_text.data() + jb.text_off, jb.ranks) != jb.ranks) return -1;
+    m->info[2]++;
+    return 0;
+}
+
+int many_run(rv_many *m, int minl, int minn, rv_align_stats *total) {
+    RV_HIP(hipSetDevice(m->device));
+    m->ran = false;
+    m->recs.clear(); m->rpos.clear(); m->out_text.clear(); m->keep_sa.clear(); m->keep_lcp.clear();
+    for (int k = 0; k < 5; k++) m->info[k] = 0;
+    if (total) memset(total, 0, sizeof *total);
+    const int nj = (int)m->jobs.size();
+    m->info[0] = nj;
+    std::vector<int> order, rest;
+    for (int j = 0; j < nj; j++) {
+        ManyJob &jb = m->jobs[(size_t)j];
+        jb.arr_off = -1;
+        if (jb.k == 2 && jb.ranks <= RV_LEAF_N && jb.clean) order.push_back(j); else rest.push_back(j);
+    }
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return m->jobs[(size_t)a].ranks < m->jobs[(size_t)b].ranks; });
+    // rounds: a round's text stays below the 32-bit library's position limit (and a bound on the device memory of a round)
+    const int64_t lim = std::max<int64_t>(std::min<int64_t>(m->round_max, (int64_t)INT_MAX - 4096), 1);
+    for (size_t lo = 0; lo < order.size();) {
+        size_t hi = lo; int64_t sum = 0;
+        while (hi < order.size() && (hi == lo || sum + m->jobs[(size_t)order[hi]].ranks <= lim)) sum += m->jobs[(size_t)order[hi++]].ranks;
+        RV_TRY(many_round(m, order, lo, hi, minl, minn, total));
+        lo = hi;
+    }
+    for (int j : rest) RV_TRY(many_ordinary(m, j, minl, minn, total));
+    // the anchors job by job
+    m->an_first.assign((size_t)nj + 1, 0);
+    for (const ManyRec &r : m->recs) m->an_first[(size_t)r.job + 1]++;
+    for (int j = 0; j < nj; j++) m->an_first[(size_t)j + 1] += m->an_first[(size_t)j];
+    const size_t na = m->recs.size();
+    std::vector<int64_t> at(m->an_first.begin(), m->an_first.end() - 1);
+    std::vector<size_t> where(na);
+    for (size_t k = 0; k < na; k++) where[(size_t)at[(size_t)m->recs[k].job]++] = k;
+    m->an_l.resize(na); m->an_off.assign(na + 1, 0); m->an_pos.clear(); m->an_pos.reserve(m->rpos.size());
+    for (size_t k = 0; k < na; k++) {
+        const ManyRec &r = m->recs[where[k]];
+        m->an_l[k] = r.l;
+        for (int q = 0; q < r.np; q++) m->an_pos.push_back(m->rpos[(size_t)r.p0 + (size_t)q]);
+        m->an_off[k + 1] = (int64_t)m->an_pos.size();
+    }
+    m->recs.clear(); m->rpos.clear();
+    m->ran = true;
+    return 0;
+}
+
+}  // namespace
+
+#define MANY_GUARD(body, fail)                                                                                   \
+    try { body }                                                                                                 \
+    catch (const std::exception &e) { rv_set_error("rv_many: %s", e.what()); return fail; }                      \
+    catch (...) { rv_set_error("rv_many: failed"); return fail; }
+
+extern "C" {
+
+rv_many *rv_many_new(int device) {
+    const int nd = rv_device_count();
+    if (nd <= 0) { rv_set_error("no HIP device visible: reveal_amd has no CPU fallback"); return nullptr; }
+    if (device < 0 || device >= nd) { rv_set_error("device %d out of range (%d visible)", device, nd); return nullptr; }
+    MANY_GUARD(rv_many *m = new rv_many(); m->device = device; return m;, nullptr)
+}
+
+void rv_many_free(rv_many *m) {
+    if (!m) return;
+    (void)hipSetDevice(m->device);
+    if (m->hs) rv_free(m->hs);
+    if (m->ho) rv_free(m->ho);
+    m->dJobs.release(); m->dSA.release(); m->dLCP.release(); m->dBWT.release(); m->dCnt.release();
+    delete m;
+}
+
+int rv_many_option(rv_many *m, const char *name, int64_t value) {
+    if (!m || !name) { rv_set_error("rv_many_option: null argument"); return -1; }
+    if (strcmp(name, "RV_MANY_KEEP") == 0) { m->keep = value; return 0; }
+    if (strcmp(name, "RV_MANY_ROUND") == 0) { if (value < 1) { rv_set_error("RV_MANY_ROUND: at least 1"); return -1; } m->round_max = value; return 0; }
+    if (strcmp(name, "RV_MANY_WAVE_MAX") == 0) { if (value < 0) { rv_set_error("RV_MANY_WAVE_MAX: negative"); return -1; } m->wave_max = value; return 0; }
+    RvOptions probe;
+    if (!probe.find(name)) { rv_set_error("rv_many_option: unknown option %s", name); return -1; }
+    MANY_GUARD(
+        m->fwd.push_back({std::string(name), value});
+        if (m->hs) RV_TRY(rv_set_option(m->hs, name, value));
+        if (m->ho) RV_TRY(rv_set_option(m->ho, name, value));
+        return 0;, -1)
+}
+
+int64_t rv_many_add(rv_many *m, const char *const *seqs, const int64_t *lens, int k) {
+    if (!m || !seqs || !lens) { rv_set_error("rv_many_add: null argument"); return -1; }
+    if (k < 2) { rv_set_error("rv_many_add: a job needs at least two sequences (%d given)", k); return -1; }
+    int64_t ranks = 0; bool clean = true;
+    for (int s = 0; s < k; s++) {
+        if (!seqs[s] || lens[s] < 1) { rv_set_error("rv_many_add: sequence %d of the job is empty", s); return -1; }
+        for (int64_t i = 0; i < lens[s]; i++) {
+            const uint8_t ch = (uint8_t)seqs[s][i];
+            if (ch & 0x80u) { rv_set_error("addsequence: the sequence contains non-ASCII bytes"); return -1; }
+            if (ch == 0) clean = false;
+        }
+        ranks += lens[s] + 1;
+    }
+    if (m->jobs.size() >= (size_t)INT_MAX - 1) { rv_set_error("rv_many_add: too many jobs"); return -1; }
+    MANY_GUARD(
+        ManyJob jb; jb.k = k; jb.seq0 = m->lens.size(); jb.ranks = ranks; jb.clean = clean;
+        for (int s = 0; s < k; s++) {
+            m->starts.push_back((int64_t)m->in.size()); m->lens.push_back(lens[s]);
+            m->in.insert(m->in.end(), seqs[s], seqs[s] + lens[s]);
+        }
+        m->jobs.push_back(jb);
+        m->ran = false;
+        return (int64_t)m->jobs.size() - 1;, -1)
+}
+
+int rv_many_clear(rv_many *m) {
+    if (!m) { rv_set_error("rv_many_clear: null handle"); return -1; }
+    m->in.clear(); m->lens.clear(); m->starts.clear(); m->jobs.clear();
+    m->an_first.clear(); m->an_l.clear(); m->an_off.clear(); m->an_pos.clear(); m->out_text.clear(); m->keep_sa.clear(); m->keep_lcp.clear();
+    m->ran = false;
+    return 0;
+}
+
+int rv_many_run(rv_many *m, int minl, int minn, rv_align_stats *total) {
+    if (!m) { rv_set_error("rv_many_run: null handle"); return -1; }
+    MANY_GUARD(return many_run(m, minl, minn, total);, -1)
+}
+
+int64_t rv_many_anchor_count(rv_many *m, int64_t *first, int64_t *members) {
+    if (!m || !m->ran) { rv_set_error("rv_many_anchor_count: no finished run"); return -1; }
+    if (first) for (size_t k = 0; k < m->an_first.size(); k++) first[k] = m->an_first[k];
+    if (members) *members = (int64_t)m->an_pos.size();
+    return (int64_t)m->an_l.size();
+}
+
+int rv_many_fetch(rv_many *m, uint32_t *l, int64_t *off, int64_t *pos) {
+    if (!m || !m->ran || !l || !off || !pos) { rv_set_error("rv_many_fetch: no finished run, or null argument"); return -1; }
+    if (!m->an_l.empty()) memcpy(l, m->an_l.data(), m->an_l.size() * sizeof(u32));
+    memcpy(off, m->an_off.data(), m->an_off.size() * sizeof(int64_t));
+    if (!m->an_pos.empty()) memcpy(pos, m->an_pos.data(), m->an_pos.size() * sizeof(int64_t));
+    return 0;
+}
+
+int64_t rv_many_text(rv_many *m, int64_t job, char *out, int64_t cap) {
+    if (!m || !m->ran || job < 0 || job >= (int64_t)m->jobs.size() || !out) { rv_set_error("rv_many_text: no finished run, or no such job"); return -1; }
+    const ManyJob &jb = m->jobs[(size_t)job];
+    if (cap < jb.ranks) { rv_set_error("buffer too small"); return -1; }
+    memcpy(out, m->out_text.data() + jb.text_off, (size_t)jb.ranks);
+    return jb.ranks;
+}
+
+int rv_many_info(const rv_many *m, int64_t *out) {
+    if (!m || !out) { rv_set_error("rv_many_info: null argument"); return -1; }
+    for (int k = 0; k < 5; k++) out[k] = m->info[k];
+    return 0;
+}
+
+int64_t rv_many_arrays(rv_many *m, int64_t job, int which, void *out, int64_t cap) {
+    if (!m || !m->ran || job < 0 || job >= (int64_t)m->jobs.size() || !out) { rv_set_error("rv_many_arrays: no finished run, or no such job"); return -1; }
+    const ManyJob &jb = m->jobs[(size_t)job];
+    if (jb.arr_off < 0) { rv_set_error("rv_many_arrays: job %lld did not go through the shared launches with RV_MANY_KEEP set", (long long)job); return -2; }
+    if (cap < jb.ranks) { rv_set_error("buffer too small"); return -1; }
+    if (which == RV_SA) memcpy(out, m->keep_sa.data() + jb.arr_off, (size_t)jb.ranks * sizeof(sa_t));
+    else if (which == RV_LCP) memcpy(out, m->keep_lcp.data() + jb.arr_off, (size_t)jb.ranks * sizeof(lcp_t));
+    else { rv_set_error("rv_many_arrays: RV_SA or RV_LCP"); return -1; }
+    return jb.ranks;
+}
+
+}  // extern "C"

@@ -1,0 +1,186 @@
+"""Many small alignments in one call (include/reveal_amd.h "many small alignments", csrc/rv_many.hip).
+
+`reveal refine --method reveal_rem` calls `rem.align` once per bubble (reveal/refine.py:220-229).  `align_many` takes the
+sequences of many bubbles at once: the pair jobs of at most 2048 ranks share their kernel launches (one index build per size
+class with the text in LDS, one launch of the leaf kernel for every job's recursion), every other job runs the ordinary way
+inside the same call.  The built-in picker only (as `index.align_builtin`); no CPU fallback.
+"""
+import ctypes
+import os
+
+import numpy as np
+
+from . import _lib
+
+LEAF_RANKS = 2048          # RV_LEAF_N: a pair job of la + lb + 2 ranks up to this goes through the shared launches
+
+
+class error(Exception):
+    pass
+
+
+def job_sequences(job, toupper=True):
+    """a job as given -- a list of (name, seq) or of plain sequences (str / bytes) -> list of bytes; raises `error` for a job
+    the library would refuse (fewer than two sequences, an empty sequence)"""
+    if isinstance(job, (str, bytes, bytearray)) or not hasattr(job, "__len__"):
+        raise error("a job is a list of sequences or of (name, sequence) pairs")
+    seqs = []
+    for item in job:
+        s = item[1] if isinstance(item, (tuple, list)) else item
+        if isinstance(s, str):
+            s = s.encode("latin-1")
+        elif isinstance(s, (bytes, bytearray)):
+            s = bytes(s)
+        else:
+            raise error("a sequence is a str or bytes, not %s" % type(s).__name__)
+        seqs.append(s.upper() if toupper else s)
+    if len(seqs) < 2:
+        raise error("a job needs at least two sequences (%d given)" % len(seqs))
+    for k, s in enumerate(seqs):
+        if len(s) == 0:
+            raise error("sequence %d of the job is empty" % k)
+    return seqs
+
+
+def takes_shared_launch(seqs):
+    """whether the library builds and finishes this job in the shared launches"""
+    return len(seqs) == 2 and len(seqs[0]) + len(seqs[1]) + 2 <= LEAF_RANKS and all(b"\0" not in s for s in seqs)
+
+
+def shared_layout(pairs):
+    """the shared text of pair jobs [(a, b), ..] in the given order: every first sequence, then every second one, a '$' behind
+    each -> (text, a_begin[], b_begin[])"""
+    text, abeg, bbeg = bytearray(), [], []
+    for a, _ in pairs:
+        abeg.append(len(text))
+        text += a + b"$"
+    for _, b in pairs:
+        bbeg.append(len(text))
+        text += b + b"$"
+    return bytes(text), abeg, bbeg
+
+
+def to_local(pos, side, abeg, bbeg, la):
+    """position of the shared text inside job's sequence `side` -> stand-alone coordinate of the job's text `a$b$`"""
+    return pos - abeg if side == 0 else pos - bbeg + la + 1
+
+
+def to_shared(loc, abeg, bbeg, la):
+    """stand-alone coordinate of `a$b$` -> (side, position of the shared text)"""
+    return (0, abeg + loc) if loc <= la else (1, bbeg + loc - la - 1)
+
+
+class Batch:
+    """the C object behind align_many (rv_many_*): add jobs, run, read the results; clear() keeps the allocations"""
+
+    def __init__(self, sa64=False, device=None):
+        self._lib = _lib.get(sa64)
+        self._dll = self._lib.dll
+        self._m = self._dll.rv_many_new(_lib.device() if device is None else int(device))
+        if not self._m:
+            raise error(self._lib.err())
+        self._lens = []
+        for k in range(self._dll.rv_option_count()):      # RV_* switches of the environment, as a new index object applies them
+            name = self._dll.rv_option_name(k).decode()
+            v = os.environ.get(name)
+            if v is not None:
+                try:
+                    iv = int(v) if v.strip() else 1
+                except ValueError:
+                    iv = 1
+                self.option(name, iv)
+        for name in ("RV_MANY_KEEP", "RV_MANY_ROUND", "RV_MANY_WAVE_MAX"):
+            v = os.environ.get(name)
+            if v is not None and v.strip():
+                self.option(name, int(v))
+
+    def __del__(self):
+        m, self._m = getattr(self, "_m", None), None
+        if m:
+            self._dll.rv_many_free(m)
+
+    def _fail(self):
+        raise error(self._lib.err())
+
+    def option(self, name, value=1):
+        if self._dll.rv_many_option(self._m, name.encode(), int(value)) != 0:
+            self._fail()
+
+    def add(self, seqs):
+        k = len(seqs)
+        ptrs = (ctypes.c_char_p * k)(*seqs)
+        lens = (ctypes.c_int64 * k)(*[len(s) for s in seqs])
+        j = self._dll.rv_many_add(self._m, ptrs, lens, k)
+        if j < 0:
+            self._fail()
+        self._lens.append(sum(len(s) for s in seqs) + k)
+        return j
+
+    def clear(self):
+        if self._dll.rv_many_clear(self._m) != 0:
+            self._fail()
+        self._lens = []
+
+    def info(self):
+        o = (ctypes.c_int64 * 5)()
+        self._dll.rv_many_info(self._m, o)
+        return dict(jobs=int(o[0]), shared=int(o[1]), ordinary=int(o[2]), rounds=int(o[3]), launches=int(o[4]))
+
+    def run(self, minlength=20, minn=2):
+        st = _lib.RvAlignStats()
+        if self._dll.rv_many_run(self._m, int(minlength), int(minn), ctypes.byref(st)) != 0:
+            self._fail()
+        return {f[0]: getattr(st, f[0]) for f in _lib.RvAlignStats._fields_}
+
+    def anchors(self):
+        """-> (first[jobs + 1], l, off, pos): job j owns the anchors first[j] .. first[j+1]"""
+        nj = len(self._lens)
+        first = np.zeros(nj + 1, np.int64)
+        mem = ctypes.c_int64(0)
+        na = self._dll.rv_many_anchor_count(self._m, first.ctypes.data, ctypes.byref(mem))
+        if na < 0:
+            self._fail()
+        l = np.zeros(max(na, 1), np.uint32); off = np.zeros(na + 1, np.int64); pos = np.zeros(max(mem.value, 1), np.int64)
+        if self._dll.rv_many_fetch(self._m, l.ctypes.data, off.ctypes.data, pos.ctypes.data) != 0:
+            self._fail()
+        return first, l[:na], off, pos[:mem.value]
+
+    def text(self, j):
+        buf = ctypes.create_string_buffer(self._lens[j])
+        if self._dll.rv_many_text(self._m, j, buf, self._lens[j]) != self._lens[j]:
+            self._fail()
+        return buf.raw
+
+    def arrays(self, j):
+        """test hook (RV_MANY_KEEP): (SA, LCP) of a shared-launch job, job-local positions"""
+        n = self._lens[j]
+        sa = np.zeros(n, self._lib.sa_t); lcp = np.zeros(n, self._lib.lcp_t)
+        if self._dll.rv_many_arrays(self._m, j, _lib.RV_SA, sa.ctypes.data, n) != n or self._dll.rv_many_arrays(self._m, j, _lib.RV_LCP, lcp.ctypes.data, n) != n:
+            self._fail()
+        return sa, lcp
+
+
+def align_many(jobs, minlength=20, minn=2, sa64=False, toupper=True, batch=None):
+    """jobs: a list of jobs, each a list of (name, seq) or of plain sequences (two or more, none empty; every sequence is a sample
+    of its own, like the inputs of `reveal rem`).  -> (results, info): results[j] = dict(anchors=[(l, (pos, ..)), ..], T=final text
+    `s0$s1$..` lower-cased where aligned), positions in the coordinates of the job's own text -- what index.align_builtin gives a
+    stand-alone index of the job; info = dict(jobs, shared, ordinary, rounds, launches, stats).  `batch`: a Batch to reuse."""
+    if isinstance(jobs, (str, bytes, bytearray)) or not hasattr(jobs, "__iter__"):
+        raise error("jobs is a list of jobs")
+    if int(minlength) < 0 or int(minn) < 2:
+        raise error("minlength >= 0 and minn >= 2")
+    prepared = [job_sequences(j, toupper) for j in jobs]      # (argument errors before the library is asked for a device)
+    b = batch if batch is not None else Batch(sa64)
+    b.clear()
+    for seqs in prepared:
+        b.add(seqs)
+    stats = b.run(minlength, minn)
+    first, l, off, pos = b.anchors()
+    l, off, pos, first = l.tolist(), off.tolist(), pos.tolist(), first.tolist()
+    results = []
+    for j in range(len(prepared)):
+        an = [(l[k], tuple(pos[off[k]:off[k + 1]])) for k in range(first[j], first[j + 1])]
+        results.append(dict(anchors=an, T=b.text(j).decode("latin-1")))
+    info = b.info()
+    info["stats"] = stats
+    return results, info
