@@ -226,6 +226,9 @@ struct Align {
     size_t last_leaf_count = 0;
     bool running = false;        // a built-in run is between its set-up and its collection
     u32 *lf_counters = nullptr; unsigned long long *lf_stats = nullptr; u32 *lf_l = nullptr; int64_t *lf_pos = nullptr; rv_trace *lf_tr = nullptr;
+    // anchors [0, early_sent) of the device's list left for the caller's arrays at early_l / early_pos while the cascade's levels ran
+    // (builtin_cascade); builtin_finish copies the rest when they still belong there
+    size_t early_sent = 0; u32 *early_l = nullptr; int64_t *early_pos = nullptr;
     size_t leaf_na = 0;          // anchors of the leaf launches of the last run: they stay in the pinned staging buffer (hLeafOut: pos[2 na], l[na]) until fetched
     void release() {
         // (the side streams may still be writing pinned buffers that go back to the process-wide pool below: after an aborted run nothing else waits for them)
@@ -684,6 +687,7 @@ static int early_split(rv_index *h) {
     const bool all_classes = a->multi || ns > 4096;
     if (biggest <= a->par_min_cur && !h->ws.opt.no_early_bubble &&
         (a->multi || (!h->ws.opt.bubble_lds_always && (!all_classes || h->ws.opt.early_bubble_many)))) {
+        RV_TRY(rv_ensure_working_text(h));
         RV_TRY(rv_lower_ranges_launch(h->ws, h->dT.as<uint8_t>(), t.mb, t.me, W * ns));
         RV_TRY(bubble_flags(h, m));
         RvBubbleArgs ba;
@@ -1411,6 +1415,7 @@ static int commit_split(rv_index *h, const Commit &cm, RvSplitArgs &sa) {
     }
     h->prof.end(q, id);
     if (!a->early_bubble) {
+        RV_TRY(rv_ensure_working_text(h));
         // many short ranges (the deep levels: 10^5 matches of ~100 bases): a wave per range; few long ones: a thread per base, which looks
         // its range up by a binary search over the prefix sums (17 dependent loads per base at 10^5 ranges: 0.2 ms per level at C4)
         if (lt.nmatch > 256 && a->mpre.back() / lt.nmatch <= 512) RV_TRY(rv_lower_ranges_launch(h->ws, h->dT.as<uint8_t>(), lt.mbegin, lt.mend, lt.nmatch));
@@ -1589,7 +1594,7 @@ static int builtin_setup(rv_index *h, int minl, int minn) {
     RV_TRY(align_begin(h, minl, minn, h->al && h->al->trace_on));
     Align *a = h->al;
     a->full_only = !a->trace_on && a->picker == 0;      // (the chain picker looks at every match of a sub-index: the scans hand their whole lists to the host)
-    a->an_l.clear(); a->an_off.assign(1, 0); a->an_pos.clear(); a->trace.clear(); a->leaf_na = 0;
+    a->an_l.clear(); a->an_off.assign(1, 0); a->an_pos.clear(); a->trace.clear(); a->leaf_na = 0; a->early_sent = 0;
     a->seeds_cur.clear(); a->seeds_lead.clear(); a->seeds_trail.clear(); a->picker_calls = a->picker_seeded = 0; a->picker_ns = a->picker_list_ns = a->galign_ns = 0;
     if (a->picker == 1) {
         if ((int)h->nodes.size() != h->nsamples) { rv_set_error("the native picker (rv_set_picker) takes one sequence per sample: %d sequences in %d samples", (int)h->nodes.size(), h->nsamples); return -1; }
@@ -2044,9 +2049,14 @@ static int builtin_finish(rv_index *h, rv_align_stats *out) {
             int64_t *pp; u32 *pl;
             if (rb.direct) { pp = rb.pos + np; pl = rb.l + nl; }
             else { RV_TRY(a->hLeafOut.reserve(na * 20 + 64)); pp = a->hLeafOut.as<int64_t>(); pl = (u32 *)(pp + 2 * na); }
-            // (both streams are idle here: the copies to the host run on the side stream beside the lower-casing -- 0.9 and 0.7 ms at 2 x 250 Mbp)
-            RV_HIP(hipMemcpyAsync(pp, lf_pos, na * 16, hipMemcpyDeviceToHost, a->leaf_stream));
-            RV_HIP(hipMemcpyAsync(pl, lf_l, na * 4, hipMemcpyDeviceToHost, a->leaf_stream));
+            // (both streams are idle here: the copies to the host run on the side stream beside the lower-casing -- 0.9 and 0.7 ms at 2 x 250 Mbp
+            //  for all of them; what the cascade has delivered under its levels is not copied again)
+            const size_t sent = (rb.direct && a->early_l == pl && a->early_pos == pp) ? std::min(a->early_sent, na) : 0;
+            if (sent < na) {
+                RV_HIP(hipMemcpyAsync(pp + 2 * sent, lf_pos + 2 * sent, (na - sent) * 16, hipMemcpyDeviceToHost, a->leaf_stream));
+                RV_HIP(hipMemcpyAsync(pl + sent, lf_l + sent, (na - sent) * 4, hipMemcpyDeviceToHost, a->leaf_stream));
+            }
+            RV_TRY(rv_ensure_working_text(h));
             RV_TRY(rv_leaf_lower_launch(h->ws, h->dT.as<uint8_t>(), lf_pos, lf_l, (u32)na));      // their matched text (nothing read it during the run)
             if (rb.direct) fill_offsets(rb.off + nl + 1, na, (int64_t)np);      // (two members per anchor: the host writes them while the GPU works)
             RV_HIP(hipStreamSynchronize(a->leaf_stream));
@@ -2114,17 +2124,29 @@ static int builtin_cascade(rv_index *h) {
     io.anchor_count = a->lf_counters; io.anchor_cap = (u32)a->leaf_anchor_cap; io.anchor_l = a->lf_l; io.anchor_pos = a->lf_pos;
     io.stats = a->lf_stats; io.leaf_err = a->lf_counters + 2;
     io.stage_cap = (u32)h->ws.opt.leaf_acap;
+    // beside the level loop, on the (idle) first leaf stream: the working text's copy, and the anchors into the caller's arrays when it has set them
+    RvCascadeHost hx;
+    hx.side = a->leaf_stream;
+    a->early_sent = 0;
+    if (h->rb.l) {
+        const int64_t nl = (int64_t)a->an_l.size(), np = (int64_t)a->an_pos.size();
+        const int64_t room = std::min(std::min(h->rb.l_cap - nl, h->rb.off_cap - nl - 1), (h->rb.pos_cap - np) / 2);
+        if (room > 0) { hx.l = h->rb.l + nl; hx.pos = h->rb.pos + np; hx.cap = (u32)std::min<int64_t>(room, 0xffffffffll); }
+    }
     io.lvSA = &a->lvSA[0]; io.lvLCP = &a->lvLCP[0]; io.lvBWT = &a->lvBWT[0]; io.roots = &a->dLeafRoots[0];
     // RV_CASCADE_DANGER=0: no second attempt of this kind; =2: the first attempt already decides large undecided sub-indices from their witnesses (test hook)
     const int dmode = (int)h->ws.opt.cascade_danger;
-    RV_TRY(rv_cascade_run(h, a->cas, io, a->minl, &a->cas_out, dmode == 2 ? 1 : 0, 0));
+    RV_TRY(rv_cascade_run(h, a->cas, io, a->minl, &a->cas_out, dmode == 2 ? 1 : 0, 0, &hx));
     if (!a->cas_out.done && a->cas_out.undecided > 0 && dmode == 1) {
         // an undecided sub-index above the leaf kernel's size: the same cascade again (its lists are still there), now with the large
         // undecided sub-indices decided from their witnesses (k_cas_dwalk)
         RV_HIP(hipMemsetAsync(a->dLeaf.p, 0, 256, h->ws.stream));      // anchors and counters of the attempt
-        RV_TRY(rv_cascade_run(h, a->cas, io, a->minl, &a->cas_out, 1, 1));
+        RV_TRY(rv_cascade_run(h, a->cas, io, a->minl, &a->cas_out, 1, 1, &hx));
     }
     if (!a->cas_out.done) {
+        // what the dropped attempt sent ahead to the caller's arrays counts for nothing (early_sent stays 0) and has landed before anything else
+        // writes there.  (A second attempt above sends on the same stream, in order behind the first one's.)
+        if (hx.l) RV_HIP(hipStreamSynchronize(a->leaf_stream));
         RV_HIP(hipMemsetAsync(a->dLeaf.p, 0, 256, h->ws.stream));      // anchors and counters of the attempt
         // still one left: another attempt with the bound of rv_cascade_multi.hip (repeats inside one
         // sample: tighter) whose undecided sub-indices -- up to 8192 suffixes -- go to the level pipeline instead of the leaf kernel
@@ -2133,6 +2155,7 @@ static int builtin_cascade(rv_index *h) {
     }
     a->st.levels += a->cas_out.levels;
     a->st.scanned_ranks += h->n;
+    a->early_sent = a->cas_out.sent; a->early_l = hx.l; a->early_pos = hx.pos;
     if (!a->cas.lin_rest.empty() && h->nodes.size() > 2) {
         // several sequences per sample: the chain of rest sub-indices stopped at a member the match list does not decide (left-over sequences whose
         // only matches are as short as their repeats).  It becomes the level pipeline's frontier: ONE split of the root whose rest class is that
@@ -2370,7 +2393,7 @@ int rv_frontier_import(rv_index *h, int minl, int minn, uint32_t maxlcp, int lev
             if (h->rc) { rv_set_error("the native picker (rv_set_picker) with construct(rc=1) is not supported"); return -1; }
         }
         a->picker_calls = a->picker_seeded = 0; a->picker_ns = a->picker_list_ns = a->galign_ns = 0;
-        a->an_l.clear(); a->an_off.assign(1, 0); a->an_pos.clear(); a->trace.clear(); a->leaf_na = 0;
+        a->an_l.clear(); a->an_off.assign(1, 0); a->an_pos.clear(); a->trace.clear(); a->leaf_na = 0; a->early_sent = 0;
         RV_TRY(builtin_leaf_setup(h));
     }
     RV_TRY(install_frontier(h, level, nsubs, meta, node_first, nodes, m, sa, lcp, bwt, on_device));

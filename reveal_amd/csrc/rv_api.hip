@@ -102,6 +102,8 @@ void rv_free(rv_index *h) {
     for (auto &b : h->ps) b.release();
     h->hupload.release();
     if (h->ev_picks) { (void)hipEventDestroy(h->ev_picks); h->ev_picks = nullptr; }
+    if (h->ev_text) { (void)hipEventDestroy(h->ev_text); h->ev_text = nullptr; }
+    if (h->ev_text_in) { (void)hipEventDestroy(h->ev_text_in); h->ev_text_in = nullptr; }
     if (h->ws.stream) rv_stream_put(h->ws.stream);
     delete h;
 }
@@ -161,7 +163,7 @@ rv_index *rv_clone(rv_index *h) {
     c->ws.opt = h->ws.opt;
     const int64_t n = h->n;
     hipStream_t q = c->ws.stream;
-    bool ok = rv_upload(c) == 0;
+    bool ok = rv_upload(c) == 0 && rv_ensure_working_text(h) == 0;
     ok = ok && c->dT.reserve((size_t)n + 64) == 0 && c->dSA.reserve((size_t)(n + 64) * sizeof(sa_t)) == 0 && c->dSAi.reserve((size_t)(n + 64) * sizeof(sa_t)) == 0
             && c->dLCP.reserve((size_t)(n + 64) * sizeof(lcp_t)) == 0 && c->dBWT.reserve((size_t)n + 64) == 0 && c->dNsep.reserve((h->nsep.size() + 1) * sizeof(sa_t)) == 0;
     ok = ok && hipStreamSynchronize(h->ws.stream) == hipSuccess;
@@ -449,10 +451,12 @@ int rv_construct(rv_index *h, int rc, const char *safile, const char *lcpfile, i
     if (h->al) (void)rv_align_end(h);        /* a new construct ends any recursion in flight; its device scratch is kept */
     h->nT = n;
     hipStream_t q = h->ws.stream;
-    // working copy of the (HBM-resident) text: align() lower-cases it in place
+    // working copy of the (HBM-resident) text: align() lower-cases it in place.  Only marked as due here (rv_ensure_working_text): the index
+    // is built from the pristine text -- the same bytes, the same padding
+    if (h->dT_inflight) { RV_HIP(hipStreamWaitEvent(q, h->ev_text, 0)); h->dT_inflight = false; }      // (a copy nobody has waited for yet: before its buffers change)
     RV_TRY(rv_upload(h));
     RV_TRY(h->dT.reserve((size_t)n + 64));
-    RV_HIP(hipMemcpyAsync(h->dT.p, h->dT0.p, (size_t)n + 64, hipMemcpyDeviceToDevice, q));
+    h->dT_pending = true;
     RV_TRY(h->dSA.reserve((size_t)(n + 64) * sizeof(sa_t)));
     RV_TRY(h->dSAi.reserve((size_t)(n + 64) * sizeof(sa_t)));
     RV_TRY(h->dLCP.reserve((size_t)(n + 64) * sizeof(lcp_t)));
@@ -466,8 +470,8 @@ int rv_construct(rv_index *h, int rc, const char *safile, const char *lcpfile, i
     SaScratchInUse in_use(h->ws);
     if (!safile || !safile[0]) {
         int id = h->prof.begin(q, RV_K_SA_SORT, 5.0 * (double)n);
-        if (lcp_from_file) RV_TRY(rv_build_sa(h->ws, h->dT.as<uint8_t>(), n, h->dSA.as<sa_t>(), &h->sa_stats));
-        else RV_TRY(rv_build_sa(h->ws, h->dT.as<uint8_t>(), n, h->dSA.as<sa_t>(), &h->sa_stats, h->dLCP.as<lcp_t>(), h->dBWT.as<uint8_t>(), side_sep, d_max, &lcp_done,
+        if (lcp_from_file) RV_TRY(rv_build_sa(h->ws, h->dT0.as<uint8_t>(), n, h->dSA.as<sa_t>(), &h->sa_stats));
+        else RV_TRY(rv_build_sa(h->ws, h->dT0.as<uint8_t>(), n, h->dSA.as<sa_t>(), &h->sa_stats, h->dLCP.as<lcp_t>(), h->dBWT.as<uint8_t>(), side_sep, d_max, &lcp_done,
                                  h->nsep.data(), (int)h->nsep.size()));
         h->prof.end(q, id);
     } else {
@@ -481,7 +485,7 @@ int rv_construct(rv_index *h, int rc, const char *safile, const char *lcpfile, i
     if (!lcp_from_file) {
         if (!lcp_done) {       // (SA from a file, or an order the first key + text round did not finish)
             int id = h->prof.begin(q, RV_K_LCP, 13.0 * (double)n);
-            RV_TRY(rv_build_lcp(h->ws, h->dT.as<uint8_t>(), h->dSA.as<sa_t>(), false, h->dLCP.as<lcp_t>(), n, d_max, h->dBWT.as<uint8_t>(), side_sep));
+            RV_TRY(rv_build_lcp(h->ws, h->dT0.as<uint8_t>(), h->dSA.as<sa_t>(), false, h->dLCP.as<lcp_t>(), n, d_max, h->dBWT.as<uint8_t>(), side_sep));
             h->prof.end(q, id);
         }
         RV_TRY(rv_read_back(h->ws, &h->maxlcp, d_max, 4));
@@ -492,7 +496,7 @@ int rv_construct(rv_index *h, int rc, const char *safile, const char *lcpfile, i
         for (int64_t i = 0; i < n; i++) if ((u32)tmp[(size_t)i] > mx) mx = (u32)tmp[(size_t)i];
         h->maxlcp = mx;
         RV_HIP(hipMemcpyAsync(h->dLCP.p, tmp.data(), (size_t)n * sizeof(lcp_t), hipMemcpyHostToDevice, q));
-        RV_TRY(rv_build_bwt(h->ws, h->dT.as<uint8_t>(), h->dSA.as<sa_t>(), n, h->dBWT.as<uint8_t>(), side_sep));
+        RV_TRY(rv_build_bwt(h->ws, h->dT0.as<uint8_t>(), h->dSA.as<sa_t>(), n, h->dBWT.as<uint8_t>(), side_sep));
         RV_HIP(hipStreamSynchronize(q));
     }
     if (cache == 1) {
@@ -525,6 +529,8 @@ int64_t rv_get_array(rv_index *h, int which, void *out, int64_t cap) {
     case RV_T:
         if (cap < n) { rv_set_error("buffer too small"); return -1; }
         if (h->constructed || h->text_only) {
+            if (rv_ensure_working_text(h) != 0) return -1;
+            if (hipStreamSynchronize(h->ws.stream) != hipSuccess) { rv_set_error("stream failed"); return -1; }
             if (hipMemcpy(out, h->dT.p, (size_t)n, hipMemcpyDeviceToHost) != hipSuccess) { rv_set_error("D2H failed"); return -1; }
         } else {
             memcpy(out, h->T.data(), (size_t)n);
@@ -577,6 +583,33 @@ int rv_need_sai(rv_index *h) {
     return 0;
 }
 
+int rv_ensure_working_text(rv_index *h) {
+    hipStream_t q = h->ws.stream;
+    if (h->dT_inflight) {      // (only rv_working_text_begin sets it, and it has made ev_text by then)
+        RV_HIP(hipStreamWaitEvent(q, h->ev_text, 0));
+        h->dT_inflight = false;
+    }
+    if (!h->dT_pending) return 0;
+    RV_TRY(h->dT.reserve((size_t)h->n + 64));
+    RV_HIP(hipMemcpyAsync(h->dT.p, h->dT0.p, (size_t)h->n + 64, hipMemcpyDeviceToDevice, q));
+    h->dT_pending = false;
+    return 0;
+}
+
+int rv_working_text_begin(rv_index *h, hipStream_t side) {
+    if (!h->dT_pending) return 0;
+    if (!side || side == h->ws.stream) return rv_ensure_working_text(h);
+    if (!h->ev_text) RV_HIP(hipEventCreateWithFlags(&h->ev_text, hipEventDisableTiming));
+    if (!h->ev_text_in) RV_HIP(hipEventCreateWithFlags(&h->ev_text_in, hipEventDisableTiming));
+    RV_TRY(h->dT.reserve((size_t)h->n + 64));
+    RV_HIP(hipEventRecord(h->ev_text_in, h->ws.stream));
+    RV_HIP(hipStreamWaitEvent(side, h->ev_text_in, 0));
+    RV_HIP(hipMemcpyAsync(h->dT.p, h->dT0.p, (size_t)h->n + 64, hipMemcpyDeviceToDevice, side));
+    RV_HIP(hipEventRecord(h->ev_text, side));
+    h->dT_pending = false; h->dT_inflight = true;
+    return 0;
+}
+
 int rv_text_only(rv_index *h, u32 maxlcp) {
     RV_HIP(hipSetDevice(h->device));
     if (h->n == 0) { rv_set_error("No text to index."); return -1; }
@@ -585,8 +618,8 @@ int rv_text_only(rv_index *h, u32 maxlcp) {
     hipStream_t q = h->ws.stream;
     h->rc = 0; h->nT = n;
     RV_TRY(rv_upload(h));
-    RV_TRY(h->dT.reserve((size_t)n + 64));
-    RV_HIP(hipMemcpyAsync(h->dT.p, h->dT0.p, (size_t)n + 64, hipMemcpyDeviceToDevice, q));
+    h->dT_pending = true;
+    RV_TRY(rv_ensure_working_text(h));
     RV_TRY(h->dSAi.reserve((size_t)(n + 64) * sizeof(sa_t)));      // written by every split in front of its cuts before bubble_sort reads there
     std::vector<sa_t> ns(h->nsep.size() + 1, 0);
     for (size_t k = 0; k < h->nsep.size(); k++) ns[k] = (sa_t)h->nsep[k];

@@ -35,12 +35,22 @@ struct RvCascadeIO {
     DBuf *lvSA, *lvLCP, *lvBWT, *roots;
 };
 
+// what the host side of the two-sample cascade may use beside its level loop (the levels are a chain of small kernels: HBM and the link to the
+// host stand idle under them)
+struct RvCascadeHost {
+    hipStream_t side = nullptr;       // an idle stream of the caller: the working text's copy, the anchors' way to the host
+    // the caller's page-locked result arrays (rv_set_result_buffers) where anchor 0 of this run belongs, with room for `cap` anchors; null: none.
+    // Anchors the host knows to be complete leave for them while the next levels run; RvCascadeOut::sent of them have when the run is done
+    int64_t *pos = nullptr; u32 *l = nullptr; u32 cap = 0;
+};
+
 struct RvCascadeOut {
     bool done;                         // false: nothing was decided, the caller runs the level pipeline from the top
     int levels;
     int64_t cands, witnesses, children, undecided, rebuilt_ranks;
     int64_t solved, unsolved;          // second attempt: large undecided sub-indices decided from their witnesses / left undecided
     const char *why;                   // done == false: the reason
+    u32 sent;                          // done: anchors [0, sent) are in (or on the side stream to) RvCascadeHost's arrays; never set by an attempt that gave up
 };
 
 // more than two samples (rv_cascade_multi.hip): the decided part's anchors come back on the host (the level pipeline keeps its anchors
@@ -65,4 +75,5 @@ void rv_batch_group_info(const RvBatchGroup *g, int64_t *out);      // out[0] jo
 int rv_cascade_multi_run(rv_index *h, RvCascadeBufs &cb, int minl, RvCascadeMultiOut *out);
 // danger: large undecided sub-indices are decided from their witnesses (the second attempt, rv_cascade.hip); reuse: the match and
 // witness lists of the previous run on this handle are still in cb (same index, same minl)
-int rv_cascade_run(rv_index *h, RvCascadeBufs &cb, const RvCascadeIO &io, int minl, RvCascadeOut *out, int danger = 0, int reuse = 0);
+int rv_cascade_run(rv_index *h, RvCascadeBufs &cb, const RvCascadeIO &io, int minl, RvCascadeOut *out, int danger = 0, int reuse = 0,
+                   const RvCascadeHost *host = nullptr);

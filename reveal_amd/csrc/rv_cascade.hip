@@ -55,7 +55,8 @@ constexpr u64 KEY_LOW = (1ull << KEY_SHIFT) - 1;
 
 struct CasIv { sa_t a0, a1, b0, b1; };
 struct CasRes { sa_t qa, qb; u32 ql, lead, trail, state; };      // state: 0 not decided yet, 1 split, 2 ended
-enum { C_NCHILD = 0, C_NUND = 1, C_NWIT = 2, C_ERR = 3, C_MAXN = 4, C_LO = 5, C_HI = 6, C_LEVELS = 7, C_NSOLVED = 8, C_NUNSOLVED = 9, C_NRETRY = 10, C_TICKET = 11 };
+enum { C_NCHILD = 0, C_NUND = 1, C_NWIT = 2, C_ERR = 3, C_MAXN = 4, C_LO = 5, C_HI = 6, C_LEVELS = 7, C_NSOLVED = 8, C_NUNSOLVED = 9, C_NRETRY = 10, C_TICKET = 11,
+       C_NANCH = 12 /* the anchor count as of the last finished level: a copy, so that it reaches the host with the other counters */ };
 
 // the match (pa, pb, len) of the root cut to a sub-index: start shifted behind the sub-index' begin on both sides, length
 // capped at its ends
@@ -695,6 +696,7 @@ __global__ __launch_bounds__(TB) void k_cas_decide(CasIv *__restrict__ iv, u64 *
         if (atomicAdd(&counters[C_TICKET], 1u) == gridDim.x - 1) {
             if (hi > lo) counters[C_LEVELS]++;
             counters[C_LO] = hi; counters[C_HI] = atomicAdd(&counters[C_NCHILD], 0u);
+            counters[C_NANCH] = atomicAdd(io.anchor_count, 0u);
             counters[C_TICKET] = 0;
         }
     }
@@ -969,7 +971,7 @@ static int cas_lineage(rv_index *h, RvCascadeBufs &cb, u32 M, u32 NW, u32 minl, 
     return 0;
 }
 
-int rv_cascade_run(rv_index *h, RvCascadeBufs &cb, const RvCascadeIO &io, int minl_in, RvCascadeOut *out, int danger, int reuse) {
+int rv_cascade_run(rv_index *h, RvCascadeBufs &cb, const RvCascadeIO &io, int minl_in, RvCascadeOut *out, int danger, int reuse, const RvCascadeHost *host) {
     memset(out, 0, sizeof *out);
     out->done = false;
     Workspace &ws = h->ws;
@@ -1187,6 +1189,19 @@ int rv_cascade_run(rv_index *h, RvCascadeBufs &cb, const RvCascadeIO &io, int mi
     const unsigned agrid = (unsigned)(ceil_div((int64_t)M, TB * CAS_ITEMS) + ceil_div((int64_t)NW, TB * CAS_ITEMS));
     const int batch = std::max(1, (int)ws.opt.cascade_batch);
     int queued = 0;
+    // the working text, if its copy is still due: on the side stream, behind the scan and the witness pass (which run at HBM's speed),
+    // beside the levels' small kernels (which leave it idle); the leaf anchors' lower-casing waits for it
+    RV_TRY(rv_working_text_begin(h, host ? host->side : nullptr));
+    // The anchors' way to the host: what the counters of a batch show is complete (its kernels have ended), so [sent, known) is copied on the
+    // side stream while the next batch runs.  An attempt that gives up has copied for nothing: the arrays are written again by whatever follows.
+    u32 sent = 0, known = 0;
+    auto send_known = [&]() -> int {
+        if (!host || !host->side || !host->l || known <= sent || known > host->cap) return 0;
+        RV_HIP(hipMemcpyAsync(host->pos + 2 * (size_t)sent, io.anchor_pos + 2 * (size_t)sent, (size_t)(known - sent) * 16, hipMemcpyDeviceToHost, host->side));
+        RV_HIP(hipMemcpyAsync(host->l + sent, io.anchor_l + sent, (size_t)(known - sent) * 4, hipMemcpyDeviceToHost, host->side));
+        sent = known;
+        return 0;
+    };
     // (RV_CASCADE_PRIO=1: the level loop on a stream of the highest priority, fenced by events against the handle's own -- see rv_cascade_multi.hip)
     struct PrioScope {
         Workspace &w; hipStream_t home; RvCascadeBufs &cb; bool on = false;
@@ -1243,11 +1258,13 @@ int rv_cascade_run(rv_index *h, RvCascadeBufs &cb, const RvCascadeIO &io, int mi
                                bres.as<CasRes>(), minl, counters, ccap, bund.as<u32>(), (u32)RV_LEAF_N, io, dg, (danger && NW) ? 1 : 0);
             RV_LAUNCH_CHECK();
         }
+        RV_TRY(send_known());      // (behind the batch's launches: the host's time for it is hidden, too)
         RV_TRY(rv_read_back(ws, hc, counters, sizeof hc));
         // (bits 1 and 4: the table of sub-indices / the anchor area is full -- retries of the second attempt take a slot each: not an error of the
         // input, the level pipeline completes such a run)
         if (hc[C_ERR] & ~5u) { rv_set_error("cascade: device error %u", hc[C_ERR]); return -1; }
         if (hc[C_ERR]) GIVE_UP("the cascade's tables are full");
+        known = hc[C_NANCH];
         if (hc[C_MAXN] > (u32)RV_LEAF_N) break;      // an undecided sub-index the leaf kernel cannot take
         if (hc[C_HI] == hc[C_LO]) break;
         if (queued > 1000000) { rv_set_error("cascade: no progress"); return -1; }
@@ -1267,6 +1284,7 @@ int rv_cascade_run(rv_index *h, RvCascadeBufs &cb, const RvCascadeIO &io, int mi
     }
     hipLaunchKernelGGL(k_cas_stats, dim3(256), dim3(TB), 0, q, (const u32 *)counters, (const int32_t *)bdep.as<int32_t>(), io);
     RV_LAUNCH_CHECK();
+    RV_TRY(send_known());      // the last batch's, beside the rebuilt sub-indices and the leaf kernel (whose anchors the caller collects)
     if (chain) {      // the members of the chain were visited on the host
         hipLaunchKernelGGL(k_cas_lineage_stats, dim3(1), dim3(64), 0, q, io.stats, (unsigned long long)cb.lin_steps, (unsigned long long)cb.lin_maxdepth);
         RV_LAUNCH_CHECK();
@@ -1311,6 +1329,7 @@ int rv_cascade_run(rv_index *h, RvCascadeBufs &cb, const RvCascadeIO &io, int mi
                 danger ? " (second attempt)" : "", M, NW, level, hi, U, (long long)out->rebuilt_ranks, (long long)out->solved, (tp[1] - tp[0]) * 1e3, (tp[2] - tp[1]) * 1e3, (tp[3] - tp[2]) * 1e3, (tp[4] - tp[3]) * 1e3);
     }
     out->done = true;
+    out->sent = sent;
     return 0;
 #undef GIVE_UP
 }

@@ -1214,6 +1214,7 @@ static int batch_joint_phase(RvBatchGroup *g, Workspace &ws) {
 }
 
 int rv_cascade_multi_run(rv_index *h, RvCascadeBufs &cb, int minl_in, RvCascadeMultiOut *out) {
+    RV_TRY(rv_ensure_working_text(h));      // (the decided anchors are lower-cased here, by this handle's stream or a batch leader's)
     out->done = false; out->levels = 0; out->cands = out->witnesses = out->children = out->undecided = out->rebuilt_ranks = 0; out->steps = 0; out->maxdepth = 0;
     out->why = nullptr; out->big = out->big_ranks = 0; out->an_l.clear(); out->an_pos.clear(); out->meta.clear(); out->node_first.clear(); out->nodes.clear(); out->d_sa = out->d_lcp = out->d_bwt = nullptr;
     Workspace &ws = h->ws;

@@ -382,7 +382,11 @@ int rv_inclusive_max_u64(Workspace &ws, const u64 *in, u64 *out, int64_t n);
 int rv_radix_passes(const Workspace &ws, int nbits);
 template <class V>
 int rv_radix_sort_pairs(Workspace &ws, u64 *k0, V *v0, u64 *k1, V *v1, int64_t n,
-                        int bit_lo, int bit_hi, int *result_in_1);
+                        int bit_lo, int bit_hi, int *result_in_1, bool first_digits = false);
+// Where a caller that makes the keys itself may leave the first pass' digit of every key -- (uint8_t)(key >> bit_lo), a byte per key in
+// the keys' order -- so that the sort's first histogram reads a byte per key instead of the key: the pointer (n + 64 bytes), or null when
+// this sort would not use them.  Nothing else may sort on this workspace in between; the sort is then called with first_digits = true.
+uint8_t *rv_radix_first_digits(Workspace &ws, int64_t n, int bit_lo, int bit_hi);
 
 // A few bytes the host needs before it can go on (counts that size the next launch): device -> pinned memory -> dst, waiting on
 // an event by polling.  A pageable destination is staged by the runtime and hipStreamSynchronize sleeps: ~35 us per read

@@ -80,6 +80,7 @@ __global__ __launch_bounds__(TB) void k_hist256(const uint8_t *__restrict__ T, i
     __syncthreads();
     const u32 tot = hh[threadIdx.x];
     if (tot) atomicAdd(&hist[threadIdx.x], tot);
+    if (blockIdx.x == 0 && threadIdx.x == 0) hist[257] = T[n - 1];      // the text's last byte rides along (rv_build_sa's shorter alphabet)
 }
 
 // ---- first key: K symbols as digits of a base-(sigma+1) number -----------------
@@ -341,6 +342,7 @@ __global__ __launch_bounds__(TB) void k_tw_count(const u64 *__restrict__ stop, i
     for (int d = 8; d >= 1; d >>= 1) c += __shfl_down(c, d, 16);      // KEY_TILE / 64 = 16 words per tile
     const int64_t tile = w >> 4;
     if ((threadIdx.x & 15) == 0 && tile < ntiles) tilecnt[tile] = c;
+    if (w == 0) tilecnt[ntiles] = 0;      // the extra slot: the scan over ntiles + 1 counts leaves the total there
 }
 // layout of the key's upper bits on the fused path: [0, bits) the sort key; [nd_shift, nd_shift + nd_bits) nd, all ones = not
 // known; bit nd_shift + nd_bits: the suffix is smaller than its twin; [at_shift, at_shift + at_bits) first stop among the K
@@ -453,7 +455,8 @@ __device__ inline void ik_fetch(IkFetch &f, const uint8_t *__restrict__ T, int64
 template <int G>
 __global__ __launch_bounds__(TB) void k_init_keys(const uint8_t *__restrict__ T, int64_t n, const uint8_t *__restrict__ lut, int K, KeyPack kp,
                                                   u64 *__restrict__ keys, sav_t *__restrict__ vals, int pay, u32 stop0, u32 stop1,
-                                                  KeyLayout ly, DiagBits dg, const u32 *__restrict__ tw_off /* != NULL: twins leave (k_tw_count's scan) */, int64_t ntiles) {
+                                                  KeyLayout ly, DiagBits dg, const u32 *__restrict__ tw_off /* != NULL: twins leave (k_tw_count's scan) */, int64_t ntiles,
+                                                  uint8_t *__restrict__ dig0 /* != NULL: every key's lowest byte beside it, the sort's first digit (rv_radix_first_digits) */) {
     __shared__ u32 code32[IK_WORDS + 2];
     __shared__ u32 s_sc[IK_WORDS / 8 + 3];      // bit k: code[k] is a stop
     __shared__ uint8_t slut[256], sstop[256];
@@ -584,6 +587,7 @@ __global__ __launch_bounds__(TB) void k_init_keys(const uint8_t *__restrict__ T,
                 key |= (u64)(known ? (u32)d | ((f >> 1) << ly.nd_bits) : (u32)nd_none) << ly.nd_shift;
             }
             keys[obase + j] = key; vals[obase + j] = (sav_t)i;
+            if (dig0) dig0[obase + j] = (uint8_t)key;
         }
     } else {
     // ---- every position of the tile: four in a row per thread ----
@@ -647,9 +651,10 @@ __global__ __launch_bounds__(TB) void k_init_keys(const uint8_t *__restrict__ T,
                 ulonglong2 *vd2 = reinterpret_cast<ulonglong2 *>(vals + i0);
                 vd2[0] = make_ulonglong2((u64)oval[0], (u64)oval[1]); vd2[1] = make_ulonglong2((u64)oval[2], (u64)oval[3]);
             }
+            if (dig0) *reinterpret_cast<u32 *>(dig0 + i0) = ((u32)okey[0] & 0xffu) | (((u32)okey[1] & 0xffu) << 8) | (((u32)okey[2] & 0xffu) << 16) | ((u32)okey[3] << 24);
         } else {
 #pragma unroll
-            for (int r = 0; r < PER; r++) if (i0 + r < n) { keys[i0 + r] = okey[r]; vals[i0 + r] = oval[r]; }
+            for (int r = 0; r < PER; r++) if (i0 + r < n) { keys[i0 + r] = okey[r]; vals[i0 + r] = oval[r]; if (dig0) dig0[i0 + r] = (uint8_t)okey[r]; }
         }
     } else {
         // the tile the second sample starts in
@@ -660,11 +665,12 @@ __global__ __launch_bounds__(TB) void k_init_keys(const uint8_t *__restrict__ T,
             if (i >= n) continue;
             const int xw = k >> 6, b = k & 63;
             const bool twin = (s_tw[xw] >> b) & 1ull;
-            if (i < dg.D) { keys[i] = okey[r]; vals[i] = (sav_t)i | (twin ? TW_FLAG : (sav_t)0); }
+            if (i < dg.D) { keys[i] = okey[r]; vals[i] = (sav_t)i | (twin ? TW_FLAG : (sav_t)0); if (dig0) dig0[i] = (uint8_t)okey[r]; }
             else if (!twin) {
                 // what stays of the second sample behind the first, in text order
                 const int64_t o = dg.D + (int64_t)tw_off[tile] + s_kpre[xw] + (u32)__popcll(s_keep[xw] & ((b == 0) ? 0ull : (~0ull >> (64 - b))));
                 keys[o] = okey[r]; vals[o] = (sav_t)i;
+                if (dig0) dig0[o] = (uint8_t)okey[r];
             }
         }
     }
@@ -1145,7 +1151,10 @@ __global__ __launch_bounds__(TB) void k_cp_count(const uint8_t *__restrict__ hea
     for (int d = 32; d >= 1; d >>= 1) c += __shfl_down(c, d, 64);
     if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
     __syncthreads();
-    if (threadIdx.x == 0) tilecnt[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    if (threadIdx.x == 0) {
+        tilecnt[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+        if (blockIdx.x + 1 == gridDim.x) tilecnt[gridDim.x] = 0;      // the extra slot: the scan over one count more leaves the total there
+    }
 }
 
 // emit: P[q] = position in SA, S[q] = suffix, G[q] = group rank.
@@ -1200,6 +1209,7 @@ __global__ __launch_bounds__(TB) void k_cp_count_g(const uint8_t *__restrict__ h
     __syncthreads();
     if (threadIdx.x == 0) {
         tilecnt[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+        if (blockIdx.x + 1 == gridDim.x) tilecnt[gridDim.x] = 0;      // the extra slot (see k_cp_count)
         u32 l = wlast[0];
         for (int k = 1; k < TB / 64; k++) l = wlast[k] > l ? wlast[k] : l;
         tilelast[blockIdx.x] = l;
@@ -2150,7 +2160,10 @@ __global__ __launch_bounds__(TB) void k_flag_count(const uint8_t *__restrict__ f
     for (int d = 32; d >= 1; d >>= 1) c += __shfl_down(c, d, 64);
     if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
     __syncthreads();
-    if (threadIdx.x == 0) tilecnt[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    if (threadIdx.x == 0) {
+        tilecnt[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+        if (blockIdx.x + 1 == gridDim.x) tilecnt[gridDim.x] = 0;      // the extra slot: the scan over one count more leaves the total there
+    }
 }
 __global__ __launch_bounds__(TB) void k_flag_emit(const uint8_t *__restrict__ flag, int64_t n, const u32 *__restrict__ tileoff,
                                                   const u32 *__restrict__ P, const sav_t *__restrict__ S, const u32 *__restrict__ G, int64_t nn, int64_t h,
@@ -2514,7 +2527,7 @@ int rv_build_sa(Workspace &ws, const uint8_t *T, int64_t n, sa_t *SA, RvSaStats 
         hipLaunchKernelGGL(k_hist256, dim3((unsigned)blocks), dim3(TB), 0, q, T, n, d_hist.as<u32>());
         RV_LAUNCH_CHECK();
     }
-    u32 hist[257];
+    u32 hist[258];      // 256 bytes' counts, the adjacent separators, the text's last byte
     RV_TRY(rv_read_back(ws, hist, d_hist.p, sizeof hist));
     uint8_t lut[256];
     int sigma = 0;
@@ -2531,7 +2544,7 @@ int rv_build_sa(Workspace &ws, const uint8_t *T, int64_t n, sa_t *SA, RvSaStats 
     // it that far stand in front of another '$' -- they go on with a larger character, so the order is the same and no two keys tie on padding.
     const bool short_alphabet = sigma >= 2 && sigma < 255 && T != nullptr && hist[(uint8_t)'$'] > 0 && lut[(uint8_t)'$'] == 1 && hist[256] == 0 && !ws.opt.no_short_alphabet;
     bool ends_with_sep = false;
-    if (short_alphabet) { uint8_t last = 0; RV_TRY(rv_read_back(ws, &last, T + (n - 1), 1)); ends_with_sep = last == (uint8_t)'$'; }
+    if (short_alphabet) ends_with_sep = hist[257] == (u32)(uint8_t)'$';
     if (short_alphabet && ends_with_sep) {
         for (int c = 0; c < 256; c++) lut[c] = hist[c] ? (uint8_t)(lut[c] - 1) : (uint8_t)0;      // (absent bytes are never looked up)
         radix = (u32)sigma;       // code 0 = '$' = past the end
@@ -2658,8 +2671,7 @@ int rv_build_sa(Workspace &ws, const uint8_t *T, int64_t n, sa_t *SA, RvSaStats 
         // what stays of the second sample in the sort, along the diagonals the bit arrays describe right now
         auto count_kept = [&](int tab, u32 *kept_out) -> int {
             hipLaunchKernelGGL(k_tw_count, dim3((unsigned)ceil_div(nw, TB)), dim3(TB), 0, q, (const u64 *)dg.stop, nw, K, kd.D, n, tc, ntiles, tab);
-            RV_LAUNCH_CHECK();
-            RV_HIP(hipMemsetAsync(tc + ntiles, 0, 4, q));
+            RV_LAUNCH_CHECK();      // (tc[ntiles] = 0 comes from the kernel)
             RV_TRY(rv_exclusive_sum_u32(ws, tc, tc, ntiles + 1));
             return rv_read_back(ws, kept_out, tc + ntiles, 4);
         };
@@ -2703,11 +2715,13 @@ int rv_build_sa(Workspace &ws, const uint8_t *T, int64_t n, sa_t *SA, RvSaStats 
         tw_off = tc;
         s.diag_table = dg.tab;
     }
+    uint8_t *dig0 = nullptr;
     {
         const int64_t iktiles = ceil_div(n, KEY_TILE);
         const dim3 ig((unsigned)std::min<int64_t>(iktiles, 256 * 8));      // persistent: eight workgroups of four waves per CU
+        dig0 = rv_radix_first_digits(ws, nsort, 0, bits);      // (the kernel has every key in registers: the sort's first histogram need not read them back)
 #define RV_IK_(G) hipLaunchKernelGGL(k_init_keys<G>, ig, dim3(TB), 0, q, T, n, d_lut.as<uint8_t>(), K, kp, bk0.as<u64>(), bv0.as<sav_t>(), fused ? 1 : 0, \
-                                     kd.stop0, kd.stop1, kd.ly, dg, tw_off, iktiles)
+                                     kd.stop0, kd.stop1, kd.ly, dg, tw_off, iktiles, dig0)
         const int ikid = ws.prof_begin(12 /* RV_K_INIT_KEYS */, (double)n + (double)nsort * (8.0 + sizeof(sav_t) + 1.0));
         switch (kp.g) { case 1: RV_IK_(1); break; case 2: RV_IK_(2); break; case 3: RV_IK_(3); break; case 4: RV_IK_(4); break; default: RV_IK_(5); break; }
         ws.prof_end(ikid);
@@ -2715,7 +2729,7 @@ int rv_build_sa(Workspace &ws, const uint8_t *T, int64_t n, sa_t *SA, RvSaStats 
     }
     SA_HIP(hipGetLastError());
     int in1 = 0;
-    SA_TRY(rv_radix_sort_pairs<sav_t>(ws, bk0.as<u64>(), bv0.as<sav_t>(), bk1.as<u64>(), bv1.as<sav_t>(), nsort, 0, bits, &in1));
+    SA_TRY(rv_radix_sort_pairs<sav_t>(ws, bk0.as<u64>(), bv0.as<sav_t>(), bk1.as<u64>(), bv1.as<sav_t>(), nsort, 0, bits, &in1, dig0 != nullptr));
     s.radix_passes += rv_radix_passes(ws, bits); s.sorted_elems += nsort;
     u64 *ks = in1 ? bk1.as<u64>() : bk0.as<u64>();
     sav_t *vs = in1 ? bv1.as<sav_t>() : bv0.as<sav_t>();
@@ -2788,8 +2802,7 @@ int rv_build_sa(Workspace &ws, const uint8_t *T, int64_t n, sa_t *SA, RvSaStats 
         const int64_t nt = ceil_div(len, CP_TILE);
         hipLaunchKernelGGL(k_cp_count, dim3((unsigned)nt), dim3(TB), 0, q, hd, len, tile);
         RV_LAUNCH_CHECK();
-        // one extra slot so the scan also yields the total
-        RV_HIP(hipMemsetAsync(tile + nt, 0, 4, q));
+        // one extra slot so the scan also yields the total: zeroed by the kernel
         RV_TRY(rv_exclusive_sum_u32(ws, tile, tile, nt + 1));
         u32 tot = 0;
         RV_TRY(rv_read_back(ws, &tot, tile + nt, 4));
@@ -2812,7 +2825,6 @@ int rv_build_sa(Workspace &ws, const uint8_t *T, int64_t n, sa_t *SA, RvSaStats 
         u32 *tlast = tile + (ntile + 1);
         hipLaunchKernelGGL(k_cp_count_g, dim3((unsigned)ntile), dim3(TB), 0, q, (const uint8_t *)head, n, tile, tlast);
         SA_HIP(hipGetLastError());
-        SA_HIP(hipMemsetAsync(tile + ntile, 0, 4, q));
         SA_TRY(rv_exclusive_sum_u32(ws, tile, tile, ntile + 1));
         SA_TRY(rv_inclusive_max_u32(ws, tlast, tlast, ntile));
         u32 tot = 0;
@@ -2973,7 +2985,6 @@ int rv_build_sa(Workspace &ws, const uint8_t *T, int64_t n, sa_t *SA, RvSaStats 
             const int64_t nt = ceil_div(m, CP_TILE);
             hipLaunchKernelGGL(k_flag_count, dim3((unsigned)nt), dim3(TB), 0, q, (const uint8_t *)bigflag, m, tile);
             SA_HIP(hipGetLastError());
-            SA_HIP(hipMemsetAsync(tile + nt, 0, 4, q));
             SA_TRY(rv_exclusive_sum_u32(ws, tile, tile, nt + 1));
             u32 mbig = 0;
             SA_TRY(rv_read_back(ws, &mbig, tile + nt, 4));

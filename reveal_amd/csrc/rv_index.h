@@ -132,6 +132,11 @@ struct rv_index {
     // ---- device state
     DBuf dT, dT0, dSA, dSAi, dLCP, dBWT, dNsep;   // dT0 = pristine text, dT = working copy (lower-cased by align)
     bool text_dirty = true;
+    // The working copy is made when something first needs it (rv_ensure_working_text): construct() builds the index from dT0 and only marks
+    // it as due -- in a construct() + align the 2 x (n + 64) bytes of the copy run beside the cascade's small kernels instead of in front of
+    // the SA build.  dT_inflight: queued on a side stream (rv_working_text_begin), ev_text behind it.
+    bool dT_pending = false, dT_inflight = false;
+    hipEvent_t ev_text = nullptr, ev_text_in = nullptr;
     bool text_only = false;            // a worker of a divided alignment: text and shared inverse in HBM, no main SA / LCP
     HBuf hscan;                        // pinned staging for the scan records
     HBuf hupload;                      // two pinned chunks for the text's way into HBM (rv_upload)
@@ -176,6 +181,13 @@ int rv_text_only(rv_index *h, u32 maxlcp);
 // untraced built-in recursion (the split writes the windows of the shared inverse that bubble_sort reads) needs it, so it is
 // made when somebody asks: the SAi getter, copy(), the detached-index steps, and align() with callbacks / tracing (rv_api.hip).
 int rv_need_sai(rv_index *h);
+
+// dT as the handle's stream may read and write it: makes the copy of dT0 when it is still due, or lets the stream wait for the one a
+// side stream is making.  Everything that touches dT calls it first.
+int rv_ensure_working_text(rv_index *h);
+// the copy that is due on `side` instead, behind everything queued on the handle's stream so far; the handle's stream does not wait
+// for it before rv_ensure_working_text.  Nothing happens when no copy is due.
+int rv_working_text_begin(rv_index *h, hipStream_t side);
 
 // rv_align.hip
 void rv_align_free(rv_index *h);

@@ -369,6 +369,8 @@ int many_round(rv_many *m, const std::vector<int> &order, size_t lo, size_t hi, 
     m->info[4] += st.levels + (m->recs.size() > rec0 ? 2 : 0);      // leaf launches, and the two of the lower-casing when there are anchors
     // final text of every job: a$b$
     std::vector<char> txt((size_t)n);
+    RV_TRY(rv_ensure_working_text(h));
+    RV_HIP(hipStreamSynchronize(h->ws.stream));
     RV_HIP(hipMemcpy(txt.data(), h->dT.p, (size_t)n, hipMemcpyDeviceToHost));
     for (size_t s = 0; s < J; s++) {
         ManyJob &jb = m->jobs[(size_t)ord[s]];

@@ -347,8 +347,17 @@ int rv_radix_passes(const Workspace &ws, int nbits) {
     return nbits <= 0 ? 0 : (nbits + w - 1) / w;
 }
 
+// the digits of the next pass as a byte per key (8-bit digits, inputs large enough for the saved reads to matter)
+static bool rs_digit_bytes(const Workspace &ws, int64_t n, int bit_lo, int bit_hi) {
+    return ws.opt.rs_bits != 10 && !ws.opt.rs_no_digit_bytes && n > 1 && n >= ((int64_t)1 << 20) && n < ((int64_t)1 << 32) && bit_hi - bit_lo > 8;
+}
+uint8_t *rv_radix_first_digits(Workspace &ws, int64_t n, int bit_lo, int bit_hi) {
+    if (!rs_digit_bytes(ws, n, bit_lo, bit_hi) || ws.rs_digits.reserve((size_t)n + 64)) return nullptr;
+    return ws.rs_digits.as<uint8_t>();
+}
+
 template <class V>
-int rv_radix_sort_pairs(Workspace &ws, u64 *k0, V *v0, u64 *k1, V *v1, int64_t n, int bit_lo, int bit_hi, int *result_in_1) {
+int rv_radix_sort_pairs(Workspace &ws, u64 *k0, V *v0, u64 *k1, V *v1, int64_t n, int bit_lo, int bit_hi, int *result_in_1, bool first_digits) {
     *result_in_1 = 0;
     if (n <= 1 || bit_hi <= bit_lo) return 0;
     if (n >= ((int64_t)1 << 32)) { rv_set_error("radix sort: n >= 2^32 not supported"); return -1; }
@@ -357,11 +366,11 @@ int rv_radix_sort_pairs(Workspace &ws, u64 *k0, V *v0, u64 *k1, V *v1, int64_t n
     const u32 nb = (u32)ceil_div(n, RS_TILE);
     RV_TRY(ws.rs_hist.reserve(((size_t)1 << width) * nb * sizeof(u32)));
     u32 *bh = ws.rs_hist.as<u32>();
-    // the digits of the next pass as a byte per key (8-bit digits, inputs large enough for the saved reads to matter)
-    const bool bytes = width == 8 && !ws.opt.rs_no_digit_bytes && n >= ((int64_t)1 << 20) && bit_hi - bit_lo > width;
+    const bool bytes = rs_digit_bytes(ws, n, bit_lo, bit_hi);
+    if (first_digits && (!bytes || ws.rs_digits.cap < (size_t)n + 64)) { rv_set_error("radix sort: first digits announced but the byte path is off"); return -1; }
     if (bytes) RV_TRY(ws.rs_digits.reserve((size_t)n + 64));
     uint8_t *dig = bytes ? ws.rs_digits.as<uint8_t>() : nullptr;
-    bool have_digits = false;
+    bool have_digits = first_digits;      // (the caller left the first pass' digits where a scatter leaves the next pass')
     u64 *ki = k0, *ko = k1;
     V *vi = v0, *vo = v1;
     int flip = 0;
@@ -429,5 +438,5 @@ int rv_h2d_copy(Workspace &ws, const void *pinned_src, void *dst, size_t bytes) 
     return 0;
 }
 
-template int rv_radix_sort_pairs<u32>(Workspace &, u64 *, u32 *, u64 *, u32 *, int64_t, int, int, int *);
-template int rv_radix_sort_pairs<u64>(Workspace &, u64 *, u64 *, u64 *, u64 *, int64_t, int, int, int *);
+template int rv_radix_sort_pairs<u32>(Workspace &, u64 *, u32 *, u64 *, u32 *, int64_t, int, int, int *, bool);
+template int rv_radix_sort_pairs<u64>(Workspace &, u64 *, u64 *, u64 *, u64 *, int64_t, int, int, int *, bool);
