@@ -458,6 +458,9 @@ void rv_batch_free(rv_batch *b);
  * leaf kernel.  Every other job -- more than two sequences (each a sample of its own), more than 2048 ranks -- runs the ordinary way inside the same
  * call (construct + rv_align_builtin on one internal handle, rv_reset in between).  The built-in picker only (as rv_align_builtin).  A job's result is
  * what rv_align_builtin gives a stand-alone index of its sequences, in that index' coordinates (text `s0$s1$..`).
+ * With RV_MANY_MULTI set (off by default) the jobs of 3 .. 16 sequences with at most 2048 ranks (sum of lengths + k) and no NUL byte share their launches
+ * too, in rounds of their own: every job contiguous in the round's text (s0$s1$..s(k-1)$, job after job), the same index build, then ONE launch of a leaf
+ * kernel that runs the whole recursion of a job in one workgroup (rv_leaf_multi.hip: one interval per sample in a frame) and lower-cases its text.
  *   rv_many_add     a job of k >= 2 non-empty sequences -> its id (0, 1, ..), < 0 on error (an empty sequence, k < 2, non-ASCII bytes)
  *   rv_many_clear   forgets the jobs and results, keeps every allocation for the next batch
  *   rv_many_run     runs every job; *total (may be NULL) = the sums of the runs' statistics.  A text beyond the 32-bit library's position limit (or
@@ -468,8 +471,9 @@ void rv_batch_free(rv_batch *b);
  *   rv_many_info    out[0] jobs, out[1] jobs built and finished by the shared launches, out[2] jobs through the ordinary path, out[3] rounds,
  *                   out[4] kernel launches of the shared part of the last run (index build, leaf kernel, lower-casing; copies not counted)
  *   rv_many_option  RV_MANY_KEEP (test hook: keep SA / LCP of the shared-launch jobs for rv_many_arrays), RV_MANY_ROUND (positions per round),
- *                   RV_MANY_WAVE_MAX (ranks up to which a wavefront builds a job, at most 512; above: a workgroup); any other name: rv_set_option on
- *                   the internal handles
+ *                   RV_MANY_WAVE_MAX (ranks up to which a wavefront builds a job, at most 512; above: a workgroup), RV_MANY_MULTI (0 / 1: jobs of
+ *                   3 .. 16 sequences through shared launches; they count in out[1] then), RV_MANY_STAGE (test hook: anchors such a job stages in LDS,
+ *                   at most 256); any other name: rv_set_option on the internal handles
  *   rv_many_arrays  test hook: which = RV_SA / RV_LCP of a shared-launch job in job-local positions, native element width; -2: not kept */
 typedef struct rv_many rv_many;
 rv_many *rv_many_new(int device);       /* NULL on failure */

@@ -1,0 +1,28 @@
+// rv_leaf_multi.h -- host interface of the leaf kernel for jobs of several samples (rv_leaf_multi.hip)
+#pragma once
+#include "rv_common.h"
+#include "rv_leaf.h"
+
+#define RV_MANY_KMAX 16        // samples of a job the kernel takes (one interval per sample and frame)
+
+// a job of rv_many: k sequences, every one a sample, `s0$s1$..s(k-1)$` contiguous in the round's text; its n <= RV_LEAF_N ranks
+// lie at the same offset of the index arrays
+struct RvLeafMultiJob { int64_t beg; int32_t n, pad; };
+
+// anchor k of a launch: length l, n members an_pos[moff .. moff + n) ascending, positions local to job `job`
+struct RvLeafMultiAnchor { u32 l, job, n, moff; };
+
+struct RvLeafMultiArgs {
+    const RvLeafMultiJob *jobs;
+    const sa_t *SA; const lcp_t *LCP; const uint8_t *BWT;    // of the round (read only); SA in positions of the round's text
+    uint8_t *T;                                              // the round's text: the kernel lower-cases what it anchors
+    int minl, minn;
+    u32 stage_cap;                                           // anchors a workgroup stages in LDS before it writes them out (<= 256)
+    unsigned long long *count;                               // anchors << 32 | members: one reservation takes both
+    u32 anchor_cap, member_cap;
+    RvLeafMultiAnchor *anchors; uint16_t *an_pos;
+    unsigned long long *stats;                               // [0] sub-indices visited, [1] anchors, [2] anchored bp, [3] max depth
+    u32 *err;                                                // 4: stack full, 8: a sub-index is not the suffixes of its intervals, 16: a bad job, 32: output full
+};
+
+int rv_leaf_multi_launch(hipStream_t q, const RvLeafMultiArgs &a, int njobs);

@@ -11,6 +11,14 @@
 // Jobs the shared launches do not take (more than two sequences, more than RV_LEAF_N ranks) run the ordinary way -- construct() +
 // rv_align_builtin -- on one internal handle reused with rv_reset.
 //
+// RV_MANY_MULTI (off by default): the jobs of 3 .. RV_MANY_KMAX sequences with at most RV_LEAF_N ranks (sum of lengths + k) and no NUL
+// byte share their launches as well, in rounds of their own (many_round_multi):
+//   text     every job contiguous, s0$s1$..s(k-1)$, job after job: a position minus the job's begin is its stand-alone coordinate
+//   build    k_many_build as it is: to it such a job is its first sequence and "the rest" -- the job-local text is the stand-alone
+//            text whatever '$' it holds (the side bit of the BWT byte means nothing here; the leaf kernel masks it)
+//   finish   ONE launch of k_leaf_multi (rv_leaf_multi.hip) over the built segments: a job's whole recursion in one workgroup, one
+//            interval per sample in a frame; it lower-cases the text itself.  No frontier, no handle: three launches per round
+//
 // k_many_build, per job (n = la + lb + 2 <= 2048 ranks, local positions in 16 bits):
 //   order    prefix doubling: first key = six text bytes (past the end: 0, so a suffix that is a prefix of another sorts first and
 //            suffixes that tie through a '$' come out in the stand-alone order), then keys (rank[i], rank[i + h]), h = 6, 12, 24 ..
@@ -24,6 +32,7 @@
 // seven workgroups per CU.
 #include "rv_index.h"
 #include "rv_leaf.h"
+#include "rv_leaf_multi.h"
 #include <algorithm>
 #include <limits.h>
 #include <new>
@@ -209,6 +218,7 @@ struct rv_many {
     std::vector<int64_t> lens, starts;
     std::vector<ManyJob> jobs;
     int64_t keep = 0, round_max = (int64_t)1 << 27, wave_max = CAP_S;
+    int64_t multi = 0, stage = 256;             // RV_MANY_MULTI, RV_MANY_STAGE
     std::vector<std::pair<std::string, int64_t>> fwd;      // switches for the internal handles
     // results of the last run
     bool ran = false;
@@ -218,6 +228,7 @@ struct rv_many {
     std::vector<sa_t> keep_sa; std::vector<lcp_t> keep_lcp;
     int64_t info[5] = {0, 0, 0, 0, 0};
     DBuf dJobs, dSA, dLCP, dBWT, dCnt;
+    DBuf dTxt, dMJobs, dAn, dAnPos;             // rounds of multi-sequence jobs: their text, jobs, anchors
     // scratch of a run
     std::vector<ManyRec> recs; std::vector<int64_t> rpos;
 };
@@ -266,6 +277,23 @@ void many_add_stats(rv_align_stats *t, const rv_align_stats &s) {
     t->steps += s.steps; t->splits += s.splits; t->anchored_bp += s.anchored_bp; t->levels += s.levels;
     if (s.maxdepth > t->maxdepth) t->maxdepth = s.maxdepth;
     t->scanned_ranks += s.scanned_ranks; t->t_scan += s.t_scan; t->t_host += s.t_host; t->t_split += s.t_split; t->t_bubble += s.t_bubble;
+}
+
+// the index build of a round: the jobs [0, nsmall) a wavefront each, the others a workgroup each
+int many_build(rv_many *m, hipStream_t q, const ManyDevJob *djobs, size_t J, size_t nsmall, const uint8_t *dT, u32 *d_max, u32 *d_err) {
+    if (nsmall) {
+        hipLaunchKernelGGL((k_many_build<CAP_S, 64>), dim3((unsigned)ceil_div((int64_t)nsmall, MT / 64)), dim3(MT), 0, q, djobs, (int)nsmall, dT,
+                           m->dSA.as<sa_t>(), m->dLCP.as<lcp_t>(), m->dBWT.as<uint8_t>(), d_max, d_err);
+        RV_LAUNCH_CHECK();
+        m->info[4]++;
+    }
+    if (nsmall < J) {
+        hipLaunchKernelGGL((k_many_build<CAP_L, MT>), dim3((unsigned)(J - nsmall)), dim3(MT), 0, q, djobs + nsmall, (int)(J - nsmall), dT,
+                           m->dSA.as<sa_t>(), m->dLCP.as<lcp_t>(), m->dBWT.as<uint8_t>(), d_max, d_err);
+        RV_LAUNCH_CHECK();
+        m->info[4]++;
+    }
+    return 0;
 }
 
 // one round of the shared launches: the jobs order[lo .. hi) (ascending size)
@@ -327,18 +355,7 @@ int many_round(rv_many *m, const std::vector<int> &order, size_t lo, size_t hi, 
     u32 *d_max = m->dCnt.as<u32>(), *d_err = d_max + 1;
     const ManyDevJob *djobs = m->dJobs.as<ManyDevJob>();
     const uint8_t *dT = h->dT0.as<uint8_t>();
-    if (nsmall) {
-        hipLaunchKernelGGL((k_many_build<CAP_S, 64>), dim3((unsigned)ceil_div((int64_t)nsmall, MT / 64)), dim3(MT), 0, q, djobs, (int)nsmall, dT,
-                           m->dSA.as<sa_t>(), m->dLCP.as<lcp_t>(), m->dBWT.as<uint8_t>(), d_max, d_err);
-        RV_LAUNCH_CHECK();
-        m->info[4]++;
-    }
-    if (nsmall < J) {
-        hipLaunchKernelGGL((k_many_build<CAP_L, MT>), dim3((unsigned)(J - nsmall)), dim3(MT), 0, q, djobs + nsmall, (int)(J - nsmall), dT,
-                           m->dSA.as<sa_t>(), m->dLCP.as<lcp_t>(), m->dBWT.as<uint8_t>(), d_max, d_err);
-        RV_LAUNCH_CHECK();
-        m->info[4]++;
-    }
+    RV_TRY(many_build(m, q, djobs, J, nsmall, dT, d_max, d_err));
     u32 cnt[2] = {0, 0};
     RV_TRY(rv_read_back(h->ws, cnt, d_max, 8));
     if (cnt[1]) { rv_set_error("rv_many_run: the index build refused a job (error bits %u)", cnt[1]); return -1; }
@@ -383,6 +400,117 @@ int many_round(rv_many *m, const std::vector<int> &order, size_t lo, size_t hi, 
     return 0;
 }
 
+// one round of jobs of three and more sequences (RV_MANY_MULTI): the jobs order[lo .. hi) (ascending size).  Every job is laid out
+// contiguously, s0$s1$..s(k-1)$, job after job: a job's ranks lie where its text lies, and a position minus the job's begin is its
+// stand-alone coordinate.  k_many_build sees such a job as its first sequence and "the rest" (the side bit of the BWT byte means
+// nothing here); k_leaf_multi then finishes every job in one workgroup and lower-cases its text.  No handle is involved beyond
+// the stream and the read-back buffer of the shared one: the launches of a round do not depend on the number of jobs.
+int many_round_multi(rv_many *m, const std::vector<int> &order, size_t lo, size_t hi, int minl, int minn, rv_align_stats *total) {
+    RV_TRY(many_handle(m, &m->hs));
+    rv_index *h = m->hs;
+    const size_t J = hi - lo;
+    std::vector<ManyDevJob> dj(J);
+    std::vector<RvLeafMultiJob> mj(J);
+    int64_t n = 0;
+    size_t nsmall = 0;
+    for (size_t s = 0; s < J; s++) n += m->jobs[(size_t)order[lo + s]].ranks;
+    std::vector<char> txt((size_t)n);
+    int64_t at = 0;
+    for (size_t s = 0; s < J; s++) {
+        const ManyJob &jb = m->jobs[(size_t)order[lo + s]];
+        const int64_t la = m->lens[jb.seq0];
+        dj[s].abeg = at; dj[s].bbeg = at + la + 1; dj[s].off = at; dj[s].la = (int32_t)la; dj[s].lb = (int32_t)(jb.ranks - la - 2);
+        mj[s].beg = at; mj[s].n = (int32_t)jb.ranks; mj[s].pad = 0;
+        if (jb.ranks <= m->wave_max && jb.ranks <= CAP_S) nsmall = s + 1;      // (ascending sizes: the small class is a prefix)
+        for (int q = 0; q < jb.k; q++) {
+            const int64_t len = m->lens[jb.seq0 + (size_t)q];
+            memcpy(txt.data() + at, m->in.data() + m->starts[jb.seq0 + (size_t)q], (size_t)len);
+            txt[(size_t)(at + len)] = '$';
+            at += len + 1;
+        }
+    }
+    if (at != n) { rv_set_error("rv_many_run: the jobs' ranks do not add up to the text"); return -1; }
+    hipStream_t q = h->ws.stream;
+    // anchors cover disjoint text, and a member at least one position: at most n members, n / 2 anchors
+    const u32 acap = (u32)(n / 2 + 1), mcap = (u32)n;
+    RV_TRY(m->dJobs.reserve(J * sizeof(ManyDevJob)));
+    RV_TRY(m->dMJobs.reserve(J * sizeof(RvLeafMultiJob)));
+    RV_TRY(m->dTxt.reserve((size_t)n + 64));
+    RV_TRY(m->dSA.reserve((size_t)(n + 64) * sizeof(sa_t)));
+    RV_TRY(m->dLCP.reserve((size_t)(n + 64) * sizeof(lcp_t)));
+    RV_TRY(m->dBWT.reserve((size_t)n + 64));
+    RV_TRY(m->dAn.reserve((size_t)acap * sizeof(RvLeafMultiAnchor)));
+    RV_TRY(m->dAnPos.reserve((size_t)mcap * sizeof(uint16_t)));
+    RV_TRY(m->dCnt.reserve(64));
+    RV_HIP(hipMemcpyAsync(m->dJobs.p, dj.data(), J * sizeof(ManyDevJob), hipMemcpyHostToDevice, q));
+    RV_HIP(hipMemcpyAsync(m->dMJobs.p, mj.data(), J * sizeof(RvLeafMultiJob), hipMemcpyHostToDevice, q));
+    RV_HIP(hipMemcpyAsync(m->dTxt.p, txt.data(), (size_t)n, hipMemcpyHostToDevice, q));
+    RV_HIP(hipMemsetAsync(m->dCnt.p, 0, 64, q));
+    // dCnt: [0] max LCP, [1] error bits of the build, [2] of the leaf kernel, [4..5] anchors << 32 | members, [6..13] statistics
+    u32 *d_max = m->dCnt.as<u32>(), *d_err = d_max + 1;
+    RV_TRY(many_build(m, q, m->dJobs.as<ManyDevJob>(), J, nsmall, m->dTxt.as<uint8_t>(), d_max, d_err));
+    RvLeafMultiArgs a;
+    a.jobs = m->dMJobs.as<RvLeafMultiJob>();
+    a.SA = m->dSA.as<sa_t>(); a.LCP = m->dLCP.as<lcp_t>(); a.BWT = m->dBWT.as<uint8_t>(); a.T = m->dTxt.as<uint8_t>();
+    a.minl = minl; a.minn = minn; a.stage_cap = (u32)std::min<int64_t>(m->stage, 256);
+    a.count = (unsigned long long *)(d_max + 4); a.anchor_cap = acap; a.member_cap = mcap;
+    a.anchors = m->dAn.as<RvLeafMultiAnchor>(); a.an_pos = m->dAnPos.as<uint16_t>();
+    a.stats = (unsigned long long *)(d_max + 6); a.err = d_max + 2;
+    RV_TRY(rv_leaf_multi_launch(q, a, (int)J));
+    m->info[4]++;
+    u32 cnt[16];
+    RV_TRY(rv_read_back(h->ws, cnt, d_max, sizeof cnt));
+    if (cnt[1]) { rv_set_error("rv_many_run: the index build refused a job (error bits %u)", cnt[1]); return -1; }
+    if (cnt[2]) { rv_set_error("rv_many_run: the leaf kernel for jobs of several sequences failed (error bits %u: 4 stack, 8 intervals, 16 job, 32 output)", cnt[2]); return -1; }
+    unsigned long long both, st4[4];
+    memcpy(&both, cnt + 4, 8); memcpy(st4, cnt + 6, 32);
+    const size_t na = (size_t)(both >> 32), nm = (size_t)(both & 0xFFFFFFFFull);
+    if (na > acap || nm > mcap) { rv_set_error("rv_many_run: more anchors than the text has room for"); return -1; }
+    std::vector<RvLeafMultiAnchor> an(std::max<size_t>(na, 1)); std::vector<uint16_t> ap(std::max<size_t>(nm, 1));
+    std::vector<sa_t> sa; std::vector<lcp_t> lc;
+    if (na) RV_HIP(hipMemcpyAsync(an.data(), m->dAn.p, na * sizeof(RvLeafMultiAnchor), hipMemcpyDeviceToHost, q));
+    if (nm) RV_HIP(hipMemcpyAsync(ap.data(), m->dAnPos.p, nm * sizeof(uint16_t), hipMemcpyDeviceToHost, q));
+    if (m->keep) {
+        sa.resize((size_t)n); lc.resize((size_t)n);
+        RV_HIP(hipMemcpyAsync(sa.data(), m->dSA.p, (size_t)n * sizeof(sa_t), hipMemcpyDeviceToHost, q));
+        RV_HIP(hipMemcpyAsync(lc.data(), m->dLCP.p, (size_t)n * sizeof(lcp_t), hipMemcpyDeviceToHost, q));
+    }
+    const size_t tbase = m->out_text.size();
+    m->out_text.resize(tbase + (size_t)n);
+    RV_HIP(hipMemcpyAsync(m->out_text.data() + tbase, m->dTxt.p, (size_t)n, hipMemcpyDeviceToHost, q));
+    RV_HIP(hipStreamSynchronize(q));
+    for (size_t k = 0; k < na; k++) {
+        const RvLeafMultiAnchor &r = an[k];
+        if (r.job >= J || r.n < 2 || r.n > (u32)RV_MANY_KMAX || (size_t)r.moff + r.n > nm) { rv_set_error("rv_many_run: a malformed anchor"); return -1; }
+        const int64_t ranks = mj[r.job].n;
+        ManyRec rec; rec.job = order[lo + r.job]; rec.l = r.l; rec.np = (int)r.n; rec.p0 = (int64_t)m->rpos.size();
+        for (u32 x = 0; x < r.n; x++) {
+            const int64_t p = ap[(size_t)r.moff + x];
+            if (p + r.l > ranks) { rv_set_error("rv_many_run: an anchor outside its job"); return -1; }
+            m->rpos.push_back(p);
+        }
+        m->recs.push_back(rec);
+    }
+    const size_t kbase = m->keep_sa.size();
+    if (m->keep) {
+        // test hook: SA / LCP of every job in job-local positions
+        m->keep_sa.resize(kbase + (size_t)n); m->keep_lcp.resize(kbase + (size_t)n);
+        for (size_t s = 0; s < J; s++)
+            for (int64_t r = mj[s].beg; r < mj[s].beg + mj[s].n; r++) { m->keep_sa[kbase + (size_t)r] = (sa_t)(sa[(size_t)r] - (sa_t)mj[s].beg); m->keep_lcp[kbase + (size_t)r] = lc[(size_t)r]; }
+    }
+    for (size_t s = 0; s < J; s++) {
+        ManyJob &jb = m->jobs[(size_t)order[lo + s]];
+        jb.text_off = (int64_t)tbase + mj[s].beg; jb.shared = true;
+        if (m->keep) jb.arr_off = (int64_t)kbase + mj[s].beg;
+    }
+    rv_align_stats st;
+    memset(&st, 0, sizeof st);
+    st.steps = (int64_t)st4[0]; st.splits = (int64_t)st4[1]; st.anchored_bp = (int64_t)st4[2]; st.maxdepth = (int)st4[3]; st.levels = 1; st.scanned_ranks = n;
+    many_add_stats(total, st);
+    m->info[1] += (int64_t)J; m->info[3]++;
+    return 0;
+}
+
 // a job the shared launches do not take: construct() + rv_align_builtin on the reused handle, every sequence a sample
 int many_ordinary(rv_many *m, int job, int minl, int minn, rv_align_stats *total) {
     RV_TRY(many_handle(m, &m->ho));
@@ -416,19 +544,29 @@ int many_run(rv_many *m, int minl, int minn, rv_align_stats *total) {
     if (total) memset(total, 0, sizeof *total);
     const int nj = (int)m->jobs.size();
     m->info[0] = nj;
-    std::vector<int> order, rest;
+    std::vector<int> order, morder, rest;
     for (int j = 0; j < nj; j++) {
         ManyJob &jb = m->jobs[(size_t)j];
         jb.arr_off = -1;
-        if (jb.k == 2 && jb.ranks <= RV_LEAF_N && jb.clean) order.push_back(j); else rest.push_back(j);
+        if (jb.k == 2 && jb.ranks <= RV_LEAF_N && jb.clean) order.push_back(j);
+        else if (m->multi && jb.k >= 3 && jb.k <= RV_MANY_KMAX && jb.ranks <= RV_LEAF_N && jb.clean) morder.push_back(j);
+        else rest.push_back(j);
     }
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return m->jobs[(size_t)a].ranks < m->jobs[(size_t)b].ranks; });
+    const auto by_size = [&](int a, int b) { return m->jobs[(size_t)a].ranks < m->jobs[(size_t)b].ranks; };
+    std::stable_sort(order.begin(), order.end(), by_size);
+    std::stable_sort(morder.begin(), morder.end(), by_size);
     // rounds: a round's text stays below the 32-bit library's position limit (and a bound on the device memory of a round)
     const int64_t lim = std::max<int64_t>(std::min<int64_t>(m->round_max, (int64_t)INT_MAX - 4096), 1);
     for (size_t lo = 0; lo < order.size();) {
         size_t hi = lo; int64_t sum = 0;
         while (hi < order.size() && (hi == lo || sum + m->jobs[(size_t)order[hi]].ranks <= lim)) sum += m->jobs[(size_t)order[hi++]].ranks;
         RV_TRY(many_round(m, order, lo, hi, minl, minn, total));
+        lo = hi;
+    }
+    for (size_t lo = 0; lo < morder.size();) {      // the jobs of three and more sequences: rounds of their own
+        size_t hi = lo; int64_t sum = 0;
+        while (hi < morder.size() && (hi == lo || sum + m->jobs[(size_t)morder[hi]].ranks <= lim)) sum += m->jobs[(size_t)morder[hi++]].ranks;
+        RV_TRY(many_round_multi(m, morder, lo, hi, minl, minn, total));
         lo = hi;
     }
     for (int j : rest) RV_TRY(many_ordinary(m, j, minl, minn, total));
@@ -474,6 +612,7 @@ void rv_many_free(rv_many *m) {
     if (m->hs) rv_free(m->hs);
     if (m->ho) rv_free(m->ho);
     m->dJobs.release(); m->dSA.release(); m->dLCP.release(); m->dBWT.release(); m->dCnt.release();
+    m->dTxt.release(); m->dMJobs.release(); m->dAn.release(); m->dAnPos.release();
     delete m;
 }
 
@@ -481,6 +620,8 @@ int rv_many_option(rv_many *m, const char *name, int64_t value) {
     if (!m || !name) { rv_set_error("rv_many_option: null argument"); return -1; }
     if (strcmp(name, "RV_MANY_KEEP") == 0) { m->keep = value; return 0; }
     if (strcmp(name, "RV_MANY_ROUND") == 0) { if (value < 1) { rv_set_error("RV_MANY_ROUND: at least 1"); return -1; } m->round_max = value; return 0; }
+    if (strcmp(name, "RV_MANY_MULTI") == 0) { m->multi = value != 0; return 0; }
+    if (strcmp(name, "RV_MANY_STAGE") == 0) { if (value < 0) { rv_set_error("RV_MANY_STAGE: negative"); return -1; } m->stage = value; return 0; }
     if (strcmp(name, "RV_MANY_WAVE_MAX") == 0) { if (value < 0) { rv_set_error("RV_MANY_WAVE_MAX: negative"); return -1; } m->wave_max = value; return 0; }
     RvOptions probe;
     if (!probe.find(name)) { rv_set_error("rv_many_option: unknown option %s", name); return -1; }

@@ -4,6 +4,12 @@
 sequences of many bubbles at once: the pair jobs of at most 2048 ranks share their kernel launches (one index build per size
 class with the text in LDS, one launch of the leaf kernel for every job's recursion), every other job runs the ordinary way
 inside the same call.  The built-in picker only (as `index.align_builtin`); no CPU fallback.
+
+Jobs of three and more sequences -- a bubble of a graph of N genomes carries up to N -- run the ordinary way unless the switch
+RV_MANY_MULTI is on (`align_many(.., multi=True)`, `Batch.option("RV_MANY_MULTI", 1)` or the environment variable; off by default).
+With it the jobs of 3 .. 16 sequences and at most 2048 ranks share their launches as well, in rounds of their own: every job
+contiguous in the round's text, the same index build, and one launch of a leaf kernel that runs the whole recursion of a job in
+one workgroup (csrc/rv_leaf_multi.hip).  The results do not depend on the switch.
 """
 import ctypes
 import os
@@ -12,7 +18,8 @@ import numpy as np
 
 from . import _lib
 
-LEAF_RANKS = 2048          # RV_LEAF_N: a pair job of la + lb + 2 ranks up to this goes through the shared launches
+LEAF_RANKS = 2048          # RV_LEAF_N: a job of sum of lengths + k ranks up to this goes through the shared launches
+MULTI_KMAX = 16            # RV_MANY_KMAX: sequences of a job the shared launches take with RV_MANY_MULTI
 
 
 class error(Exception):
@@ -42,9 +49,10 @@ def job_sequences(job, toupper=True):
     return seqs
 
 
-def takes_shared_launch(seqs):
-    """whether the library builds and finishes this job in the shared launches"""
-    return len(seqs) == 2 and len(seqs[0]) + len(seqs[1]) + 2 <= LEAF_RANKS and all(b"\0" not in s for s in seqs)
+def takes_shared_launch(seqs, multi=False):
+    """whether the library builds and finishes this job in the shared launches; multi: with RV_MANY_MULTI on"""
+    kmax = MULTI_KMAX if multi else 2
+    return 2 <= len(seqs) <= kmax and sum(len(s) for s in seqs) + len(seqs) <= LEAF_RANKS and all(b"\0" not in s for s in seqs)
 
 
 def shared_layout(pairs):
@@ -89,7 +97,7 @@ class Batch:
                 except ValueError:
                     iv = 1
                 self.option(name, iv)
-        for name in ("RV_MANY_KEEP", "RV_MANY_ROUND", "RV_MANY_WAVE_MAX"):
+        for name in ("RV_MANY_KEEP", "RV_MANY_ROUND", "RV_MANY_WAVE_MAX", "RV_MANY_MULTI"):
             v = os.environ.get(name)
             if v is not None and v.strip():
                 self.option(name, int(v))
@@ -160,17 +168,21 @@ class Batch:
         return sa, lcp
 
 
-def align_many(jobs, minlength=20, minn=2, sa64=False, toupper=True, batch=None):
+def align_many(jobs, minlength=20, minn=2, sa64=False, toupper=True, batch=None, multi=None):
     """jobs: a list of jobs, each a list of (name, seq) or of plain sequences (two or more, none empty; every sequence is a sample
     of its own, like the inputs of `reveal rem`).  -> (results, info): results[j] = dict(anchors=[(l, (pos, ..)), ..], T=final text
     `s0$s1$..` lower-cased where aligned), positions in the coordinates of the job's own text -- what index.align_builtin gives a
-    stand-alone index of the job; info = dict(jobs, shared, ordinary, rounds, launches, stats).  `batch`: a Batch to reuse."""
+    stand-alone index of the job; info = dict(jobs, shared, ordinary, rounds, launches, stats).  `batch`: a Batch to reuse.
+    `multi`: True / False sets RV_MANY_MULTI (jobs of 3 .. 16 sequences through the shared launches) for this and later runs of
+    the batch; None leaves it as the batch has it (off, unless the environment variable is set)."""
     if isinstance(jobs, (str, bytes, bytearray)) or not hasattr(jobs, "__iter__"):
         raise error("jobs is a list of jobs")
     if int(minlength) < 0 or int(minn) < 2:
         raise error("minlength >= 0 and minn >= 2")
     prepared = [job_sequences(j, toupper) for j in jobs]      # (argument errors before the library is asked for a device)
     b = batch if batch is not None else Batch(sa64)
+    if multi is not None:
+        b.option("RV_MANY_MULTI", 1 if multi else 0)
     b.clear()
     for seqs in prepared:
         b.add(seqs)

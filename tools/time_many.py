@@ -2,12 +2,16 @@
 """Many small pair alignments: ONE align_many call against the same jobs one after the other through one reused handle (GPU box).
 
     python tools/time_many.py [--jobs 10000] [--lmin 50] [--lmax 1000] [--reps 5] [--minlength 20] [--wave-max N] [--only loop|many] [--check]
+                              [--seqs K] [--multi 0|1|ab]
 
 Workload: J jobs of 2 x L bases, L uniform in lmin .. lmax, 1 % substitutions.  The two sides run alternately, `reps` times each:
   loop   rv_reset, rv_add_sample / rv_add_sequence x 2, rv_construct, rv_align_builtin, rv_fetch_anchors, the text -- per job, straight at
          the C ABI (no Python object per job); with RV_LIB_DIR set this side runs on another build of the libraries (the parent commit's)
   many   reveal_amd.many: Batch.add x J, run, anchors (the C part), and align_many as a whole (with the Python result lists)
-Prints medians, the loop's spread, the ratio and one JSON line.  --check compares the two sides' anchors job by job."""
+Prints medians, the loop's spread, the ratio and one JSON line.  --check compares the two sides' anchors job by job.
+--seqs K: jobs of K sequences (K copies of one ancestor, 1 % substitutions each; lmax is cut so that every job stays within 2048 ranks).
+--multi 0 / 1 sets RV_MANY_MULTI of the `many` side (jobs of 3 .. 16 sequences through the shared launches).  --multi ab: no loop; two batches,
+switch off and on, run alternately in one process -- medians, both spreads, the ratio, and with --check the jobs that differ between the sides."""
 import argparse
 import ctypes
 import json
@@ -22,13 +26,25 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from reveal_amd import _lib, reveallib      # noqa: E402
 
 
-def workload(jobs, lmin, lmax, seed=1):
+def workload(jobs, lmin, lmax, seed=1, seqs=2):
     rng = np.random.default_rng(seed)
     lut = np.frombuffer(b"ACGT", np.uint8)
     out = []
+    if seqs > 2:
+        lmax = min(lmax, (2048 - seqs) // seqs)
+        lmin = min(lmin, lmax)
     for _ in range(jobs):
         L = int(rng.integers(lmin, lmax + 1))
         a = rng.integers(0, 4, L)
+        if seqs > 2:
+            job = []
+            for _ in range(seqs):
+                b = a.copy()
+                hit = rng.random(L) < 0.01
+                b[hit] = (b[hit] + rng.integers(1, 4, int(hit.sum()))) % 4
+                job.append(lut[b].tobytes())
+            out.append(job)
+            continue
         b = a.copy()
         hit = rng.random(L) < 0.01
         b[hit] = (b[hit] + rng.integers(1, 4, int(hit.sum()))) % 4
@@ -37,14 +53,14 @@ def workload(jobs, lmin, lmax, seed=1):
 
 
 def run_loop(idx, jobs, minl):
-    """the jobs one after the other through one handle; -> per job sorted [(l, (a, b))]"""
+    """the jobs one after the other through one handle; -> per job (l[], pos[] of all members, off[])"""
     dll, h = idx._dll, idx._h
     st = _lib.RvAlignStats()
     mem = ctypes.c_int64(0)
     res = []
-    for a, b in jobs:
+    for job in jobs:
         ok = dll.rv_reset(h) == 0
-        for s in (a, b):
+        for s in job:
             ok = ok and dll.rv_add_sample(h) == 0 and dll.rv_add_sequence(h, s, len(s), None, None) == 0
         ok = ok and dll.rv_construct(h, 0, None, None, 0) == 0 and dll.rv_align_builtin(h, minl, 2, ctypes.byref(st)) == 0
         if not ok:
@@ -52,11 +68,11 @@ def run_loop(idx, jobs, minl):
         na = dll.rv_anchor_count(h, ctypes.byref(mem))
         l = np.empty(max(na, 1), np.uint32); off = np.empty(na + 1, np.int64); pos = np.empty(max(mem.value, 1), np.int64)
         off[0] = 0
-        n = len(a) + len(b) + 2
+        n = sum(len(s) for s in job) + len(job)
         T = ctypes.create_string_buffer(n)
         if dll.rv_fetch_anchors(h, l.ctypes.data, off.ctypes.data, pos.ctypes.data) != 0 or dll.rv_get_array(h, _lib.RV_T, T, n) != n:
             raise RuntimeError(idx._lib.err())
-        res.append((l[:na], pos[:2 * na]))
+        res.append((l[:na], pos[:mem.value], off))
     return res
 
 
@@ -66,6 +82,46 @@ def run_many_c(batch, jobs, minl):
         batch.add(j)
     batch.run(minl, 2)
     return batch.anchors()
+
+
+def as_lists(first, l, off, pos):
+    """Batch.anchors() -> per job sorted [(l, members)]"""
+    l, off, pos, first = l.tolist(), off.tolist(), pos.tolist(), first.tolist()
+    return [sorted((l[k], tuple(pos[off[k]:off[k + 1]])) for k in range(first[j], first[j + 1])) for j in range(len(first) - 1)]
+
+
+def main_ab(a, jobs, bases):
+    """RV_MANY_MULTI off against on: two batches, alternately"""
+    from reveal_amd import many
+    sides = {}
+    for name, v in (("off", 0), ("on", 1)):
+        b = many.Batch(False)
+        b.option("RV_MANY_MULTI", v)
+        if a.wave_max is not None:
+            b.option("RV_MANY_WAVE_MAX", a.wave_max)
+        run_many_c(b, jobs[:64], a.minlength)
+        sides[name] = dict(batch=b, t=[], res=None)
+    for rep in range(a.reps):
+        for name in ("off", "on"):
+            s = sides[name]
+            t = time.perf_counter(); s["res"] = run_many_c(s["batch"], jobs, a.minlength); s["t"].append(time.perf_counter() - t)
+    out = dict(jobs=a.jobs, seqs=a.seqs, lmin=a.lmin, lmax=a.lmax, bases=bases, minlength=a.minlength, reps=a.reps)
+    for name in ("off", "on"):
+        t = sides[name]["t"]
+        out[name + "_s"] = t; out[name + "_median_s"] = statistics.median(t); out[name + "_spread_s"] = max(t) - min(t)
+        out[name + "_info"] = sides[name]["batch"].info()
+        print("%-3s   : runs %s s; median %.4f s, spread (max - min) %.4f s, %.0f jobs/s; info %r"
+              % (name, " ".join("%.4f" % x for x in t), out[name + "_median_s"], out[name + "_spread_s"], a.jobs / out[name + "_median_s"], out[name + "_info"]))
+    out["ratio"] = out["off_median_s"] / out["on_median_s"]
+    out["gain_s"] = out["off_median_s"] - out["on_median_s"]
+    print("ratio : %.1f x  (gain %.4f s against the off side's spread of %.4f s)" % (out["ratio"], out["gain_s"], out["off_spread_s"]))
+    if a.check:
+        x, y = as_lists(*sides["off"]["res"]), as_lists(*sides["on"]["res"])
+        out["check_bad_jobs"] = sum(1 for p, q in zip(x, y) if p != q)
+        out["anchors"] = sum(len(p) for p in y)
+        print("check : %d of %d jobs differ between the two sides (%d anchors)" % (out["check_bad_jobs"], a.jobs, out["anchors"]))
+    print(json.dumps(out))
+    return 1 if out.get("check_bad_jobs") else 0
 
 
 def main():
@@ -78,9 +134,13 @@ def main():
     ap.add_argument("--wave-max", type=int, default=None)
     ap.add_argument("--only", choices=("loop", "many"), default=None)
     ap.add_argument("--check", action="store_true")
+    ap.add_argument("--seqs", type=int, default=2, help="sequences per job")
+    ap.add_argument("--multi", choices=("0", "1", "ab"), default=None, help="RV_MANY_MULTI of the many side; ab: off against on, no loop")
     a = ap.parse_args()
-    jobs = workload(a.jobs, a.lmin, a.lmax)
-    bases = sum(len(x) + len(y) for x, y in jobs)
+    jobs = workload(a.jobs, a.lmin, a.lmax, seqs=a.seqs)
+    bases = sum(len(s) for j in jobs for s in j)
+    if a.multi == "ab":
+        return main_ab(a, jobs, bases)
     t_loop, t_many, t_many_py = [], [], []
     idx = reveallib.index() if a.only != "many" else None
     batch = None
@@ -89,6 +149,8 @@ def main():
         batch = many.Batch(False)
         if a.wave_max is not None:
             batch.option("RV_MANY_WAVE_MAX", a.wave_max)
+        if a.multi is not None:
+            batch.option("RV_MANY_MULTI", int(a.multi))
         run_many_c(batch, jobs[:64], a.minlength)      # (first use: allocations, code objects)
     if idx is not None:
         run_loop(idx, jobs[:64], a.minlength)
@@ -99,7 +161,7 @@ def main():
         if batch is not None:
             t = time.perf_counter(); many_res = run_many_c(batch, jobs, a.minlength); t_many.append(time.perf_counter() - t)
             t = time.perf_counter(); many.align_many(jobs, a.minlength, 2, toupper=False, batch=batch); t_many_py.append(time.perf_counter() - t)
-    out = dict(jobs=a.jobs, lmin=a.lmin, lmax=a.lmax, bases=bases, minlength=a.minlength, reps=a.reps, lib_dir=os.environ.get("RV_LIB_DIR", ""))
+    out = dict(jobs=a.jobs, seqs=a.seqs, lmin=a.lmin, lmax=a.lmax, bases=bases, minlength=a.minlength, reps=a.reps, lib_dir=os.environ.get("RV_LIB_DIR", ""))
     if t_loop:
         out.update(loop_s=t_loop, loop_median_s=statistics.median(t_loop), loop_spread_s=max(t_loop) - min(t_loop),
                    loop_jobs_per_s=a.jobs / statistics.median(t_loop))
@@ -114,12 +176,9 @@ def main():
         out["gain_s"] = out["loop_median_s"] - out["many_median_s"]
         print("ratio : %.1f x  (gain %.3f s against a spread of %.3f s)" % (out["ratio"], out["gain_s"], out["loop_spread_s"]))
     if a.check and loop_res is not None and many_res is not None:
-        first, l, off, pos = many_res
         bad = 0
-        for j, (ll, lp) in enumerate(loop_res):
-            lo, hi = int(first[j]), int(first[j + 1])
-            got = sorted((int(l[k]), int(pos[2 * k]), int(pos[2 * k + 1])) for k in range(lo, hi))
-            ref = sorted((int(ll[k]), int(lp[2 * k]), int(lp[2 * k + 1])) for k in range(len(ll)))
+        for got, (ll, lp, lo) in zip(as_lists(*many_res), loop_res):
+            ref = sorted((int(ll[k]), tuple(int(x) for x in lp[lo[k]:lo[k + 1]])) for k in range(len(ll)))
             bad += got != ref
         out["check_bad_jobs"] = bad
         print("check : %d of %d jobs differ between the two sides" % (bad, a.jobs))
