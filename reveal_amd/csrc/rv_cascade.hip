@@ -100,7 +100,7 @@ __device__ inline void seg_atomic_max32(u32 *__restrict__ dst, u32 child, u32 va
 // ---- witnesses: positions whose suffix shares minl characters or more with a suffix that is not its cross-pair partner ----
 constexpr int WT_ITEMS = 8;
 constexpr int WT_TILE = TB * WT_ITEMS;
-constexpr int WT_REGIONS = 64;
+constexpr int WT_REGIONS = RV_WIT_REGIONS;
 __global__ __launch_bounds__(TB) void k_cas_witness(const sa_t *__restrict__ SA, const lcp_t *__restrict__ LCP, const uint8_t *__restrict__ BWT, int64_t n,
                                                     u32 minl, sa_t *__restrict__ w_pos, u32 *__restrict__ w_val, u32 *__restrict__ w_rank, u32 cap /* per region */, u32 *__restrict__ counters /* one per region */) {
     __shared__ __attribute__((aligned(16))) u32 sl0[WT_TILE + 8];          // sl = sl0 + 3: LCP of ranks j0-1 .. j0+TILE+1 (0 outside the array)
@@ -1010,19 +1010,35 @@ int rv_cascade_run(rv_index *h, RvCascadeBufs &cb, const RvCascadeIO &io, int mi
     if (bovf.cap < 4096 * sizeof(RvPairRec)) RV_TRY(bovf.reserve(4096 * sizeof(RvPairRec)));
     if (bout.cap < 4096 * sizeof(RvPairRec)) RV_TRY(bout.reserve(sizeof(RvPairRec) * (size_t)std::max<int64_t>(4096, n / 64)));
     u32 *tilecnt = btab.as<u32>(), *tileovf = tilecnt + (ntile + 1), *tileoff = tileovf + (ntile + 1);
+    // The witnesses come out of the same scan (k_scan_pair<true>; RV_CAS_WITNESS_PASS=1: a pass of their own behind it, k_cas_witness).
+    // A region of the witness list takes every WT_REGIONS-th tile: n / WT_REGIONS + a tile's worth of entries can never overflow (small inputs
+    // get that: a low-complexity stretch puts all its witnesses into two or three regions); large inputs a 1024th of n per region
+    const bool wit_pass = ws.opt.cas_witness_pass != 0;
+    const int64_t wtile = wit_pass ? WT_TILE : RV_PAIR_WG_TILE;
+    const int64_t rcap64 = std::min<int64_t>(n / WT_REGIONS + wtile, std::max<int64_t>(16384, n / 1024));
+    const u32 wcap = (u32)std::min<int64_t>(rcap64 * WT_REGIONS, 0x7fffffff);
+    const u32 wrcap = wcap / WT_REGIONS;
+    DBuf &bwp0 = cb.d[19], &bwv0 = cb.d[20], &bwr = cb.d[21], &bwrk = cb.d[22], &bwrk0 = cb.d[23];
+    u32 hreg[2 * WT_REGIONS];
+    RV_TRY(bwp0.reserve((size_t)wcap * sizeof(sa_t))); RV_TRY(bwv0.reserve((size_t)wcap * 4)); RV_TRY(bwr.reserve(2 * WT_REGIONS * 4 + 64));
+    RV_TRY(bwrk.reserve((size_t)wcap * 4)); RV_TRY(bwrk0.reserve((size_t)wcap * 4));
+    const RvScanWit swit = {bwp0.as<sa_t>(), bwv0.as<u32>(), bwrk0.as<u32>(), wrcap, bwr.as<u32>()};
     u32 M = reuse ? cb.M : 0;
     for (int attempt = 0; !reuse; attempt++) {
         if (attempt == 3) { rv_set_error("cascade: scan buffer sizing failed"); return -1; }
         const size_t ocap = bout.cap / sizeof(RvPairRec) - RV_PAIR_HDR, vcap = bovf.cap / sizeof(RvPairRec);
+        if (!wit_pass) RV_HIP(hipMemsetAsync(bwr.p, 0, 2 * WT_REGIONS * 4, q));
         hipEvent_t ev_a, ev_b;
         (void)h->prof.attach(RV_K_SCAN_PAIR, (double)n * 8.0, &ev_a, &ev_b);      // 8 B per rank (a 4-byte suffix + a 4-byte LCP value), also for the 64-bit library -- the kernel reads suffixes only where a match may start
         RV_TRY(rv_scan_pair_launch(ws, SA, LCP, n, BWT, (sa_t)h->nsep[0], (int)minl, bslot.as<RvPairRec>(), bovf.as<RvPairRec>(),
-                                   (u32)std::min<size_t>(vcap, 0xffffffffu), bcnt.as<u32>(), tilecnt, tileovf, nullptr, nullptr, 0, ev_a, ev_b));
+                                   (u32)std::min<size_t>(vcap, 0xffffffffu), bcnt.as<u32>(), tilecnt, tileovf, nullptr, nullptr, 0, ev_a, ev_b, wit_pass ? nullptr : &swit));
         RV_TRY(rv_exclusive_sum_u32(ws, tilecnt, tileoff, ntile + 1));
         RV_TRY(rv_pair_compact_launch(ws, bslot.as<RvPairRec>(), bovf.as<RvPairRec>(), tilecnt, tileovf, tileoff, ntile, bout.as<RvPairRec>(),
                                       (u32)std::min<size_t>(ocap, 0xffffffffu), bcnt.as<u32>(), nullptr, (u32)std::min<size_t>(vcap, 0xffffffffu)));
+        // the header and, behind it in the same read-back, the scan's witness counts
         u32 hdr[4];
-        RV_TRY(rv_read_back(ws, hdr, bout.p, sizeof hdr));
+        if (wit_pass) RV_TRY(rv_read_back(ws, hdr, bout.p, sizeof hdr));
+        else RV_TRY(rv_read_back2(ws, hdr, bout.p, sizeof hdr, hreg, bwr.p, WT_REGIONS * 4));
         const u32 total = hdr[0], novf = hdr[1];
         if (total <= ocap && novf <= vcap) { M = total; break; }
         if (novf > vcap) RV_TRY(bovf.reserve((size_t)novf * sizeof(RvPairRec)));
@@ -1030,16 +1046,12 @@ int rv_cascade_run(rv_index *h, RvCascadeBufs &cb, const RvCascadeIO &io, int mi
     }
     if (verbose) tp[1] = cas_now();
     out->cands = M;
-    struct ProfSpan { Workspace &w; int id; ~ProfSpan() { w.prof_end(id); } } span{ws, ws.prof_begin(RV_K_CASCADE, 5.0 * (double)n)};      // (bytes: the witness pass over LCP + BWT)
+    struct ProfSpan { Workspace &w; int id; ~ProfSpan() { w.prof_end(id); } } span{ws, ws.prof_begin(RV_K_CASCADE, (wit_pass ? 5.0 * (double)n : 0.0) + 16.0 * (double)M)};      // (bytes: the witness pass over LCP + BWT where it still runs, the match records)
     if (M == 0) GIVE_UP("no match at the top level");
     const RvPairRec *recs = bout.as<RvPairRec>() + RV_PAIR_HDR;
     cb.M = M;
 
     // ---- buffers
-    // a region of the witness list takes every WT_REGIONS-th tile: n / WT_REGIONS + a tile's worth of entries can never overflow (small inputs
-    // get that: a low-complexity stretch puts all its witnesses into two or three regions); large inputs a 1024th of n per region
-    const int64_t rcap64 = std::min<int64_t>(n / WT_REGIONS + WT_TILE, std::max<int64_t>(16384, n / 1024));
-    const u32 wcap = (u32)std::min<int64_t>(rcap64 * WT_REGIONS, 0x7fffffff);
     const int64_t ccap64 = n / (int64_t)minl + 16;      // every anchor covers 2 * minl positions and makes two sub-indices at most
     if (ccap64 >= 0x7fffffff) GIVE_UP("too many sub-indices possible");
     const u32 ccap = (u32)ccap64;
@@ -1054,17 +1066,33 @@ int rv_cascade_run(rv_index *h, RvCascadeBufs &cb, const RvCascadeIO &io, int mi
     RV_HIP(hipMemsetAsync(counters, 0, 64, q));
 
     // ---- witnesses
-    DBuf &bwp0 = cb.d[19], &bwv0 = cb.d[20], &bwr = cb.d[21], &bwrk = cb.d[22], &bwrk0 = cb.d[23];
-    RV_TRY(bwp0.reserve((size_t)wcap * sizeof(sa_t))); RV_TRY(bwv0.reserve((size_t)wcap * 4)); RV_TRY(bwr.reserve(2 * WT_REGIONS * 4 + 64));
-    RV_TRY(bwrk.reserve((size_t)wcap * 4)); RV_TRY(bwrk0.reserve((size_t)wcap * 4));
     u32 hc[16];
     u32 NW = reuse ? cb.NW : 0;
     if (!reuse) {
         u32 *wreg = bwr.as<u32>();
-        RV_HIP(hipMemsetAsync(wreg, 0, 2 * WT_REGIONS * 4, q));
-        const u32 wrcap = wcap / WT_REGIONS;
-        hipLaunchKernelGGL(k_cas_witness, dim3((unsigned)ceil_div(n, WT_TILE)), dim3(TB), 0, q, SA, LCP, BWT, n, minl, bwp0.as<sa_t>(), bwv0.as<u32>(), bwrk0.as<u32>(), wrcap, wreg);
-        RV_LAUNCH_CHECK();
+        u32 wmaxc = 0;
+        // hreg = the regions' counts: their offsets go back, k_cas_wpack makes the list dense
+        auto pack = [&]() -> int {
+            for (int r = 0; r < WT_REGIONS; r++) { hreg[WT_REGIONS + r] = NW; NW += hreg[r]; wmaxc = std::max(wmaxc, hreg[r]); }
+            out->witnesses = NW;
+            if (wmaxc > wrcap || NW == 0) return 0;
+            RV_HIP(hipMemcpyAsync(wreg + WT_REGIONS, hreg + WT_REGIONS, WT_REGIONS * 4, hipMemcpyHostToDevice, q));
+            RV_HIP(hipStreamSynchronize(q));      // (hreg lives on this stack frame)
+            hipLaunchKernelGGL(k_cas_wpack, dim3((unsigned)std::max<int64_t>(1, ceil_div((int64_t)wmaxc, TB)), WT_REGIONS), dim3(TB), 0, q, (const sa_t *)bwp0.as<sa_t>(),
+                               (const u32 *)bwv0.as<u32>(), (const u32 *)bwrk0.as<u32>(), wrcap, (const u32 *)wreg, (const u32 *)(wreg + WT_REGIONS), bwp.as<sa_t>(), bwv.as<u32>(),
+                               bwrk.as<u32>());
+            RV_LAUNCH_CHECK();
+            return 0;
+        };
+        if (wit_pass) {
+            RV_HIP(hipMemsetAsync(wreg, 0, 2 * WT_REGIONS * 4, q));
+            hipLaunchKernelGGL(k_cas_witness, dim3((unsigned)ceil_div(n, WT_TILE)), dim3(TB), 0, q, SA, LCP, BWT, n, minl, bwp0.as<sa_t>(), bwv0.as<u32>(), bwrk0.as<u32>(), wrcap, wreg);
+            RV_LAUNCH_CHECK();
+        } else {
+            // (the counts came with the scan's header: the stream is idle here, as it was behind the witness pass' read-back)
+            RV_TRY(pack());
+            if (wmaxc > wrcap) GIVE_UP("too many repeat witnesses (a repetitive input)");
+        }
         // ---- matches by first coordinate
         {
             const unsigned mb = (unsigned)ceil_div((int64_t)M, TB);
@@ -1076,19 +1104,10 @@ int rv_cascade_run(rv_index *h, RvCascadeBufs &cb, const RvCascadeIO &io, int mi
                                blen.as<u32>(), bcc.as<u32>());
             RV_LAUNCH_CHECK();
         }
-        u32 hreg[2 * WT_REGIONS];
-        RV_TRY(rv_read_back(ws, hreg, wreg, WT_REGIONS * 4));
-        u32 wmaxc = 0;
-        for (int r = 0; r < WT_REGIONS; r++) { hreg[WT_REGIONS + r] = NW; NW += hreg[r]; wmaxc = std::max(wmaxc, hreg[r]); }
-        out->witnesses = NW;
-        if (wmaxc > wrcap) GIVE_UP("too many repeat witnesses (a repetitive input)");
-        if (NW) {
-            RV_HIP(hipMemcpyAsync(wreg + WT_REGIONS, hreg + WT_REGIONS, WT_REGIONS * 4, hipMemcpyHostToDevice, q));
-            RV_HIP(hipStreamSynchronize(q));      // (hreg lives on this stack frame)
-            hipLaunchKernelGGL(k_cas_wpack, dim3((unsigned)std::max<int64_t>(1, ceil_div((int64_t)wmaxc, TB)), WT_REGIONS), dim3(TB), 0, q, (const sa_t *)bwp0.as<sa_t>(),
-                               (const u32 *)bwv0.as<u32>(), (const u32 *)bwrk0.as<u32>(), wrcap, (const u32 *)wreg, (const u32 *)(wreg + WT_REGIONS), bwp.as<sa_t>(), bwv.as<u32>(),
-                               bwrk.as<u32>());
-            RV_LAUNCH_CHECK();
+        if (wit_pass) {
+            RV_TRY(rv_read_back(ws, hreg, wreg, WT_REGIONS * 4));
+            RV_TRY(pack());
+            if (wmaxc > wrcap) GIVE_UP("too many repeat witnesses (a repetitive input)");
         }
         cb.NW = NW;
         if (chain) {

@@ -105,7 +105,8 @@ void rv_set_error(const char *fmt, ...);
     X(presel_dev_min, "RV_PRESEL_DEV_MIN", 65536) \
     X(scan_v1, "RV_SCAN_V1", 0) \
     X(pick_threads, "RV_PICK_THREADS", 0) \
-    X(cascade_prio, "RV_CASCADE_PRIO", 0)
+    X(cascade_prio, "RV_CASCADE_PRIO", 0) \
+    X(cas_witness_pass, "RV_CAS_WITNESS_PASS", 0)
 struct RvOptions {
 #define RV_X_(f, name, def) int64_t f = def;
     RV_OPTION_LIST(RV_X_)
@@ -392,6 +393,8 @@ uint8_t *rv_radix_first_digits(Workspace &ws, int64_t n, int bit_lo, int bit_hi)
 // an event by polling.  A pageable destination is staged by the runtime and hipStreamSynchronize sleeps: ~35 us per read
 // against ~12 us this way, five reads per construct().
 int rv_read_back(Workspace &ws, void *dst, const void *dsrc, size_t bytes);
+// two such pieces behind one wait
+int rv_read_back2(Workspace &ws, void *dst_a, const void *dsrc_a, size_t bytes_a, void *dst_b, const void *dsrc_b, size_t bytes_b);
 
 // copy of a small table from pinned host memory by a kernel (bytes rounded up to 16: both buffers must have that room)
 int rv_h2d_copy(Workspace &ws, const void *pinned_src, void *dst, size_t bytes);

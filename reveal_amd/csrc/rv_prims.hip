@@ -428,6 +428,20 @@ int rv_read_back(Workspace &ws, void *dst, const void *dsrc, size_t bytes) {
     return 0;
 }
 
+int rv_read_back2(Workspace &ws, void *dst_a, const void *dsrc_a, size_t bytes_a, void *dst_b, const void *dsrc_b, size_t bytes_b) {
+    const size_t off = (bytes_a + 63) & ~(size_t)63;
+    RV_TRY(ws.hpin.reserve(off + bytes_b < 4096 ? 4096 : off + bytes_b));
+    if (!ws.ev_rb) RV_HIP(hipEventCreateWithFlags(&ws.ev_rb, hipEventDisableTiming));
+    RV_HIP(hipMemcpyAsync(ws.hpin.p, dsrc_a, bytes_a, hipMemcpyDeviceToHost, ws.stream));
+    RV_HIP(hipMemcpyAsync((uint8_t *)ws.hpin.p + off, dsrc_b, bytes_b, hipMemcpyDeviceToHost, ws.stream));
+    RV_HIP(hipEventRecord(ws.ev_rb, ws.stream));
+    const hipError_t e = rv_event_wait(ws.ev_rb);
+    if (e != hipSuccess) { rv_set_error("rv_read_back2: %s", hipGetErrorString(e)); return -1; }
+    memcpy(dst_a, ws.hpin.p, bytes_a);
+    memcpy(dst_b, (const uint8_t *)ws.hpin.p + off, bytes_b);
+    return 0;
+}
+
 int rv_h2d_copy(Workspace &ws, const void *pinned_src, void *dst, size_t bytes) {
     const size_t n16 = (bytes + 15) / 16;
     if (n16 == 0) return 0;

@@ -22,10 +22,17 @@ struct RvPairRec {
 // tilecnt[t] = number of survivors, tilecnt[ntile] = 0.  rv_pair_compact_launch packs them densely in rank order given
 // tileoff = exclusive scan of tilecnt.
 // nsubs > 0: also initialises the tables of the device-side picker (best, picks) that rv_pick_slots_launch fills.
+// wit given (the anchor cascade's top-level scan): the scan also lists the repeat witnesses of k_cas_witness (rv_cascade.hip), in any order, in
+// RV_WIT_REGIONS regions of cap entries each: entry i of region r at r * cap + i, counters[r] (zeroed by the caller) counts also what did not fit.
+// A workgroup's RV_PAIR_WG_TILE ranks go to one region, region = workgroup mod RV_WIT_REGIONS.
+#define RV_WIT_REGIONS 64
+#define RV_PAIR_WG_TILE (4 * RV_PAIR_TILE)
+struct RvScanWit { sa_t *pos; u32 *val; u32 *rank; u32 cap; u32 *counters; };
 int rv_scan_pair_launch(Workspace &ws, const sa_t *SA, const lcp_t *LCP, int64_t m, const uint8_t *BWT, sa_t nsep0, int minl,
                         RvPairRec *slots, RvPairRec *ovf, u32 ovf_cap, u32 *ovf_counter, u32 *tilecnt, u32 *tileovf,
                         unsigned long long *best, RvPairRec *picks, int nsubs,
-                        hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);   // both given: the kernel's own start / stop (hipExtLaunchKernelGGL)
+                        hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr,    // both given: the kernel's own start / stop (hipExtLaunchKernelGGL)
+                        const RvScanWit *wit = nullptr);
 // built-in picker straight from the slots (no compaction): picks[0] = header {0, overflow count, *err, 0}, picks[1+s] = longest
 // record of sub-index s (smallest a on ties), rank 0xFFFFFFFF = none; resets *ovf_counter
 int rv_pick_slots_launch(Workspace &ws, const RvPairRec *slots, const RvPairRec *ovf, u32 ovf_cap, const u32 *tilecnt, const u32 *tileovf, int64_t ntile,

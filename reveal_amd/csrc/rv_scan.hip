@@ -99,11 +99,14 @@ __device__ inline u32 bits4_of_bytes(u32 e) {      // bit 7 of the four bytes ->
     return v & 0xfu;
 }
 
+// WIT: the anchor cascade's top-level scan also lists the repeat witnesses (rv_cascade.hip, k_cas_witness: the same ranks, values and positions) --
+// their predicate looks at LCP[j-1 .. j+2] and the side bits of ranks j-1 .. j+1, all of which stream through here anyway.
+template <bool WIT>
 __global__ __launch_bounds__(TB) void k_scan_pair(const sa_t *__restrict__ SA, const lcp_t *__restrict__ LCP, int64_t m,
                                                   const uint8_t *__restrict__ BWT, sa_t nsep0, int minl,
                                                   RvPairRec *__restrict__ slots, RvPairRec *__restrict__ ovf, u32 ovf_cap,
                                                   u32 *__restrict__ ovf_counter, u32 *__restrict__ tilecnt, u32 *__restrict__ tileovf,
-                                                  unsigned long long *__restrict__ best, RvPairRec *__restrict__ picks, int nsubs) {
+                                                  unsigned long long *__restrict__ best, RvPairRec *__restrict__ picks, int nsubs, RvScanWit wit) {
     static_assert(PAIR_ITEMS == 16, "sixteen ranks per lane: four 16-byte loads of LCP, one of BWT");
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     // one stretch of TB x 16 ranks per block (persistent blocks walking several tiles measured 25 % slower: the
@@ -122,6 +125,11 @@ __global__ __launch_bounds__(TB) void k_scan_pair(const sa_t *__restrict__ SA, c
     u32 h_lc = 0, h_nlc = 0, h_bw = 0;
     if (wfirst > 0 && wfirst - 1 < m) { h_lc = (u32)LCP[wfirst - 1]; h_bw = BWT[wfirst - 1]; }
     if (wnext < m) h_nlc = (u32)LCP[wnext];
+    u32 h_nlc2 = 0, h_nbw = 0;      // WIT: one rank further behind the wave
+    if constexpr (WIT) {
+        if (wnext < m) h_nbw = BWT[wnext];
+        if (wnext + 1 < m) h_nlc2 = (u32)LCP[wnext + 1];
+    }
 
     // What is streamed: LCP (4 B) and the BWT byte, whose bit 7 says on which side of the separator the suffix starts
     // (RV_BWT_SIDE, rv_common.h) -- the predicate of reveal.c:61-85 needs nothing else of SA.  SA is fetched for the
@@ -173,6 +181,37 @@ __global__ __launch_bounds__(TB) void k_scan_pair(const sa_t *__restrict__ SA, c
         const u32 y = __builtin_amdgcn_alignbit(bx[k], k ? bx[k - 1] : plast, 24);      // byte i = the BWT byte of the rank in front of rank 4k + i
         okb |= bits4_of_bytes(pair_bytes4(bx[k], y)) << (4 * k);
     }
+    // WIT.  Gap g (between ranks g - 1 and g) is "long" when LCP[g] >= minl and a "pair" when it is long, larger than both neighbours and its two
+    // suffixes start on different sides of the separator.  k_cas_witness' test of rank j, in these terms: gap j a pair -> a neighbour of it long
+    // (gaps j - 1, j + 1); else gap j + 1 a pair -> gaps j, j + 2; else gaps j, j + 1.  (Its pairs need not be long, but a pair that is not has no
+    // long neighbour and makes no witness either way.)  All of it on bit masks of the lane's sixteen ranks and the three gaps around them.
+    u32 wit16 = 0, wp0 = 0, wp1 = 0;
+    if constexpr (WIT) {
+        u32 g = 0, d = 0;
+#pragma unroll
+        for (int k = 0; k < PAIR_ITEMS; k++) g |= (u32)(lc[k + 1] > thr) << k;
+#pragma unroll
+        for (int k = 0; k < PAIR_ITEMS / 4; k++) {
+            const u32 y = __builtin_amdgcn_alignbit(bx[k], k ? bx[k - 1] : plast, 24);
+            d |= bits4_of_bytes(bx[k] ^ y) << (4 * k);
+        }
+        u32 u = hit & d;                       // (hit: long and larger than both neighbours)
+        if (i0 == 0) u &= ~1u;                 // (no gap in front of rank 0)
+        const u32 pack = g | (u << 16);
+        u32 prev = (u32)__shfl_up((int)pack, 1, 64), next = (u32)__shfl_down((int)pack, 1, 64);
+        if (lane == 0) prev = (u32)(h_lc > thr) << 15;
+        if (lane == 63) {
+            u32 mx = lc[PAIR_ITEMS] > h_nlc2 ? lc[PAIR_ITEMS] : h_nlc2;
+            mx = mx > thr ? mx : thr;
+            const u32 un = (u32)(h_nlc > mx) & (((h_nbw << 24) ^ bx[PAIR_ITEMS / 4 - 1]) >> 31);
+            next = (u32)(h_nlc > thr) | ((u32)(h_nlc2 > thr) << 1) | (un << 16);
+        }
+        const u32 gw = ((prev >> 15) & 1u) | (g << 1) | ((next & 3u) << 17);      // bit b: gap i0 - 1 + b
+        wp0 = u;                                                                  // bit k: gap i0 + k is a pair
+        wp1 = ((u >> 1) | ((next >> 16) << 15)) & ~wp0;                           // bit k: gap i0 + k + 1 is
+        wit16 = ((wp0 & (gw | (gw >> 2))) | (wp1 & ((gw >> 1) | (gw >> 3))) | (~(wp0 | wp1) & ((gw >> 1) | (gw >> 2)))) & 0xffffu;
+        if (i0 + PAIR_ITEMS > m) wit16 &= i0 < m ? (1u << (int)(m - i0)) - 1u : 0u;
+    }
     hit &= okb;
     // order-preserving append of the survivors.  A tile is what one wave scans: no workgroup barrier, a wave
     // retires as soon as its own loads are consumed.
@@ -205,6 +244,27 @@ __global__ __launch_bounds__(TB) void k_scan_pair(const sa_t *__restrict__ SA, c
         if (q < RV_PAIR_SLOTS) slots[(size_t)wtile * RV_PAIR_SLOTS + q] = r;
         else { const u32 o = base + (q - RV_PAIR_SLOTS); if (o < ovf_cap) ovf[o] = r; }
         q++;
+    }
+    // the witnesses (one rank in thousands): appended as k_cas_witness does, one atomic per wave with hits on the counter of the workgroup's region
+    if constexpr (WIT) {
+        if (__ballot(wit16 != 0)) {
+            const u32 cnt = __popc(wit16);
+            const u32 winc = rv_wave_incl_sum_u32(cnt);
+            const u32 reg = blockIdx.x & (RV_WIT_REGIONS - 1);
+            u32 wbase = 0;
+            if (lane == 63) wbase = atomicAdd(&wit.counters[reg], winc);
+            u32 o = (u32)__shfl((int)wbase, 63, 64) + winc - cnt;
+            u32 ww = wit16;
+            while (ww) {
+                const int k = __builtin_ctz(ww);
+                ww &= ww - 1;
+                const int64_t j = i0 + k;
+                const u32 lm1 = j >= 1 ? (u32)LCP[j - 1] : 0u, l0 = (u32)LCP[j], l1 = j + 1 < m ? (u32)LCP[j + 1] : 0u, l2 = j + 2 < m ? (u32)LCP[j + 2] : 0u;
+                const u32 v = ((wp0 >> k) & 1u) ? (lm1 > l1 ? lm1 : l1) : ((wp1 >> k) & 1u) ? (l0 > l2 ? l0 : l2) : (l0 > l1 ? l0 : l1);
+                if (o < wit.cap) { const size_t f = (size_t)reg * wit.cap + o; wit.pos[f] = SA[j]; wit.val[f] = v; wit.rank[f] = (u32)j; }
+                o++;
+            }
+        }
     }
 }
 
@@ -1021,15 +1081,18 @@ int rv_scan_multi_launch(Workspace &ws, const sa_t *SA, const lcp_t *LCP, int64_
 
 int rv_scan_pair_launch(Workspace &ws, const sa_t *SA, const lcp_t *LCP, int64_t m, const uint8_t *BWT, sa_t nsep0, int minl,
                         RvPairRec *slots, RvPairRec *ovf, u32 ovf_cap, u32 *ovf_counter, u32 *tilecnt, u32 *tileovf,
-                        unsigned long long *best, RvPairRec *picks, int nsubs, hipEvent_t ev_start, hipEvent_t ev_stop) {
+                        unsigned long long *best, RvPairRec *picks, int nsubs, hipEvent_t ev_start, hipEvent_t ev_stop, const RvScanWit *wit) {
     if (m <= 0) return 0;
+    static_assert(PAIR_TILE == RV_PAIR_WG_TILE, "rv_scan.h names the workgroup's stretch of ranks");
     const int64_t nb = ceil_div(m, PAIR_TILE);
+    const auto kern = wit ? k_scan_pair<true> : k_scan_pair<false>;
+    const RvScanWit w = wit ? *wit : RvScanWit{nullptr, nullptr, nullptr, 0, nullptr};
     if (ev_start && ev_stop)      // timed launch: the events ride on the kernel's own dispatch packet (no marker packets around it)
-        hipExtLaunchKernelGGL(k_scan_pair, dim3((unsigned)nb), dim3(TB), 0, ws.stream, ev_start, ev_stop, 0, SA, LCP, m, BWT, nsep0, minl, slots, ovf, ovf_cap, ovf_counter,
-                              tilecnt, tileovf, best, picks, nsubs);
+        hipExtLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(TB), 0, ws.stream, ev_start, ev_stop, 0, SA, LCP, m, BWT, nsep0, minl, slots, ovf, ovf_cap, ovf_counter,
+                              tilecnt, tileovf, best, picks, nsubs, w);
     else
-        hipLaunchKernelGGL(k_scan_pair, dim3((unsigned)nb), dim3(TB), 0, ws.stream, SA, LCP, m, BWT, nsep0, minl, slots, ovf, ovf_cap, ovf_counter, tilecnt, tileovf,
-                           best, picks, nsubs);
+        hipLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(TB), 0, ws.stream, SA, LCP, m, BWT, nsep0, minl, slots, ovf, ovf_cap, ovf_counter, tilecnt, tileovf,
+                           best, picks, nsubs, w);
     RV_LAUNCH_CHECK();
     return 0;
 }
