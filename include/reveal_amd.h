@@ -461,6 +461,13 @@ void rv_batch_free(rv_batch *b);
  * With RV_MANY_MULTI set (off by default) the jobs of 3 .. 16 sequences with at most 2048 ranks (sum of lengths + k) and no NUL byte share their launches
  * too, in rounds of their own: every job contiguous in the round's text (s0$s1$..s(k-1)$, job after job), the same index build, then ONE launch of a leaf
  * kernel that runs the whole recursion of a job in one workgroup (rv_leaf_multi.hip: one interval per sample in a frame) and lower-cases its text.
+ * With RV_MANY_LARGE set (off by default) the pair jobs of more than 2048 and at most RV_MANY_LARGE_MAX ranks with no NUL byte share their launches too,
+ * in rounds of their own (sorted by size, at most RV_MANY_ROUND positions; a job that does not fit a round stays ordinary): the pair layout of the small
+ * jobs, the SA / LCP / BWT segments of every job of the round built at once by a segmented prefix doubling in device memory (rv_many_large.hip: radix
+ * sorts over all jobs' suffixes; the launches depend on the doubling rounds, the size of the largest job and the depth of the scans, not on the number
+ * of jobs), and the segments finish as a frontier of J roots through the level pipeline -- one scan, split and bubble launch per level for every job's
+ * sub-indices together, the leaf kernel for those that have shrunk to 2048 ranks.  A call with fewer than RV_MANY_LARGE_MIN such jobs leaves them on
+ * the ordinary path, and so do jobs of three and more sequences above 2048 ranks, always.  The results do not depend on the switch.
  *   rv_many_add     a job of k >= 2 non-empty sequences -> its id (0, 1, ..), < 0 on error (an empty sequence, k < 2, non-ASCII bytes)
  *   rv_many_clear   forgets the jobs and results, keeps every allocation for the next batch
  *   rv_many_run     runs every job; *total (may be NULL) = the sums of the runs' statistics.  A text beyond the 32-bit library's position limit (or
@@ -469,11 +476,15 @@ void rv_batch_free(rv_batch *b);
  *   rv_many_fetch   l[k], off[k .. k+1] -> pos[]: the layout and member order of rv_fetch_anchors
  *   rv_many_text    the job's text after the run (lower-cased where aligned): sum of lengths + k bytes; returns that count
  *   rv_many_info    out[0] jobs, out[1] jobs built and finished by the shared launches, out[2] jobs through the ordinary path, out[3] rounds,
- *                   out[4] kernel launches of the shared part of the last run (index build, leaf kernel, lower-casing; copies not counted)
+ *                   out[4] kernel launches of the shared part of the last run (index build, leaf kernel, lower-casing; copies not counted).  A round
+ *                   of large jobs adds every kernel of its index build (those of the radix sorts and scans included), one per level of its finish
+ *                   (rv_align_stats.levels: a level is a handful of launches whatever the number of jobs) and the two of the lower-casing
  *   rv_many_option  RV_MANY_KEEP (test hook: keep SA / LCP of the shared-launch jobs for rv_many_arrays), RV_MANY_ROUND (positions per round),
  *                   RV_MANY_WAVE_MAX (ranks up to which a wavefront builds a job, at most 512; above: a workgroup), RV_MANY_MULTI (0 / 1: jobs of
  *                   3 .. 16 sequences through shared launches; they count in out[1] then), RV_MANY_STAGE (test hook: anchors such a job stages in LDS,
- *                   at most 256); any other name: rv_set_option on the internal handles
+ *                   at most 256), RV_MANY_LARGE (0 / 1: pair jobs above 2048 ranks through shared launches; they count in out[1] then),
+ *                   RV_MANY_LARGE_MAX (ranks of the largest job these rounds take, default 2^17; larger jobs stay ordinary), RV_MANY_LARGE_MIN
+ *                   (fewer such jobs than this in a call stay ordinary, default 4); any other name: rv_set_option on the internal handles
  *   rv_many_arrays  test hook: which = RV_SA / RV_LCP of a shared-launch job in job-local positions, native element width; -2: not kept */
 typedef struct rv_many rv_many;
 rv_many *rv_many_new(int device);       /* NULL on failure */

@@ -27,12 +27,20 @@
 //   LCP      text order with Kasai's carry (interface.c:97-114: stops at '$' / 'N'), eight bytes per step; a thread takes
 //            consecutive text positions, so its work is its share plus one LCP value, not share x LCP
 //   BWT      the character in front ('$' for local position 0), RV_BWT_SIDE for the suffixes of the second sequence
+//
+// RV_MANY_LARGE (off by default): the pair jobs of more than RV_LEAF_N and at most RV_MANY_LARGE_MAX ranks with no NUL byte share their launches
+// too, in rounds of their own (many_round with `large`): the pair layout above, the index built by a segmented prefix doubling in HBM over every
+// job of the round at once (rv_many_large.hip), and the same finish -- rv_frontier_import of J roots + rv_align_builtin_resume.  The roots are not
+// leaf-sized, so the resume runs the level pipeline: every sub-index of a level in one scan, split and bubble launch, children dropping into the
+// leaf kernel as they shrink.  A level-0 frontier of several roots is to builtin_levels what a worker of a divided alignment imports (install_frontier
+// makes it level 1; a root is told from a child by nothing but its depth, which only the statistics read).
 // Size classes (DESIGN.md "Many small alignments" has the measurements): up to `wave_max` ranks (default 512) a wavefront per job,
 // four jobs per workgroup, no workgroup barrier; above, a workgroup of 256 threads per job.  Both hold 22.6 KB of LDS per workgroup:
 // seven workgroups per CU.
 #include "rv_index.h"
 #include "rv_leaf.h"
 #include "rv_leaf_multi.h"
+#include "rv_many_large.h"
 #include <algorithm>
 #include <limits.h>
 #include <new>
@@ -44,8 +52,6 @@ constexpr int MT = 256;                    // threads per workgroup
 constexpr int CAP_L = RV_LEAF_N;           // ranks of the largest job a workgroup builds
 constexpr int CAP_S = 512;                 // ... a wavefront builds
 static_assert(CAP_L <= 2048, "local ranks are packed in 12 bits, positions in 16");
-
-struct ManyDevJob { int64_t abeg, bbeg, off; int32_t la, lb; };      // where the two sequences begin in the shared text, first rank of the segment
 
 #define MANY_WSYNC() do { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); __builtin_amdgcn_wave_barrier(); } while (0)
 
@@ -219,6 +225,7 @@ struct rv_many {
     std::vector<ManyJob> jobs;
     int64_t keep = 0, round_max = (int64_t)1 << 27, wave_max = CAP_S;
     int64_t multi = 0, stage = 256;             // RV_MANY_MULTI, RV_MANY_STAGE
+    int64_t large = 0, large_max = RV_MANY_LARGE_MAX_DEFAULT, large_min = RV_MANY_LARGE_MIN_DEFAULT;      // RV_MANY_LARGE, RV_MANY_LARGE_MAX, RV_MANY_LARGE_MIN
     std::vector<std::pair<std::string, int64_t>> fwd;      // switches for the internal handles
     // results of the last run
     bool ran = false;
@@ -229,6 +236,7 @@ struct rv_many {
     int64_t info[5] = {0, 0, 0, 0, 0};
     DBuf dJobs, dSA, dLCP, dBWT, dCnt;
     DBuf dTxt, dMJobs, dAn, dAnPos;             // rounds of multi-sequence jobs: their text, jobs, anchors
+    RvManyLargeBufs large_bufs;                      // rounds of large pair jobs: the scratch of their index build
     // scratch of a run
     std::vector<ManyRec> recs; std::vector<int64_t> rpos;
 };
@@ -296,8 +304,8 @@ int many_build(rv_many *m, hipStream_t q, const ManyDevJob *djobs, size_t J, siz
     return 0;
 }
 
-// one round of the shared launches: the jobs order[lo .. hi) (ascending size)
-int many_round(rv_many *m, const std::vector<int> &order, size_t lo, size_t hi, int minl, int minn, rv_align_stats *total) {
+// one round of the shared launches: the jobs order[lo .. hi) (ascending size); large: jobs above RV_LEAF_N ranks (RV_MANY_LARGE)
+int many_round(rv_many *m, const std::vector<int> &order, size_t lo, size_t hi, int minl, int minn, rv_align_stats *total, bool large) {
     RV_TRY(many_handle(m, &m->hs));
     rv_index *h = m->hs;
     const size_t J = hi - lo;
@@ -355,7 +363,9 @@ int many_round(rv_many *m, const std::vector<int> &order, size_t lo, size_t hi, 
     u32 *d_max = m->dCnt.as<u32>(), *d_err = d_max + 1;
     const ManyDevJob *djobs = m->dJobs.as<ManyDevJob>();
     const uint8_t *dT = h->dT0.as<uint8_t>();
-    RV_TRY(many_build(m, q, djobs, J, nsmall, dT, d_max, d_err));
+    if (large) {
+        RV_TRY(rv_many_large_build(h->ws, m->large_bufs, djobs, (int64_t)J, n, la[J - 1] + lb[J - 1] + 2, dT, m->dSA.as<sa_t>(), m->dLCP.as<lcp_t>(), m->dBWT.as<uint8_t>(), d_max, &m->info[4]));
+    } else RV_TRY(many_build(m, q, djobs, J, nsmall, dT, d_max, d_err));
     u32 cnt[2] = {0, 0};
     RV_TRY(rv_read_back(h->ws, cnt, d_max, 8));
     if (cnt[1]) { rv_set_error("rv_many_run: the index build refused a job (error bits %u)", cnt[1]); return -1; }
@@ -375,7 +385,7 @@ int many_round(rv_many *m, const std::vector<int> &order, size_t lo, size_t hi, 
             }
         }
     }
-    // the segments as a frontier of J roots; every root is leaf-sized: one leaf launch
+    // the segments as a frontier of J roots; every root is leaf-sized: one leaf launch (large: the level pipeline, leaves as the children shrink)
     RV_TRY(rv_frontier_import(h, minl, minn, cnt[0], 0, (int)J, meta.data(), node_first.data(), nodes.data(), n, m->dSA.p, m->dLCP.p, m->dBWT.p, 1));
     rv_align_stats st;
     memset(&st, 0, sizeof st);
@@ -383,7 +393,7 @@ int many_round(rv_many *m, const std::vector<int> &order, size_t lo, size_t hi, 
     many_add_stats(total, st);
     const size_t rec0 = m->recs.size();
     RV_TRY(many_collect(m, h, -1, ord, abeg, bbeg));
-    m->info[4] += st.levels + (m->recs.size() > rec0 ? 2 : 0);      // leaf launches, and the two of the lower-casing when there are anchors
+    m->info[4] += st.levels + (m->recs.size() > rec0 ? 2 : 0);      // leaf launches (large: levels), and the two of the lower-casing when there are anchors
     // final text of every job: a$b$
     std::vector<char> txt((size_t)n);
     RV_TRY(rv_ensure_working_text(h));
@@ -544,23 +554,36 @@ int many_run(rv_many *m, int minl, int minn, rv_align_stats *total) {
     if (total) memset(total, 0, sizeof *total);
     const int nj = (int)m->jobs.size();
     m->info[0] = nj;
-    std::vector<int> order, morder, rest;
+    std::vector<int> order, morder, lorder, rest;
+    // rounds: a round's text stays below the 32-bit library's position limit (and a bound on the device memory of a round)
+    const int64_t lim = std::max<int64_t>(std::min<int64_t>(m->round_max, (int64_t)INT_MAX - 4096), 1);
+    // (a large job has to fit a round: one that does not goes the ordinary way)
+    const auto is_large = [&](const ManyJob &jb) { return m->large && jb.k == 2 && jb.clean && jb.ranks > RV_LEAF_N && jb.ranks <= m->large_max && jb.ranks <= lim; };
+    int64_t nlarge = 0;
+    for (const ManyJob &jb : m->jobs) nlarge += is_large(jb) ? 1 : 0;
+    const bool take_large = nlarge > 0 && nlarge >= m->large_min;
     for (int j = 0; j < nj; j++) {
         ManyJob &jb = m->jobs[(size_t)j];
         jb.arr_off = -1;
         if (jb.k == 2 && jb.ranks <= RV_LEAF_N && jb.clean) order.push_back(j);
+        else if (take_large && is_large(jb)) lorder.push_back(j);
         else if (m->multi && jb.k >= 3 && jb.k <= RV_MANY_KMAX && jb.ranks <= RV_LEAF_N && jb.clean) morder.push_back(j);
         else rest.push_back(j);
     }
     const auto by_size = [&](int a, int b) { return m->jobs[(size_t)a].ranks < m->jobs[(size_t)b].ranks; };
     std::stable_sort(order.begin(), order.end(), by_size);
     std::stable_sort(morder.begin(), morder.end(), by_size);
-    // rounds: a round's text stays below the 32-bit library's position limit (and a bound on the device memory of a round)
-    const int64_t lim = std::max<int64_t>(std::min<int64_t>(m->round_max, (int64_t)INT_MAX - 4096), 1);
+    std::stable_sort(lorder.begin(), lorder.end(), by_size);
     for (size_t lo = 0; lo < order.size();) {
         size_t hi = lo; int64_t sum = 0;
         while (hi < order.size() && (hi == lo || sum + m->jobs[(size_t)order[hi]].ranks <= lim)) sum += m->jobs[(size_t)order[hi++]].ranks;
-        RV_TRY(many_round(m, order, lo, hi, minl, minn, total));
+        RV_TRY(many_round(m, order, lo, hi, minl, minn, total, false));
+        lo = hi;
+    }
+    for (size_t lo = 0; lo < lorder.size();) {      // the pair jobs above RV_LEAF_N ranks: rounds of their own
+        size_t hi = lo; int64_t sum = 0;
+        while (hi < lorder.size() && (hi == lo || sum + m->jobs[(size_t)lorder[hi]].ranks <= lim)) sum += m->jobs[(size_t)lorder[hi++]].ranks;
+        RV_TRY(many_round(m, lorder, lo, hi, minl, minn, total, true));
         lo = hi;
     }
     for (size_t lo = 0; lo < morder.size();) {      // the jobs of three and more sequences: rounds of their own
@@ -613,6 +636,7 @@ void rv_many_free(rv_many *m) {
     if (m->ho) rv_free(m->ho);
     m->dJobs.release(); m->dSA.release(); m->dLCP.release(); m->dBWT.release(); m->dCnt.release();
     m->dTxt.release(); m->dMJobs.release(); m->dAn.release(); m->dAnPos.release();
+    m->large_bufs.release();
     delete m;
 }
 
@@ -621,6 +645,9 @@ int rv_many_option(rv_many *m, const char *name, int64_t value) {
     if (strcmp(name, "RV_MANY_KEEP") == 0) { m->keep = value; return 0; }
     if (strcmp(name, "RV_MANY_ROUND") == 0) { if (value < 1) { rv_set_error("RV_MANY_ROUND: at least 1"); return -1; } m->round_max = value; return 0; }
     if (strcmp(name, "RV_MANY_MULTI") == 0) { m->multi = value != 0; return 0; }
+    if (strcmp(name, "RV_MANY_LARGE") == 0) { m->large = value != 0; return 0; }
+    if (strcmp(name, "RV_MANY_LARGE_MAX") == 0) { if (value < 0) { rv_set_error("RV_MANY_LARGE_MAX: negative"); return -1; } m->large_max = value; return 0; }
+    if (strcmp(name, "RV_MANY_LARGE_MIN") == 0) { if (value < 0) { rv_set_error("RV_MANY_LARGE_MIN: negative"); return -1; } m->large_min = value; return 0; }
     if (strcmp(name, "RV_MANY_STAGE") == 0) { if (value < 0) { rv_set_error("RV_MANY_STAGE: negative"); return -1; } m->stage = value; return 0; }
     if (strcmp(name, "RV_MANY_WAVE_MAX") == 0) { if (value < 0) { rv_set_error("RV_MANY_WAVE_MAX: negative"); return -1; } m->wave_max = value; return 0; }
     RvOptions probe;

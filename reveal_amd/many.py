@@ -10,6 +10,14 @@ RV_MANY_MULTI is on (`align_many(.., multi=True)`, `Batch.option("RV_MANY_MULTI"
 With it the jobs of 3 .. 16 sequences and at most 2048 ranks share their launches as well, in rounds of their own: every job
 contiguous in the round's text, the same index build, and one launch of a leaf kernel that runs the whole recursion of a job in
 one workgroup (csrc/rv_leaf_multi.hip).  The results do not depend on the switch.
+
+Pair jobs above 2048 ranks -- `reveal refine` takes bubbles with alleles of up to 10 kbp, 20 000 ranks -- run the ordinary way unless the
+switch RV_MANY_LARGE is on (`align_many(.., large=True)`, `Batch.option("RV_MANY_LARGE", 1)` or the environment variable; off by default).
+With it the pair jobs of 2049 .. RV_MANY_LARGE_MAX ranks (default 2^17) share their launches too, in rounds of their own: the pair layout of
+the small jobs, the index of every job of a round built at once by a segmented prefix doubling in device memory
+(csrc/rv_many_large.hip), and the level pipeline of the recursion over all of them together.  A call with fewer than RV_MANY_LARGE_MIN
+such jobs (default 4) leaves them on the ordinary path.  Jobs of three and more sequences above 2048 ranks always run the ordinary way.
+The results do not depend on these switches either.
 """
 import ctypes
 import os
@@ -20,6 +28,7 @@ from . import _lib
 
 LEAF_RANKS = 2048          # RV_LEAF_N: a job of sum of lengths + k ranks up to this goes through the shared launches
 MULTI_KMAX = 16            # RV_MANY_KMAX: sequences of a job the shared launches take with RV_MANY_MULTI
+LARGE_MAX = 1 << 17        # default of RV_MANY_LARGE_MAX: ranks of the largest pair job the shared launches take with RV_MANY_LARGE
 
 
 class error(Exception):
@@ -49,10 +58,14 @@ def job_sequences(job, toupper=True):
     return seqs
 
 
-def takes_shared_launch(seqs, multi=False):
-    """whether the library builds and finishes this job in the shared launches; multi: with RV_MANY_MULTI on"""
+def takes_shared_launch(seqs, multi=False, large=False, large_max=LARGE_MAX):
+    """whether the library builds and finishes this job in the shared launches; multi: with RV_MANY_MULTI on; large: with RV_MANY_LARGE
+    on and RV_MANY_LARGE_MAX = large_max (in a call with at least RV_MANY_LARGE_MIN such jobs, and with rounds that hold the job)"""
     kmax = MULTI_KMAX if multi else 2
-    return 2 <= len(seqs) <= kmax and sum(len(s) for s in seqs) + len(seqs) <= LEAF_RANKS and all(b"\0" not in s for s in seqs)
+    ranks = sum(len(s) for s in seqs) + len(seqs)
+    if not (2 <= len(seqs) <= kmax) or any(b"\0" in s for s in seqs):
+        return False
+    return ranks <= LEAF_RANKS or (bool(large) and len(seqs) == 2 and ranks <= large_max)
 
 
 def shared_layout(pairs):
@@ -97,7 +110,7 @@ class Batch:
                 except ValueError:
                     iv = 1
                 self.option(name, iv)
-        for name in ("RV_MANY_KEEP", "RV_MANY_ROUND", "RV_MANY_WAVE_MAX", "RV_MANY_MULTI"):
+        for name in ("RV_MANY_KEEP", "RV_MANY_ROUND", "RV_MANY_WAVE_MAX", "RV_MANY_MULTI", "RV_MANY_LARGE", "RV_MANY_LARGE_MAX", "RV_MANY_LARGE_MIN"):
             v = os.environ.get(name)
             if v is not None and v.strip():
                 self.option(name, int(v))
@@ -168,13 +181,14 @@ class Batch:
         return sa, lcp
 
 
-def align_many(jobs, minlength=20, minn=2, sa64=False, toupper=True, batch=None, multi=None):
+def align_many(jobs, minlength=20, minn=2, sa64=False, toupper=True, batch=None, multi=None, large=None):
     """jobs: a list of jobs, each a list of (name, seq) or of plain sequences (two or more, none empty; every sequence is a sample
     of its own, like the inputs of `reveal rem`).  -> (results, info): results[j] = dict(anchors=[(l, (pos, ..)), ..], T=final text
     `s0$s1$..` lower-cased where aligned), positions in the coordinates of the job's own text -- what index.align_builtin gives a
     stand-alone index of the job; info = dict(jobs, shared, ordinary, rounds, launches, stats).  `batch`: a Batch to reuse.
     `multi`: True / False sets RV_MANY_MULTI (jobs of 3 .. 16 sequences through the shared launches) for this and later runs of
-    the batch; None leaves it as the batch has it (off, unless the environment variable is set)."""
+    the batch; None leaves it as the batch has it (off, unless the environment variable is set).  `large`: the same for RV_MANY_LARGE
+    (pair jobs of 2049 .. RV_MANY_LARGE_MAX ranks through the shared launches)."""
     if isinstance(jobs, (str, bytes, bytearray)) or not hasattr(jobs, "__iter__"):
         raise error("jobs is a list of jobs")
     if int(minlength) < 0 or int(minn) < 2:
@@ -183,6 +197,8 @@ def align_many(jobs, minlength=20, minn=2, sa64=False, toupper=True, batch=None,
     b = batch if batch is not None else Batch(sa64)
     if multi is not None:
         b.option("RV_MANY_MULTI", 1 if multi else 0)
+    if large is not None:
+        b.option("RV_MANY_LARGE", 1 if large else 0)
     b.clear()
     for seqs in prepared:
         b.add(seqs)

@@ -2,7 +2,7 @@
 """Many small pair alignments: ONE align_many call against the same jobs one after the other through one reused handle (GPU box).
 
     python tools/time_many.py [--jobs 10000] [--lmin 50] [--lmax 1000] [--reps 5] [--minlength 20] [--wave-max N] [--only loop|many] [--check]
-                              [--seqs K] [--multi 0|1|ab]
+                              [--seqs K] [--multi 0|1|ab] [--large 0|1|ab] [--large-max R] [--large-min J]
 
 Workload: J jobs of 2 x L bases, L uniform in lmin .. lmax, 1 % substitutions.  The two sides run alternately, `reps` times each:
   loop   rv_reset, rv_add_sample / rv_add_sequence x 2, rv_construct, rv_align_builtin, rv_fetch_anchors, the text -- per job, straight at
@@ -11,7 +11,9 @@ Workload: J jobs of 2 x L bases, L uniform in lmin .. lmax, 1 % substitutions.  
 Prints medians, the loop's spread, the ratio and one JSON line.  --check compares the two sides' anchors job by job.
 --seqs K: jobs of K sequences (K copies of one ancestor, 1 % substitutions each; lmax is cut so that every job stays within 2048 ranks).
 --multi 0 / 1 sets RV_MANY_MULTI of the `many` side (jobs of 3 .. 16 sequences through the shared launches).  --multi ab: no loop; two batches,
-switch off and on, run alternately in one process -- medians, both spreads, the ratio, and with --check the jobs that differ between the sides."""
+switch off and on, run alternately in one process -- medians, both spreads, the ratio, and with --check the jobs that differ between the sides.
+--large 0 / 1 / ab: the same for RV_MANY_LARGE (pair jobs above 2048 ranks through shared launches; choose --lmin / --lmax above 1023);
+--large-max / --large-min set RV_MANY_LARGE_MAX / RV_MANY_LARGE_MIN of every batch."""
 import argparse
 import ctypes
 import json
@@ -90,13 +92,25 @@ def as_lists(first, l, off, pos):
     return [sorted((l[k], tuple(pos[off[k]:off[k + 1]])) for k in range(first[j], first[j + 1])) for j in range(len(first) - 1)]
 
 
-def main_ab(a, jobs, bases):
-    """RV_MANY_MULTI off against on: two batches, alternately"""
+def more_options(a, b):
+    if a.large_max is not None:
+        b.option("RV_MANY_LARGE_MAX", a.large_max)
+    if a.large_min is not None:
+        b.option("RV_MANY_LARGE_MIN", a.large_min)
+
+
+def main_ab(a, jobs, bases, switch="RV_MANY_MULTI"):
+    """`switch` (RV_MANY_MULTI or RV_MANY_LARGE) off against on: two batches, alternately"""
     from reveal_amd import many
     sides = {}
     for name, v in (("off", 0), ("on", 1)):
         b = many.Batch(False)
-        b.option("RV_MANY_MULTI", v)
+        if switch != "RV_MANY_MULTI" and a.multi in ("0", "1"):
+            b.option("RV_MANY_MULTI", int(a.multi))
+        if switch != "RV_MANY_LARGE" and a.large in ("0", "1"):
+            b.option("RV_MANY_LARGE", int(a.large))
+        more_options(a, b)
+        b.option(switch, v)
         if a.wave_max is not None:
             b.option("RV_MANY_WAVE_MAX", a.wave_max)
         run_many_c(b, jobs[:64], a.minlength)
@@ -105,7 +119,7 @@ def main_ab(a, jobs, bases):
         for name in ("off", "on"):
             s = sides[name]
             t = time.perf_counter(); s["res"] = run_many_c(s["batch"], jobs, a.minlength); s["t"].append(time.perf_counter() - t)
-    out = dict(jobs=a.jobs, seqs=a.seqs, lmin=a.lmin, lmax=a.lmax, bases=bases, minlength=a.minlength, reps=a.reps)
+    out = dict(jobs=a.jobs, seqs=a.seqs, lmin=a.lmin, lmax=a.lmax, bases=bases, minlength=a.minlength, reps=a.reps, switch=switch)
     for name in ("off", "on"):
         t = sides[name]["t"]
         out[name + "_s"] = t; out[name + "_median_s"] = statistics.median(t); out[name + "_spread_s"] = max(t) - min(t)
@@ -136,11 +150,18 @@ def main():
     ap.add_argument("--check", action="store_true")
     ap.add_argument("--seqs", type=int, default=2, help="sequences per job")
     ap.add_argument("--multi", choices=("0", "1", "ab"), default=None, help="RV_MANY_MULTI of the many side; ab: off against on, no loop")
+    ap.add_argument("--large", choices=("0", "1", "ab"), default=None, help="RV_MANY_LARGE of the many side; ab: off against on, no loop")
+    ap.add_argument("--large-max", type=int, default=None, help="RV_MANY_LARGE_MAX")
+    ap.add_argument("--large-min", type=int, default=None, help="RV_MANY_LARGE_MIN")
     a = ap.parse_args()
+    if a.multi == "ab" and a.large == "ab":
+        ap.error("one switch at a time: --multi ab or --large ab")
     jobs = workload(a.jobs, a.lmin, a.lmax, seqs=a.seqs)
     bases = sum(len(s) for j in jobs for s in j)
     if a.multi == "ab":
         return main_ab(a, jobs, bases)
+    if a.large == "ab":
+        return main_ab(a, jobs, bases, "RV_MANY_LARGE")
     t_loop, t_many, t_many_py = [], [], []
     idx = reveallib.index() if a.only != "many" else None
     batch = None
@@ -151,6 +172,9 @@ def main():
             batch.option("RV_MANY_WAVE_MAX", a.wave_max)
         if a.multi is not None:
             batch.option("RV_MANY_MULTI", int(a.multi))
+        if a.large is not None:
+            batch.option("RV_MANY_LARGE", int(a.large))
+        more_options(a, batch)
         run_many_c(batch, jobs[:64], a.minlength)      # (first use: allocations, code objects)
     if idx is not None:
         run_loop(idx, jobs[:64], a.minlength)
