@@ -467,7 +467,17 @@ void rv_batch_free(rv_batch *b);
  * sorts over all jobs' suffixes; the launches depend on the doubling rounds, the size of the largest job and the depth of the scans, not on the number
  * of jobs), and the segments finish as a frontier of J roots through the level pipeline -- one scan, split and bubble launch per level for every job's
  * sub-indices together, the leaf kernel for those that have shrunk to 2048 ranks.  A call with fewer than RV_MANY_LARGE_MIN such jobs leaves them on
- * the ordinary path, and so do jobs of three and more sequences above 2048 ranks, always.  The results do not depend on the switch.
+ * the ordinary path.  The results do not depend on the switch.
+ * With RV_MANY_LARGE_MULTI set (off by default) the jobs of 3 .. 16 sequences with more than 2048 and at most RV_MANY_LARGE_MAX ranks and no NUL byte
+ * share their launches too, in rounds of their own (sorted by size, at most RV_MANY_ROUND positions, jobs of different k mixed; a job that does not fit
+ * a round stays ordinary).  The round's text is sample-major: it has K samples, K its widest job, and sample q holds the q-th sequence of every job
+ * that has one, in the round's job order, each followed by '$' -- the generalisation of the pair layout.  The sample of a position is then right for
+ * every job at once, and a job's stand-alone coordinate -> shared position map is strictly increasing, so ties by position come out as in the job's own
+ * index.  The same segmented prefix doubling builds the segments from the job-local texts s0$s1$..s(k-1)$ (the side bit of a BWT byte: behind the first
+ * sequence's '$'), and they finish as a frontier of J roots of k samples each through the level pipeline for more than two samples, down to the last
+ * sub-index (no leaf kernel there).  A call with fewer than RV_MANY_LARGE_MULTI_MIN such jobs leaves them on the ordinary path.  With RV_MANY_MULTI, RV_MANY_LARGE and RV_MANY_LARGE_MULTI all
+ * set, every job of 2 .. 16 sequences without a NUL byte and of at most RV_MANY_LARGE_MAX ranks that fits a round goes through shared launches -- in a
+ * call that holds at least RV_MANY_LARGE_MIN pair jobs and RV_MANY_LARGE_MULTI_MIN jobs of three and more sequences above 2048 ranks, where it has any.
  *   rv_many_add     a job of k >= 2 non-empty sequences -> its id (0, 1, ..), < 0 on error (an empty sequence, k < 2, non-ASCII bytes)
  *   rv_many_clear   forgets the jobs and results, keeps every allocation for the next batch
  *   rv_many_run     runs every job; *total (may be NULL) = the sums of the runs' statistics.  A text beyond the 32-bit library's position limit (or
@@ -484,7 +494,10 @@ void rv_batch_free(rv_batch *b);
  *                   3 .. 16 sequences through shared launches; they count in out[1] then), RV_MANY_STAGE (test hook: anchors such a job stages in LDS,
  *                   at most 256), RV_MANY_LARGE (0 / 1: pair jobs above 2048 ranks through shared launches; they count in out[1] then),
  *                   RV_MANY_LARGE_MAX (ranks of the largest job these rounds take, default 2^17; larger jobs stay ordinary), RV_MANY_LARGE_MIN
- *                   (fewer such jobs than this in a call stay ordinary, default 4); any other name: rv_set_option on the internal handles
+ *                   (fewer such jobs than this in a call stay ordinary, default 4), RV_MANY_LARGE_MULTI (0 / 1: jobs of 3 .. 16 sequences above 2048
+ *                   ranks through shared launches, within the same RV_MANY_LARGE_MAX; they count in out[1] then, and out[4] follows the convention
+ *                   of the large pair rounds), RV_MANY_LARGE_MULTI_MIN (fewer such jobs than this in a call stay ordinary, default 16: a threshold of
+ *                   their own, so RV_MANY_LARGE_MIN and what a call does with its pair jobs do not change); any other name: rv_set_option on the internal handles
  *   rv_many_arrays  test hook: which = RV_SA / RV_LCP of a shared-launch job in job-local positions, native element width; -2: not kept */
 typedef struct rv_many rv_many;
 rv_many *rv_many_new(int device);       /* NULL on failure */

@@ -34,6 +34,16 @@
 // leaf-sized, so the resume runs the level pipeline: every sub-index of a level in one scan, split and bubble launch, children dropping into the
 // leaf kernel as they shrink.  A level-0 frontier of several roots is to builtin_levels what a worker of a divided alignment imports (install_frontier
 // makes it level 1; a root is told from a child by nothing but its depth, which only the statistics read).
+//
+// RV_MANY_LARGE_MULTI (off by default): the jobs of 3 .. RV_MANY_KMAX sequences with more than RV_LEAF_N and at most RV_MANY_LARGE_MAX ranks and no
+// NUL byte share their launches too, in rounds of their own (many_round_large_multi).  A round may mix jobs of different k; its handle has K
+// samples, K the round's widest job:
+//   text     sample-major: sample q holds the q-th sequence of every job that has one, in the round's job order, a '$' behind each; nsep[q] is the
+//            '$' behind the last of them.  The sample of a position is then right for every job at once, and a job's stand-alone coordinate ->
+//            shared position map is strictly increasing, so every tie-break by position comes out as in the stand-alone index
+//   build    the segmented prefix doubling of rv_many_large.hip over job-local texts s0$s1$..s(k-1)$ gathered from the k places
+//   finish   rv_frontier_import of J roots (nsamples = the job's k, k intervals each) + rv_align_builtin_resume: the level pipeline for more
+//            than two samples, down to the last sub-index (there is no leaf kernel for multi-sample sub-indices of a handle)
 // Size classes (DESIGN.md "Many small alignments" has the measurements): up to `wave_max` ranks (default 512) a wavefront per job,
 // four jobs per workgroup, no workgroup barrier; above, a workgroup of 256 threads per job.  Both hold 22.6 KB of LDS per workgroup:
 // seven workgroups per CU.
@@ -226,6 +236,7 @@ struct rv_many {
     int64_t keep = 0, round_max = (int64_t)1 << 27, wave_max = CAP_S;
     int64_t multi = 0, stage = 256;             // RV_MANY_MULTI, RV_MANY_STAGE
     int64_t large = 0, large_max = RV_MANY_LARGE_MAX_DEFAULT, large_min = RV_MANY_LARGE_MIN_DEFAULT;      // RV_MANY_LARGE, RV_MANY_LARGE_MAX, RV_MANY_LARGE_MIN
+    int64_t large_multi = 0, large_multi_min = 16;      // RV_MANY_LARGE_MULTI, RV_MANY_LARGE_MULTI_MIN (DESIGN.md "Many small alignments": 4 such jobs lose, 16 win)
     std::vector<std::pair<std::string, int64_t>> fwd;      // switches for the internal handles
     // results of the last run
     bool ran = false;
@@ -234,7 +245,7 @@ struct rv_many {
     std::vector<char> out_text;
     std::vector<sa_t> keep_sa; std::vector<lcp_t> keep_lcp;
     int64_t info[5] = {0, 0, 0, 0, 0};
-    DBuf dJobs, dSA, dLCP, dBWT, dCnt;
+    DBuf dJobs, dKJobs, dSA, dLCP, dBWT, dCnt;
     DBuf dTxt, dMJobs, dAn, dAnPos;             // rounds of multi-sequence jobs: their text, jobs, anchors
     RvManyLargeBufs large_bufs;                      // rounds of large pair jobs: the scratch of their index build
     // scratch of a run
@@ -521,6 +532,178 @@ int many_round_multi(rv_many *m, const std::vector<int> &order, size_t lo, size_
     return 0;
 }
 
+// a sample-major round (RV_MANY_LARGE_MULTI): where its jobs lie.  dj[s]: job ord[s] (begins in the shared text, local prefix ends); send[q]: the
+// '$' behind the last sequence of sample q (the handle's nsep[q]); sbeg[q] / sslot[q]: begin and slot of the sequences of sample q, ascending
+struct ManyRoundK {
+    std::vector<int> ord;
+    std::vector<ManyDevJobK> dj;
+    std::vector<int64_t> send;
+    std::vector<std::vector<int64_t>> sbeg;
+    std::vector<std::vector<int>> sslot;
+    // shared position inside sequence q of slot s -> stand-alone coordinate of the job's text s0$s1$..
+    int64_t local(size_t s, int q, int64_t p) const { return p - dj[s].beg[q] + (q ? dj[s].pend[q - 1] : 0); }
+    int sample_of(int64_t p) const { return (int)(std::lower_bound(send.begin(), send.end(), p) - send.begin()); }
+};
+
+// anchors of the handle's last run over a sample-major round -> records of their jobs.  An anchor's job comes from its first member (search among
+// the begins of that member's sample), every member maps back to the job's stand-alone coordinate.  The map is strictly increasing, so the members
+// stay in the (sorted) order rv_fetch_anchors gives a stand-alone index.
+int many_collect_k(rv_many *m, rv_index *h, const ManyRoundK &R) {
+    int64_t members = 0;
+    const int64_t na = rv_anchor_count(h, &members);
+    if (na < 0) return -1;
+    std::vector<u32> l((size_t)std::max<int64_t>(na, 1));
+    std::vector<int64_t> off((size_t)na + 1, 0), pos((size_t)std::max<int64_t>(members, 1));
+    RV_TRY(rv_fetch_anchors(h, l.data(), off.data(), pos.data()));
+    const int K = (int)R.send.size();
+    for (int64_t k = 0; k < na; k++) {
+        ManyRec r; r.l = l[(size_t)k]; r.np = (int)(off[(size_t)k + 1] - off[(size_t)k]); r.p0 = (int64_t)m->rpos.size();
+        const int64_t *p = pos.data() + off[(size_t)k];
+        if (r.np < 2 || r.np > K) { rv_set_error("rv_many_run: an anchor of %d members in a round of %d samples", r.np, K); return -1; }
+        const int q0 = R.sample_of(p[0]);
+        if (q0 >= K) { rv_set_error("rv_many_run: an anchor outside the text"); return -1; }
+        const size_t at = (size_t)(std::upper_bound(R.sbeg[(size_t)q0].begin(), R.sbeg[(size_t)q0].end(), p[0]) - R.sbeg[(size_t)q0].begin());
+        if (at == 0) { rv_set_error("rv_many_run: an anchor outside the text"); return -1; }
+        const size_t s = (size_t)R.sslot[(size_t)q0][at - 1];
+        const ManyDevJobK &J = R.dj[s];
+        int64_t last = -1;
+        for (int x = 0; x < r.np; x++) {
+            const int q = R.sample_of(p[x]);
+            if (q >= J.k) { rv_set_error("rv_many_run: an anchor outside its job"); return -1; }
+            const int64_t lo = q ? J.pend[q - 1] : 0, loc = R.local(s, q, p[x]);
+            if (loc < lo || loc + r.l > J.pend[q] - 1 || loc <= last) { rv_set_error("rv_many_run: an anchor outside its job"); return -1; }
+            m->rpos.push_back(loc);
+            last = loc;
+        }
+        r.job = R.ord[s];
+        m->recs.push_back(r);
+    }
+    return 0;
+}
+
+// one round of jobs of three and more sequences above RV_LEAF_N ranks (RV_MANY_LARGE_MULTI): the jobs order[lo .. hi) (ascending size), k mixed.
+// The sample-major text goes into the shared handle (K samples, K the widest job), the index of every job is built at once
+// (rv_many_large_build_k), the segments become a level-0 frontier of J roots of k samples each, and the level pipeline finishes them together.
+int many_round_large_multi(rv_many *m, const std::vector<int> &order, size_t lo, size_t hi, int minl, int minn, rv_align_stats *total) {
+    RV_TRY(many_handle(m, &m->hs));
+    rv_index *h = m->hs;
+    const size_t J = hi - lo;
+    RV_TRY(rv_reset(h));
+    ManyRoundK R;
+    R.ord.assign(order.begin() + (ptrdiff_t)lo, order.begin() + (ptrdiff_t)hi);
+    R.dj.resize(J);
+    int K = 0;
+    for (size_t s = 0; s < J; s++) K = std::max(K, m->jobs[(size_t)R.ord[s]].k);
+    if (K < 3 || K > RV_MANY_KMAX) { rv_set_error("rv_many_run: a round of jobs of %d sequences", K); return -1; }
+    R.send.resize((size_t)K); R.sbeg.resize((size_t)K); R.sslot.resize((size_t)K);
+    // text: sample q = the q-th sequence of every job that has one
+    std::vector<char> buf;
+    std::vector<int64_t> lens;
+    int64_t n = 0, maxn = 0, nnodes = 0;
+    for (int q = 0; q < K; q++) {
+        buf.clear(); lens.clear();
+        for (size_t s = 0; s < J; s++) {
+            const ManyJob &jb = m->jobs[(size_t)R.ord[s]];
+            if (q >= jb.k) continue;
+            const int64_t len = m->lens[jb.seq0 + (size_t)q];
+            R.dj[s].beg[q] = n + (int64_t)buf.size();
+            R.sbeg[(size_t)q].push_back(R.dj[s].beg[q]); R.sslot[(size_t)q].push_back((int)s);
+            const char *src = m->in.data() + m->starts[jb.seq0 + (size_t)q];
+            buf.insert(buf.end(), src, src + len);
+            buf.push_back('$');
+            lens.push_back(len);
+        }
+        RV_TRY(rv_add_sample(h));
+        RV_TRY(rv_add_sequences(h, buf.data(), (int64_t)buf.size(), lens.data(), (int64_t)lens.size()));
+        n += (int64_t)buf.size();
+        R.send[(size_t)q] = n - 1;
+    }
+    RV_TRY(rv_upload(h));
+    // jobs, segment offsets, frontier tables
+    std::vector<int64_t> meta(6 * J), node_first(J + 1);
+    int64_t off = 0;
+    for (size_t s = 0; s < J; s++) {
+        const ManyJob &jb = m->jobs[(size_t)R.ord[s]];
+        ManyDevJobK &d = R.dj[s];
+        d.off = off; d.k = jb.k; d.n = (int32_t)jb.ranks;
+        int64_t pe = 0;
+        for (int q = 0; q < RV_MANY_KMAX; q++) {
+            if (q < jb.k) pe += m->lens[jb.seq0 + (size_t)q] + 1; else d.beg[q] = 0;
+            d.pend[q] = (int32_t)pe;
+        }
+        if (pe != jb.ranks) { rv_set_error("rv_many_run: the lengths of a job do not add up to its ranks"); return -1; }
+        int64_t *m6 = meta.data() + 6 * s;
+        m6[0] = off; m6[1] = jb.ranks; m6[2] = 0; m6[3] = jb.k; m6[4] = 0; m6[5] = -1;
+        node_first[s] = nnodes; nnodes += jb.k;
+        maxn = std::max(maxn, jb.ranks);
+        off += jb.ranks;
+    }
+    node_first[J] = nnodes;
+    if (off != n) { rv_set_error("rv_many_run: the jobs' ranks do not add up to the text"); return -1; }
+    std::vector<int64_t> nodes((size_t)(2 * nnodes));
+    for (size_t s = 0; s < J; s++)
+        for (int q = 0; q < R.dj[s].k; q++) {
+            const size_t x = (size_t)(2 * (node_first[s] + q));
+            nodes[x] = R.dj[s].beg[q]; nodes[x + 1] = R.dj[s].beg[q] + (R.dj[s].pend[q] - (q ? R.dj[s].pend[q - 1] : 0) - 1);
+        }
+    hipStream_t q = h->ws.stream;
+    RV_TRY(m->dKJobs.reserve(J * sizeof(ManyDevJobK)));
+    RV_TRY(m->dSA.reserve((size_t)(n + 64) * sizeof(sa_t)));
+    RV_TRY(m->dLCP.reserve((size_t)(n + 64) * sizeof(lcp_t)));
+    RV_TRY(m->dBWT.reserve((size_t)n + 64));
+    RV_TRY(m->dCnt.reserve(64));
+    RV_HIP(hipMemcpyAsync(m->dKJobs.p, R.dj.data(), J * sizeof(ManyDevJobK), hipMemcpyHostToDevice, q));
+    RV_HIP(hipMemsetAsync(m->dCnt.p, 0, 64, q));
+    u32 *d_max = m->dCnt.as<u32>();
+    RV_TRY(rv_many_large_build_k(h->ws, m->large_bufs, m->dKJobs.as<ManyDevJobK>(), (int64_t)J, n, maxn, h->dT0.as<uint8_t>(), n, m->dSA.as<sa_t>(), m->dLCP.as<lcp_t>(),
+                                 m->dBWT.as<uint8_t>(), d_max, &m->info[4]));
+    u32 cnt[2] = {0, 0};
+    RV_TRY(rv_read_back(h->ws, cnt, d_max, 8));
+    if (cnt[1]) { rv_set_error("rv_many_run: the index build refused a job (error bits %u)", cnt[1]); return -1; }
+    if (m->keep) {
+        // test hook: SA / LCP of every job in job-local positions
+        std::vector<sa_t> sa((size_t)n); std::vector<lcp_t> lc((size_t)n);
+        RV_HIP(hipMemcpy(sa.data(), m->dSA.p, (size_t)n * sizeof(sa_t), hipMemcpyDeviceToHost));
+        RV_HIP(hipMemcpy(lc.data(), m->dLCP.p, (size_t)n * sizeof(lcp_t), hipMemcpyDeviceToHost));
+        const size_t base = m->keep_sa.size();
+        m->keep_sa.resize(base + (size_t)n); m->keep_lcp.resize(base + (size_t)n);
+        for (size_t s = 0; s < J; s++) {
+            m->jobs[(size_t)R.ord[s]].arr_off = (int64_t)base + R.dj[s].off;
+            for (int64_t r = R.dj[s].off; r < R.dj[s].off + R.dj[s].n; r++) {
+                const int64_t p = (int64_t)sa[(size_t)r];
+                const int sq = R.sample_of(p);
+                if (sq >= R.dj[s].k) { rv_set_error("rv_many_run: a suffix outside its job"); return -1; }
+                m->keep_sa[base + (size_t)r] = (sa_t)R.local(s, sq, p);
+                m->keep_lcp[base + (size_t)r] = lc[(size_t)r];
+            }
+        }
+    }
+    RV_TRY(rv_frontier_import(h, minl, minn, cnt[0], 0, (int)J, meta.data(), node_first.data(), nodes.data(), n, m->dSA.p, m->dLCP.p, m->dBWT.p, 1));
+    rv_align_stats st;
+    memset(&st, 0, sizeof st);
+    RV_TRY(rv_align_builtin_resume(h, &st));
+    many_add_stats(total, st);
+    const size_t rec0 = m->recs.size();
+    RV_TRY(many_collect_k(m, h, R));
+    m->info[4] += st.levels + (m->recs.size() > rec0 ? 2 : 0);      // one per level, and the two of the lower-casing when there are anchors
+    // final text of every job, gathered from its k places
+    std::vector<char> txt((size_t)n);
+    RV_TRY(rv_ensure_working_text(h));
+    RV_HIP(hipStreamSynchronize(h->ws.stream));
+    RV_HIP(hipMemcpy(txt.data(), h->dT.p, (size_t)n, hipMemcpyDeviceToHost));
+    for (size_t s = 0; s < J; s++) {
+        ManyJob &jb = m->jobs[(size_t)R.ord[s]];
+        jb.text_off = (int64_t)m->out_text.size();
+        jb.shared = true;
+        for (int sq = 0; sq < jb.k; sq++) {
+            const int64_t b = R.dj[s].beg[sq], len1 = R.dj[s].pend[sq] - (sq ? R.dj[s].pend[sq - 1] : 0);
+            m->out_text.insert(m->out_text.end(), txt.begin() + (ptrdiff_t)b, txt.begin() + (ptrdiff_t)(b + len1));
+        }
+    }
+    m->info[1] += (int64_t)J; m->info[3]++;
+    return 0;
+}
+
 // a job the shared launches do not take: construct() + rv_align_builtin on the reused handle, every sequence a sample
 int many_ordinary(rv_many *m, int job, int minl, int minn, rv_align_stats *total) {
     RV_TRY(many_handle(m, &m->ho));
@@ -554,7 +737,7 @@ int many_run(rv_many *m, int minl, int minn, rv_align_stats *total) {
     if (total) memset(total, 0, sizeof *total);
     const int nj = (int)m->jobs.size();
     m->info[0] = nj;
-    std::vector<int> order, morder, lorder, rest;
+    std::vector<int> order, morder, lorder, lmorder, rest;
     // rounds: a round's text stays below the 32-bit library's position limit (and a bound on the device memory of a round)
     const int64_t lim = std::max<int64_t>(std::min<int64_t>(m->round_max, (int64_t)INT_MAX - 4096), 1);
     // (a large job has to fit a round: one that does not goes the ordinary way)
@@ -562,11 +745,17 @@ int many_run(rv_many *m, int minl, int minn, rv_align_stats *total) {
     int64_t nlarge = 0;
     for (const ManyJob &jb : m->jobs) nlarge += is_large(jb) ? 1 : 0;
     const bool take_large = nlarge > 0 && nlarge >= m->large_min;
+    // (the jobs of three and more sequences are counted on their own, against a threshold of their own: what a call does with its pair jobs does not depend on them)
+    const auto is_large_multi = [&](const ManyJob &jb) { return m->large_multi && jb.k >= 3 && jb.k <= RV_MANY_KMAX && jb.clean && jb.ranks > RV_LEAF_N && jb.ranks <= m->large_max && jb.ranks <= lim; };
+    int64_t nlmulti = 0;
+    for (const ManyJob &jb : m->jobs) nlmulti += is_large_multi(jb) ? 1 : 0;
+    const bool take_large_multi = nlmulti > 0 && nlmulti >= m->large_multi_min;
     for (int j = 0; j < nj; j++) {
         ManyJob &jb = m->jobs[(size_t)j];
         jb.arr_off = -1;
         if (jb.k == 2 && jb.ranks <= RV_LEAF_N && jb.clean) order.push_back(j);
         else if (take_large && is_large(jb)) lorder.push_back(j);
+        else if (take_large_multi && is_large_multi(jb)) lmorder.push_back(j);
         else if (m->multi && jb.k >= 3 && jb.k <= RV_MANY_KMAX && jb.ranks <= RV_LEAF_N && jb.clean) morder.push_back(j);
         else rest.push_back(j);
     }
@@ -574,6 +763,7 @@ int many_run(rv_many *m, int minl, int minn, rv_align_stats *total) {
     std::stable_sort(order.begin(), order.end(), by_size);
     std::stable_sort(morder.begin(), morder.end(), by_size);
     std::stable_sort(lorder.begin(), lorder.end(), by_size);
+    std::stable_sort(lmorder.begin(), lmorder.end(), by_size);
     for (size_t lo = 0; lo < order.size();) {
         size_t hi = lo; int64_t sum = 0;
         while (hi < order.size() && (hi == lo || sum + m->jobs[(size_t)order[hi]].ranks <= lim)) sum += m->jobs[(size_t)order[hi++]].ranks;
@@ -590,6 +780,12 @@ int many_run(rv_many *m, int minl, int minn, rv_align_stats *total) {
         size_t hi = lo; int64_t sum = 0;
         while (hi < morder.size() && (hi == lo || sum + m->jobs[(size_t)morder[hi]].ranks <= lim)) sum += m->jobs[(size_t)morder[hi++]].ranks;
         RV_TRY(many_round_multi(m, morder, lo, hi, minl, minn, total));
+        lo = hi;
+    }
+    for (size_t lo = 0; lo < lmorder.size();) {     // the jobs of three and more sequences above RV_LEAF_N ranks: rounds of their own
+        size_t hi = lo; int64_t sum = 0;
+        while (hi < lmorder.size() && (hi == lo || sum + m->jobs[(size_t)lmorder[hi]].ranks <= lim)) sum += m->jobs[(size_t)lmorder[hi++]].ranks;
+        RV_TRY(many_round_large_multi(m, lmorder, lo, hi, minl, minn, total));
         lo = hi;
     }
     for (int j : rest) RV_TRY(many_ordinary(m, j, minl, minn, total));
@@ -634,7 +830,7 @@ void rv_many_free(rv_many *m) {
     (void)hipSetDevice(m->device);
     if (m->hs) rv_free(m->hs);
     if (m->ho) rv_free(m->ho);
-    m->dJobs.release(); m->dSA.release(); m->dLCP.release(); m->dBWT.release(); m->dCnt.release();
+    m->dJobs.release(); m->dKJobs.release(); m->dSA.release(); m->dLCP.release(); m->dBWT.release(); m->dCnt.release();
     m->dTxt.release(); m->dMJobs.release(); m->dAn.release(); m->dAnPos.release();
     m->large_bufs.release();
     delete m;
@@ -646,6 +842,8 @@ int rv_many_option(rv_many *m, const char *name, int64_t value) {
     if (strcmp(name, "RV_MANY_ROUND") == 0) { if (value < 1) { rv_set_error("RV_MANY_ROUND: at least 1"); return -1; } m->round_max = value; return 0; }
     if (strcmp(name, "RV_MANY_MULTI") == 0) { m->multi = value != 0; return 0; }
     if (strcmp(name, "RV_MANY_LARGE") == 0) { m->large = value != 0; return 0; }
+    if (strcmp(name, "RV_MANY_LARGE_MULTI") == 0) { m->large_multi = value != 0; return 0; }
+    if (strcmp(name, "RV_MANY_LARGE_MULTI_MIN") == 0) { if (value < 0) { rv_set_error("RV_MANY_LARGE_MULTI_MIN: negative"); return -1; } m->large_multi_min = value; return 0; }
     if (strcmp(name, "RV_MANY_LARGE_MAX") == 0) { if (value < 0) { rv_set_error("RV_MANY_LARGE_MAX: negative"); return -1; } m->large_max = value; return 0; }
     if (strcmp(name, "RV_MANY_LARGE_MIN") == 0) { if (value < 0) { rv_set_error("RV_MANY_LARGE_MIN: negative"); return -1; } m->large_min = value; return 0; }
     if (strcmp(name, "RV_MANY_STAGE") == 0) { if (value < 0) { rv_set_error("RV_MANY_STAGE: negative"); return -1; } m->stage = value; return 0; }

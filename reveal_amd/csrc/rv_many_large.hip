@@ -19,6 +19,7 @@
 // Every kernel is a streaming pass of a few bytes per element, plus the gather rank[e + h] inside a job's segment.
 #include "rv_many_large.h"
 #include "rv_index.h"
+#include <type_traits>
 
 namespace {
 
@@ -31,6 +32,15 @@ constexpr int MAX_ROUNDS = 40;
 constexpr int TIE_SLOTS = 1024;            // words of the tie flag: a workgroup marks slot blockIdx % TIE_SLOTS, the host reads them all
 
 __device__ inline u64 ml_zero_bytes(u64 v) { return (v - 0x0101010101010101ull) & ~v & 0x8080808080808080ull; }
+
+// the first rank behind a job's segment
+template <class JobT>
+__device__ inline int64_t ml_end(const JobT *jobs, u32 j, int64_t n) {
+    if constexpr (std::is_same_v<JobT, ManyDevJobK>) {      // never behind the round's last element, whatever a descriptor the gather has refused says
+        const int64_t end = jobs[j].off + jobs[j].n;
+        return end < n ? end : n;
+    } else return jobs[j].off + jobs[j].la + jobs[j].lb + 2;
+}
 
 __global__ __launch_bounds__(LT) void k_ml_gather(const ManyDevJob *__restrict__ jobs, int njobs, int64_t n, const uint8_t *__restrict__ T,
                                                    uint8_t *__restrict__ txt, u32 *__restrict__ job, u32 *__restrict__ d_err) {
@@ -45,12 +55,13 @@ __global__ __launch_bounds__(LT) void k_ml_gather(const ManyDevJob *__restrict__
     job[e] = (u32)lo;
 }
 
-__global__ __launch_bounds__(LT) void k_ml_first_keys(const ManyDevJob *__restrict__ jobs, int64_t n, const uint8_t *__restrict__ txt, const u32 *__restrict__ job,
+template <class JobT>
+__global__ __launch_bounds__(LT) void k_ml_first_keys(const JobT *__restrict__ jobs, int64_t n, const uint8_t *__restrict__ txt, const u32 *__restrict__ job,
                                                        u64 *__restrict__ key, u32 *__restrict__ val) {
     const int64_t e = (int64_t)blockIdx.x * LT + threadIdx.x;
     if (e >= n) return;
     const u32 j = job[e];
-    const int64_t rem = jobs[j].off + jobs[j].la + jobs[j].lb + 2 - e;      // characters the job has left from e on
+    const int64_t rem = ml_end(jobs, j, n) - e;      // characters the job has left from e on
     u64 w;
     __builtin_memcpy(&w, txt + e, 8);      // (the buffer is padded behind n)
     u64 k = 0;
@@ -78,12 +89,13 @@ __global__ __launch_bounds__(LT) void k_ml_ranks(const u32 *__restrict__ val, co
     if (i < n) rank[val[i]] = run[i];
 }
 
-__global__ __launch_bounds__(LT) void k_ml_pair_keys(const ManyDevJob *__restrict__ jobs, int64_t n, const u32 *__restrict__ job, const u32 *__restrict__ rank,
+template <class JobT>
+__global__ __launch_bounds__(LT) void k_ml_pair_keys(const JobT *__restrict__ jobs, int64_t n, const u32 *__restrict__ job, const u32 *__restrict__ rank,
                                                       int64_t h, int b2, u64 *__restrict__ key, u32 *__restrict__ val) {
     const int64_t e = (int64_t)blockIdx.x * LT + threadIdx.x;
     if (e >= n) return;
     const u32 j = job[e];
-    const int64_t off = jobs[j].off, end = off + jobs[j].la + jobs[j].lb + 2;
+    const int64_t off = jobs[j].off, end = ml_end(jobs, j, n);
     const u64 r1 = rank[e], r2 = e + h < end ? (u64)(rank[e + h] - (u32)off) : 0ull;
     key[e] = (r1 << b2) | r2;
     val[e] = (u32)e;
@@ -122,6 +134,78 @@ __global__ __launch_bounds__(LT) void k_ml_finish(const ManyDevJob *__restrict__
     if ((threadIdx.x & 63) == 0 && lmax > __atomic_load_n(d_maxlcp, __ATOMIC_RELAXED)) atomicMax(d_maxlcp, lmax);
 }
 
+// The gather of a sample-major round: element -> job by the search in the offsets, local position -> sequence by a scan of the (at most 16)
+// prefix ends, byte from the shared text.  The thread of a job's first element checks the whole descriptor; every thread checks what it reads
+// with: a malformed descriptor sets the error word and reads nothing outside T.
+__global__ __launch_bounds__(LT) void k_mlk_gather(const ManyDevJobK *__restrict__ jobs, int njobs, int64_t n, const uint8_t *__restrict__ T, int64_t nT,
+                                                   uint8_t *__restrict__ txt, u32 *__restrict__ job, u32 *__restrict__ d_err) {
+    const int64_t e = (int64_t)blockIdx.x * LT + threadIdx.x;
+    if (e >= n) return;
+    int lo = 0, hi = njobs;                // the last job whose segment begins at or in front of e
+    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (jobs[mid].off <= e) lo = mid; else hi = mid; }
+    const ManyDevJobK *J = jobs + lo;
+    const int64_t p = e - J->off;
+    const int k = J->k, nj = J->n;
+    job[e] = (u32)lo;
+    bool bad = k < 3 || k > RV_MANY_KMAX || p < 0 || p >= nj;
+    uint8_t ch = (uint8_t)'$';
+    if (!bad) {
+        if (p == 0) {                      // the whole descriptor, once per job: its sequences, and its segment between its neighbours
+            if (J->off + nj != (lo + 1 < njobs ? jobs[lo + 1].off : n)) bad = true;
+            int prev = 0;
+            for (int q = 0; q < k; q++) { const int pe = J->pend[q]; if (pe - prev < 2) bad = true; prev = pe; }      // (a sequence of at least one base and its '$')
+            if (prev != nj) bad = true;
+        }
+        int q = 0, prev = 0;
+        while (q < k - 1 && p >= J->pend[q]) prev = J->pend[q++];
+        const int64_t src = J->beg[q] + (p - prev);
+        if (p < prev || p >= J->pend[q] || src < 0 || src >= nT) bad = true;
+        else ch = T[src];
+    }
+    if (bad) atomicOr(d_err, 1u);
+    txt[e] = ch;
+}
+
+// The finish of a sample-major round: k_ml_finish with the position map of k sequences.  A thread walks 16 consecutive elements, so the sequence
+// of the local position moves forward with it; the side bit of the BWT byte is "behind the first sequence's '$'" (p > la, la = pend[0] - 1).
+// Where the gather has refused a descriptor the kernel does nothing: the host reports the error word.
+__global__ __launch_bounds__(LT) void k_mlk_finish(const ManyDevJobK *__restrict__ jobs, int64_t n, const uint8_t *__restrict__ txt, const u32 *__restrict__ job,
+                                                    const u32 *__restrict__ rank, const u32 *__restrict__ order, sa_t *__restrict__ SA, lcp_t *__restrict__ LCP,
+                                                    uint8_t *__restrict__ BWT, u32 *__restrict__ d_maxlcp, const u32 *__restrict__ d_err) {
+    if (__atomic_load_n(d_err, __ATOMIC_RELAXED)) return;      // (a text the gather did not finish need not end in '$')
+    const int64_t e0 = ((int64_t)blockIdx.x * LT + threadIdx.x) * FIN_CHUNK;
+    u32 lmax = 0, jcur = ~0u;
+    const ManyDevJobK *J = jobs;
+    int64_t off = 0, la = 0, hh = 0, sbeg = 0;      // sbeg: shared-text position of local position 0 of the current sequence, minus its local begin
+    int q = 0, kk = 0, pe = 0;
+    for (int64_t e = e0; e < e0 + FIN_CHUNK && e < n; e++) {
+        const u32 j = job[e];
+        if (j != jcur) { J = jobs + j; off = J->off; la = J->pend[0] - 1; kk = J->k < RV_MANY_KMAX ? J->k : RV_MANY_KMAX; jcur = j; hh = 0; q = 0; pe = J->pend[0]; sbeg = J->beg[0]; }      // (a job's first position: no carry)
+        const int64_t p = e - off, k = (int64_t)rank[e] - 1;
+        while (q < kk - 1 && p >= pe) { sbeg = J->beg[q + 1] - pe; pe = J->pend[++q]; }
+        if (k > off) {
+            const int64_t o = order[k - 1];
+            for (;;) {
+                u64 a, b;
+                __builtin_memcpy(&a, txt + e + hh, 8);
+                __builtin_memcpy(&b, txt + o + hh, 8);
+                const u64 x = a ^ b, z = ml_zero_bytes(a ^ 0x2424242424242424ull) | ml_zero_bytes(a ^ 0x4E4E4E4E4E4E4E4Eull);      // '$', 'N'
+                const int m = x ? (int)(__builtin_ctzll(x) >> 3) : 8, s = z ? (int)(__builtin_ctzll(z) >> 3) : 8;
+                const int step = m < s ? m : s;
+                hh += step;
+                if (step < 8) break;       // (a job's text ends with '$': no comparison runs past it)
+            }
+            LCP[k] = (lcp_t)hh;
+            if ((u32)hh > lmax) lmax = (u32)hh;
+        } else { LCP[k] = 0; hh = 0; }     // the job's first rank
+        SA[k] = (sa_t)(sbeg + p);
+        BWT[k] = (uint8_t)((p > 0 ? txt[e - 1] : (uint8_t)'$') | (p > la ? RV_BWT_SIDE : 0u));
+        if (hh > 0) hh--;
+    }
+    lmax = (u32)rv_wave_max_u64((u64)lmax);
+    if ((threadIdx.x & 63) == 0 && lmax > __atomic_load_n(d_maxlcp, __ATOMIC_RELAXED)) atomicMax(d_maxlcp, lmax);
+}
+
 int ml_bits(int64_t v) { int b = 1; while (b < 63 && ((int64_t)1 << b) <= v) b++; return b; }      // bits that hold 0 .. v
 
 // kernels of the primitives (rv_prims.hip), for the launch count
@@ -131,10 +215,11 @@ int ml_sort_launches(const Workspace &ws, int64_t n, int bits) {
     return rv_radix_passes(ws, bits) * (2 + ml_scan_launches(((int64_t)1 << width) * ceil_div(n, 4096)));
 }
 
-}  // namespace
-
-int rv_many_large_build(Workspace &ws, RvManyLargeBufs &B, const ManyDevJob *djobs, int64_t njobs, int64_t n, int64_t maxn, const uint8_t *T,
-                        sa_t *SA, lcp_t *LCP, uint8_t *BWT, u32 *d_cnt, int64_t *launches) {
+// JobT: ManyDevJob (pair rounds) or ManyDevJobK (sample-major rounds: their own gather and finish; nT, the bytes of T, is theirs alone); the kernels
+// in between only need a segment's end
+template <class JobT>
+int ml_build(Workspace &ws, RvManyLargeBufs &B, const JobT *djobs, int64_t njobs, int64_t n, int64_t maxn, const uint8_t *T, int64_t nT,
+             sa_t *SA, lcp_t *LCP, uint8_t *BWT, u32 *d_cnt, int64_t *launches) {
     if (njobs < 1 || njobs >= ((int64_t)1 << JOB_BITS) || n < 1 || n >= ((int64_t)1 << RANK_BITS) || maxn < 1 || maxn > n) { rv_set_error("rv_many_run: a round of large jobs of bad sizes"); return -1; }
     const int b2 = ml_bits(maxn);          // a job-local rank is 0 .. maxn
     hipStream_t q = ws.stream;
@@ -152,9 +237,10 @@ int rv_many_large_build(Workspace &ws, RvManyLargeBufs &B, const ManyDevJob *djo
     std::vector<u32> slots(TIE_SLOTS);
     const dim3 grid((unsigned)ceil_div(n, LT)), block(LT);
     RV_HIP(hipMemsetAsync(txt + n, 0, 64, q));
-    hipLaunchKernelGGL(k_ml_gather, grid, block, 0, q, djobs, (int)njobs, n, T, txt, job, d_err);
+    if constexpr (std::is_same_v<JobT, ManyDevJobK>) hipLaunchKernelGGL(k_mlk_gather, grid, block, 0, q, djobs, (int)njobs, n, T, nT, txt, job, d_err);
+    else hipLaunchKernelGGL(k_ml_gather, grid, block, 0, q, djobs, (int)njobs, n, T, txt, job, d_err);
     RV_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_ml_first_keys, grid, block, 0, q, djobs, n, (const uint8_t *)txt, (const u32 *)job, key[0], val[0]);
+    hipLaunchKernelGGL(k_ml_first_keys<JobT>, grid, block, 0, q, djobs, n, (const uint8_t *)txt, (const u32 *)job, key[0], val[0]);
     RV_LAUNCH_CHECK();
     *launches += 2;
     int cur = 0, bits = 7 * FIRST_CHARS + JOB_BITS;
@@ -174,15 +260,30 @@ int rv_many_large_build(Workspace &ws, RvManyLargeBufs &B, const ManyDevJob *djo
         for (u32 x : slots) tied |= x;
         if (!tied) break;
         if (round >= MAX_ROUNDS) { rv_set_error("rv_many_run: the order of a round of large jobs is not final after %d doubling rounds", round); return -1; }      // (cannot happen: h passes 2^31 first)
-        hipLaunchKernelGGL(k_ml_pair_keys, grid, block, 0, q, djobs, n, (const u32 *)job, (const u32 *)rank, h, b2, key[0], val[0]);
+        hipLaunchKernelGGL(k_ml_pair_keys<JobT>, grid, block, 0, q, djobs, n, (const u32 *)job, (const u32 *)rank, h, b2, key[0], val[0]);
         RV_LAUNCH_CHECK();
         (*launches)++;
         bits = RANK_BITS + b2;
         h <<= 1;
     }
-    hipLaunchKernelGGL(k_ml_finish, dim3((unsigned)ceil_div(ceil_div(n, FIN_CHUNK), LT)), block, 0, q, djobs, n, (const uint8_t *)txt, (const u32 *)job,
-                       (const u32 *)rank, (const u32 *)val[cur], SA, LCP, BWT, d_max);
+    const dim3 fgrid((unsigned)ceil_div(ceil_div(n, FIN_CHUNK), LT));
+    if constexpr (std::is_same_v<JobT, ManyDevJobK>)
+        hipLaunchKernelGGL(k_mlk_finish, fgrid, block, 0, q, djobs, n, (const uint8_t *)txt, (const u32 *)job, (const u32 *)rank, (const u32 *)val[cur], SA, LCP, BWT, d_max, (const u32 *)d_err);
+    else
+        hipLaunchKernelGGL(k_ml_finish, fgrid, block, 0, q, djobs, n, (const uint8_t *)txt, (const u32 *)job, (const u32 *)rank, (const u32 *)val[cur], SA, LCP, BWT, d_max);
     RV_LAUNCH_CHECK();
     (*launches)++;
     return 0;
+}
+
+}  // namespace
+
+int rv_many_large_build(Workspace &ws, RvManyLargeBufs &B, const ManyDevJob *djobs, int64_t njobs, int64_t n, int64_t maxn, const uint8_t *T,
+                        sa_t *SA, lcp_t *LCP, uint8_t *BWT, u32 *d_cnt, int64_t *launches) {
+    return ml_build(ws, B, djobs, njobs, n, maxn, T, 0, SA, LCP, BWT, d_cnt, launches);
+}
+
+int rv_many_large_build_k(Workspace &ws, RvManyLargeBufs &B, const ManyDevJobK *djobs, int64_t njobs, int64_t n, int64_t maxn, const uint8_t *T, int64_t nT,
+                          sa_t *SA, lcp_t *LCP, uint8_t *BWT, u32 *d_cnt, int64_t *launches) {
+    return ml_build(ws, B, djobs, njobs, n, maxn, T, nT, SA, LCP, BWT, d_cnt, launches);
 }

@@ -16,7 +16,17 @@ switch RV_MANY_LARGE is on (`align_many(.., large=True)`, `Batch.option("RV_MANY
 With it the pair jobs of 2049 .. RV_MANY_LARGE_MAX ranks (default 2^17) share their launches too, in rounds of their own: the pair layout of
 the small jobs, the index of every job of a round built at once by a segmented prefix doubling in device memory
 (csrc/rv_many_large.hip), and the level pipeline of the recursion over all of them together.  A call with fewer than RV_MANY_LARGE_MIN
-such jobs (default 4) leaves them on the ordinary path.  Jobs of three and more sequences above 2048 ranks always run the ordinary way.
+such jobs (default 4) leaves them on the ordinary path.
+
+Jobs of three and more sequences above 2048 ranks -- a bubble of a graph of more than two genomes with alleles above about 700 bases -- run the
+ordinary way unless the switch RV_MANY_LARGE_MULTI is on (`align_many(.., large_multi=True)`, `Batch.option("RV_MANY_LARGE_MULTI", 1)` or the
+environment variable; off by default).  With it the jobs of 3 .. 16 sequences and 2049 .. RV_MANY_LARGE_MAX ranks share their launches too, in
+rounds of their own that may mix jobs of different k: the round's text is sample-major (`sample_major_layout`: sample q holds the q-th sequence
+of every job that has one), the same segmented prefix doubling builds every job's index from its job-local text, and the level pipeline for
+more than two samples finishes all of them together.  A call with fewer than RV_MANY_LARGE_MULTI_MIN such jobs (default 16, counted on their
+own) leaves them on the ordinary path.  With all three switches on, every
+clean job of 2 .. 16 sequences up to RV_MANY_LARGE_MAX ranks that fits a round goes through shared launches -- in a call that holds at least
+RV_MANY_LARGE_MIN pair jobs and RV_MANY_LARGE_MULTI_MIN jobs of three and more sequences above 2048 ranks, where it has any.
 The results do not depend on these switches either.
 """
 import ctypes
@@ -58,14 +68,17 @@ def job_sequences(job, toupper=True):
     return seqs
 
 
-def takes_shared_launch(seqs, multi=False, large=False, large_max=LARGE_MAX):
+def takes_shared_launch(seqs, multi=False, large=False, large_max=LARGE_MAX, large_multi=False):
     """whether the library builds and finishes this job in the shared launches; multi: with RV_MANY_MULTI on; large: with RV_MANY_LARGE
-    on and RV_MANY_LARGE_MAX = large_max (in a call with at least RV_MANY_LARGE_MIN such jobs, and with rounds that hold the job)"""
-    kmax = MULTI_KMAX if multi else 2
-    ranks = sum(len(s) for s in seqs) + len(seqs)
-    if not (2 <= len(seqs) <= kmax) or any(b"\0" in s for s in seqs):
+    on and RV_MANY_LARGE_MAX = large_max (in a call with at least RV_MANY_LARGE_MIN such jobs, and with rounds that hold the job);
+    large_multi: with RV_MANY_LARGE_MULTI on (in a call with at least RV_MANY_LARGE_MULTI_MIN such jobs, and with rounds that hold the job)"""
+    k = len(seqs)
+    ranks = sum(len(s) for s in seqs) + k
+    if not (2 <= k <= MULTI_KMAX) or any(b"\0" in s for s in seqs):
         return False
-    return ranks <= LEAF_RANKS or (bool(large) and len(seqs) == 2 and ranks <= large_max)
+    if ranks <= LEAF_RANKS:
+        return k == 2 or bool(multi)
+    return ranks <= large_max and bool(large if k == 2 else large_multi)
 
 
 def shared_layout(pairs):
@@ -91,6 +104,36 @@ def to_shared(loc, abeg, bbeg, la):
     return (0, abeg + loc) if loc <= la else (1, bbeg + loc - la - 1)
 
 
+def sample_major_layout(jobs):
+    """the shared text of jobs of several sequences [[s0, s1, ..], ..] in the given order, k mixed: sample q holds the q-th sequence of every
+    job that has one, a '$' behind each -> (text, nsep, begins): nsep[q] = the '$' behind the last sequence of sample q, begins[j][q] = where
+    sequence q of job j begins"""
+    K = max(len(j) for j in jobs)
+    text, nsep, begins = bytearray(), [], [[] for _ in jobs]
+    for q in range(K):
+        for j, seqs in enumerate(jobs):
+            if q < len(seqs):
+                begins[j].append(len(text))
+                text += seqs[q] + b"$"
+        nsep.append(len(text) - 1)
+    return bytes(text), nsep, begins
+
+
+def to_shared_k(loc, begins, lens):
+    """stand-alone coordinate of the job's text `s0$s1$..` (begins, lens: of its sequences) -> (sequence, position of the shared text)"""
+    at = 0
+    for q, n in enumerate(lens):
+        if loc <= at + n:
+            return q, begins[q] + loc - at
+        at += n + 1
+    raise error("coordinate %d outside a job of %d ranks" % (loc, at))
+
+
+def to_local_k(pos, q, begins, lens):
+    """position of the shared text inside the job's sequence q (or on its '$') -> stand-alone coordinate of the job's text `s0$s1$..`"""
+    return pos - begins[q] + sum(lens[:q]) + q
+
+
 class Batch:
     """the C object behind align_many (rv_many_*): add jobs, run, read the results; clear() keeps the allocations"""
 
@@ -110,7 +153,8 @@ class Batch:
                 except ValueError:
                     iv = 1
                 self.option(name, iv)
-        for name in ("RV_MANY_KEEP", "RV_MANY_ROUND", "RV_MANY_WAVE_MAX", "RV_MANY_MULTI", "RV_MANY_LARGE", "RV_MANY_LARGE_MAX", "RV_MANY_LARGE_MIN"):
+        for name in ("RV_MANY_KEEP", "RV_MANY_ROUND", "RV_MANY_WAVE_MAX", "RV_MANY_MULTI", "RV_MANY_LARGE", "RV_MANY_LARGE_MAX", "RV_MANY_LARGE_MIN",
+                     "RV_MANY_LARGE_MULTI", "RV_MANY_LARGE_MULTI_MIN"):
             v = os.environ.get(name)
             if v is not None and v.strip():
                 self.option(name, int(v))
@@ -181,14 +225,15 @@ class Batch:
         return sa, lcp
 
 
-def align_many(jobs, minlength=20, minn=2, sa64=False, toupper=True, batch=None, multi=None, large=None):
+def align_many(jobs, minlength=20, minn=2, sa64=False, toupper=True, batch=None, multi=None, large=None, large_multi=None):
     """jobs: a list of jobs, each a list of (name, seq) or of plain sequences (two or more, none empty; every sequence is a sample
     of its own, like the inputs of `reveal rem`).  -> (results, info): results[j] = dict(anchors=[(l, (pos, ..)), ..], T=final text
     `s0$s1$..` lower-cased where aligned), positions in the coordinates of the job's own text -- what index.align_builtin gives a
     stand-alone index of the job; info = dict(jobs, shared, ordinary, rounds, launches, stats).  `batch`: a Batch to reuse.
     `multi`: True / False sets RV_MANY_MULTI (jobs of 3 .. 16 sequences through the shared launches) for this and later runs of
     the batch; None leaves it as the batch has it (off, unless the environment variable is set).  `large`: the same for RV_MANY_LARGE
-    (pair jobs of 2049 .. RV_MANY_LARGE_MAX ranks through the shared launches)."""
+    (pair jobs of 2049 .. RV_MANY_LARGE_MAX ranks through the shared launches), `large_multi`: the same for RV_MANY_LARGE_MULTI (jobs of
+    3 .. 16 sequences of 2049 .. RV_MANY_LARGE_MAX ranks through the shared launches)."""
     if isinstance(jobs, (str, bytes, bytearray)) or not hasattr(jobs, "__iter__"):
         raise error("jobs is a list of jobs")
     if int(minlength) < 0 or int(minn) < 2:
@@ -199,6 +244,8 @@ def align_many(jobs, minlength=20, minn=2, sa64=False, toupper=True, batch=None,
         b.option("RV_MANY_MULTI", 1 if multi else 0)
     if large is not None:
         b.option("RV_MANY_LARGE", 1 if large else 0)
+    if large_multi is not None:
+        b.option("RV_MANY_LARGE_MULTI", 1 if large_multi else 0)
     b.clear()
     for seqs in prepared:
         b.add(seqs)

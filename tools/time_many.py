@@ -2,7 +2,7 @@
 """Many small pair alignments: ONE align_many call against the same jobs one after the other through one reused handle (GPU box).
 
     python tools/time_many.py [--jobs 10000] [--lmin 50] [--lmax 1000] [--reps 5] [--minlength 20] [--wave-max N] [--only loop|many] [--check]
-                              [--seqs K] [--multi 0|1|ab] [--large 0|1|ab] [--large-max R] [--large-min J]
+                              [--seqs K] [--multi 0|1|ab] [--large 0|1|ab] [--large-multi 0|1|ab] [--large-max R] [--large-min J]
 
 Workload: J jobs of 2 x L bases, L uniform in lmin .. lmax, 1 % substitutions.  The two sides run alternately, `reps` times each:
   loop   rv_reset, rv_add_sample / rv_add_sequence x 2, rv_construct, rv_align_builtin, rv_fetch_anchors, the text -- per job, straight at
@@ -13,7 +13,9 @@ Prints medians, the loop's spread, the ratio and one JSON line.  --check compare
 --multi 0 / 1 sets RV_MANY_MULTI of the `many` side (jobs of 3 .. 16 sequences through the shared launches).  --multi ab: no loop; two batches,
 switch off and on, run alternately in one process -- medians, both spreads, the ratio, and with --check the jobs that differ between the sides.
 --large 0 / 1 / ab: the same for RV_MANY_LARGE (pair jobs above 2048 ranks through shared launches; choose --lmin / --lmax above 1023);
---large-max / --large-min set RV_MANY_LARGE_MAX / RV_MANY_LARGE_MIN of every batch."""
+--large-multi 0 / 1 / ab: the same for RV_MANY_LARGE_MULTI (jobs of --seqs K >= 3 sequences above 2048 ranks; lmax is not cut then: choose
+--lmin / --lmax so that K x (L + 1) lies above 2048).  The ab legs also print the levels and scanned ranks of a call (the run's statistics).
+--large-max / --large-min set RV_MANY_LARGE_MAX / RV_MANY_LARGE_MIN of every batch (with --large-multi: RV_MANY_LARGE_MULTI_MIN too)."""
 import argparse
 import ctypes
 import json
@@ -28,11 +30,11 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from reveal_amd import _lib, reveallib      # noqa: E402
 
 
-def workload(jobs, lmin, lmax, seed=1, seqs=2):
+def workload(jobs, lmin, lmax, seed=1, seqs=2, cut=True):
     rng = np.random.default_rng(seed)
     lut = np.frombuffer(b"ACGT", np.uint8)
     out = []
-    if seqs > 2:
+    if seqs > 2 and cut:
         lmax = min(lmax, (2048 - seqs) // seqs)
         lmin = min(lmin, lmax)
     for _ in range(jobs):
@@ -82,7 +84,7 @@ def run_many_c(batch, jobs, minl):
     batch.clear()
     for j in jobs:
         batch.add(j)
-    batch.run(minl, 2)
+    batch.last_stats = batch.run(minl, 2)
     return batch.anchors()
 
 
@@ -97,10 +99,17 @@ def more_options(a, b):
         b.option("RV_MANY_LARGE_MAX", a.large_max)
     if a.large_min is not None:
         b.option("RV_MANY_LARGE_MIN", a.large_min)
+        if a.large_multi is not None:
+            from reveal_amd import many
+            try:
+                b.option("RV_MANY_LARGE_MULTI_MIN", a.large_min)
+            except many.error:      # (RV_LIB_DIR: a build from before the switch has no such jobs to count)
+                if a.large_multi != "0":
+                    raise
 
 
 def main_ab(a, jobs, bases, switch="RV_MANY_MULTI"):
-    """`switch` (RV_MANY_MULTI or RV_MANY_LARGE) off against on: two batches, alternately"""
+    """`switch` (RV_MANY_MULTI, RV_MANY_LARGE or RV_MANY_LARGE_MULTI) off against on: two batches, alternately"""
     from reveal_amd import many
     sides = {}
     for name, v in (("off", 0), ("on", 1)):
@@ -109,6 +118,8 @@ def main_ab(a, jobs, bases, switch="RV_MANY_MULTI"):
             b.option("RV_MANY_MULTI", int(a.multi))
         if switch != "RV_MANY_LARGE" and a.large in ("0", "1"):
             b.option("RV_MANY_LARGE", int(a.large))
+        if switch != "RV_MANY_LARGE_MULTI" and a.large_multi in ("0", "1"):
+            b.option("RV_MANY_LARGE_MULTI", int(a.large_multi))
         more_options(a, b)
         b.option(switch, v)
         if a.wave_max is not None:
@@ -124,8 +135,11 @@ def main_ab(a, jobs, bases, switch="RV_MANY_MULTI"):
         t = sides[name]["t"]
         out[name + "_s"] = t; out[name + "_median_s"] = statistics.median(t); out[name + "_spread_s"] = max(t) - min(t)
         out[name + "_info"] = sides[name]["batch"].info()
-        print("%-3s   : runs %s s; median %.4f s, spread (max - min) %.4f s, %.0f jobs/s; info %r"
-              % (name, " ".join("%.4f" % x for x in t), out[name + "_median_s"], out[name + "_spread_s"], a.jobs / out[name + "_median_s"], out[name + "_info"]))
+        st = sides[name]["batch"].last_stats
+        out[name + "_levels"] = int(st["levels"]); out[name + "_scanned_ranks"] = int(st["scanned_ranks"])
+        print("%-3s   : runs %s s; median %.4f s, spread (max - min) %.4f s, %.0f jobs/s; info %r; levels %d, scanned ranks %d"
+              % (name, " ".join("%.4f" % x for x in t), out[name + "_median_s"], out[name + "_spread_s"], a.jobs / out[name + "_median_s"], out[name + "_info"],
+                 out[name + "_levels"], out[name + "_scanned_ranks"]))
     out["ratio"] = out["off_median_s"] / out["on_median_s"]
     out["gain_s"] = out["off_median_s"] - out["on_median_s"]
     print("ratio : %.1f x  (gain %.4f s against the off side's spread of %.4f s)" % (out["ratio"], out["gain_s"], out["off_spread_s"]))
@@ -151,17 +165,22 @@ def main():
     ap.add_argument("--seqs", type=int, default=2, help="sequences per job")
     ap.add_argument("--multi", choices=("0", "1", "ab"), default=None, help="RV_MANY_MULTI of the many side; ab: off against on, no loop")
     ap.add_argument("--large", choices=("0", "1", "ab"), default=None, help="RV_MANY_LARGE of the many side; ab: off against on, no loop")
+    ap.add_argument("--large-multi", choices=("0", "1", "ab"), default=None, help="RV_MANY_LARGE_MULTI of the many side; ab: off against on, no loop")
     ap.add_argument("--large-max", type=int, default=None, help="RV_MANY_LARGE_MAX")
     ap.add_argument("--large-min", type=int, default=None, help="RV_MANY_LARGE_MIN")
     a = ap.parse_args()
-    if a.multi == "ab" and a.large == "ab":
-        ap.error("one switch at a time: --multi ab or --large ab")
-    jobs = workload(a.jobs, a.lmin, a.lmax, seqs=a.seqs)
+    if [a.multi, a.large, a.large_multi].count("ab") > 1:
+        ap.error("one switch at a time: --multi ab, --large ab or --large-multi ab")
+    if a.large_multi is not None and a.seqs < 3:
+        ap.error("--large-multi wants jobs of three and more sequences: --seqs K")
+    jobs = workload(a.jobs, a.lmin, a.lmax, seqs=a.seqs, cut=a.large_multi is None)
     bases = sum(len(s) for j in jobs for s in j)
     if a.multi == "ab":
         return main_ab(a, jobs, bases)
     if a.large == "ab":
         return main_ab(a, jobs, bases, "RV_MANY_LARGE")
+    if a.large_multi == "ab":
+        return main_ab(a, jobs, bases, "RV_MANY_LARGE_MULTI")
     t_loop, t_many, t_many_py = [], [], []
     idx = reveallib.index() if a.only != "many" else None
     batch = None
@@ -174,6 +193,13 @@ def main():
             batch.option("RV_MANY_MULTI", int(a.multi))
         if a.large is not None:
             batch.option("RV_MANY_LARGE", int(a.large))
+        if a.large_multi == "1":
+            batch.option("RV_MANY_LARGE_MULTI", 1)
+        elif a.large_multi == "0":
+            try:
+                batch.option("RV_MANY_LARGE_MULTI", 0)
+            except many.error:      # (RV_LIB_DIR: a build from before the switch -- off is all it knows)
+                pass
         more_options(a, batch)
         run_many_c(batch, jobs[:64], a.minlength)      # (first use: allocations, code objects)
     if idx is not None:
