@@ -226,6 +226,15 @@ uint32_t rv_maxlcp(const rv_index *h);
  * witnesses, out[4] sub-indices visited, out[5] sub-indices left undecided (rebuilt from their text and handed to the leaf
  * kernel), out[6] ranks rebuilt, out[7] large undecided sub-indices decided from their repeat witnesses (the second attempt) */
 int rv_cascade_info(const rv_index *h, int64_t *out);
+/* Every device list whose capacity is an estimate is filled behind a guard and counted beyond it; the host then goes round again with a
+ * list of the counted size.  out[0..9] = how often it did so since the last rv_construct / rv_reset (a worker handle: since rv_new), per
+ * place: [0] pair_ovf, [1] pair_out -- the pair scan's overflow buffer / output list (level pipeline and anchor cascade), [2] pair_pick_ovf
+ * -- the overflow buffer under the built-in picker, [3] pair_second_copy -- a level's records beyond the first host copy, [4] multi_rec,
+ * [5] multi_mem -- the multi scan's records / members, [6] multi_cand -- the multi picker's candidate list, [7] mems_rec, [8] mems_mem,
+ * [9] mems_long -- getmultimems' records / members / listed runs.  Host counters; nothing is read from the device.  (The anchor cascade's
+ * own lists have no retry: it gives up, rv_cascade_why says which list.)  The switches RV_CAP_LIMIT / RV_CAP_SITES (rv_set_option) are
+ * the test hook that makes a first attempt small: DESIGN.md, "Lists filled by atomics". */
+int rv_capacity_events(const rv_index *h, int64_t *out);
 const char *rv_cascade_why(const rv_index *h);      /* why the cascade left the last built-in run to the level pipeline ("": it did the run, or was not tried) */
 /* anchors chosen by the last rv_align_builtin: l[k], members off[k..k+1] -> pos[] (sorted) */
 int64_t rv_anchor_count(rv_index *h, int64_t *members);

@@ -689,6 +689,14 @@ def make_index_type(sa64, error):
             return dict(done=bool(o[0]), levels=int(o[1]), matches=int(o[2]), witnesses=int(o[3]), subindices=int(o[4]), undecided=int(o[5]), rebuilt_ranks=int(o[6]), decided_from_witnesses=int(o[7]),
                         why=(self._dll.rv_cascade_why(self._h) or b"").decode())
 
+        def capacity_events(self):
+            """how often the host went round again because a device list was too small, per place, since the last construct() / reset()
+            (rv_capacity_events; DESIGN.md "Lists filled by atomics")"""
+            o = np.zeros(len(_lib.CAPACITY_EVENTS), dtype=np.int64)
+            if self._dll.rv_capacity_events(self._main._h, o.ctypes.data) != 0:
+                self._fail()
+            return {k: int(v) for k, v in zip(_lib.CAPACITY_EVENTS, o)}
+
         def align_builtin_until(self, stop_subs, minl=20, minn=2, trace=False):
             """align_builtin that stops once the frontier holds >= stop_subs sub-indices.
             -> frontier size (0: the run finished first; align_builtin_resume() still returns its result)"""

@@ -16,6 +16,12 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 RV_T, RV_SA, RV_SAI, RV_LCP, RV_SO, RV_NSEP, RV_NODES = range(7)
 K_SCAN_PAIR, K_SCAN_MULTI, K_SA_SORT, K_LCP, K_SPLIT, K_LABEL, K_BUBBLE, K_RADIX_SCATTER, K_RADIX_HIST, K_TEXT_ROUND, K_CASCADE, K_DIAG_TABLE, K_INIT_KEYS, K_PUBLISH = range(14)
 
+# rv_capacity_events: the order of RvCapEvent (rv_common.h); RV_CAP_SITES: the bits of RvCapSite
+CAPACITY_EVENTS = ("pair_ovf", "pair_out", "pair_pick_ovf", "pair_second_copy", "multi_rec", "multi_mem", "multi_cand",
+                   "mems_rec", "mems_mem", "mems_long")
+CAP_SITES = {"multi_cand": 1, "cas_wit": 2, "cas_tables": 4, "casm_matches": 8, "casm_wit": 16, "casm_tables": 32,
+             "mems_rec": 64, "mems_mem": 128, "mems_long": 256}
+
 c_i64p = ctypes.POINTER(ctypes.c_int64)
 V = ctypes.c_void_p
 
@@ -87,6 +93,7 @@ SYMBOLS = {
     "rv_maxlcp": (ctypes.c_uint32, [V]),
     "rv_cascade_info": (ctypes.c_int, [V, V]),
     "rv_cascade_why": (ctypes.c_char_p, [V]),
+    "rv_capacity_events": (_I, [V, V]),
     "rv_anchor_count": (_L, [V, c_i64p]),
     "rv_fetch_anchors": (_I, [V, V, V, V]),
     "rv_set_result_buffers": (_I, [V, V, _L, V, _L, V, _L]),

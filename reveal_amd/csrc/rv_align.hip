@@ -658,13 +658,13 @@ static int early_split(rv_index *h) {
         // the picker's device buffers (rv_run_multi_pick, rv_api.hip)
         d.pick_l = h->ws.misc[13].as<u32>(); d.pick_pos = h->ws.misc[7].as<sa_t>();
         d.cand_count = h->ws.misc[1].as<u32>() + RV_MULTI_REGIONS * 64;
-        d.cand_cap = (u32)std::min<size_t>(h->ws.misc[8].cap / RV_MULTI_CAND_BYTES / RV_MULTI_REGIONS, 0xffffffffu);
+        d.cand_cap = h->ws.multi_cand_cap;      // (per region, as the picker's kernels were given it)
         RV_TRY(rv_decide_multi_launch(h->ws, d));
     } else {
         RvDecideArgs d;
         outputs(d);
         d.nodes = a->d_next_nodes; d.flags = a->d_next_flags; d.picks = h->hscan.as<RvPairRec>();
-        d.ovf_cap = (u32)std::min<size_t>(h->ws.misc[4].cap / sizeof(RvPairRec), 0xffffffffu);      // (the scan's overflow buffer)
+        d.ovf_cap = h->ws.pair_ovf_cap;      // (the scan's overflow buffer, as the scan's kernels were given it)
         RV_TRY(rv_decide_launch(h->ws, d));
     }
     RvLabelTabs lt; RvSplitArgs sa;
@@ -816,7 +816,9 @@ int rv_frontier_scan(rv_index *h) {
             bool redo = false;
             RV_TRY(rv_run_multi_pick(h, cur_sa(h), cur_lcp(h), cur_bwt(h), a->lv.m, a->minl, a->minn, a->d_next_ss, a->d_next_want, ns, a->d_next_tsub, a->pick_l, a->pick_pos,
                                      early ? early_split : nullptr, &redo));
-            if (redo) a->early_done = false;      // (the early split saw an overflowed candidate list and decided nothing: the commit splits again)
+            // (the early split saw an overflowed candidate list and decided nothing: the commit splits again -- and lower-cases and bubbles, too:
+            //  the early bubble behind that split ran over empty descriptors)
+            if (redo) a->early_done = a->early_bubble = false;
             a->ml.clear(); a->mn.clear(); a->moff.assign(1, 0); a->mso.clear(); a->mpos.clear();
             const int W = h->nsamples;
             for (int s2 = 0; s2 < ns; s2++) {

@@ -325,6 +325,15 @@ int rv_reset(rv_index *h) {
     h->maxlcp = 0;
     h->m_l.clear(); h->m_a.clear(); h->m_b.clear();
     h->mm_l.clear(); h->mm_n.clear(); h->mm_off.clear(); h->mm_pos.clear(); h->mm_so.clear();
+    memset(h->ws.cap_events, 0, sizeof h->ws.cap_events);
+    return 0;
+}
+
+/* How often the host went round again because a device list was too small, since the last rv_construct / rv_reset: the order of RvCapEvent
+ * (rv_common.h).  Host counters only. */
+int rv_capacity_events(const rv_index *h, int64_t *out) {
+    if (!h || !out) { rv_set_error("rv_capacity_events: null argument"); return -1; }
+    for (int k = 0; k < RV_CE_COUNT; k++) out[k] = h->ws.cap_events[k];
     return 0;
 }
 
@@ -434,6 +443,7 @@ int rv_upload_again(rv_index *h) {
 /* interface.c:160-291 */
 int rv_construct(rv_index *h, int rc, const char *safile, const char *lcpfile, int cache) {
     RV_HIP(hipSetDevice(h->device));
+    memset(h->ws.cap_events, 0, sizeof h->ws.cap_events);
     if (rc == 1) {
         if (h->nsep.empty()) { rv_set_error("construct(rc=1) needs at least two samples"); return -1; }
         h->rc = 1;
@@ -714,6 +724,7 @@ int rv_run_pair_scan(rv_index *h, const sa_t *SA, const lcp_t *LCP, const uint8_
     u32 *tilecnt = btab.as<u32>(), *tileovf = tilecnt + (ntile + 1), *tileoff = tileovf + (ntile + 1);
     for (int attempt = 0; attempt < 3; attempt++) {
         const size_t ocap = bout.cap / sizeof(RvPairRec) - RV_PAIR_HDR, vcap = bovf.cap / sizeof(RvPairRec);
+        h->ws.pair_ovf_cap = (u32)std::min<size_t>(vcap, 0xffffffffu);      // (what k_decide compares the header's overflow count with)
         // picker tables; the picks go straight to pinned host memory (the kernels write them over PCIe: a few KB), so the level's
         // round trip needs no copy command, only the wait for the stream
         DBuf &bbest = h->ws.misc[12];
@@ -749,6 +760,7 @@ int rv_run_pair_scan(rv_index *h, const sa_t *SA, const lcp_t *LCP, const uint8_
                 for (int s2 = 0; s2 < nsubs; s2++) if (src[s2].rank != 0xFFFFFFFFu) out.push_back(src[s2]);
                 return 0;
             }
+            h->ws.cap_events[RV_CE_PAIR_PICK_OVF]++;
             RV_TRY(bovf.reserve((size_t)novf * sizeof(RvPairRec)));
             continue;
         }
@@ -777,12 +789,15 @@ int rv_run_pair_scan(rv_index *h, const sa_t *SA, const lcp_t *LCP, const uint8_
             const RvPairRec *src = h->hscan.as<RvPairRec>() + RV_PAIR_HDR;
             const size_t have = std::min<size_t>(total, guess);
             if (have) memcpy(out.data(), src, have * sizeof(RvPairRec));
-            if (total > have) RV_HIP(hipMemcpy(out.data() + have, bout.as<RvPairRec>() + RV_PAIR_HDR + have, (total - have) * sizeof(RvPairRec), hipMemcpyDeviceToHost));
+            if (total > have) {
+                h->ws.cap_events[RV_CE_PAIR_SECOND_COPY]++;
+                RV_HIP(hipMemcpy(out.data() + have, bout.as<RvPairRec>() + RV_PAIR_HDR + have, (total - have) * sizeof(RvPairRec), hipMemcpyDeviceToHost));
+            }
             h->scan_guess = (size_t)total + total / 16 + 64;
             return 0;
         }
-        if (novf > vcap) RV_TRY(bovf.reserve((size_t)novf * sizeof(RvPairRec)));
-        if (total > ocap) RV_TRY(bout.reserve(((size_t)total + RV_PAIR_HDR) * sizeof(RvPairRec)));
+        if (novf > vcap) { h->ws.cap_events[RV_CE_PAIR_OVF]++; RV_TRY(bovf.reserve((size_t)novf * sizeof(RvPairRec))); }
+        if (total > ocap) { h->ws.cap_events[RV_CE_PAIR_OUT]++; RV_TRY(bout.reserve(((size_t)total + RV_PAIR_HDR) * sizeof(RvPairRec))); }
     }
     rv_set_error("pair scan: output buffer sizing failed");
     return -1;
@@ -804,6 +819,7 @@ int rv_run_multi_scan(rv_index *h, const sa_t *SA, const lcp_t *LCP, const uint8
         hipStream_t q = h->ws.stream;
         DBuf &brec = h->ws.misc[13], &bso = h->ws.misc[6], &bpos = h->ws.misc[7];
         size_t rcap = (size_t)std::max<int64_t>(4096, m / 16), mcap = (size_t)std::max<int64_t>(8192, m / 2);
+        rcap = h->ws.cap_first(RV_CS_MEMS_REC, rcap); mcap = h->ws.cap_first(RV_CS_MEMS_MEM, mcap);
         for (int attempt = 0; attempt < 2; attempt++) {
             RV_TRY(brec.reserve(64 + rcap * 16 + 64));
             RV_TRY(bso.reserve(mcap * 2 + 64));
@@ -837,6 +853,8 @@ int rv_run_multi_scan(rv_index *h, const sa_t *SA, const lcp_t *LCP, const uint8
                 pos.assign(rpos.begin(), rpos.end());
                 return 0;
             }
+            if (res[0] > rcap) h->ws.cap_events[RV_CE_MEMS_REC]++;
+            if (res[1] > mcap) h->ws.cap_events[RV_CE_MEMS_MEM]++;
             rcap = std::max<size_t>(rcap, (size_t)res[0]); mcap = std::max<size_t>(mcap, (size_t)res[1]);
         }
         rv_set_error("getmultimems: output buffer sizing failed");
@@ -887,8 +905,8 @@ int rv_run_multi_scan(rv_index *h, const sa_t *SA, const lcp_t *LCP, const uint8
             for (size_t k = 0; k < n.size(); k++) { acc += n[k]; off.push_back(acc); }
             return 0;
         }
-        if (tot[0] > rcap) RV_TRY(brec.reserve((size_t)tot[0] * sizeof(RvMultiRec)));
-        if (tot[1] > mcap) { RV_TRY(bso.reserve((size_t)tot[1] * 2)); RV_TRY(bpos.reserve((size_t)tot[1] * sizeof(sa_t))); }
+        if (tot[0] > rcap) { h->ws.cap_events[RV_CE_MULTI_REC]++; RV_TRY(brec.reserve((size_t)tot[0] * sizeof(RvMultiRec))); }
+        if (tot[1] > mcap) { h->ws.cap_events[RV_CE_MULTI_MEM]++; RV_TRY(bso.reserve((size_t)tot[1] * 2)); RV_TRY(bpos.reserve((size_t)tot[1] * sizeof(sa_t))); }
     }
     rv_set_error("multi scan: output buffer sizing failed");
     return -1;
@@ -907,12 +925,14 @@ int rv_run_multi_pick(rv_index *h, const sa_t *SA, const lcp_t *LCP, const uint8
     RV_TRY(bcnt.reserve((RV_MULTI_REGIONS * 64 + 16) * 4));
     if (bcand.cap < 65536 * RV_MULTI_CAND_BYTES) RV_TRY(bcand.reserve((size_t)std::max<int64_t>(65536, m / 64) * RV_MULTI_CAND_BYTES));
     for (int attempt = 0; attempt < 2; attempt++) {
-        const size_t ccap = bcand.cap / RV_MULTI_CAND_BYTES;
+        size_t ccap = std::min<size_t>(bcand.cap / RV_MULTI_CAND_BYTES, 0xffffffffu);
+        if (attempt == 0) ccap = h->ws.cap_first<size_t>(RV_CS_MULTI_CAND, ccap, RV_MULTI_REGIONS);
+        h->ws.multi_cand_cap = (u32)(ccap / RV_MULTI_REGIONS);      // (per region: what k_decide_multi compares the fullest region's count with)
         hipEvent_t ev_a, ev_b;      // the streaming kernel alone, as for the pair scan (8 B per rank)
         (void)h->prof.attach(RV_K_SCAN_MULTI, (double)m * 8.0, &ev_a, &ev_b);
         RV_TRY(rv_multi_pick_launch(h->ws, SA, LCP, m, BWT, h->dNsep.as<sa_t>(), W, minl, minn, d_sub_start, d_sub_want, nsubs, d_tile_sub,
                                     bbest.as<unsigned long long>(), bl.as<u32>(), bpos.as<sa_t>(), (RvMultiCand *)bcand.p,
-                                    (u32)std::min<size_t>(ccap, 0xffffffffu), bcnt.as<u32>(), ev_a, ev_b));
+                                    (u32)ccap, bcnt.as<u32>(), ev_a, ev_b));
         u32 ncand = 0;
         pick_pos.resize((size_t)nsubs * W);
         {   // the level's one round trip: three arrays into pinned memory, one polled event (pageable destinations are staged copy by copy)
@@ -931,6 +951,7 @@ int rv_run_multi_pick(rv_index *h, const sa_t *SA, const lcp_t *LCP, const uint8
         }
         if ((size_t)ncand <= ccap / RV_MULTI_REGIONS) return 0;
         if (redo) *redo = true;
+        h->ws.cap_events[RV_CE_MULTI_CAND]++;
         RV_TRY(bcand.reserve(((size_t)ncand + ncand / 2 + 64) * RV_MULTI_REGIONS * RV_MULTI_CAND_BYTES));
     }
     rv_set_error("multi picker: candidate buffer sizing failed");

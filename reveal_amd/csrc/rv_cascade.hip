@@ -695,7 +695,10 @@ __global__ __launch_bounds__(TB) void k_cas_decide(CasIv *__restrict__ iv, u64 *
         __threadfence();         //  waves, behind the barrier above -- in front of its ticket, so the last ticket holder reads the final count)
         if (atomicAdd(&counters[C_TICKET], 1u) == gridDim.x - 1) {
             if (hi > lo) counters[C_LEVELS]++;
-            counters[C_LO] = hi; counters[C_HI] = atomicAdd(&counters[C_NCHILD], 0u);
+            // (a full table -- C_ERR bit 1, the host gives up at the end of the batch -- has counted children it holds no row for: the levels queued
+            //  behind this one in the same batch stay inside the table)
+            const u32 made = atomicAdd(&counters[C_NCHILD], 0u);
+            counters[C_LO] = hi; counters[C_HI] = made < child_cap ? made : child_cap;
             counters[C_NANCH] = atomicAdd(io.anchor_count, 0u);
             counters[C_TICKET] = 0;
         }
@@ -1017,7 +1020,7 @@ int rv_cascade_run(rv_index *h, RvCascadeBufs &cb, const RvCascadeIO &io, int mi
     const int64_t wtile = wit_pass ? WT_TILE : RV_PAIR_WG_TILE;
     const int64_t rcap64 = std::min<int64_t>(n / WT_REGIONS + wtile, std::max<int64_t>(16384, n / 1024));
     const u32 wcap = (u32)std::min<int64_t>(rcap64 * WT_REGIONS, 0x7fffffff);
-    const u32 wrcap = wcap / WT_REGIONS;
+    const u32 wrcap = ws.cap_first(RV_CS_CAS_WIT, wcap / WT_REGIONS);      // (RV_CAP_LIMIT: the buffers are as large as ever; the regions lie wrcap entries apart inside them)
     DBuf &bwp0 = cb.d[19], &bwv0 = cb.d[20], &bwr = cb.d[21], &bwrk = cb.d[22], &bwrk0 = cb.d[23];
     u32 hreg[2 * WT_REGIONS];
     RV_TRY(bwp0.reserve((size_t)wcap * sizeof(sa_t))); RV_TRY(bwv0.reserve((size_t)wcap * 4)); RV_TRY(bwr.reserve(2 * WT_REGIONS * 4 + 64));
@@ -1041,8 +1044,8 @@ int rv_cascade_run(rv_index *h, RvCascadeBufs &cb, const RvCascadeIO &io, int mi
         else RV_TRY(rv_read_back2(ws, hdr, bout.p, sizeof hdr, hreg, bwr.p, WT_REGIONS * 4));
         const u32 total = hdr[0], novf = hdr[1];
         if (total <= ocap && novf <= vcap) { M = total; break; }
-        if (novf > vcap) RV_TRY(bovf.reserve((size_t)novf * sizeof(RvPairRec)));
-        if (total > ocap) RV_TRY(bout.reserve(((size_t)total + RV_PAIR_HDR) * sizeof(RvPairRec)));
+        if (novf > vcap) { ws.cap_events[RV_CE_PAIR_OVF]++; RV_TRY(bovf.reserve((size_t)novf * sizeof(RvPairRec))); }
+        if (total > ocap) { ws.cap_events[RV_CE_PAIR_OUT]++; RV_TRY(bout.reserve(((size_t)total + RV_PAIR_HDR) * sizeof(RvPairRec))); }
     }
     if (verbose) tp[1] = cas_now();
     out->cands = M;
@@ -1055,6 +1058,11 @@ int rv_cascade_run(rv_index *h, RvCascadeBufs &cb, const RvCascadeIO &io, int mi
     const int64_t ccap64 = n / (int64_t)minl + 16;      // every anchor covers 2 * minl positions and makes two sub-indices at most
     if (ccap64 >= 0x7fffffff) GIVE_UP("too many sub-indices possible");
     const u32 ccap = (u32)ccap64;
+    // what the level kernels and the chain's check are told: the tables' size, or RV_CAP_LIMIT (the tables keep their size).  The leaf kernel behind a
+    // finished cascade keeps the whole anchor area: an overflow there is an error, not a give-up
+    const u32 ccap_k = ws.cap_first(RV_CS_CAS_TABLES, ccap, 32u);
+    RvCascadeIO iok = io;
+    iok.anchor_cap = ws.cap_first(RV_CS_CAS_TABLES, io.anchor_cap);
     DBuf &k0 = cb.d[0], &k1 = cb.d[1], &v0 = cb.d[2], &v1 = cb.d[3], &bpa = cb.d[4], &bpb = cb.d[5], &blen = cb.d[6], &bcc = cb.d[7], &bwp = cb.d[8], &bwv = cb.d[9],
          &bwc = cb.d[10], &biv = cb.d[11], &bbest = cb.d[12], &bwm = cb.d[13], &bdep = cb.d[14], &bres = cb.d[15], &bctr = cb.d[16], &bund = cb.d[17], &bsz = cb.d[18];
     RV_TRY(k0.reserve((size_t)M * 8)); RV_TRY(k1.reserve((size_t)M * 8)); RV_TRY(v0.reserve((size_t)M * 4)); RV_TRY(v1.reserve((size_t)M * 4));
@@ -1183,7 +1191,7 @@ int rv_cascade_run(rv_index *h, RvCascadeBufs &cb, const RvCascadeIO &io, int mi
     } else {
         // the roots are the leading / trailing children of the chain's choices; its anchors go in front of the device's
         const u32 R = cb.lin_roots, P = cb.lin_picks;
-        if ((int64_t)R + 16 > (int64_t)ccap || P > io.anchor_cap) GIVE_UP("more sequences than the cascade's tables hold");
+        if ((int64_t)R + 16 > (int64_t)ccap_k || P > iok.anchor_cap) GIVE_UP("more sequences than the cascade's tables hold");
         const uint8_t *tb = cb.d[32].as<uint8_t>();
         CasRootTabs rt;
         rt.beginA = (const sa_t *)(tb + cb.lin_off[0]); rt.beginB = (const sa_t *)(tb + cb.lin_off[1]);
@@ -1274,7 +1282,7 @@ int rv_cascade_run(rv_index *h, RvCascadeBufs &cb, const RvCascadeIO &io, int mi
                 RV_LAUNCH_CHECK();
             }
             hipLaunchKernelGGL(k_cas_decide, dim3(256), dim3(TB), 0, q, biv.as<CasIv>(), bbest.as<u64>(), bwm.as<u32>(), bdep.as<int32_t>(),
-                               bres.as<CasRes>(), minl, counters, ccap, bund.as<u32>(), (u32)RV_LEAF_N, io, dg, (danger && NW) ? 1 : 0);
+                               bres.as<CasRes>(), minl, counters, ccap_k, bund.as<u32>(), (u32)RV_LEAF_N, iok, dg, (danger && NW) ? 1 : 0);
             RV_LAUNCH_CHECK();
         }
         RV_TRY(send_known());      // (behind the batch's launches: the host's time for it is hidden, too)

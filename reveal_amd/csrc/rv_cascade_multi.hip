@@ -586,7 +586,9 @@ __global__ __launch_bounds__(TB) void k_casm_decide(CmTabs t, int k, u32 minl, u
         __threadfence();         //  waves, behind the barrier above -- in front of its ticket, so the last ticket holder reads the final count)
         if (atomicAdd(&counters[C_TICKET], 1u) == gridDim.x - 1) {
             if (hi > lo) counters[C_LEVELS]++;
-            counters[C_LO] = hi; counters[C_HI] = atomicAdd(&counters[C_NCHILD], 0u);
+            // (a full table: the levels queued behind this one in the same batch stay inside it -- k_cas_decide, rv_cascade.hip)
+            const u32 made = atomicAdd(&counters[C_NCHILD], 0u);
+            counters[C_LO] = hi; counters[C_HI] = made < child_cap ? made : child_cap;
             counters[C_TICKET] = 0;
         }
     }
@@ -1251,6 +1253,11 @@ int rv_cascade_multi_run(rv_index *h, RvCascadeBufs &cb, int minl_in, RvCascadeM
     const int64_t ccap64 = 2 * n / ((int64_t)minl * k) + 16;
     if (ccap64 >= 0x7fffffff) GIVE_UP("too many sub-indices possible");
     const u32 ccap = (u32)ccap64, acap = ccap / 2 + 8;
+    // RV_CAP_LIMIT: what the kernels and the checks below are told about the four lists.  The buffers are as large as ever; the match list's regions lie
+    // mcap_k / CM_REGIONS entries apart inside theirs, the tables keep the layout of ccap rows.  A job of a batch (rv_batch_run, below) carries the whole
+    // ccap / acap into the joint loop: the limit on the tables does not reach that path, only the witness limit does (a job that gave up on it never joins)
+    const u32 mcap_k = ws.cap_first(RV_CS_CASM_MATCHES, mcap, (u32)CM_REGIONS), wcap_k = ws.cap_first(RV_CS_CASM_WIT, wcap);
+    const u32 ccap_k = ws.cap_first(RV_CS_CASM_TABLES, ccap, 32u), acap_k = ws.cap_first(RV_CS_CASM_TABLES, acap);
     DBuf &bso = cb.d[0], &bcl0 = cb.d[1], &bcp0 = cb.d[2], &bk0 = cb.d[3], &bk1 = cb.d[4], &bv0 = cb.d[5], &bv1 = cb.d[6], &bcl = cb.d[7], &bcp = cb.d[8], &bcc = cb.d[9],
          &bwp = cb.d[10], &bwv = cb.d[11], &bwc = cb.d[12], &btb = cb.d[13], &bctr = cb.d[14], &bund = cb.d[15], &banl = cb.d[16], &banp = cb.d[17], &broot = cb.d[18],
          &bsa = cb.d[19], &blcp = cb.d[20], &bbwt = cb.d[21], &brt = cb.d[22], &bexp = cb.d[23], &brows = cb.d[34];
@@ -1273,7 +1280,7 @@ int rv_cascade_multi_run(rv_index *h, RvCascadeBufs &cb, int minl_in, RvCascadeM
     u32 *region_cnt = counters + 16, *region_off = region_cnt + CM_REGIONS;      // (the match list's regions: counts, then where each starts in the dense list)
     u32 *region_spread = counters + 256;
     RV_HIP(hipMemsetAsync(counters, 0, 1024 + (size_t)CM_REGIONS * CNT_STRIDE * 4, q));
-    const u32 rcap = mcap / CM_REGIONS;
+    const u32 rcap = mcap_k / CM_REGIONS;
     {
         std::vector<sa_t> rr(rb); rr.insert(rr.end(), re.begin(), re.end());
         RV_HIP(hipMemcpyAsync(broot.p, rr.data(), rr.size() * sizeof(sa_t), hipMemcpyHostToDevice, q));
@@ -1300,7 +1307,7 @@ int rv_cascade_multi_run(rv_index *h, RvCascadeBufs &cb, int minl_in, RvCascadeM
         RV_LAUNCH_CHECK();
         h->prof.end(q, pid);
     }
-    hipLaunchKernelGGL(k_casm_witness, dim3((unsigned)ceil_div(n, MS_TILE)), dim3(TB), 0, q, SA, LCP, (const uint8_t *)bso.as<uint8_t>(), n, minl, bwp.as<sa_t>(), bwv.as<u32>(), wcap, counters);
+    hipLaunchKernelGGL(k_casm_witness, dim3((unsigned)ceil_div(n, MS_TILE)), dim3(TB), 0, q, SA, LCP, (const uint8_t *)bso.as<uint8_t>(), n, minl, bwp.as<sa_t>(), bwv.as<u32>(), wcap_k, counters);
     RV_LAUNCH_CHECK();
     u32 hc[16];
     RV_TRY(rv_read_back(ws, hc, counters, sizeof hc));
@@ -1311,7 +1318,7 @@ int rv_cascade_multi_run(rv_index *h, RvCascadeBufs &cb, int minl_in, RvCascadeM
     const u32 NW = hc[C_NWIT];
     out->cands = M; out->witnesses = NW;
     if (rmaxc > rcap) GIVE_UP("more full matches than the list holds");
-    if (NW > wcap) GIVE_UP("too many repeat witnesses (a repetitive input)");
+    if (NW > wcap_k) GIVE_UP("too many repeat witnesses (a repetitive input)");
     if (M == 0) GIVE_UP("no full match at the top level");
     struct ProfSpan { Workspace &w; int id; ~ProfSpan() { w.prof_end(id); } } span{ws, ws.prof_begin(RV_K_CASCADE, 5.0 * (double)n)};
     RV_TRY(bk0.reserve((size_t)M * 8)); RV_TRY(bk1.reserve((size_t)M * 8)); RV_TRY(bv0.reserve((size_t)M * 4)); RV_TRY(bv1.reserve((size_t)M * 4));
@@ -1342,7 +1349,7 @@ int rv_cascade_multi_run(rv_index *h, RvCascadeBufs &cb, int minl_in, RvCascadeM
     RvBatchJob bjob;
     if (h->batch && !h->batch_settled) {
         h->batch_settled = true; ticket.settled = true;
-        bjob.k = k; bjob.minl = minl; bjob.M = M; bjob.NW = std::min(NW, wcap); bjob.ccap = ccap; bjob.acap = acap;
+        bjob.k = k; bjob.minl = minl; bjob.M = M; bjob.NW = std::min(NW, wcap_k); bjob.ccap = ccap; bjob.acap = acap;
         bjob.c_len = bcl.as<u32>(); bjob.c_pos = bcp.as<sa_t>(); bjob.w_pos = bwp.as<sa_t>(); bjob.w_val = bwv.as<u32>();
         bjob.nsep = nsep; bjob.dT = h->dT.as<uint8_t>();
         bjob.rb = rb; bjob.re = re;
@@ -1402,7 +1409,7 @@ int rv_cascade_multi_run(rv_index *h, RvCascadeBufs &cb, int minl_in, RvCascadeM
             hipLaunchKernelGGL(k_casm_winner, dim3((unsigned)ceil_div((int64_t)M, TB)), dim3(TB), 0, q, (const sa_t *)bcp.as<sa_t>(), (const u32 *)bcl.as<u32>(), (const u32 *)bcc.as<u32>(), M, t, k,
                                (int64_t)minl);
             RV_LAUNCH_CHECK();
-            hipLaunchKernelGGL(k_casm_decide, dim3(192), dim3(TB), 0, q, t, k, minl, counters, ccap, bund.as<u32>(), (u32)big_min, banl.as<u32>(), banp.as<sa_t>(), acap);
+            hipLaunchKernelGGL(k_casm_decide, dim3(192), dim3(TB), 0, q, t, k, minl, counters, ccap_k, bund.as<u32>(), (u32)big_min, banl.as<u32>(), banp.as<sa_t>(), acap_k);
             RV_LAUNCH_CHECK();
         }
         RV_TRY(rv_read_back(ws, hc, counters, sizeof hc));

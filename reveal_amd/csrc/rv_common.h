@@ -4,6 +4,7 @@
 // (reveallib/reveal.h:7-13): default = reveallib (int32 SA, int32 LCP),
 // -DRV_SA64 = reveallib64 (int64 SA, uint32 LCP).
 #pragma once
+#include <algorithm>
 #include <mutex>
 #include <thread>
 #include <vector>
@@ -106,7 +107,9 @@ void rv_set_error(const char *fmt, ...);
     X(scan_v1, "RV_SCAN_V1", 0) \
     X(pick_threads, "RV_PICK_THREADS", 0) \
     X(cascade_prio, "RV_CASCADE_PRIO", 0) \
-    X(cas_witness_pass, "RV_CAS_WITNESS_PASS", 0)
+    X(cas_witness_pass, "RV_CAS_WITNESS_PASS", 0) \
+    X(cap_limit, "RV_CAP_LIMIT", 0) \
+    X(cap_sites, "RV_CAP_SITES", -1)
 struct RvOptions {
 #define RV_X_(f, name, def) int64_t f = def;
     RV_OPTION_LIST(RV_X_)
@@ -328,10 +331,29 @@ struct HBuf {
     template <class T> T *as() const { return (T *)p; }
 };
 
+// ---- capacity protocols ("Lists filled by atomics").  A list whose capacity is an estimate is filled behind a guard, counted
+// beyond it, and the host goes round again with a list of the counted size.  RvCapEvent: one counter per place where the host decides that
+// (rv_capacity_events, include/reveal_amd.h: host integers, nothing on the device).  RvCapSite: the estimates that no small input overflows;
+// RV_CAP_LIMIT = an upper limit on what the FIRST attempt of the sites named by the bit mask RV_CAP_SITES passes to its kernels (test hook;
+// the buffers are allocated as without it -- a list kept in regions is laid out with the limited stride inside its buffer --, a retry sizes
+// from the count as ever).
+enum RvCapEvent { RV_CE_PAIR_OVF = 0, RV_CE_PAIR_OUT, RV_CE_PAIR_PICK_OVF, RV_CE_PAIR_SECOND_COPY, RV_CE_MULTI_REC, RV_CE_MULTI_MEM, RV_CE_MULTI_CAND,
+                  RV_CE_MEMS_REC, RV_CE_MEMS_MEM, RV_CE_MEMS_LONG, RV_CE_COUNT };
+enum RvCapSite { RV_CS_MULTI_CAND = 1, RV_CS_CAS_WIT = 2, RV_CS_CAS_TABLES = 4, RV_CS_CASM_MATCHES = 8, RV_CS_CASM_WIT = 16, RV_CS_CASM_TABLES = 32,
+                 RV_CS_MEMS_REC = 64, RV_CS_MEMS_MEM = 128, RV_CS_MEMS_LONG = 256 };
 // Scratch slots used by the primitives (one set per index handle, one stream).
 struct Workspace {
     hipStream_t stream = nullptr;
     RvOptions opt;         // the owning handle's switches (rv_set_option)
+    int64_t cap_events[RV_CE_COUNT] = {0};
+    // what the last pair scan / multi picker passed to its kernels as the overflow buffer's / candidate list's capacity: the early split's
+    // decide kernels test the same header words against the same values (rv_align.hip early_split)
+    u32 pair_ovf_cap = 0, multi_cand_cap = 0;
+    template <class T> T cap_first(int site, T cap, T least = 1) const {
+        if (opt.cap_limit <= 0 || !(opt.cap_sites & (int64_t)site)) return cap;
+        const T lim = (T)std::max<int64_t>(opt.cap_limit, (int64_t)least);
+        return cap < lim ? cap : lim;
+    }
     DBuf scan_tmp[4];      // block sums of the multi-level scan
     DBuf rs_hist;          // radix sort: per-block digit histograms
     DBuf rs_digits;        // radix sort: the next pass' digit of every key, a byte each

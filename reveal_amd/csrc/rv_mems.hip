@@ -393,6 +393,7 @@ int rv_multimems_launch(Workspace &ws, const sa_t *SA, const lcp_t *LCP, const u
     // are enough for the latter (tandem arrays, homopolymers: up to n / 26 runs), so a count pass that finds more than the list holds is repeated
     // with a list of that size
     A.long_cap = (u32)std::min<int64_t>(n / 64 + 1024, 0x7fffffff);
+    A.long_cap = ws.cap_first(RV_CS_MEMS_LONG, A.long_cap);
     A.nlong = 0; A.g_lcp = nullptr; A.g_lb = nullptr; A.g_cap = 0;
     const unsigned grid = (unsigned)ceil_div(A.ntiles, TB);
     unsigned long long res[4] = {0, 0, 0, 0};
@@ -406,6 +407,7 @@ int rv_multimems_launch(Workspace &ws, const sa_t *SA, const lcp_t *LCP, const u
         RV_TRY(rv_read_back(ws, res, out, sizeof res));
         if (res[3] <= A.long_cap) break;
         if (attempt || res[3] > 0x7fffffffull) { rv_set_error("getmultimems: more long runs than the list holds"); return -1; }
+        ws.cap_events[RV_CE_MEMS_LONG]++;
         A.long_cap = (u32)res[3];
     }
     A.nlong = (u32)res[3];

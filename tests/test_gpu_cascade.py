@@ -189,12 +189,9 @@ def _multi_equal(seqs, minl, sa64=False):
     return info
 
 
-@pytest.mark.parametrize("sa64", [False, True])
-def test_multi_cascade_rebuilds_large_undecided_subindices(monkeypatch, sa64):
-    """a sample that lost kilobases leaves the others' kilobases behind as one sub-index that lacks a sample: above the 8192 ranks a workgroup rebuilds
-    in LDS they go through global memory (k_casmb_keys / place / emit) instead of ending the cascade; with what makes suffixes tie there -- an N run,
-    a tandem array, a copy of another stretch, ends that agree (all of them shorter than the matches of the five samples: a repeat longer than those
-    leaves the ROOT undecided)"""
+def large_undecided_input():
+    """five samples of 260 kbp; what samples 1 and 2 lost leaves 4 x 7 kb and 4 x 13 kb of the others behind as sub-indices that lack a sample
+    (also the input of tests/test_gpu_capacity.py for RV_CASM_BIG_ROOT / RV_CASM_BIG_TOTAL)"""
     rng = random.Random(5)
     rnd = lambda n: "".join(rng.choice("ACGT") for _ in range(n))
     base = rnd(260000)
@@ -208,6 +205,16 @@ def test_multi_cascade_rebuilds_large_undecided_subindices(monkeypatch, sa64):
     seqs[2] = seqs[2][:118000] + seqs[2][131000:]                # 13 kb
     seqs[3] = seqs[3][:200000] + rnd(6000) + seqs[3][200000:]    # an insertion: a sub-index with one sample
     seqs[4] = seqs[4][:230000] + seqs[4][233000:233120] + seqs[4][230000:]      # a short duplication
+    return seqs
+
+
+@pytest.mark.parametrize("sa64", [False, True])
+def test_multi_cascade_rebuilds_large_undecided_subindices(monkeypatch, sa64):
+    """a sample that lost kilobases leaves the others' kilobases behind as one sub-index that lacks a sample: above the 8192 ranks a workgroup rebuilds
+    in LDS they go through global memory (k_casmb_keys / place / emit) instead of ending the cascade; with what makes suffixes tie there -- an N run,
+    a tandem array, a copy of another stretch, ends that agree (all of them shorter than the matches of the five samples: a repeat longer than those
+    leaves the ROOT undecided)"""
+    seqs = large_undecided_input()
     info = _multi_equal(seqs, 20, sa64)
     assert info["done"] and info["rebuilt_ranks"] > 4 * 13000, info
     monkeypatch.setenv("RV_CASM_NO_BIG", "1")      # up to round 4: the cascade gave up and the level pipeline ran from the top

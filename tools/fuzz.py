@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Randomised parity soak: the GPU recursion (traced and untraced, default and forced code paths) against the CPU oracle
 on random inputs -- SNPs, indels, tandem repeats, N runs, several contigs, 2-4 samples.  Test infrastructure.
-usage: python tools/fuzz.py [seconds] [seed]      (FUZZ_BIG=1 adds inputs of 1 and 2.5 Mbp per sample)"""
+usage: python tools/fuzz.py [seconds] [seed]      (FUZZ_BIG=1 adds inputs of 1 and 2.5 Mbp per sample; FUZZ_CASES=N stops after N cases whatever
+the time; FUZZ_ENVS=3,27 runs those entries of ENVS only)"""
 import os
 import random
 import sys
@@ -46,6 +47,7 @@ ENVS = [
     {"RV_SCAN_V1": "1"},                                  # round 5's staged multi-sample scans (k_casm_scan, k_multi_pick1) instead of k_full_scan
     {"RV_PICK_THREADS": "1"},                             # (no effect on the built-in picker: the switch must at least be accepted)
     {"RV_CAS_WITNESS_PASS": "1"},                         # the cascade's witnesses from a pass of their own (k_cas_witness), not from the top-level pair scan
+    {"RV_CAP_LIMIT": "48", "RV_CAP_SITES": "511"},        # every estimated capacity RV_CAP_LIMIT reaches starts at 48: the cascades give up on a full list, the multi picker goes round again
 ]
 
 
@@ -148,8 +150,10 @@ def main():
     seed = int(sys.argv[2]) if len(sys.argv) > 2 else int(time.time())
     rng = random.Random(seed)
     t_end = time.time() + budget
+    max_cases = int(os.environ.get("FUZZ_CASES", "0"))
+    envs = [ENVS[int(k)] for k in os.environ["FUZZ_ENVS"].split(",")] if os.environ.get("FUZZ_ENVS") else ENVS
     ncase = 0
-    while time.time() < t_end:
+    while time.time() < t_end and not (max_cases and ncase >= max_cases):
         seqs, minl = make_case(rng)
         seqs = maybe_contigs(rng, seqs)
         sa64 = rng.random() < 0.2
@@ -166,7 +170,7 @@ def main():
         sa_ref, lcp_ref = c["SA"].copy(), c["LCP"].copy()
         ref = O.align_bench(c, nodes, minl, 2, trace_cap=4 * len(T) // max(minl, 1) + 1000)
         rd, ra = digest(ref["trace"]), anchors_set(ref["anchors"])
-        for env in ENVS:
+        for env in envs:
             for k in list(os.environ):
                 if k.startswith("RV_"):
                     del os.environ[k]
@@ -203,7 +207,7 @@ def main():
                 for f in FIELDS:
                     assert len(gd[f]) == len(rd[f]) and (gd[f] == rd[f]).all(), "trace field %s %s" % (f, tag)
         ncase += 1
-    print("fuzz: %d cases x (%d configurations + divided run) x 2 (traced / untraced) identical to the oracle (seed %d)" % (ncase, len(ENVS), seed))
+    print("fuzz: %d cases x (%d configurations + divided run) x 2 (traced / untraced) identical to the oracle (seed %d)" % (ncase, len(envs), seed))
 
 
 if __name__ == "__main__":
