@@ -487,6 +487,12 @@ void rv_batch_free(rv_batch *b);
  * sub-index (no leaf kernel there).  A call with fewer than RV_MANY_LARGE_MULTI_MIN such jobs leaves them on the ordinary path.  With RV_MANY_MULTI, RV_MANY_LARGE and RV_MANY_LARGE_MULTI all
  * set, every job of 2 .. 16 sequences without a NUL byte and of at most RV_MANY_LARGE_MAX ranks that fits a round goes through shared launches -- in a
  * call that holds at least RV_MANY_LARGE_MIN pair jobs and RV_MANY_LARGE_MULTI_MIN jobs of three and more sequences above 2048 ranks, where it has any.
+ * With RV_MANY_WIDE set (off by default, independent of the three switches above) the jobs of 17 .. 64 sequences with no NUL byte share their launches
+ * too, in rounds of their own (the rounds of the other classes stay as they are): up to 2048 ranks the layout and the index build of RV_MANY_MULTI and ONE
+ * launch of the 64-sample form of the same leaf kernel; at 2049 .. RV_MANY_LARGE_MAX ranks the sample-major rounds of RV_MANY_LARGE_MULTI with up to 64
+ * samples, in a call with at least RV_MANY_WIDE_LARGE_MIN such jobs (counted on their own).  64 is the limit of this class: a lane of a wavefront owns a
+ * sample in the leaf kernel, the sample id has six bits of its per-position byte, and the level pipeline's multi-sample scan keeps a one-word census up
+ * to 64 samples.  A job of more than 64 sequences always runs the ordinary way.  The results do not depend on the switch.
  *   rv_many_add     a job of k >= 2 non-empty sequences -> its id (0, 1, ..), < 0 on error (an empty sequence, k < 2, non-ASCII bytes)
  *   rv_many_clear   forgets the jobs and results, keeps every allocation for the next batch
  *   rv_many_run     runs every job; *total (may be NULL) = the sums of the runs' statistics.  A text beyond the 32-bit library's position limit (or
@@ -506,7 +512,9 @@ void rv_batch_free(rv_batch *b);
  *                   (fewer such jobs than this in a call stay ordinary, default 4), RV_MANY_LARGE_MULTI (0 / 1: jobs of 3 .. 16 sequences above 2048
  *                   ranks through shared launches, within the same RV_MANY_LARGE_MAX; they count in out[1] then, and out[4] follows the convention
  *                   of the large pair rounds), RV_MANY_LARGE_MULTI_MIN (fewer such jobs than this in a call stay ordinary, default 16: a threshold of
- *                   their own, so RV_MANY_LARGE_MIN and what a call does with its pair jobs do not change); any other name: rv_set_option on the internal handles
+ *                   their own, so RV_MANY_LARGE_MIN and what a call does with its pair jobs do not change), RV_MANY_WIDE (0 / 1: jobs of 17 .. 64
+ *                   sequences up to RV_MANY_LARGE_MAX ranks through shared launches; they count in out[1] then), RV_MANY_WIDE_LARGE_MIN (fewer such jobs
+ *                   above 2048 ranks than this in a call stay ordinary, default 8); any other name: rv_set_option on the internal handles
  *   rv_many_arrays  test hook: which = RV_SA / RV_LCP of a shared-launch job in job-local positions, native element width; -2: not kept */
 typedef struct rv_many rv_many;
 rv_many *rv_many_new(int device);       /* NULL on failure */

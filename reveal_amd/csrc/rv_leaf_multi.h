@@ -3,7 +3,9 @@
 #include "rv_common.h"
 #include "rv_leaf.h"
 
-#define RV_MANY_KMAX 16        // samples of a job the kernel takes (one interval per sample and frame)
+#define RV_MANY_KMAX 16        // samples of a job the kernel's narrow form takes (one interval per sample and frame)
+#define RV_MANY_WIDE_KMAX 64   // ... its wide form (RV_MANY_WIDE): lane s of a wavefront owns sample s, the sample id has six bits of the
+                               // `smp` byte, and the level pipeline's multi-sample scan keeps a one-word census up to 64 samples (rv_scan.hip)
 
 // a job of rv_many: k sequences, every one a sample, `s0$s1$..s(k-1)$` contiguous in the round's text; its n <= RV_LEAF_N ranks
 // lie at the same offset of the index arrays
@@ -25,4 +27,5 @@ struct RvLeafMultiArgs {
     u32 *err;                                                // 4: stack full, 8: a sub-index is not the suffixes of its intervals, 16: a bad job, 32: output full
 };
 
-int rv_leaf_multi_launch(hipStream_t q, const RvLeafMultiArgs &a, int njobs);
+// kmax: RV_MANY_KMAX or RV_MANY_WIDE_KMAX -- the form of the kernel; every job of the launch has at most that many samples
+int rv_leaf_multi_launch(hipStream_t q, const RvLeafMultiArgs &a, int njobs, int kmax);

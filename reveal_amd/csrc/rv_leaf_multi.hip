@@ -1,4 +1,5 @@
-// rv_leaf_multi.hip -- the whole recursion of a job of 3 .. RV_MANY_KMAX samples inside one workgroup (rv_many.hip, RV_MANY_MULTI).
+// rv_leaf_multi.hip -- the whole recursion of a job of 3 .. RV_MANY_KMAX samples inside one workgroup (rv_many.hip, RV_MANY_MULTI), and in its
+// wide form of a job of up to RV_MANY_WIDE_KMAX = 64 samples (RV_MANY_WIDE: the jobs of 17 .. 64 sequences).
 //
 // k_leaf (rv_leaf.hip) with one interval per SAMPLE in a frame instead of two: one workgroup per job, the arrays in LDS in two
 // copies, one wavefront per sub-index, the waves taking sub-indices from a shared stack.  A job is `s0$s1$..s(k-1)$`, at most
@@ -12,6 +13,14 @@
 //           member position of its own sample.  Running-minimum LCP per child (reveal.c:582-664)
 //   bubble  bubble_sort on the leading child, one cut per sample with a leading interval, ascending (reveal.c:666-727)
 // Every sub-index of such a job takes this path, also once it is down to two samples (scan_index decides by the main index).
+//
+// The kernel is a template over the sample bound KM.  Lane s of a wavefront owns sample s (64-bit ballots), the sample id lies in the low bits
+// of the `smp` byte below SMP_SEP (0x40), and the scan's census has a bit per sample: 64 is the bound of all three, and of the one-word
+// census of the level pipeline's multi-sample scan (rv_scan.hip) that finishes such jobs above RV_LEAF_N ranks.  Wider jobs stay ordinary.
+//   KM = 16   FrameM 72 B, a 32-bit census, 39 664 B of LDS per workgroup: the code, the footprint and the results it had before the template
+//   KM = 64   FrameM 264 B (96 stack + 4 current frames: 26 400 B), a 64-bit census, arrays 32 256 B, the picked members 512 B: 59 248 B of
+//             LDS per workgroup (compiler remark, gfx950; a workgroup may declare 160 KiB): two workgroups per CU; 103 VGPRs, no scratch
+// MAXSTACK does not depend on KM: the frames that wait are O(waves x log n), n <= RV_LEAF_N ranks whatever the number of samples.
 #include "rv_leaf_multi.h"
 
 namespace {
@@ -19,14 +28,16 @@ namespace {
 constexpr int NT = 256;
 constexpr int LN = RV_LEAF_N;
 constexpr int NW = NT / 64;
-constexpr int KM = RV_MANY_KMAX;
 constexpr int MAXSTACK = 96;             // frames waiting for a wave: O(waves x log n), a wave goes on with the smaller child
 constexpr int ACAP = 256;            // anchors staged per workgroup; their members (at most LN: anchors cover disjoint text) all fit
 constexpr u32 INF = 0xFFFFFFFFu;
-constexpr uint8_t SMP_ID = 0x0F, SMP_SEP = 0x40, SMP_DONE = 0x80;
-static_assert(LN <= 2048 && KM <= 16, "positions in 16 bits, 8 per thread when a job is loaded; the sample in 4 bits");
+constexpr uint8_t SMP_SEP = 0x40, SMP_DONE = 0x80;      // (the sample id lies below them: KM - 1, at most six bits)
+static_assert(LN <= 2048, "positions in 16 bits, 8 per thread when a job is loaded");
 
-struct FrameM { uint16_t start, len, depth, buf; uint16_t b[KM], e[KM]; };      // interval [b, e) of every sample, job-local; empty: b >= e
+template <int KM>
+struct FrameMT { uint16_t start, len, depth, buf; uint16_t b[KM], e[KM]; };      // interval [b, e) of every sample, job-local; empty: b >= e
+template <int KM> struct Census { typedef u32 type; };      // a bit per sample of the window the scan looks at
+template <> struct Census<RV_MANY_WIDE_KMAX> { typedef u64 type; };
 
 #define WSYNC() do { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); __builtin_amdgcn_wave_barrier(); } while (0)
 
@@ -54,7 +65,14 @@ __device__ inline MinSt2 wave_incl_ms2(MinSt2 m) {
     return m;
 }
 
+// KM: the sample bound of the form, RV_MANY_KMAX (16) or RV_MANY_WIDE_KMAX (64) -- a power of two and at most a wavefront's lanes
+template <int KM>
 __global__ __launch_bounds__(NT) void k_leaf_multi(RvLeafMultiArgs A) {
+    static_assert(KM == RV_MANY_KMAX || KM == RV_MANY_WIDE_KMAX, "the sample in KM - 1 <= 0x3F of the smp byte, lane s owns sample s");
+    static_assert((KM & (KM - 1)) == 0 && KM <= 64 && KM - 1 < SMP_SEP && KM <= NT, "lane & (KM - 1), 64-bit ballots, tid < KM");
+    constexpr uint8_t SMP_ID = (uint8_t)(KM - 1);
+    typedef typename Census<KM>::type cen_t;
+    typedef FrameMT<KM> FrameM;
     __shared__ uint16_t sa2[2][LN], lc2[2][LN];
     __shared__ uint8_t bw2[2][LN];
     __shared__ uint8_t smp[LN];
@@ -162,10 +180,10 @@ __global__ __launch_bounds__(NT) void k_leaf_multi(RvLeafMultiArgs A) {
                 if (l < need) continue;
                 if (i > S && (u32)cl[i] >= l) continue;
                 if (i + ns < E && (u32)cl[i + ns] >= l) continue;
-                u32 seen = 0, minp = 0xFFFFu; bool dup = false, lm = false; uint8_t cprev = 0;
+                cen_t seen = 0; u32 minp = 0xFFFFu; bool dup = false, lm = false; uint8_t cprev = 0;
                 for (int j = 0; j < ns; j++) {
                     const u32 p = cs[i + j]; const uint8_t sb = smp[p], c = cb[i + j];
-                    const u32 bit = 1u << (sb & SMP_ID);
+                    const cen_t bit = (cen_t)1 << (sb & SMP_ID);
                     dup |= (seen & bit) != 0 || (sb & SMP_SEP) != 0;
                     seen |= bit;
                     minp = p < minp ? p : minp;
@@ -395,9 +413,11 @@ __global__ __launch_bounds__(NT) void k_leaf_multi(RvLeafMultiArgs A) {
 
 }  // namespace
 
-int rv_leaf_multi_launch(hipStream_t q, const RvLeafMultiArgs &a, int njobs) {
+int rv_leaf_multi_launch(hipStream_t q, const RvLeafMultiArgs &a, int njobs, int kmax) {
     if (njobs <= 0) return 0;
-    hipLaunchKernelGGL(k_leaf_multi, dim3((unsigned)njobs), dim3(NT), 0, q, a);
+    if (kmax == RV_MANY_KMAX) hipLaunchKernelGGL(k_leaf_multi<RV_MANY_KMAX>, dim3((unsigned)njobs), dim3(NT), 0, q, a);
+    else if (kmax == RV_MANY_WIDE_KMAX) hipLaunchKernelGGL(k_leaf_multi<RV_MANY_WIDE_KMAX>, dim3((unsigned)njobs), dim3(NT), 0, q, a);
+    else { rv_set_error("rv_leaf_multi_launch: no form of the kernel for %d samples", kmax); return -1; }
     RV_LAUNCH_CHECK();
     return 0;
 }

@@ -44,6 +44,13 @@
 //   build    the segmented prefix doubling of rv_many_large.hip over job-local texts s0$s1$..s(k-1)$ gathered from the k places
 //   finish   rv_frontier_import of J roots (nsamples = the job's k, k intervals each) + rv_align_builtin_resume: the level pipeline for more
 //            than two samples, down to the last sub-index (there is no leaf kernel for multi-sample sub-indices of a handle)
+//
+// RV_MANY_WIDE (off by default, independent of the other switches): the jobs of 17 .. RV_MANY_WIDE_KMAX = 64 sequences with no NUL byte share their
+// launches too, in rounds of their own -- the composition of the other classes' rounds does not change.  Up to RV_LEAF_N ranks: many_round_multi
+// with the 64-sample form of k_leaf_multi (k_many_build does not know k).  Above, up to RV_MANY_LARGE_MAX ranks and from RV_MANY_WIDE_LARGE_MIN such
+// jobs in a call on: many_round_large_multi with K up to 64.  64: a lane of a wavefront owns a sample in the leaf kernel, the sample id has six
+// bits of its `smp` byte, and the level pipeline's multi-sample scan keeps a one-word census up to 64 samples.  Jobs of more than 64 sequences
+// stay ordinary.
 // Size classes (DESIGN.md "Many small alignments" has the measurements): up to `wave_max` ranks (default 512) a wavefront per job,
 // four jobs per workgroup, no workgroup barrier; above, a workgroup of 256 threads per job.  Both hold 22.6 KB of LDS per workgroup:
 // seven workgroups per CU.
@@ -237,6 +244,7 @@ struct rv_many {
     int64_t multi = 0, stage = 256;             // RV_MANY_MULTI, RV_MANY_STAGE
     int64_t large = 0, large_max = RV_MANY_LARGE_MAX_DEFAULT, large_min = RV_MANY_LARGE_MIN_DEFAULT;      // RV_MANY_LARGE, RV_MANY_LARGE_MAX, RV_MANY_LARGE_MIN
     int64_t large_multi = 0, large_multi_min = 16;      // RV_MANY_LARGE_MULTI, RV_MANY_LARGE_MULTI_MIN (DESIGN.md "Many small alignments": 4 such jobs lose, 16 win)
+    int64_t wide = 0, wide_large_min = RV_MANY_WIDE_LARGE_MIN_DEFAULT;      // RV_MANY_WIDE, RV_MANY_WIDE_LARGE_MIN
     std::vector<std::pair<std::string, int64_t>> fwd;      // switches for the internal handles
     // results of the last run
     bool ran = false;
@@ -426,7 +434,9 @@ int many_round(rv_many *m, const std::vector<int> &order, size_t lo, size_t hi, 
 // stand-alone coordinate.  k_many_build sees such a job as its first sequence and "the rest" (the side bit of the BWT byte means
 // nothing here); k_leaf_multi then finishes every job in one workgroup and lower-cases its text.  No handle is involved beyond
 // the stream and the read-back buffer of the shared one: the launches of a round do not depend on the number of jobs.
-int many_round_multi(rv_many *m, const std::vector<int> &order, size_t lo, size_t hi, int minl, int minn, rv_align_stats *total) {
+// kmax: the sample bound of the round's class and the form of k_leaf_multi that takes it -- RV_MANY_KMAX, or RV_MANY_WIDE_KMAX for the
+// rounds of jobs of 17 .. 64 sequences (RV_MANY_WIDE)
+int many_round_multi(rv_many *m, const std::vector<int> &order, size_t lo, size_t hi, int minl, int minn, rv_align_stats *total, int kmax) {
     RV_TRY(many_handle(m, &m->hs));
     rv_index *h = m->hs;
     const size_t J = hi - lo;
@@ -434,7 +444,11 @@ int many_round_multi(rv_many *m, const std::vector<int> &order, size_t lo, size_
     std::vector<RvLeafMultiJob> mj(J);
     int64_t n = 0;
     size_t nsmall = 0;
-    for (size_t s = 0; s < J; s++) n += m->jobs[(size_t)order[lo + s]].ranks;
+    for (size_t s = 0; s < J; s++) {
+        const ManyJob &jb = m->jobs[(size_t)order[lo + s]];
+        if (jb.k < 3 || jb.k > kmax || jb.ranks > CAP_L) { rv_set_error("rv_many_run: a job of %d sequences in a round of at most %d", jb.k, kmax); return -1; }
+        n += jb.ranks;
+    }
     std::vector<char> txt((size_t)n);
     int64_t at = 0;
     for (size_t s = 0; s < J; s++) {
@@ -477,7 +491,7 @@ int many_round_multi(rv_many *m, const std::vector<int> &order, size_t lo, size_
     a.count = (unsigned long long *)(d_max + 4); a.anchor_cap = acap; a.member_cap = mcap;
     a.anchors = m->dAn.as<RvLeafMultiAnchor>(); a.an_pos = m->dAnPos.as<uint16_t>();
     a.stats = (unsigned long long *)(d_max + 6); a.err = d_max + 2;
-    RV_TRY(rv_leaf_multi_launch(q, a, (int)J));
+    RV_TRY(rv_leaf_multi_launch(q, a, (int)J, kmax));
     m->info[4]++;
     u32 cnt[16];
     RV_TRY(rv_read_back(h->ws, cnt, d_max, sizeof cnt));
@@ -502,7 +516,7 @@ int many_round_multi(rv_many *m, const std::vector<int> &order, size_t lo, size_
     RV_HIP(hipStreamSynchronize(q));
     for (size_t k = 0; k < na; k++) {
         const RvLeafMultiAnchor &r = an[k];
-        if (r.job >= J || r.n < 2 || r.n > (u32)RV_MANY_KMAX || (size_t)r.moff + r.n > nm) { rv_set_error("rv_many_run: a malformed anchor"); return -1; }
+        if (r.job >= J || r.n < 2 || r.n > (u32)kmax || (size_t)r.moff + r.n > nm) { rv_set_error("rv_many_run: a malformed anchor"); return -1; }
         const int64_t ranks = mj[r.job].n;
         ManyRec rec; rec.job = order[lo + r.job]; rec.l = r.l; rec.np = (int)r.n; rec.p0 = (int64_t)m->rpos.size();
         for (u32 x = 0; x < r.n; x++) {
@@ -584,7 +598,8 @@ int many_collect_k(rv_many *m, rv_index *h, const ManyRoundK &R) {
 // one round of jobs of three and more sequences above RV_LEAF_N ranks (RV_MANY_LARGE_MULTI): the jobs order[lo .. hi) (ascending size), k mixed.
 // The sample-major text goes into the shared handle (K samples, K the widest job), the index of every job is built at once
 // (rv_many_large_build_k), the segments become a level-0 frontier of J roots of k samples each, and the level pipeline finishes them together.
-int many_round_large_multi(rv_many *m, const std::vector<int> &order, size_t lo, size_t hi, int minl, int minn, rv_align_stats *total) {
+// kmax: the sample bound of the round's class (RV_MANY_KMAX; RV_MANY_WIDE_KMAX for the rounds of jobs of 17 .. 64 sequences, RV_MANY_WIDE).
+int many_round_large_multi(rv_many *m, const std::vector<int> &order, size_t lo, size_t hi, int minl, int minn, rv_align_stats *total, int kmax) {
     RV_TRY(many_handle(m, &m->hs));
     rv_index *h = m->hs;
     const size_t J = hi - lo;
@@ -594,7 +609,7 @@ int many_round_large_multi(rv_many *m, const std::vector<int> &order, size_t lo,
     R.dj.resize(J);
     int K = 0;
     for (size_t s = 0; s < J; s++) K = std::max(K, m->jobs[(size_t)R.ord[s]].k);
-    if (K < 3 || K > RV_MANY_KMAX) { rv_set_error("rv_many_run: a round of jobs of %d sequences", K); return -1; }
+    if (K < 3 || K > kmax || kmax > RV_MANY_WIDE_KMAX) { rv_set_error("rv_many_run: a round of jobs of %d sequences", K); return -1; }
     R.send.resize((size_t)K); R.sbeg.resize((size_t)K); R.sslot.resize((size_t)K);
     // text: sample q = the q-th sequence of every job that has one
     std::vector<char> buf;
@@ -627,7 +642,7 @@ int many_round_large_multi(rv_many *m, const std::vector<int> &order, size_t lo,
         ManyDevJobK &d = R.dj[s];
         d.off = off; d.k = jb.k; d.n = (int32_t)jb.ranks;
         int64_t pe = 0;
-        for (int q = 0; q < RV_MANY_KMAX; q++) {
+        for (int q = 0; q < RV_MANY_WIDE_KMAX; q++) {
             if (q < jb.k) pe += m->lens[jb.seq0 + (size_t)q] + 1; else d.beg[q] = 0;
             d.pend[q] = (int32_t)pe;
         }
@@ -750,6 +765,13 @@ int many_run(rv_many *m, int minl, int minn, rv_align_stats *total) {
     int64_t nlmulti = 0;
     for (const ManyJob &jb : m->jobs) nlmulti += is_large_multi(jb) ? 1 : 0;
     const bool take_large_multi = nlmulti > 0 && nlmulti >= m->large_multi_min;
+    // (the jobs of 17 .. 64 sequences: classes of their own, rounds of their own -- what a call does with its other jobs does not depend on them)
+    const auto is_wide = [&](const ManyJob &jb) { return m->wide && jb.k > RV_MANY_KMAX && jb.k <= RV_MANY_WIDE_KMAX && jb.clean; };
+    const auto is_wide_large = [&](const ManyJob &jb) { return is_wide(jb) && jb.ranks > RV_LEAF_N && jb.ranks <= m->large_max && jb.ranks <= lim; };
+    int64_t nwlarge = 0;
+    for (const ManyJob &jb : m->jobs) nwlarge += is_wide_large(jb) ? 1 : 0;
+    const bool take_wide_large = nwlarge > 0 && nwlarge >= m->wide_large_min;
+    std::vector<int> worder, wlorder;
     for (int j = 0; j < nj; j++) {
         ManyJob &jb = m->jobs[(size_t)j];
         jb.arr_off = -1;
@@ -757,6 +779,8 @@ int many_run(rv_many *m, int minl, int minn, rv_align_stats *total) {
         else if (take_large && is_large(jb)) lorder.push_back(j);
         else if (take_large_multi && is_large_multi(jb)) lmorder.push_back(j);
         else if (m->multi && jb.k >= 3 && jb.k <= RV_MANY_KMAX && jb.ranks <= RV_LEAF_N && jb.clean) morder.push_back(j);
+        else if (is_wide(jb) && jb.ranks <= RV_LEAF_N) worder.push_back(j);
+        else if (take_wide_large && is_wide_large(jb)) wlorder.push_back(j);
         else rest.push_back(j);
     }
     const auto by_size = [&](int a, int b) { return m->jobs[(size_t)a].ranks < m->jobs[(size_t)b].ranks; };
@@ -764,6 +788,8 @@ int many_run(rv_many *m, int minl, int minn, rv_align_stats *total) {
     std::stable_sort(morder.begin(), morder.end(), by_size);
     std::stable_sort(lorder.begin(), lorder.end(), by_size);
     std::stable_sort(lmorder.begin(), lmorder.end(), by_size);
+    std::stable_sort(worder.begin(), worder.end(), by_size);
+    std::stable_sort(wlorder.begin(), wlorder.end(), by_size);
     for (size_t lo = 0; lo < order.size();) {
         size_t hi = lo; int64_t sum = 0;
         while (hi < order.size() && (hi == lo || sum + m->jobs[(size_t)order[hi]].ranks <= lim)) sum += m->jobs[(size_t)order[hi++]].ranks;
@@ -779,13 +805,25 @@ int many_run(rv_many *m, int minl, int minn, rv_align_stats *total) {
     for (size_t lo = 0; lo < morder.size();) {      // the jobs of three and more sequences: rounds of their own
         size_t hi = lo; int64_t sum = 0;
         while (hi < morder.size() && (hi == lo || sum + m->jobs[(size_t)morder[hi]].ranks <= lim)) sum += m->jobs[(size_t)morder[hi++]].ranks;
-        RV_TRY(many_round_multi(m, morder, lo, hi, minl, minn, total));
+        RV_TRY(many_round_multi(m, morder, lo, hi, minl, minn, total, RV_MANY_KMAX));
         lo = hi;
     }
     for (size_t lo = 0; lo < lmorder.size();) {     // the jobs of three and more sequences above RV_LEAF_N ranks: rounds of their own
         size_t hi = lo; int64_t sum = 0;
         while (hi < lmorder.size() && (hi == lo || sum + m->jobs[(size_t)lmorder[hi]].ranks <= lim)) sum += m->jobs[(size_t)lmorder[hi++]].ranks;
-        RV_TRY(many_round_large_multi(m, lmorder, lo, hi, minl, minn, total));
+        RV_TRY(many_round_large_multi(m, lmorder, lo, hi, minl, minn, total, RV_MANY_KMAX));
+        lo = hi;
+    }
+    for (size_t lo = 0; lo < worder.size();) {      // the jobs of 17 .. 64 sequences (RV_MANY_WIDE): rounds of their own, the wide form of the leaf kernel
+        size_t hi = lo; int64_t sum = 0;
+        while (hi < worder.size() && (hi == lo || sum + m->jobs[(size_t)worder[hi]].ranks <= lim)) sum += m->jobs[(size_t)worder[hi++]].ranks;
+        RV_TRY(many_round_multi(m, worder, lo, hi, minl, minn, total, RV_MANY_WIDE_KMAX));
+        lo = hi;
+    }
+    for (size_t lo = 0; lo < wlorder.size();) {     // ... above RV_LEAF_N ranks: sample-major rounds of their own
+        size_t hi = lo; int64_t sum = 0;
+        while (hi < wlorder.size() && (hi == lo || sum + m->jobs[(size_t)wlorder[hi]].ranks <= lim)) sum += m->jobs[(size_t)wlorder[hi++]].ranks;
+        RV_TRY(many_round_large_multi(m, wlorder, lo, hi, minl, minn, total, RV_MANY_WIDE_KMAX));
         lo = hi;
     }
     for (int j : rest) RV_TRY(many_ordinary(m, j, minl, minn, total));
@@ -844,6 +882,8 @@ int rv_many_option(rv_many *m, const char *name, int64_t value) {
     if (strcmp(name, "RV_MANY_LARGE") == 0) { m->large = value != 0; return 0; }
     if (strcmp(name, "RV_MANY_LARGE_MULTI") == 0) { m->large_multi = value != 0; return 0; }
     if (strcmp(name, "RV_MANY_LARGE_MULTI_MIN") == 0) { if (value < 0) { rv_set_error("RV_MANY_LARGE_MULTI_MIN: negative"); return -1; } m->large_multi_min = value; return 0; }
+    if (strcmp(name, "RV_MANY_WIDE") == 0) { m->wide = value != 0; return 0; }
+    if (strcmp(name, "RV_MANY_WIDE_LARGE_MIN") == 0) { if (value < 0) { rv_set_error("RV_MANY_WIDE_LARGE_MIN: negative"); return -1; } m->wide_large_min = value; return 0; }
     if (strcmp(name, "RV_MANY_LARGE_MAX") == 0) { if (value < 0) { rv_set_error("RV_MANY_LARGE_MAX: negative"); return -1; } m->large_max = value; return 0; }
     if (strcmp(name, "RV_MANY_LARGE_MIN") == 0) { if (value < 0) { rv_set_error("RV_MANY_LARGE_MIN: negative"); return -1; } m->large_min = value; return 0; }
     if (strcmp(name, "RV_MANY_STAGE") == 0) { if (value < 0) { rv_set_error("RV_MANY_STAGE: negative"); return -1; } m->stage = value; return 0; }

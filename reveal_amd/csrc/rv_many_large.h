@@ -1,21 +1,24 @@
 // rv_many_large.h -- the index build of rv_many's rounds of pair jobs above RV_LEAF_N ranks (rv_many_large.hip).
 #pragma once
 #include "rv_common.h"
-#include "rv_leaf_multi.h"      // RV_MANY_KMAX
+#include "rv_leaf_multi.h"      // RV_MANY_KMAX, RV_MANY_WIDE_KMAX
 
 // defaults of RV_MANY_LARGE_MAX (ranks of the largest job the large rounds take) and RV_MANY_LARGE_MIN (fewer large jobs than this in a
 // call stay ordinary): DESIGN.md "Many small alignments" has the measurements
 #define RV_MANY_LARGE_MAX_DEFAULT ((int64_t)1 << 17)
 #define RV_MANY_LARGE_MIN_DEFAULT 4
+// default of RV_MANY_WIDE_LARGE_MIN (fewer jobs of 17 .. 64 sequences above RV_LEAF_N ranks than this in a call stay ordinary): the smallest
+// count measured at which the shared rounds are not slower at k = 17, 32 and 64 (profiles/many_wide.txt: 4 jobs of 32 sequences tie, 8 win)
+#define RV_MANY_WIDE_LARGE_MIN_DEFAULT 8
 
 // a pair job of a round: where its two sequences begin in the round's shared text, the first rank of its segment
 struct ManyDevJob { int64_t abeg, bbeg, off; int32_t la, lb; };
 
-// a job of k = 3 .. RV_MANY_KMAX sequences of a sample-major round (RV_MANY_LARGE_MULTI): sample q of the round's text holds the q-th sequence of
+// a job of k = 3 .. RV_MANY_WIDE_KMAX sequences of a sample-major round (RV_MANY_LARGE_MULTI: up to RV_MANY_KMAX; RV_MANY_WIDE: above): sample q of the round's text holds the q-th sequence of
 // every job that has one.  off: the first rank of its segment; n: its ranks (sum of lengths + k); beg[q]: where sequence q begins in the shared
 // text; pend[q]: the end of sequence q's local prefix, lengths + 1 accumulated -- sequence q and its '$' are the local positions
 // [pend[q - 1], pend[q]) of the stand-alone text s0$s1$..s(k-1)$, and pend[k - 1] = n
-struct ManyDevJobK { int64_t off; int64_t beg[RV_MANY_KMAX]; int32_t pend[RV_MANY_KMAX]; int32_t k, n; };
+struct ManyDevJobK { int64_t off; int64_t beg[RV_MANY_WIDE_KMAX]; int32_t pend[RV_MANY_WIDE_KMAX]; int32_t k, n; };
 
 // scratch of the build, kept by rv_many between calls: 37 B per position (+ the radix sort's digit byte and histograms in the workspace)
 struct RvManyLargeBufs {
@@ -28,7 +31,7 @@ struct RvManyLargeBufs {
 // (device words, cleared by the caller).  The kernel launches made are added to *launches; they do not depend on the number of jobs.
 int rv_many_large_build(Workspace &ws, RvManyLargeBufs &B, const ManyDevJob *djobs, int64_t njobs, int64_t n, int64_t maxn, const uint8_t *T,
                         sa_t *SA, lcp_t *LCP, uint8_t *BWT, u32 *d_cnt, int64_t *launches);
-// the same for jobs of 3 .. RV_MANY_KMAX sequences in the sample-major layout: segment [off, off + n) of a job = construct() of its stand-alone text
+// the same for jobs of 3 .. RV_MANY_WIDE_KMAX sequences in the sample-major layout: segment [off, off + n) of a job = construct() of its stand-alone text
 // s0$s1$..s(k-1)$, SA in shared-text positions.  nT: bytes of T (a descriptor that points outside it is refused through d_cnt[1], not read).
 int rv_many_large_build_k(Workspace &ws, RvManyLargeBufs &B, const ManyDevJobK *djobs, int64_t njobs, int64_t n, int64_t maxn, const uint8_t *T, int64_t nT,
                           sa_t *SA, lcp_t *LCP, uint8_t *BWT, u32 *d_cnt, int64_t *launches);

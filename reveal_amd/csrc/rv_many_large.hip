@@ -134,7 +134,7 @@ __global__ __launch_bounds__(LT) void k_ml_finish(const ManyDevJob *__restrict__
     if ((threadIdx.x & 63) == 0 && lmax > __atomic_load_n(d_maxlcp, __ATOMIC_RELAXED)) atomicMax(d_maxlcp, lmax);
 }
 
-// The gather of a sample-major round: element -> job by the search in the offsets, local position -> sequence by a scan of the (at most 16)
+// The gather of a sample-major round: element -> job by the search in the offsets, local position -> sequence by a scan of the (at most RV_MANY_WIDE_KMAX)
 // prefix ends, byte from the shared text.  The thread of a job's first element checks the whole descriptor; every thread checks what it reads
 // with: a malformed descriptor sets the error word and reads nothing outside T.
 __global__ __launch_bounds__(LT) void k_mlk_gather(const ManyDevJobK *__restrict__ jobs, int njobs, int64_t n, const uint8_t *__restrict__ T, int64_t nT,
@@ -147,7 +147,7 @@ __global__ __launch_bounds__(LT) void k_mlk_gather(const ManyDevJobK *__restrict
     const int64_t p = e - J->off;
     const int k = J->k, nj = J->n;
     job[e] = (u32)lo;
-    bool bad = k < 3 || k > RV_MANY_KMAX || p < 0 || p >= nj;
+    bool bad = k < 3 || k > RV_MANY_WIDE_KMAX || p < 0 || p >= nj;
     uint8_t ch = (uint8_t)'$';
     if (!bad) {
         if (p == 0) {                      // the whole descriptor, once per job: its sequences, and its segment between its neighbours
@@ -180,7 +180,7 @@ __global__ __launch_bounds__(LT) void k_mlk_finish(const ManyDevJobK *__restrict
     int q = 0, kk = 0, pe = 0;
     for (int64_t e = e0; e < e0 + FIN_CHUNK && e < n; e++) {
         const u32 j = job[e];
-        if (j != jcur) { J = jobs + j; off = J->off; la = J->pend[0] - 1; kk = J->k < RV_MANY_KMAX ? J->k : RV_MANY_KMAX; jcur = j; hh = 0; q = 0; pe = J->pend[0]; sbeg = J->beg[0]; }      // (a job's first position: no carry)
+        if (j != jcur) { J = jobs + j; off = J->off; la = J->pend[0] - 1; kk = J->k < RV_MANY_WIDE_KMAX ? J->k : RV_MANY_WIDE_KMAX; jcur = j; hh = 0; q = 0; pe = J->pend[0]; sbeg = J->beg[0]; }      // (a job's first position: no carry)
         const int64_t p = e - off, k = (int64_t)rank[e] - 1;
         while (q < kk - 1 && p >= pe) { sbeg = J->beg[q + 1] - pe; pe = J->pend[++q]; }
         if (k > off) {

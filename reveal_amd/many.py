@@ -28,6 +28,15 @@ own) leaves them on the ordinary path.  With all three switches on, every
 clean job of 2 .. 16 sequences up to RV_MANY_LARGE_MAX ranks that fits a round goes through shared launches -- in a call that holds at least
 RV_MANY_LARGE_MIN pair jobs and RV_MANY_LARGE_MULTI_MIN jobs of three and more sequences above 2048 ranks, where it has any.
 The results do not depend on these switches either.
+
+Jobs of more than 16 sequences -- every bubble of a graph of 25 or 100 genomes refined without --uniqueonly -- run the ordinary way unless
+the switch RV_MANY_WIDE is on (`align_many(.., wide=True)`, `Batch.option("RV_MANY_WIDE", 1)` or the environment variable; off by default,
+independent of the other switches).  With it the clean jobs of 17 .. 64 sequences share their launches too, in rounds of their own: up to
+2048 ranks the layout and the index build of RV_MANY_MULTI and one launch of the 64-sample form of the leaf kernel; at 2049 ..
+RV_MANY_LARGE_MAX ranks the sample-major rounds of RV_MANY_LARGE_MULTI with up to 64 samples, in a call with at least
+RV_MANY_WIDE_LARGE_MIN such jobs (default 8, counted on their own).  64 is the limit because a lane of a wavefront owns a sample in the
+leaf kernel, the sample id has six bits of its per-position byte, and the level pipeline's scan keeps a one-word census up to 64 samples.
+Jobs of more than 64 sequences always run the ordinary way.  The results do not depend on this switch either.
 """
 import ctypes
 import os
@@ -38,6 +47,8 @@ from . import _lib
 
 LEAF_RANKS = 2048          # RV_LEAF_N: a job of sum of lengths + k ranks up to this goes through the shared launches
 MULTI_KMAX = 16            # RV_MANY_KMAX: sequences of a job the shared launches take with RV_MANY_MULTI
+WIDE_KMAX = 64             # RV_MANY_WIDE_KMAX: sequences of a job the shared launches take with RV_MANY_WIDE (17 .. 64)
+WIDE_LARGE_MIN = 8         # default of RV_MANY_WIDE_LARGE_MIN: fewer jobs of 17 .. 64 sequences above 2048 ranks in a call stay ordinary
 LARGE_MAX = 1 << 17        # default of RV_MANY_LARGE_MAX: ranks of the largest pair job the shared launches take with RV_MANY_LARGE
 
 
@@ -68,13 +79,18 @@ def job_sequences(job, toupper=True):
     return seqs
 
 
-def takes_shared_launch(seqs, multi=False, large=False, large_max=LARGE_MAX, large_multi=False):
+def takes_shared_launch(seqs, multi=False, large=False, large_max=LARGE_MAX, large_multi=False, wide=False):
     """whether the library builds and finishes this job in the shared launches; multi: with RV_MANY_MULTI on; large: with RV_MANY_LARGE
     on and RV_MANY_LARGE_MAX = large_max (in a call with at least RV_MANY_LARGE_MIN such jobs, and with rounds that hold the job);
-    large_multi: with RV_MANY_LARGE_MULTI on (in a call with at least RV_MANY_LARGE_MULTI_MIN such jobs, and with rounds that hold the job)"""
+    large_multi: with RV_MANY_LARGE_MULTI on (in a call with at least RV_MANY_LARGE_MULTI_MIN such jobs, and with rounds that hold the job);
+    wide: with RV_MANY_WIDE on -- jobs of 17 .. 64 sequences, above 2048 ranks in a call with at least RV_MANY_WIDE_LARGE_MIN such jobs"""
     k = len(seqs)
     ranks = sum(len(s) for s in seqs) + k
-    if not (2 <= k <= MULTI_KMAX) or any(b"\0" in s for s in seqs):
+    if any(b"\0" in s for s in seqs):
+        return False
+    if MULTI_KMAX < k <= WIDE_KMAX:
+        return bool(wide) and (ranks <= LEAF_RANKS or ranks <= large_max)
+    if not (2 <= k <= MULTI_KMAX):
         return False
     if ranks <= LEAF_RANKS:
         return k == 2 or bool(multi)
@@ -154,7 +170,7 @@ class Batch:
                     iv = 1
                 self.option(name, iv)
         for name in ("RV_MANY_KEEP", "RV_MANY_ROUND", "RV_MANY_WAVE_MAX", "RV_MANY_MULTI", "RV_MANY_LARGE", "RV_MANY_LARGE_MAX", "RV_MANY_LARGE_MIN",
-                     "RV_MANY_LARGE_MULTI", "RV_MANY_LARGE_MULTI_MIN"):
+                     "RV_MANY_LARGE_MULTI", "RV_MANY_LARGE_MULTI_MIN", "RV_MANY_WIDE", "RV_MANY_WIDE_LARGE_MIN"):
             v = os.environ.get(name)
             if v is not None and v.strip():
                 self.option(name, int(v))
@@ -225,7 +241,7 @@ class Batch:
         return sa, lcp
 
 
-def align_many(jobs, minlength=20, minn=2, sa64=False, toupper=True, batch=None, multi=None, large=None, large_multi=None):
+def align_many(jobs, minlength=20, minn=2, sa64=False, toupper=True, batch=None, multi=None, large=None, large_multi=None, wide=None):
     """jobs: a list of jobs, each a list of (name, seq) or of plain sequences (two or more, none empty; every sequence is a sample
     of its own, like the inputs of `reveal rem`).  -> (results, info): results[j] = dict(anchors=[(l, (pos, ..)), ..], T=final text
     `s0$s1$..` lower-cased where aligned), positions in the coordinates of the job's own text -- what index.align_builtin gives a
@@ -233,7 +249,8 @@ def align_many(jobs, minlength=20, minn=2, sa64=False, toupper=True, batch=None,
     `multi`: True / False sets RV_MANY_MULTI (jobs of 3 .. 16 sequences through the shared launches) for this and later runs of
     the batch; None leaves it as the batch has it (off, unless the environment variable is set).  `large`: the same for RV_MANY_LARGE
     (pair jobs of 2049 .. RV_MANY_LARGE_MAX ranks through the shared launches), `large_multi`: the same for RV_MANY_LARGE_MULTI (jobs of
-    3 .. 16 sequences of 2049 .. RV_MANY_LARGE_MAX ranks through the shared launches)."""
+    3 .. 16 sequences of 2049 .. RV_MANY_LARGE_MAX ranks through the shared launches), `wide`: the same for RV_MANY_WIDE (jobs of 17 .. 64
+    sequences up to RV_MANY_LARGE_MAX ranks through the shared launches; more than 64 sequences always run the ordinary way)."""
     if isinstance(jobs, (str, bytes, bytearray)) or not hasattr(jobs, "__iter__"):
         raise error("jobs is a list of jobs")
     if int(minlength) < 0 or int(minn) < 2:
@@ -246,6 +263,8 @@ def align_many(jobs, minlength=20, minn=2, sa64=False, toupper=True, batch=None,
         b.option("RV_MANY_LARGE", 1 if large else 0)
     if large_multi is not None:
         b.option("RV_MANY_LARGE_MULTI", 1 if large_multi else 0)
+    if wide is not None:
+        b.option("RV_MANY_WIDE", 1 if wide else 0)
     b.clear()
     for seqs in prepared:
         b.add(seqs)

@@ -3,6 +3,7 @@
 
     python tools/time_many.py [--jobs 10000] [--lmin 50] [--lmax 1000] [--reps 5] [--minlength 20] [--wave-max N] [--only loop|many] [--check]
                               [--seqs K] [--multi 0|1|ab] [--large 0|1|ab] [--large-multi 0|1|ab] [--large-max R] [--large-min J]
+                              [--wide 0|1|ab] [--wide-large-min J] [--no-cut] [--sites]
 
 Workload: J jobs of 2 x L bases, L uniform in lmin .. lmax, 1 % substitutions.  The two sides run alternately, `reps` times each:
   loop   rv_reset, rv_add_sample / rv_add_sequence x 2, rv_construct, rv_align_builtin, rv_fetch_anchors, the text -- per job, straight at
@@ -15,7 +16,12 @@ switch off and on, run alternately in one process -- medians, both spreads, the 
 --large 0 / 1 / ab: the same for RV_MANY_LARGE (pair jobs above 2048 ranks through shared launches; choose --lmin / --lmax above 1023);
 --large-multi 0 / 1 / ab: the same for RV_MANY_LARGE_MULTI (jobs of --seqs K >= 3 sequences above 2048 ranks; lmax is not cut then: choose
 --lmin / --lmax so that K x (L + 1) lies above 2048).  The ab legs also print the levels and scanned ranks of a call (the run's statistics).
---large-max / --large-min set RV_MANY_LARGE_MAX / RV_MANY_LARGE_MIN of every batch (with --large-multi: RV_MANY_LARGE_MULTI_MIN too)."""
+--large-max / --large-min set RV_MANY_LARGE_MAX / RV_MANY_LARGE_MIN of every batch (with --large-multi: RV_MANY_LARGE_MULTI_MIN too).
+--wide 0 / 1 / ab: the same for RV_MANY_WIDE (jobs of --seqs K = 17 .. 64 sequences).  lmax is cut to 2048 ranks a job as with --multi; with
+--no-cut it is not (choose --lmin / --lmax so that K x (L + 1) lies above 2048: the sample-major rounds of the wide jobs).  --wide-large-min
+sets RV_MANY_WIDE_LARGE_MIN of every batch.  --sites: the K members of a job differ at one to three variant sites, each substituted in a
+random subset of the members (the bubble of K haplotypes), not by 1 % substitutions per member -- among 32 or 64 members those leave almost
+no window common to all, and a call anchors next to nothing."""
 import argparse
 import ctypes
 import json
@@ -30,7 +36,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from reveal_amd import _lib, reveallib      # noqa: E402
 
 
-def workload(jobs, lmin, lmax, seed=1, seqs=2, cut=True):
+def workload(jobs, lmin, lmax, seed=1, seqs=2, cut=True, sites=False):
     rng = np.random.default_rng(seed)
     lut = np.frombuffer(b"ACGT", np.uint8)
     out = []
@@ -40,6 +46,13 @@ def workload(jobs, lmin, lmax, seed=1, seqs=2, cut=True):
     for _ in range(jobs):
         L = int(rng.integers(lmin, lmax + 1))
         a = rng.integers(0, 4, L)
+        if seqs > 2 and sites:      # one to three variant sites, each substituted in a random non-empty proper subset of the members
+            fam = np.tile(a, (seqs, 1))
+            for p in rng.choice(L, size=min(L, int(rng.integers(1, 4))), replace=False):
+                who = rng.choice(seqs, size=int(rng.integers(1, seqs)), replace=False)
+                fam[who, p] = (a[p] + int(rng.integers(1, 4))) % 4
+            out.append([lut[r].tobytes() for r in fam])
+            continue
         if seqs > 2:
             job = []
             for _ in range(seqs):
@@ -97,6 +110,8 @@ def as_lists(first, l, off, pos):
 def more_options(a, b):
     if a.large_max is not None:
         b.option("RV_MANY_LARGE_MAX", a.large_max)
+    if a.wide_large_min is not None:
+        b.option("RV_MANY_WIDE_LARGE_MIN", a.wide_large_min)
     if a.large_min is not None:
         b.option("RV_MANY_LARGE_MIN", a.large_min)
         if a.large_multi is not None:
@@ -109,7 +124,7 @@ def more_options(a, b):
 
 
 def main_ab(a, jobs, bases, switch="RV_MANY_MULTI"):
-    """`switch` (RV_MANY_MULTI, RV_MANY_LARGE or RV_MANY_LARGE_MULTI) off against on: two batches, alternately"""
+    """`switch` (RV_MANY_MULTI, RV_MANY_LARGE, RV_MANY_LARGE_MULTI or RV_MANY_WIDE) off against on: two batches, alternately"""
     from reveal_amd import many
     sides = {}
     for name, v in (("off", 0), ("on", 1)):
@@ -120,6 +135,8 @@ def main_ab(a, jobs, bases, switch="RV_MANY_MULTI"):
             b.option("RV_MANY_LARGE", int(a.large))
         if switch != "RV_MANY_LARGE_MULTI" and a.large_multi in ("0", "1"):
             b.option("RV_MANY_LARGE_MULTI", int(a.large_multi))
+        if switch != "RV_MANY_WIDE" and a.wide in ("0", "1"):
+            b.option("RV_MANY_WIDE", int(a.wide))
         more_options(a, b)
         b.option(switch, v)
         if a.wave_max is not None:
@@ -168,12 +185,18 @@ def main():
     ap.add_argument("--large-multi", choices=("0", "1", "ab"), default=None, help="RV_MANY_LARGE_MULTI of the many side; ab: off against on, no loop")
     ap.add_argument("--large-max", type=int, default=None, help="RV_MANY_LARGE_MAX")
     ap.add_argument("--large-min", type=int, default=None, help="RV_MANY_LARGE_MIN")
+    ap.add_argument("--wide", choices=("0", "1", "ab"), default=None, help="RV_MANY_WIDE of the many side; ab: off against on, no loop")
+    ap.add_argument("--wide-large-min", type=int, default=None, help="RV_MANY_WIDE_LARGE_MIN")
+    ap.add_argument("--sites", action="store_true", help="jobs of --seqs K > 2 sequences: variant sites in subsets of the members, not 1 % per member")
+    ap.add_argument("--no-cut", action="store_true", help="leave lmax as given when jobs of --seqs K sequences pass 2048 ranks")
     a = ap.parse_args()
-    if [a.multi, a.large, a.large_multi].count("ab") > 1:
-        ap.error("one switch at a time: --multi ab, --large ab or --large-multi ab")
+    if [a.multi, a.large, a.large_multi, a.wide].count("ab") > 1:
+        ap.error("one switch at a time: --multi ab, --large ab, --large-multi ab or --wide ab")
+    if a.wide is not None and not 17 <= a.seqs <= 64:
+        ap.error("--wide wants jobs of 17 .. 64 sequences: --seqs K")
     if a.large_multi is not None and a.seqs < 3:
         ap.error("--large-multi wants jobs of three and more sequences: --seqs K")
-    jobs = workload(a.jobs, a.lmin, a.lmax, seqs=a.seqs, cut=a.large_multi is None)
+    jobs = workload(a.jobs, a.lmin, a.lmax, seqs=a.seqs, cut=a.large_multi is None and not a.no_cut, sites=a.sites)
     bases = sum(len(s) for j in jobs for s in j)
     if a.multi == "ab":
         return main_ab(a, jobs, bases)
@@ -181,6 +204,8 @@ def main():
         return main_ab(a, jobs, bases, "RV_MANY_LARGE")
     if a.large_multi == "ab":
         return main_ab(a, jobs, bases, "RV_MANY_LARGE_MULTI")
+    if a.wide == "ab":
+        return main_ab(a, jobs, bases, "RV_MANY_WIDE")
     t_loop, t_many, t_many_py = [], [], []
     idx = reveallib.index() if a.only != "many" else None
     batch = None
@@ -200,6 +225,8 @@ def main():
                 batch.option("RV_MANY_LARGE_MULTI", 0)
             except many.error:      # (RV_LIB_DIR: a build from before the switch -- off is all it knows)
                 pass
+        if a.wide is not None:
+            batch.option("RV_MANY_WIDE", int(a.wide))
         more_options(a, batch)
         run_many_c(batch, jobs[:64], a.minlength)      # (first use: allocations, code objects)
     if idx is not None:
