@@ -493,6 +493,18 @@ void rv_batch_free(rv_batch *b);
  * samples, in a call with at least RV_MANY_WIDE_LARGE_MIN such jobs (counted on their own).  64 is the limit of this class: a lane of a wavefront owns a
  * sample in the leaf kernel, the sample id has six bits of its per-position byte, and the level pipeline's multi-sample scan keeps a one-word census up
  * to 64 samples.  A job of more than 64 sequences always runs the ordinary way.  The results do not depend on the switch.
+ * rv_many_set_picker(m, 1, &args): the jobs are aligned with the reference's default picker (schemes.graphmumpicker: trim the overlaps, chain, split on
+ * the largest match of the chain -- rv_pick_chain with these options) instead of the built-in one: what `reveal refine` computes for a bubble, and
+ * what rv_set_picker(h, 1, &args) + rv_align_builtin give a stand-alone index of the job.  The shared classes above all finish with built-in-picker
+ * kernels, so under kind 1 none of them takes a job, whatever its switch says: the jobs run the ordinary way with the picker set on the internal handle
+ * and count in out[2].  With RV_MANY_CHAIN set (off by default; it means something under kind 1 only) the pair jobs of at most 2048 ranks without a NUL
+ * byte share their launches all the same when the options leave the picker nothing a workgroup cannot do: trim on, minl > 0 (no p-value cut), weights
+ * 0 .. 65536, no seed possible (seedsize <= 0 or above the longer sequence) and a maxmums that cannot bite (<= 0 or at least the shorter sequence).
+ * They take the layout, index build and frontier of the small pair jobs and ONE launch of k_leaf_chain (rv_leaf_chain.hip): the leaf kernel with the
+ * picker's decision for two samples as its pick stage.  A job that kernel flags -- where the reference's own trim_overlap raises -- runs the ordinary
+ * way afterwards and ends as it would with the switch off.  The results do not depend on the switch.
+ *   rv_many_set_picker  kind 0: the built-in picker (the default); kind 1: the reference's default picker with *args (copied).  Holds for later runs,
+ *                   like an option.  -1 with an error text: args == NULL with kind 1, an unknown gap cost model, any other kind
  *   rv_many_add     a job of k >= 2 non-empty sequences -> its id (0, 1, ..), < 0 on error (an empty sequence, k < 2, non-ASCII bytes)
  *   rv_many_clear   forgets the jobs and results, keeps every allocation for the next batch
  *   rv_many_run     runs every job; *total (may be NULL) = the sums of the runs' statistics.  A text beyond the 32-bit library's position limit (or
@@ -514,12 +526,15 @@ void rv_batch_free(rv_batch *b);
  *                   of the large pair rounds), RV_MANY_LARGE_MULTI_MIN (fewer such jobs than this in a call stay ordinary, default 16: a threshold of
  *                   their own, so RV_MANY_LARGE_MIN and what a call does with its pair jobs do not change), RV_MANY_WIDE (0 / 1: jobs of 17 .. 64
  *                   sequences up to RV_MANY_LARGE_MAX ranks through shared launches; they count in out[1] then), RV_MANY_WIDE_LARGE_MIN (fewer such jobs
- *                   above 2048 ranks than this in a call stay ordinary, default 8); any other name: rv_set_option on the internal handles
+ *                   above 2048 ranks than this in a call stay ordinary, default 8), RV_MANY_CHAIN (0 / 1: under picker kind 1, the pair jobs named above through
+ *                   shared launches; they count in out[1] then), RV_MANY_CHAIN_FLAG (test hook: every n-th job of such a round is treated as flagged by the kernel --
+ *                   dropped from the round and run the ordinary way; 0: off); any other name: rv_set_option on the internal handles
  *   rv_many_arrays  test hook: which = RV_SA / RV_LCP of a shared-launch job in job-local positions, native element width; -2: not kept */
 typedef struct rv_many rv_many;
 rv_many *rv_many_new(int device);       /* NULL on failure */
 void rv_many_free(rv_many *m);
 int rv_many_option(rv_many *m, const char *name, int64_t value);
+int rv_many_set_picker(rv_many *m, int kind, const rv_picker_args *args);
 int64_t rv_many_add(rv_many *m, const char *const *seqs, const int64_t *lens, int k);
 int rv_many_clear(rv_many *m);
 int rv_many_run(rv_many *m, int minl, int minn, rv_align_stats *total);

@@ -168,6 +168,7 @@ SYMBOLS = {
     "rv_many_new": (V, [_I]),
     "rv_many_free": (None, [V]),
     "rv_many_option": (_I, [V, ctypes.c_char_p, _L]),
+    "rv_many_set_picker": (_I, [V, _I, V]),
     "rv_many_add": (_L, [V, V, V, _I]),
     "rv_many_clear": (_I, [V]),
     "rv_many_run": (_I, [V, _I, _I, ctypes.POINTER(RvAlignStats)]),

@@ -229,6 +229,7 @@ struct Align {
     // anchors [0, early_sent) of the device's list left for the caller's arrays at early_l / early_pos while the cascade's levels ran
     // (builtin_cascade); builtin_finish copies the rest when they still belong there
     size_t early_sent = 0; u32 *early_l = nullptr; int64_t *early_pos = nullptr;
+    bool leaf_chain = false; RvLeafChainArgs chain_args{}; int64_t chain_roots = 0;      // rv_leaf_chain_route
     size_t leaf_na = 0;          // anchors of the leaf launches of the last run: they stay in the pinned staging buffer (hLeafOut: pos[2 na], l[na]) until fetched
     void release() {
         // (the side streams may still be writing pinned buffers that go back to the process-wide pool below: after an aborted run nothing else waits for them)
@@ -460,6 +461,24 @@ int rv_set_preselect(rv_index *h, int64_t maxmums) {
 
 }  // extern "C"
 
+int rv_leaf_chain_route(rv_index *h, const rv_picker_args *args, u32 *flags) {
+    if (!h || (args && !flags)) { rv_set_error("rv_leaf_chain_route: bad arguments"); return -1; }
+    if (!h->al) h->al = new Align();
+    Align *a = h->al;
+    a->leaf_chain = args != nullptr;
+    a->chain_roots = 0;
+    if (args) {
+        if (a->picker != 0 || args->wscore < 0 || args->wpen < 0 || args->wscore > RV_LEAF_CHAIN_WMAX || args->wpen > RV_LEAF_CHAIN_WMAX || args->gcmodel < 0 || args->gcmodel > 2) {
+            rv_set_error("rv_leaf_chain_route: options the chain form of the leaf kernel does not take");
+            a->leaf_chain = false;
+            return -1;
+        }
+        a->chain_args.wscore = (int32_t)args->wscore; a->chain_args.wpen = (int32_t)args->wpen; a->chain_args.gcmodel = args->gcmodel; a->chain_args.flags = flags;
+    }
+    return 0;
+}
+int64_t rv_leaf_chain_roots(const rv_index *h) { return h && h->al ? h->al->chain_roots : 0; }
+
 int rv_run_multi_scan(rv_index *h, const sa_t *SA, const lcp_t *LCP, const uint8_t *BWT, int64_t m, int minl, int minn, int mems,
                       std::vector<u32> &l, std::vector<int32_t> &n, std::vector<int64_t> &off, std::vector<uint16_t> &so,
                       std::vector<int64_t> &pos, std::vector<int64_t> *ub_out,
@@ -497,7 +516,8 @@ static int leaf_launch(rv_index *h) {
     la.err = a->lf_counters + 2;
     {
         Workspace lw; lw.stream = ls;
-        RV_TRY(rv_leaf_launch(lw, la, (int)roots.size()));
+        if (a->leaf_chain) { RV_TRY(rv_leaf_chain_launch(lw, la, a->chain_args, (int)roots.size())); a->chain_roots = (int64_t)roots.size(); }
+        else RV_TRY(rv_leaf_launch(lw, la, (int)roots.size()));
     }
     RV_HIP(hipEventRecord(a->ev_leaf[slot], ls));
     a->leaf_pending[slot] = true;
@@ -1565,7 +1585,7 @@ static int builtin_leaf_setup(rv_index *h) {
     a->use_leaf = !a->multi && !h->ws.opt.no_leaf && a->picker == 0;
     a->leaf_flip = 0;
     if (!a->use_leaf) return 0;
-    a->leaf_anchor_cap = (size_t)(h->nT / std::max(a->minl, 1)) + 1024;
+    a->leaf_anchor_cap = (size_t)(h->nT / (a->leaf_chain ? 1 : std::max(a->minl, 1))) + 1024;      // (the chain form's anchors are trimmed matches: any length from 1)
     a->leaf_trace_cap = a->trace_on ? 2 * a->leaf_anchor_cap + 1024 : 0;
     const size_t bytes = 256 + a->leaf_anchor_cap * (4 + 8 + 8) + a->leaf_trace_cap * sizeof(rv_trace) + 64;
     RV_TRY(a->dLeaf.reserve(bytes));

@@ -190,4 +190,9 @@ int rv_ensure_working_text(rv_index *h);
 int rv_working_text_begin(rv_index *h, hipStream_t side);
 
 // rv_align.hip
+// rv_many's own handle only (not part of the ABI, and not rv_set_picker): the leaf launches of the handle's next runs use k_leaf_chain
+// (rv_leaf_chain.hip) with these picker options, flags = one zeroed word per root of the frontier on the device; args == NULL: k_leaf again.
+// rv_leaf_chain_roots: the roots of the last such launch, in frontier order (root r = word r of flags).
+int rv_leaf_chain_route(rv_index *h, const rv_picker_args *args, u32 *flags);
+int64_t rv_leaf_chain_roots(const rv_index *h);
 void rv_align_free(rv_index *h);

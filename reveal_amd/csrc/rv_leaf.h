@@ -29,5 +29,17 @@ struct RvLeafArgs {
 };
 
 int rv_leaf_launch(Workspace &ws, const RvLeafArgs &a, int nroots);
+
+// k_leaf_chain (rv_leaf_chain.hip): the same kernel with the reference's default picker (schemes.graphmumpicker, rv_pick_chain for two samples) as its
+// pick stage, for roots that are whole jobs of rv_many.  What the caller must have checked (rv_many.hip many_chain_admits): trim on, minl > 0, no seeds,
+// a --maxmums that cannot bite, weights within RV_LEAF_CHAIN_WMAX.  a.trace must be 0.
+#define RV_LEAF_CHAIN_WMAX 65536
+struct RvLeafChainArgs {
+    int32_t wscore, wpen;                                    // 0 .. RV_LEAF_CHAIN_WMAX
+    int gcmodel;                                             // 0 sumofpairs, 1 star-avg, 2 star-med
+    u32 *flags;                                              // one word per root, zeroed by the caller: != 0 -- the root was not finished here (1: the reference's own
+                                                             // trim_overlap raises, 2: broken chain, 4 / 8: k_leaf's error bits, 16: rv_many's test hook); its anchors are to be dropped
+};
+int rv_leaf_chain_launch(Workspace &ws, const RvLeafArgs &a, const RvLeafChainArgs &c, int nroots);
 // lower-cases the matched text of the anchors the leaf launches wrote (reveal.c:1230-1234), once, when the run ends
 int rv_leaf_lower_launch(Workspace &ws, uint8_t *T, const int64_t *pos, const u32 *len, u32 na);

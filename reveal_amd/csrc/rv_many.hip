@@ -51,6 +51,13 @@
 // jobs in a call on: many_round_large_multi with K up to 64.  64: a lane of a wavefront owns a sample in the leaf kernel, the sample id has six
 // bits of its `smp` byte, and the level pipeline's multi-sample scan keeps a one-word census up to 64 samples.  Jobs of more than 64 sequences
 // stay ordinary.
+//
+// rv_many_set_picker(m, 1, args): the reference's default picker (schemes.graphmumpicker; rv_pick_chain, rv_chain.hip) instead of the built-in one -- what
+// `reveal refine` aligns its bubbles with.  Every shared class above finishes with built-in-picker kernels, so under kind 1 none of them takes a job,
+// whatever its switch says: the jobs run the ordinary way with rv_set_picker(h, 1, args) on the internal handle.  RV_MANY_CHAIN (off by default): the
+// pair jobs many_chain_admits names share their launches all the same -- layout, index build and frontier of the small pair jobs, and ONE launch of
+// k_leaf_chain (rv_leaf_chain.hip), the leaf kernel with the picker's decision for two samples as its pick stage.  A job the kernel flags (where the
+// reference's own trim_overlap raises) is dropped from the round's results and runs the ordinary way.  The results do not depend on the switch.
 // Size classes (DESIGN.md "Many small alignments" has the measurements): up to `wave_max` ranks (default 512) a wavefront per job,
 // four jobs per workgroup, no workgroup barrier; above, a workgroup of 256 threads per job.  Both hold 22.6 KB of LDS per workgroup:
 // seven workgroups per CU.
@@ -245,6 +252,8 @@ struct rv_many {
     int64_t large = 0, large_max = RV_MANY_LARGE_MAX_DEFAULT, large_min = RV_MANY_LARGE_MIN_DEFAULT;      // RV_MANY_LARGE, RV_MANY_LARGE_MAX, RV_MANY_LARGE_MIN
     int64_t large_multi = 0, large_multi_min = 16;      // RV_MANY_LARGE_MULTI, RV_MANY_LARGE_MULTI_MIN (DESIGN.md "Many small alignments": 4 such jobs lose, 16 win)
     int64_t wide = 0, wide_large_min = RV_MANY_WIDE_LARGE_MIN_DEFAULT;      // RV_MANY_WIDE, RV_MANY_WIDE_LARGE_MIN
+    int picker = 0; rv_picker_args pargs{};     // rv_many_set_picker
+    int64_t chain = 0, chain_flag = 0;          // RV_MANY_CHAIN, RV_MANY_CHAIN_FLAG (test hook)
     std::vector<std::pair<std::string, int64_t>> fwd;      // switches for the internal handles
     // results of the last run
     bool ran = false;
@@ -254,6 +263,7 @@ struct rv_many {
     std::vector<sa_t> keep_sa; std::vector<lcp_t> keep_lcp;
     int64_t info[5] = {0, 0, 0, 0, 0};
     DBuf dJobs, dKJobs, dSA, dLCP, dBWT, dCnt;
+    DBuf dFlag;                                 // rounds of k_leaf_chain: a word per job
     DBuf dTxt, dMJobs, dAn, dAnPos;             // rounds of multi-sequence jobs: their text, jobs, anchors
     RvManyLargeBufs large_bufs;                      // rounds of large pair jobs: the scratch of their index build
     // scratch of a run
@@ -268,6 +278,23 @@ int many_handle(rv_many *m, rv_index **h) {
     if (!*h) return -1;
     for (auto &o : m->fwd) RV_TRY(rv_set_option(*h, o.first.c_str(), o.second));
     return 0;
+}
+
+// The pair jobs k_leaf_chain finishes under picker kind 1 (RV_MANY_CHAIN): the rule, stated once (many.takes_shared_launch(.., picker=, chain=True) mirrors
+// it).  Everything the kernel leaves out has to be impossible for the job: no p-value cut (minl > 0), no untrimmed lists, no seeds for the children
+// (--seedsize above the longer sequence: no match is that long), no --maxmums cut (two MUMs never start at the same position of either sequence, so a
+// sub-index never holds more than min(la, lb)), weights that keep the scores in 32 bits (rv_leaf_chain.hip derives the bound).
+bool many_chain_admits(const rv_many *m, const ManyJob &jb, int minl) {
+    if (m->picker != 1 || !m->chain) return false;
+    if (jb.k != 2 || !jb.clean || jb.ranks > RV_LEAF_N) return false;
+    const rv_picker_args &a = m->pargs;
+    const int64_t la = m->lens[jb.seq0], lb = m->lens[jb.seq0 + 1];
+    if (!a.trim || minl <= 0) return false;
+    if (a.wscore < 0 || a.wpen < 0 || a.wscore > RV_LEAF_CHAIN_WMAX || a.wpen > RV_LEAF_CHAIN_WMAX) return false;
+    if (a.gcmodel < 0 || a.gcmodel > 2) return false;
+    if (a.seedsize > 0 && a.seedsize <= std::max(la, lb)) return false;
+    if (a.maxmums > 0 && a.maxmums < std::min(la, lb)) return false;
+    return true;
 }
 
 // anchors of the handle's last run -> records of `job`, or (job < 0) of the job whose first sequence holds the first member
@@ -323,12 +350,24 @@ int many_build(rv_many *m, hipStream_t q, const ManyDevJob *djobs, size_t J, siz
     return 0;
 }
 
-// one round of the shared launches: the jobs order[lo .. hi) (ascending size); large: jobs above RV_LEAF_N ranks (RV_MANY_LARGE)
-int many_round(rv_many *m, const std::vector<int> &order, size_t lo, size_t hi, int minl, int minn, rv_align_stats *total, bool large) {
+// one round of the shared launches: the jobs order[lo .. hi) (ascending size); large: jobs above RV_LEAF_N ranks (RV_MANY_LARGE); redo != NULL: the
+// round of picker kind 1 (RV_MANY_CHAIN) -- its leaf launch is k_leaf_chain, and the jobs that kernel flags come back in *redo for the ordinary path
+int many_round(rv_many *m, const std::vector<int> &order, size_t lo, size_t hi, int minl, int minn, rv_align_stats *total, bool large, std::vector<int> *redo = nullptr) {
     RV_TRY(many_handle(m, &m->hs));
     rv_index *h = m->hs;
     const size_t J = hi - lo;
     RV_TRY(rv_reset(h));
+    if (redo) {
+        RV_TRY(m->dFlag.reserve(J * sizeof(u32)));
+        RV_HIP(hipMemsetAsync(m->dFlag.p, 0, J * sizeof(u32), h->ws.stream));
+        if (m->chain_flag > 0) {      // test hook: every chain_flag-th job of the round counts as flagged by the kernel, whatever the kernel does with it
+            std::vector<u32> pre(J, 0u);
+            for (size_t s = 0; s < J; s += (size_t)m->chain_flag) pre[s] = 16u;
+            RV_HIP(hipMemcpyAsync(m->dFlag.p, pre.data(), J * sizeof(u32), hipMemcpyHostToDevice, h->ws.stream));
+            RV_HIP(hipStreamSynchronize(h->ws.stream));
+        }
+    }
+    RV_TRY(rv_leaf_chain_route(h, redo ? &m->pargs : nullptr, redo ? m->dFlag.as<u32>() : nullptr));
     // text: every first sequence, then every second one
     std::vector<int> ord(order.begin() + (ptrdiff_t)lo, order.begin() + (ptrdiff_t)hi);
     std::vector<int64_t> abeg(J), bbeg(J), la(J), lb(J);
@@ -413,19 +452,31 @@ int many_round(rv_many *m, const std::vector<int> &order, size_t lo, size_t hi, 
     const size_t rec0 = m->recs.size();
     RV_TRY(many_collect(m, h, -1, ord, abeg, bbeg));
     m->info[4] += st.levels + (m->recs.size() > rec0 ? 2 : 0);      // leaf launches (large: levels), and the two of the lower-casing when there are anchors
+    std::vector<u32> flag;
+    size_t nflag = 0;
+    if (redo) {
+        // the jobs the kernel did not finish: their anchors are dropped, their text is not taken from the round
+        if (rv_leaf_chain_roots(h) != (int64_t)J) { rv_set_error("rv_many_run: the chain leaf launch took %lld of the round's %lld jobs", (long long)rv_leaf_chain_roots(h), (long long)J); return -1; }
+        flag.resize(J);
+        RV_HIP(hipMemcpy(flag.data(), m->dFlag.p, J * sizeof(u32), hipMemcpyDeviceToHost));
+        std::vector<char> out((size_t)m->jobs.size(), 0);
+        for (size_t s = 0; s < J; s++) if (flag[s]) { out[(size_t)ord[s]] = 1; redo->push_back(ord[s]); nflag++; }
+        if (nflag) m->recs.erase(std::remove_if(m->recs.begin() + (ptrdiff_t)rec0, m->recs.end(), [&](const ManyRec &r) { return out[(size_t)r.job] != 0; }), m->recs.end());
+    }
     // final text of every job: a$b$
     std::vector<char> txt((size_t)n);
     RV_TRY(rv_ensure_working_text(h));
     RV_HIP(hipStreamSynchronize(h->ws.stream));
     RV_HIP(hipMemcpy(txt.data(), h->dT.p, (size_t)n, hipMemcpyDeviceToHost));
     for (size_t s = 0; s < J; s++) {
+        if (nflag && flag[s]) continue;
         ManyJob &jb = m->jobs[(size_t)ord[s]];
         jb.text_off = (int64_t)m->out_text.size();
         jb.shared = true;
         m->out_text.insert(m->out_text.end(), txt.begin() + (ptrdiff_t)abeg[s], txt.begin() + (ptrdiff_t)(abeg[s] + la[s] + 1));
         m->out_text.insert(m->out_text.end(), txt.begin() + (ptrdiff_t)bbeg[s], txt.begin() + (ptrdiff_t)(bbeg[s] + lb[s] + 1));
     }
-    m->info[1] += (int64_t)J; m->info[3]++;
+    m->info[1] += (int64_t)(J - nflag); m->info[3]++;
     return 0;
 }
 
@@ -730,6 +781,7 @@ int many_ordinary(rv_many *m, int job, int minl, int minn, rv_align_stats *total
         RV_TRY(rv_add_sequence(h, m->in.data() + m->starts[jb.seq0 + (size_t)s], m->lens[jb.seq0 + (size_t)s], nullptr, nullptr));
     }
     RV_TRY(rv_construct(h, 0, nullptr, nullptr, 0));
+    RV_TRY(rv_set_picker(h, m->picker, m->picker ? &m->pargs : nullptr));
     rv_align_stats st;
     memset(&st, 0, sizeof st);
     RV_TRY(rv_align_builtin(h, minl, minn, &st));
@@ -772,10 +824,12 @@ int many_run(rv_many *m, int minl, int minn, rv_align_stats *total) {
     for (const ManyJob &jb : m->jobs) nwlarge += is_wide_large(jb) ? 1 : 0;
     const bool take_wide_large = nwlarge > 0 && nwlarge >= m->wide_large_min;
     std::vector<int> worder, wlorder;
+    const bool chain = m->picker == 1;      // the shared classes finish with built-in-picker kernels: under kind 1 only many_chain_admits' jobs share launches
     for (int j = 0; j < nj; j++) {
         ManyJob &jb = m->jobs[(size_t)j];
         jb.arr_off = -1;
-        if (jb.k == 2 && jb.ranks <= RV_LEAF_N && jb.clean) order.push_back(j);
+        if (chain) { if (many_chain_admits(m, jb, minl)) order.push_back(j); else rest.push_back(j); }
+        else if (jb.k == 2 && jb.ranks <= RV_LEAF_N && jb.clean) order.push_back(j);
         else if (take_large && is_large(jb)) lorder.push_back(j);
         else if (take_large_multi && is_large_multi(jb)) lmorder.push_back(j);
         else if (m->multi && jb.k >= 3 && jb.k <= RV_MANY_KMAX && jb.ranks <= RV_LEAF_N && jb.clean) morder.push_back(j);
@@ -793,9 +847,10 @@ int many_run(rv_many *m, int minl, int minn, rv_align_stats *total) {
     for (size_t lo = 0; lo < order.size();) {
         size_t hi = lo; int64_t sum = 0;
         while (hi < order.size() && (hi == lo || sum + m->jobs[(size_t)order[hi]].ranks <= lim)) sum += m->jobs[(size_t)order[hi++]].ranks;
-        RV_TRY(many_round(m, order, lo, hi, minl, minn, total, false));
+        RV_TRY(many_round(m, order, lo, hi, minl, minn, total, false, chain ? &rest : nullptr));
         lo = hi;
     }
+    if (chain) std::sort(rest.begin(), rest.end());
     for (size_t lo = 0; lo < lorder.size();) {      // the pair jobs above RV_LEAF_N ranks: rounds of their own
         size_t hi = lo; int64_t sum = 0;
         while (hi < lorder.size() && (hi == lo || sum + m->jobs[(size_t)lorder[hi]].ranks <= lim)) sum += m->jobs[(size_t)lorder[hi++]].ranks;
@@ -869,7 +924,7 @@ void rv_many_free(rv_many *m) {
     if (m->hs) rv_free(m->hs);
     if (m->ho) rv_free(m->ho);
     m->dJobs.release(); m->dKJobs.release(); m->dSA.release(); m->dLCP.release(); m->dBWT.release(); m->dCnt.release();
-    m->dTxt.release(); m->dMJobs.release(); m->dAn.release(); m->dAnPos.release();
+    m->dTxt.release(); m->dMJobs.release(); m->dAn.release(); m->dAnPos.release(); m->dFlag.release();
     m->large_bufs.release();
     delete m;
 }
@@ -883,6 +938,8 @@ int rv_many_option(rv_many *m, const char *name, int64_t value) {
     if (strcmp(name, "RV_MANY_LARGE_MULTI") == 0) { m->large_multi = value != 0; return 0; }
     if (strcmp(name, "RV_MANY_LARGE_MULTI_MIN") == 0) { if (value < 0) { rv_set_error("RV_MANY_LARGE_MULTI_MIN: negative"); return -1; } m->large_multi_min = value; return 0; }
     if (strcmp(name, "RV_MANY_WIDE") == 0) { m->wide = value != 0; return 0; }
+    if (strcmp(name, "RV_MANY_CHAIN") == 0) { m->chain = value != 0; return 0; }
+    if (strcmp(name, "RV_MANY_CHAIN_FLAG") == 0) { if (value < 0) { rv_set_error("RV_MANY_CHAIN_FLAG: negative"); return -1; } m->chain_flag = value; return 0; }
     if (strcmp(name, "RV_MANY_WIDE_LARGE_MIN") == 0) { if (value < 0) { rv_set_error("RV_MANY_WIDE_LARGE_MIN: negative"); return -1; } m->wide_large_min = value; return 0; }
     if (strcmp(name, "RV_MANY_LARGE_MAX") == 0) { if (value < 0) { rv_set_error("RV_MANY_LARGE_MAX: negative"); return -1; } m->large_max = value; return 0; }
     if (strcmp(name, "RV_MANY_LARGE_MIN") == 0) { if (value < 0) { rv_set_error("RV_MANY_LARGE_MIN: negative"); return -1; } m->large_min = value; return 0; }
@@ -895,6 +952,16 @@ int rv_many_option(rv_many *m, const char *name, int64_t value) {
         if (m->hs) RV_TRY(rv_set_option(m->hs, name, value));
         if (m->ho) RV_TRY(rv_set_option(m->ho, name, value));
         return 0;, -1)
+}
+
+int rv_many_set_picker(rv_many *m, int kind, const rv_picker_args *args) {
+    if (!m) { rv_set_error("rv_many_set_picker: null handle"); return -1; }
+    if (kind != 0 && kind != 1) { rv_set_error("rv_many_set_picker: picker kind 0 (built-in) or 1 (the reference's default picker), not %d", kind); return -1; }
+    if (kind == 1 && !args) { rv_set_error("rv_many_set_picker: kind 1 needs its options"); return -1; }
+    if (kind == 1 && (args->gcmodel < 0 || args->gcmodel > 2)) { rv_set_error("rv_many_set_picker: gap cost model 0 (sumofpairs), 1 (star-avg) or 2 (star-med)"); return -1; }
+    m->picker = kind;
+    if (kind == 1) m->pargs = *args;
+    return 0;
 }
 
 int64_t rv_many_add(rv_many *m, const char *const *seqs, const int64_t *lens, int k) {

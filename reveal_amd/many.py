@@ -3,7 +3,19 @@
 `reveal refine --method reveal_rem` calls `rem.align` once per bubble (reveal/refine.py:220-229).  `align_many` takes the
 sequences of many bubbles at once: the pair jobs of at most 2048 ranks share their kernel launches (one index build per size
 class with the text in LDS, one launch of the leaf kernel for every job's recursion), every other job runs the ordinary way
-inside the same call.  The built-in picker only (as `index.align_builtin`); no CPU fallback.
+inside the same call.  The built-in picker (as `index.align_builtin`) unless `picker=` is given; no CPU fallback.
+
+`align_many(.., picker=schemes.PickerArgs(..))` (`Batch.set_picker`) aligns every job with the reference's default picker instead
+(schemes.graphmumpicker: trim the overlaps, chain, split on the largest match of the chain) -- what `reveal refine` gets from
+`rem.align` for a bubble, and what `index.set_picker(args)` + `align_builtin` give a stand-alone index of the job.  The shared
+classes below all finish with built-in-picker kernels, so with a picker set none of them takes a job, whatever its switch says:
+the jobs run the ordinary way with the picker in host C++ (`info["ordinary"]`).  With the switch RV_MANY_CHAIN on
+(`align_many(.., chain=True)`, `Batch.option("RV_MANY_CHAIN", 1)` or the environment variable; off by default, and it means
+something with a picker only) the pair jobs of at most 2048 ranks share their launches all the same, finished by the leaf kernel
+with the picker's decision for two samples as its pick stage (csrc/rv_leaf_chain.hip), when the options leave the picker nothing a
+workgroup cannot do: trim on, minlength > 0, weights 0 .. 65536, a seedsize no match can reach and a maxmums that cannot bite
+(`takes_shared_launch(.., picker=args, chain=True)`).  The results do not depend on the switch.  `PickerArgs.maxsize` and
+`.maxdepth` are not taken (the native picker has neither).
 
 Jobs of three and more sequences -- a bubble of a graph of N genomes carries up to N -- run the ordinary way unless the switch
 RV_MANY_MULTI is on (`align_many(.., multi=True)`, `Batch.option("RV_MANY_MULTI", 1)` or the environment variable; off by default).
@@ -49,6 +61,7 @@ LEAF_RANKS = 2048          # RV_LEAF_N: a job of sum of lengths + k ranks up to 
 MULTI_KMAX = 16            # RV_MANY_KMAX: sequences of a job the shared launches take with RV_MANY_MULTI
 WIDE_KMAX = 64             # RV_MANY_WIDE_KMAX: sequences of a job the shared launches take with RV_MANY_WIDE (17 .. 64)
 WIDE_LARGE_MIN = 8         # default of RV_MANY_WIDE_LARGE_MIN: fewer jobs of 17 .. 64 sequences above 2048 ranks in a call stay ordinary
+CHAIN_WMAX = 65536         # RV_LEAF_CHAIN_WMAX: weights up to this keep the chain's scores in 32 bits on the device
 LARGE_MAX = 1 << 17        # default of RV_MANY_LARGE_MAX: ranks of the largest pair job the shared launches take with RV_MANY_LARGE
 
 
@@ -79,15 +92,36 @@ def job_sequences(job, toupper=True):
     return seqs
 
 
-def takes_shared_launch(seqs, multi=False, large=False, large_max=LARGE_MAX, large_multi=False, wide=False):
+def picker_struct(args):
+    """a schemes.PickerArgs -> the C ABI's rv_picker_args; raises `error` for what the native picker does not take (maxsize, maxdepth, an unknown
+    gap cost model) -- before anything asks the library for a device"""
+    from . import schemes
+    if args.maxsize is not None or args.maxdepth is not None:
+        raise error("the native picker does not take --maxbubblesize / maxdepth")
+    if args.gcmodel not in schemes.GCMODELS:
+        raise error("unknown gap cost model %r (%s)" % (args.gcmodel, ", ".join(sorted(schemes.GCMODELS))))
+    return schemes._RvPickerArgs(int(args.wscore), int(args.wpen), int(args.maxmums or 0), int(args.seedsize or 0), schemes.GCMODELS[args.gcmodel],
+                                 1 if args.trim else 0, float(args.pcutoff))
+
+
+def takes_shared_launch(seqs, multi=False, large=False, large_max=LARGE_MAX, large_multi=False, wide=False, picker=None, chain=False, minlength=20):
     """whether the library builds and finishes this job in the shared launches; multi: with RV_MANY_MULTI on; large: with RV_MANY_LARGE
     on and RV_MANY_LARGE_MAX = large_max (in a call with at least RV_MANY_LARGE_MIN such jobs, and with rounds that hold the job);
     large_multi: with RV_MANY_LARGE_MULTI on (in a call with at least RV_MANY_LARGE_MULTI_MIN such jobs, and with rounds that hold the job);
-    wide: with RV_MANY_WIDE on -- jobs of 17 .. 64 sequences, above 2048 ranks in a call with at least RV_MANY_WIDE_LARGE_MIN such jobs"""
+    wide: with RV_MANY_WIDE on -- jobs of 17 .. 64 sequences, above 2048 ranks in a call with at least RV_MANY_WIDE_LARGE_MIN such jobs;
+    picker: a schemes.PickerArgs -- with the reference's default picker set (the other switches then mean nothing); chain: with RV_MANY_CHAIN on;
+    minlength: of the run (csrc/rv_many.hip many_chain_admits)"""
     k = len(seqs)
     ranks = sum(len(s) for s in seqs) + k
     if any(b"\0" in s for s in seqs):
         return False
+    if picker is not None:
+        if not chain or k != 2 or ranks > LEAF_RANKS:
+            return False
+        A = picker_struct(picker)
+        la, lb = len(seqs[0]), len(seqs[1])
+        return bool(A.trim and int(minlength) > 0 and 0 <= A.wscore <= CHAIN_WMAX and 0 <= A.wpen <= CHAIN_WMAX
+                    and (A.seedsize <= 0 or A.seedsize > max(la, lb)) and (A.maxmums <= 0 or A.maxmums >= min(la, lb)))
     if MULTI_KMAX < k <= WIDE_KMAX:
         return bool(wide) and (ranks <= LEAF_RANKS or ranks <= large_max)
     if not (2 <= k <= MULTI_KMAX):
@@ -170,7 +204,7 @@ class Batch:
                     iv = 1
                 self.option(name, iv)
         for name in ("RV_MANY_KEEP", "RV_MANY_ROUND", "RV_MANY_WAVE_MAX", "RV_MANY_MULTI", "RV_MANY_LARGE", "RV_MANY_LARGE_MAX", "RV_MANY_LARGE_MIN",
-                     "RV_MANY_LARGE_MULTI", "RV_MANY_LARGE_MULTI_MIN", "RV_MANY_WIDE", "RV_MANY_WIDE_LARGE_MIN"):
+                     "RV_MANY_LARGE_MULTI", "RV_MANY_LARGE_MULTI_MIN", "RV_MANY_WIDE", "RV_MANY_WIDE_LARGE_MIN", "RV_MANY_CHAIN"):
             v = os.environ.get(name)
             if v is not None and v.strip():
                 self.option(name, int(v))
@@ -185,6 +219,17 @@ class Batch:
 
     def option(self, name, value=1):
         if self._dll.rv_many_option(self._m, name.encode(), int(value)) != 0:
+            self._fail()
+
+    def set_picker(self, args=None):
+        """rv_many_set_picker: None = the built-in picker; a schemes.PickerArgs = the reference's default picker (schemes.graphmumpicker) with these
+        options, for this and later runs (args.maxsize / maxdepth are not supported)"""
+        if args is None:
+            r = self._dll.rv_many_set_picker(self._m, 0, None)
+        else:
+            A = picker_struct(args)
+            r = self._dll.rv_many_set_picker(self._m, 1, ctypes.byref(A))
+        if r != 0:
             self._fail()
 
     def add(self, seqs):
@@ -241,7 +286,7 @@ class Batch:
         return sa, lcp
 
 
-def align_many(jobs, minlength=20, minn=2, sa64=False, toupper=True, batch=None, multi=None, large=None, large_multi=None, wide=None):
+def align_many(jobs, minlength=20, minn=2, sa64=False, toupper=True, batch=None, multi=None, large=None, large_multi=None, wide=None, picker=None, chain=None):
     """jobs: a list of jobs, each a list of (name, seq) or of plain sequences (two or more, none empty; every sequence is a sample
     of its own, like the inputs of `reveal rem`).  -> (results, info): results[j] = dict(anchors=[(l, (pos, ..)), ..], T=final text
     `s0$s1$..` lower-cased where aligned), positions in the coordinates of the job's own text -- what index.align_builtin gives a
@@ -250,13 +295,22 @@ def align_many(jobs, minlength=20, minn=2, sa64=False, toupper=True, batch=None,
     the batch; None leaves it as the batch has it (off, unless the environment variable is set).  `large`: the same for RV_MANY_LARGE
     (pair jobs of 2049 .. RV_MANY_LARGE_MAX ranks through the shared launches), `large_multi`: the same for RV_MANY_LARGE_MULTI (jobs of
     3 .. 16 sequences of 2049 .. RV_MANY_LARGE_MAX ranks through the shared launches), `wide`: the same for RV_MANY_WIDE (jobs of 17 .. 64
-    sequences up to RV_MANY_LARGE_MAX ranks through the shared launches; more than 64 sequences always run the ordinary way)."""
+    sequences up to RV_MANY_LARGE_MAX ranks through the shared launches; more than 64 sequences always run the ordinary way).
+    `picker`: a schemes.PickerArgs -- the reference's default picker with these options for this run: a job's result is then what
+    index.set_picker(args) + align_builtin give a stand-alone index of it, the anchors `rem.align` chooses for a bubble; None: the built-in
+    picker, as ever (a batch that is reused goes back to it).  `chain`: True / False sets RV_MANY_CHAIN (with a picker: the pair jobs of at most
+    2048 ranks through the shared launches, see the module docstring) for this and later runs of the batch; None leaves it."""
     if isinstance(jobs, (str, bytes, bytearray)) or not hasattr(jobs, "__iter__"):
         raise error("jobs is a list of jobs")
     if int(minlength) < 0 or int(minn) < 2:
         raise error("minlength >= 0 and minn >= 2")
     prepared = [job_sequences(j, toupper) for j in jobs]      # (argument errors before the library is asked for a device)
+    if picker is not None:
+        picker_struct(picker)
     b = batch if batch is not None else Batch(sa64)
+    b.set_picker(picker)
+    if chain is not None:
+        b.option("RV_MANY_CHAIN", 1 if chain else 0)
     if multi is not None:
         b.option("RV_MANY_MULTI", 1 if multi else 0)
     if large is not None:

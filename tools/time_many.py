@@ -3,7 +3,7 @@
 
     python tools/time_many.py [--jobs 10000] [--lmin 50] [--lmax 1000] [--reps 5] [--minlength 20] [--wave-max N] [--only loop|many] [--check]
                               [--seqs K] [--multi 0|1|ab] [--large 0|1|ab] [--large-multi 0|1|ab] [--large-max R] [--large-min J]
-                              [--wide 0|1|ab] [--wide-large-min J] [--no-cut] [--sites]
+                              [--wide 0|1|ab] [--wide-large-min J] [--no-cut] [--sites] [--picker [--rem-jobs N]]
 
 Workload: J jobs of 2 x L bases, L uniform in lmin .. lmax, 1 % substitutions.  The two sides run alternately, `reps` times each:
   loop   rv_reset, rv_add_sample / rv_add_sequence x 2, rv_construct, rv_align_builtin, rv_fetch_anchors, the text -- per job, straight at
@@ -21,7 +21,12 @@ switch off and on, run alternately in one process -- medians, both spreads, the 
 --no-cut it is not (choose --lmin / --lmax so that K x (L + 1) lies above 2048: the sample-major rounds of the wide jobs).  --wide-large-min
 sets RV_MANY_WIDE_LARGE_MIN of every batch.  --sites: the K members of a job differ at one to three variant sites, each substituted in a
 random subset of the members (the bubble of K haplotypes), not by 1 % substitutions per member -- among 32 or 64 members those leave almost
-no window common to all, and a call anchors next to nothing."""
+no window common to all, and a call anchors next to nothing.
+--picker: the reference's default picker (rem.align's defaults: wpen 1, wscore 1, sumofpairs, trim, seedsize 10000, maxmums 10000) instead of the
+built-in one, no loop through a handle; three batches run alternately in one process -- RV_MANY_CHAIN on (the leaf kernel with the picker's decision
+as its pick stage), RV_MANY_CHAIN off (every job the ordinary way, the picker in host C++), and the built-in picker on the same jobs -- then
+`rem.align` per job over the first --rem-jobs jobs (default 1000), once: the route to these anchors without align_many.  --check compares the two
+picker sides job by job, and the jobs of the rem.align loop with it."""
 import argparse
 import ctypes
 import json
@@ -169,6 +174,61 @@ def main_ab(a, jobs, bases, switch="RV_MANY_MULTI"):
     return 1 if out.get("check_bad_jobs") else 0
 
 
+def main_picker(a, jobs, bases):
+    """the reference's default picker: RV_MANY_CHAIN on / off, the built-in picker beside them, rem.align per job"""
+    from reveal_amd import many, rem, schemes
+    args = schemes.PickerArgs(maxmums=10000)      # (rem.align's defaults)
+    sides = {}
+    for name, pk, chain in (("chain", args, 1), ("ordinary", args, 0), ("builtin", None, 0)):
+        b = many.Batch(False)
+        b.set_picker(pk)
+        b.option("RV_MANY_CHAIN", chain)
+        if a.wave_max is not None:
+            b.option("RV_MANY_WAVE_MAX", a.wave_max)
+        run_many_c(b, jobs[:64], a.minlength)
+        sides[name] = dict(batch=b, t=[], res=None)
+    for rep in range(a.reps):
+        for name, s in sides.items():
+            t = time.perf_counter(); s["res"] = run_many_c(s["batch"], jobs, a.minlength); s["t"].append(time.perf_counter() - t)
+    out = dict(jobs=a.jobs, lmin=a.lmin, lmax=a.lmax, bases=bases, minlength=a.minlength, reps=a.reps, picker="graphmumpicker")
+    for name, s in sides.items():
+        t = s["t"]
+        out[name + "_s"] = t; out[name + "_median_s"] = statistics.median(t); out[name + "_spread_s"] = max(t) - min(t); out[name + "_info"] = s["batch"].info()
+        print("%-8s: runs %s s; median %.4f s, spread (max - min) %.4f s, %.0f jobs/s; info %r"
+              % (name, " ".join("%.4f" % x for x in t), out[name + "_median_s"], out[name + "_spread_s"], a.jobs / out[name + "_median_s"], out[name + "_info"]))
+    nrem = min(a.rem_jobs, len(jobs))
+    rem_res = []
+    t = time.perf_counter()
+    for job in jobs[:nrem]:
+        rem_res.append(rem.align([("a", job[0].decode()), ("b", job[1].decode())], minlength=a.minlength))
+    out["rem_jobs"] = nrem; out["rem_s"] = time.perf_counter() - t
+    out["rem_per_job_s"] = out["rem_s"] / max(nrem, 1)
+    print("rem.align per job: %d jobs in %.2f s, %.2f ms a job, %.0f jobs/s" % (nrem, out["rem_s"], 1e3 * out["rem_per_job_s"], nrem / out["rem_s"]))
+    out["chain_vs_rem"] = out["rem_per_job_s"] / (out["chain_median_s"] / a.jobs)
+    out["ordinary_vs_chain"] = out["ordinary_median_s"] / out["chain_median_s"]
+    out["chain_vs_builtin"] = out["chain_median_s"] / out["builtin_median_s"]
+    print("ratio : rem.align per job / chain = %.0f x; ordinary / chain = %.1f x; chain / built-in picker = %.2f x (a job: %.2f against %.2f us)"
+          % (out["chain_vs_rem"], out["ordinary_vs_chain"], out["chain_vs_builtin"], 1e6 * out["chain_median_s"] / a.jobs, 1e6 * out["builtin_median_s"] / a.jobs))
+    if a.check:
+        x, y = as_lists(*sides["chain"]["res"]), as_lists(*sides["ordinary"]["res"])
+        out["check_bad_jobs"] = sum(1 for p, q in zip(x, y) if p != q)
+        out["anchors"] = sum(len(p) for p in x)
+        out["differ_from_builtin"] = sum(1 for p, q in zip(x, as_lists(*sides["builtin"]["res"])) if p != q)
+        # (the final text of rem.align's index says which positions its anchors cover)
+        bad = 0
+        for j, (G, idx) in enumerate(rem_res):
+            T = bytearray(jobs[j][0] + b"$" + jobs[j][1] + b"$")
+            for l, pos in x[j]:
+                for p in pos:
+                    T[p:p + l] = T[p:p + l].lower()
+            bad += bytes(T) != idx.T.encode("latin-1")
+        out["check_bad_rem_jobs"] = bad
+        print("check : %d of %d jobs differ between chain and ordinary (%d anchors; %d jobs differ from the built-in picker); %d of %d differ from rem.align's final text"
+              % (out["check_bad_jobs"], a.jobs, out["anchors"], out["differ_from_builtin"], bad, nrem))
+    print(json.dumps(out))
+    return 1 if out.get("check_bad_jobs") or out.get("check_bad_rem_jobs") else 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--jobs", type=int, default=10000)
@@ -187,9 +247,13 @@ def main():
     ap.add_argument("--large-min", type=int, default=None, help="RV_MANY_LARGE_MIN")
     ap.add_argument("--wide", choices=("0", "1", "ab"), default=None, help="RV_MANY_WIDE of the many side; ab: off against on, no loop")
     ap.add_argument("--wide-large-min", type=int, default=None, help="RV_MANY_WIDE_LARGE_MIN")
-    ap.add_argument("--sites", action="store_true", help="jobs of --seqs K > 2 sequences: variant sites in subsets of the members, not 1 % per member")
+    ap.add_argument("--sites", action="store_true", help="jobs of --seqs K > 2 sequences: variant sites in subsets of the members, not 1 %% per member")
     ap.add_argument("--no-cut", action="store_true", help="leave lmax as given when jobs of --seqs K sequences pass 2048 ranks")
+    ap.add_argument("--picker", action="store_true", help="the reference's default picker: RV_MANY_CHAIN on / off, the built-in picker, rem.align per job; no loop")
+    ap.add_argument("--rem-jobs", type=int, default=1000, help="--picker: jobs of the rem.align loop")
     a = ap.parse_args()
+    if a.picker and a.seqs != 2:
+        ap.error("--picker times pair jobs")
     if [a.multi, a.large, a.large_multi, a.wide].count("ab") > 1:
         ap.error("one switch at a time: --multi ab, --large ab, --large-multi ab or --wide ab")
     if a.wide is not None and not 17 <= a.seqs <= 64:
@@ -198,6 +262,8 @@ def main():
         ap.error("--large-multi wants jobs of three and more sequences: --seqs K")
     jobs = workload(a.jobs, a.lmin, a.lmax, seqs=a.seqs, cut=a.large_multi is None and not a.no_cut, sites=a.sites)
     bases = sum(len(s) for j in jobs for s in j)
+    if a.picker:
+        return main_picker(a, jobs, bases)
     if a.multi == "ab":
         return main_ab(a, jobs, bases)
     if a.large == "ab":
