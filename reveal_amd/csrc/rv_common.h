@@ -109,7 +109,8 @@ void rv_set_error(const char *fmt, ...);
     X(cascade_prio, "RV_CASCADE_PRIO", 0) \
     X(cas_witness_pass, "RV_CAS_WITNESS_PASS", 0) \
     X(cap_limit, "RV_CAP_LIMIT", 0) \
-    X(cap_sites, "RV_CAP_SITES", -1)
+    X(cap_sites, "RV_CAP_SITES", -1) \
+    X(many_chain_multi, "RV_MANY_CHAIN_MULTI", 0)
 struct RvOptions {
 #define RV_X_(f, name, def) int64_t f = def;
     RV_OPTION_LIST(RV_X_)

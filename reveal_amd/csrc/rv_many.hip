@@ -58,6 +58,10 @@
 // pair jobs many_chain_admits names share their launches all the same -- layout, index build and frontier of the small pair jobs, and ONE launch of
 // k_leaf_chain (rv_leaf_chain.hip), the leaf kernel with the picker's decision for two samples as its pick stage.  A job the kernel flags (where the
 // reference's own trim_overlap raises) is dropped from the round's results and runs the ordinary way.  The results do not depend on the switch.
+// RV_MANY_CHAIN_MULTI (off by default, independent of RV_MANY_CHAIN and RV_MANY_MULTI; it means something under kind 1 only): the jobs of 3 .. RV_MANY_KMAX
+// sequences many_chain_multi_admits names share their launches too, in rounds of their own -- layout and index build of RV_MANY_MULTI (many_round_multi) and
+// ONE launch of k_leaf_multi_chain (rv_leaf_multi_chain.hip), the multi-sample leaf kernel with the whole picker as its pick stage: matches on sample
+// subsets, `segment`, trim and chain over k paths, a three-way split with a `rest` child.  Flags as for k_leaf_chain, per job.
 // Size classes (DESIGN.md "Many small alignments" has the measurements): up to `wave_max` ranks (default 512) a wavefront per job,
 // four jobs per workgroup, no workgroup barrier; above, a workgroup of 256 threads per job.  Both hold 22.6 KB of LDS per workgroup:
 // seven workgroups per CU.
@@ -254,6 +258,7 @@ struct rv_many {
     int64_t wide = 0, wide_large_min = RV_MANY_WIDE_LARGE_MIN_DEFAULT;      // RV_MANY_WIDE, RV_MANY_WIDE_LARGE_MIN
     int picker = 0; rv_picker_args pargs{};     // rv_many_set_picker
     int64_t chain = 0, chain_flag = 0;          // RV_MANY_CHAIN, RV_MANY_CHAIN_FLAG (test hook)
+    int64_t chain_multi = 0;                    // RV_MANY_CHAIN_MULTI
     std::vector<std::pair<std::string, int64_t>> fwd;      // switches for the internal handles
     // results of the last run
     bool ran = false;
@@ -294,6 +299,28 @@ bool many_chain_admits(const rv_many *m, const ManyJob &jb, int minl) {
     if (a.gcmodel < 0 || a.gcmodel > 2) return false;
     if (a.seedsize > 0 && a.seedsize <= std::max(la, lb)) return false;
     if (a.maxmums > 0 && a.maxmums < std::min(la, lb)) return false;
+    return true;
+}
+
+// The jobs of 3 .. RV_MANY_KMAX sequences k_leaf_multi_chain finishes under picker kind 1 (RV_MANY_CHAIN_MULTI): the rule, stated once
+// (many.takes_shared_launch(.., picker=, chain_multi=True) mirrors it).  As above, everything the kernel leaves out has to be impossible for the job:
+//   trim on, minl > 0, gap model 0 .. 2     no p-value cut, no untrimmed lists
+//   weights 0 .. RV_LEAF_MCHAIN_WMAX        scores of up to sixteen paths in 32 bits (rv_leaf_multi_chain.hip derives the bound)
+//   seedsize <= 0 or above the longest sequence   no match is that long: no seeds for the children
+//   maxmums <= 0 or >= the job's ranks      the cut is made on the matches of ONE sub-index, every one of them an inner node of the LCP-interval tree over the
+//                                           sub-index' ranks: a tree over len leaves has fewer than len inner nodes, and len <= the job's ranks <= 2048, so
+//                                           rem.align's default of 10 000 passes whatever the job
+bool many_chain_multi_admits(const rv_many *m, const ManyJob &jb, int minl) {
+    if (m->picker != 1 || !m->chain_multi) return false;
+    if (jb.k < 3 || jb.k > RV_MANY_KMAX || !jb.clean || jb.ranks > RV_LEAF_N) return false;
+    const rv_picker_args &a = m->pargs;
+    int64_t longest = 0;
+    for (int q = 0; q < jb.k; q++) longest = std::max(longest, m->lens[jb.seq0 + (size_t)q]);
+    if (!a.trim || minl <= 0) return false;
+    if (a.wscore < 0 || a.wpen < 0 || a.wscore > RV_LEAF_MCHAIN_WMAX || a.wpen > RV_LEAF_MCHAIN_WMAX) return false;
+    if (a.gcmodel < 0 || a.gcmodel > 2) return false;
+    if (a.seedsize > 0 && a.seedsize <= longest) return false;
+    if (a.maxmums > 0 && a.maxmums < jb.ranks) return false;
     return true;
 }
 
@@ -486,8 +513,9 @@ int many_round(rv_many *m, const std::vector<int> &order, size_t lo, size_t hi, 
 // nothing here); k_leaf_multi then finishes every job in one workgroup and lower-cases its text.  No handle is involved beyond
 // the stream and the read-back buffer of the shared one: the launches of a round do not depend on the number of jobs.
 // kmax: the sample bound of the round's class and the form of k_leaf_multi that takes it -- RV_MANY_KMAX, or RV_MANY_WIDE_KMAX for the
-// rounds of jobs of 17 .. 64 sequences (RV_MANY_WIDE)
-int many_round_multi(rv_many *m, const std::vector<int> &order, size_t lo, size_t hi, int minl, int minn, rv_align_stats *total, int kmax) {
+// rounds of jobs of 17 .. 64 sequences (RV_MANY_WIDE).  redo != NULL: the round of picker kind 1 (RV_MANY_CHAIN_MULTI, kmax = RV_MANY_KMAX) -- its leaf
+// launch is k_leaf_multi_chain, and the jobs that kernel flags come back in *redo for the ordinary path: their anchors are dropped, their text is not taken
+int many_round_multi(rv_many *m, const std::vector<int> &order, size_t lo, size_t hi, int minl, int minn, rv_align_stats *total, int kmax, std::vector<int> *redo = nullptr) {
     RV_TRY(many_handle(m, &m->hs));
     rv_index *h = m->hs;
     const size_t J = hi - lo;
@@ -542,6 +570,18 @@ int many_round_multi(rv_many *m, const std::vector<int> &order, size_t lo, size_
     a.count = (unsigned long long *)(d_max + 4); a.anchor_cap = acap; a.member_cap = mcap;
     a.anchors = m->dAn.as<RvLeafMultiAnchor>(); a.an_pos = m->dAnPos.as<uint16_t>();
     a.stats = (unsigned long long *)(d_max + 6); a.err = d_max + 2;
+    if (redo) {
+        if (kmax != RV_MANY_KMAX) { rv_set_error("rv_many_run: the chain form of the leaf kernel takes jobs of at most %d sequences", RV_MANY_KMAX); return -1; }
+        for (auto &o : m->fwd) if (o.first == "RV_LEAF_ACAP" && o.second >= 0) a.stage_cap = (u32)std::min<int64_t>(a.stage_cap, o.second);      // (test hook, as for k_leaf_chain)
+        std::vector<u32> pre(J, 0u);
+        if (m->chain_flag > 0) for (size_t s = 0; s < J; s += (size_t)m->chain_flag) pre[s] = 16u;      // test hook: every chain_flag-th job of the round counts as flagged
+        RV_TRY(m->dFlag.reserve(J * sizeof(u32)));
+        RV_HIP(hipMemcpyAsync(m->dFlag.p, pre.data(), J * sizeof(u32), hipMemcpyHostToDevice, q));
+        RV_HIP(hipStreamSynchronize(q));
+        RvLeafMultiChainArgs c;
+        c.wscore = (int32_t)m->pargs.wscore; c.wpen = (int32_t)m->pargs.wpen; c.gcmodel = m->pargs.gcmodel; c.flags = m->dFlag.as<u32>();
+        RV_TRY(rv_leaf_multi_chain_launch(q, a, c, (int)J));
+    } else
     RV_TRY(rv_leaf_multi_launch(q, a, (int)J, kmax));
     m->info[4]++;
     u32 cnt[16];
@@ -556,6 +596,9 @@ int many_round_multi(rv_many *m, const std::vector<int> &order, size_t lo, size_
     std::vector<sa_t> sa; std::vector<lcp_t> lc;
     if (na) RV_HIP(hipMemcpyAsync(an.data(), m->dAn.p, na * sizeof(RvLeafMultiAnchor), hipMemcpyDeviceToHost, q));
     if (nm) RV_HIP(hipMemcpyAsync(ap.data(), m->dAnPos.p, nm * sizeof(uint16_t), hipMemcpyDeviceToHost, q));
+    std::vector<u32> flag;
+    size_t nflag = 0;
+    if (redo) { flag.resize(J); RV_HIP(hipMemcpyAsync(flag.data(), m->dFlag.p, J * sizeof(u32), hipMemcpyDeviceToHost, q)); }
     if (m->keep) {
         sa.resize((size_t)n); lc.resize((size_t)n);
         RV_HIP(hipMemcpyAsync(sa.data(), m->dSA.p, (size_t)n * sizeof(sa_t), hipMemcpyDeviceToHost, q));
@@ -565,9 +608,11 @@ int many_round_multi(rv_many *m, const std::vector<int> &order, size_t lo, size_
     m->out_text.resize(tbase + (size_t)n);
     RV_HIP(hipMemcpyAsync(m->out_text.data() + tbase, m->dTxt.p, (size_t)n, hipMemcpyDeviceToHost, q));
     RV_HIP(hipStreamSynchronize(q));
+    if (redo) for (size_t s = 0; s < J; s++) if (flag[s]) { redo->push_back(order[lo + s]); nflag++; }
     for (size_t k = 0; k < na; k++) {
         const RvLeafMultiAnchor &r = an[k];
         if (r.job >= J || r.n < 2 || r.n > (u32)kmax || (size_t)r.moff + r.n > nm) { rv_set_error("rv_many_run: a malformed anchor"); return -1; }
+        if (nflag && flag[r.job]) continue;      // (a job the kernel did not finish)
         const int64_t ranks = mj[r.job].n;
         ManyRec rec; rec.job = order[lo + r.job]; rec.l = r.l; rec.np = (int)r.n; rec.p0 = (int64_t)m->rpos.size();
         for (u32 x = 0; x < r.n; x++) {
@@ -585,6 +630,7 @@ int many_round_multi(rv_many *m, const std::vector<int> &order, size_t lo, size_
             for (int64_t r = mj[s].beg; r < mj[s].beg + mj[s].n; r++) { m->keep_sa[kbase + (size_t)r] = (sa_t)(sa[(size_t)r] - (sa_t)mj[s].beg); m->keep_lcp[kbase + (size_t)r] = lc[(size_t)r]; }
     }
     for (size_t s = 0; s < J; s++) {
+        if (nflag && flag[s]) continue;
         ManyJob &jb = m->jobs[(size_t)order[lo + s]];
         jb.text_off = (int64_t)tbase + mj[s].beg; jb.shared = true;
         if (m->keep) jb.arr_off = (int64_t)kbase + mj[s].beg;
@@ -593,7 +639,7 @@ int many_round_multi(rv_many *m, const std::vector<int> &order, size_t lo, size_
     memset(&st, 0, sizeof st);
     st.steps = (int64_t)st4[0]; st.splits = (int64_t)st4[1]; st.anchored_bp = (int64_t)st4[2]; st.maxdepth = (int)st4[3]; st.levels = 1; st.scanned_ranks = n;
     many_add_stats(total, st);
-    m->info[1] += (int64_t)J; m->info[3]++;
+    m->info[1] += (int64_t)(J - nflag); m->info[3]++;
     return 0;
 }
 
@@ -823,12 +869,13 @@ int many_run(rv_many *m, int minl, int minn, rv_align_stats *total) {
     int64_t nwlarge = 0;
     for (const ManyJob &jb : m->jobs) nwlarge += is_wide_large(jb) ? 1 : 0;
     const bool take_wide_large = nwlarge > 0 && nwlarge >= m->wide_large_min;
-    std::vector<int> worder, wlorder;
-    const bool chain = m->picker == 1;      // the shared classes finish with built-in-picker kernels: under kind 1 only many_chain_admits' jobs share launches
+    std::vector<int> worder, wlorder, cmorder;
+    const bool chain = m->picker == 1;      // the shared classes finish with built-in-picker kernels: under kind 1 only many_chain_admits' and
+                                            // many_chain_multi_admits' jobs share launches
     for (int j = 0; j < nj; j++) {
         ManyJob &jb = m->jobs[(size_t)j];
         jb.arr_off = -1;
-        if (chain) { if (many_chain_admits(m, jb, minl)) order.push_back(j); else rest.push_back(j); }
+        if (chain) { if (many_chain_admits(m, jb, minl)) order.push_back(j); else if (many_chain_multi_admits(m, jb, minl)) cmorder.push_back(j); else rest.push_back(j); }
         else if (jb.k == 2 && jb.ranks <= RV_LEAF_N && jb.clean) order.push_back(j);
         else if (take_large && is_large(jb)) lorder.push_back(j);
         else if (take_large_multi && is_large_multi(jb)) lmorder.push_back(j);
@@ -844,10 +891,17 @@ int many_run(rv_many *m, int minl, int minn, rv_align_stats *total) {
     std::stable_sort(lmorder.begin(), lmorder.end(), by_size);
     std::stable_sort(worder.begin(), worder.end(), by_size);
     std::stable_sort(wlorder.begin(), wlorder.end(), by_size);
+    std::stable_sort(cmorder.begin(), cmorder.end(), by_size);
     for (size_t lo = 0; lo < order.size();) {
         size_t hi = lo; int64_t sum = 0;
         while (hi < order.size() && (hi == lo || sum + m->jobs[(size_t)order[hi]].ranks <= lim)) sum += m->jobs[(size_t)order[hi++]].ranks;
         RV_TRY(many_round(m, order, lo, hi, minl, minn, total, false, chain ? &rest : nullptr));
+        lo = hi;
+    }
+    for (size_t lo = 0; lo < cmorder.size();) {     // picker kind 1, the jobs of 3 .. 16 sequences (RV_MANY_CHAIN_MULTI): rounds of their own
+        size_t hi = lo; int64_t sum = 0;
+        while (hi < cmorder.size() && (hi == lo || sum + m->jobs[(size_t)cmorder[hi]].ranks <= lim)) sum += m->jobs[(size_t)cmorder[hi++]].ranks;
+        RV_TRY(many_round_multi(m, cmorder, lo, hi, minl, minn, total, RV_MANY_KMAX, &rest));
         lo = hi;
     }
     if (chain) std::sort(rest.begin(), rest.end());
@@ -939,6 +993,7 @@ int rv_many_option(rv_many *m, const char *name, int64_t value) {
     if (strcmp(name, "RV_MANY_LARGE_MULTI_MIN") == 0) { if (value < 0) { rv_set_error("RV_MANY_LARGE_MULTI_MIN: negative"); return -1; } m->large_multi_min = value; return 0; }
     if (strcmp(name, "RV_MANY_WIDE") == 0) { m->wide = value != 0; return 0; }
     if (strcmp(name, "RV_MANY_CHAIN") == 0) { m->chain = value != 0; return 0; }
+    if (strcmp(name, "RV_MANY_CHAIN_MULTI") == 0) { m->chain_multi = value != 0; return 0; }
     if (strcmp(name, "RV_MANY_CHAIN_FLAG") == 0) { if (value < 0) { rv_set_error("RV_MANY_CHAIN_FLAG: negative"); return -1; } m->chain_flag = value; return 0; }
     if (strcmp(name, "RV_MANY_WIDE_LARGE_MIN") == 0) { if (value < 0) { rv_set_error("RV_MANY_WIDE_LARGE_MIN: negative"); return -1; } m->wide_large_min = value; return 0; }
     if (strcmp(name, "RV_MANY_LARGE_MAX") == 0) { if (value < 0) { rv_set_error("RV_MANY_LARGE_MAX: negative"); return -1; } m->large_max = value; return 0; }

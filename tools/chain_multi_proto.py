@@ -1,0 +1,184 @@
+#!/usr/bin/env python3
+"""The pick stage of k_leaf_multi_chain (csrc/rv_leaf_multi_chain.hip) restated as a Python picker callback and run inside `rem.align` on the REFERENCE's
+own index module, over every job and parameter set of tests/many_chain_multi_cases.py.  It has to reproduce tests/golden/many_chain_multi.json, which the
+reference's own graphmumpicker wrote.  What it pins before any kernel runs: the list order `segment` breaks its tie by (first-seen group, strict >),
+trim per member index with the stable (position, -l) order, the chain's tie order as ONE key (candidate score, predecessor's score, step of activation,
+sort order) without the `active` list, the entry of rv_chain's dictionaries that matches with one place on the first path share (`shared` counts the
+chains where that happens), and how often the kernel's give-ups would fire (1: trim_overlap raises, 2: no predecessor, 8: another match carries the
+split's offsets) -- a call that gives up falls back to the reference's picker here, as a flagged job reruns the ordinary way.  The scan's order is
+pinned separately (many_chain_multi_cases.kernel_scan, tests/test_cpu_many_chain_multi.py).  CPU only.  Prints per set: jobs equal to the golden file,
+picker calls, calls per give-up."""
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.join(ROOT, "oracle"))
+
+GCMODEL = {"sumofpairs": 0, "star-avg": 1, "star-med": 2}
+
+
+def gapcost(d, model):
+    k = len(d)
+    if model == 1:
+        return abs(sum(d)) // k
+    D = [abs(x) for x in d]
+    if model == 2:
+        return sorted(D)[k // 2]
+    return sum(abs(D[i] - D[j]) for i in range(k) for j in range(i + 1, k))
+
+
+def make_picker(seqs, args, stat, orig):
+    ends, at = [], 0
+    for s in seqs:
+        at += len(s) + 1
+        ends.append(at)
+    begins = [0] + ends[:-1]
+
+    def sample_of(p):
+        return next(q for q, e in enumerate(ends) if p < e)
+
+    def give_up(self, bit, mums, idx, minlength):
+        stat[bit] = stat.get(bit, 0) + 1
+        return orig(self, mums, idx, False, minlength)
+
+    def picker(self, mums, idx, precomputed=False, minlength=0):
+        assert not precomputed
+        stat["calls"] = stat.get("calls", 0) + 1
+        if len(mums) == 0:
+            return ()
+        iv = {sample_of(b): (b, e) for b, e in (tuple(x) for x in idx.nodes)}
+        ns = idx.nsamples
+        cand = [[m[0], [p for _, p in m[2]], 0] for m in mums]               # l, members in the order handed out, shift
+        masks = [frozenset(sample_of(p) for p in c[1]) for c in cand]
+        if any(len(c[1]) == ns for c in cand):
+            want = frozenset(iv)
+        elif ns > 2:
+            best = None
+            for i, mk in enumerate(masks):
+                z = sum(cand[j][0] for j in range(len(cand)) if masks[j] == mk) * len(mk)
+                key = (z, -masks.index(mk))
+                best = key if best is None or key > best else best
+            want = masks[-best[1]]
+        else:
+            return ()
+        A = [c for c, mk in zip(cand, masks) if mk == want]
+        kset = len(want)
+        pos = lambda x, c: x[1][c] + x[2]
+        for c in range(kset):
+            if len(A) <= 1:
+                break
+            B = sorted(A, key=lambda x: (pos(x, c), -x[0]))
+            end = lambda x: pos(x, c) + x[0]
+            A = [x for i, x in enumerate(B) if (i == 0 and end(B[1]) > end(x)) or end(B[i - 1]) < end(x)]
+            if len(A) <= 1:
+                break
+            st = [list(A[0])]
+            for mum in A[1:]:
+                if not st:
+                    return give_up(self, 1, mums, idx, minlength)
+                pm = st[-1]
+                ov = end(pm) - pos(mum, c)
+                if ov > 0:
+                    if pm[0] - ov > 0:
+                        pm[0] -= ov
+                    else:
+                        st.pop()
+                    if mum[0] - ov > 0:
+                        st.append([mum[0] - ov, mum[1], mum[2] + ov])
+                else:
+                    st.append(list(mum))
+            A = st
+        if not A:
+            return ()
+        coord = lambda x: {sample_of(p): p + x[2] for p in x[1]}
+        if len(A) == 1:
+            split = A[0]
+        else:
+            s0 = min(want)
+            # rv_chain's stable sort by the first path's coordinate over rv_pick_chain's list (ascending l, equal lengths in trim's order)
+            B = sorted(A, key=lambda x: (coord(x)[s0], x[0]))
+            keys = [coord(x)[s0] for x in B]
+            if len(set(keys)) != len(keys):
+                stat["shared"] = stat.get("shared", 0) + 1
+            C = [coord(x) for x in B]
+            m = len(B)
+            step, score, link = [None] * m, [0] * m, [None] * m
+            order = sorted(want)
+            linkR = None
+            for e in range(m + 1):
+                start = C[e] if e < m else {s: iv[s][1] for s in order}
+                l_e, n_e = (B[e][0], len(B[e][1])) if e < m else (0, 0)
+                gain = args.wscore * l_e * (n_e * (n_e - 1) // 2)
+                best = None
+                for p in range(-1, e):
+                    endp = {s: iv[s][0] - 1 for s in order} if p < 0 else {s: C[p][s] + B[p][0] for s in order}
+                    d = [endp[s] - start[s] for s in order]
+                    if any(x > 0 for x in d):
+                        continue
+                    if p >= 0 and step[p] is None:
+                        step[p] = e
+                    sc = 0 if p < 0 else score[p]
+                    tmpw = sc + gain - args.wpen * gapcost(d, GCMODEL[args.gcmodel])
+                    key = (tmpw, sc, -(0 if p < 0 else ((step[p] + 1) << 12) | p))
+                    if best is None or key > best[0]:
+                        best = (key, p)
+                if best is None:
+                    return give_up(self, 2, mums, idx, minlength)
+                # rv_chain keeps score and link per first-path coordinate: matches that share it share the entry, the last one's values stand, and a
+                # link leads to the last match of the predecessor's coordinate
+                lk = best[1]
+                while 0 <= lk < m - 1 and keys[lk + 1] == keys[lk]:
+                    lk += 1
+                if e < m:
+                    j = e
+                    while j >= 0 and keys[j] == keys[e]:
+                        score[j], link[j] = best[0][0], lk
+                        j -= 1
+                else:
+                    linkR = lk
+            split, c = None, linkR
+            while c >= 0:
+                if split is None or B[c][0] > split[0]:
+                    split = B[c]
+                c = link[c]
+            if split is None:
+                return ()
+        rel = lambda x: tuple(p + x[2] - begins[sample_of(p)] for p in x[1])
+        if any(x is not split and rel(x) == rel(split) for x in A):
+            return give_up(self, 8, mums, idx, minlength)
+        return (split[0], len(split[1]), tuple((sample_of(p), p + split[2]) for p in split[1])), [], []
+    return picker
+
+
+def main():
+    import many_chain_multi_cases as cm
+    import pin_oracle
+    from reveal_amd import schemes
+    refmod = pin_oracle.load_refmod(False)
+    if refmod is None:
+        sys.exit("oracle/_ref/reveallib.so is not built: make -C oracle && make -C oracle refmod")
+    jobs, golden = cm.jobs(), cm.load_golden()
+    orig = schemes.GraphPicker.graphmumpicker
+    bad = 0
+    for name, kw in cm.SETS:
+        stat, same = {}, 0
+        for j, (cls, seqs) in enumerate(jobs):
+            schemes.GraphPicker.graphmumpicker = make_picker([s.upper() for s in seqs], cm.picker_args(kw), stat, orig)
+            try:
+                an, T = cm.rem_align_job(seqs, indexmod=refmod, **kw)
+            finally:
+                schemes.GraphPicker.graphmumpicker = orig
+            ok = (an, cm.sha(T)) == golden[name][j]
+            same += ok
+            if not ok:
+                print("  %s job %d (%s) differs" % (name, j, cls))
+        bad += len(jobs) - same
+        print("%-9s %3d of %3d jobs equal the golden file; picker calls %d, gave up: %s" % (name, same, len(jobs), stat.get("calls", 0),
+              {k: v for k, v in stat.items() if k != "calls"} or "never"))
+    sys.exit(1 if bad else 0)
+
+
+if __name__ == "__main__":
+    main()

@@ -26,7 +26,10 @@ no window common to all, and a call anchors next to nothing.
 built-in one, no loop through a handle; three batches run alternately in one process -- RV_MANY_CHAIN on (the leaf kernel with the picker's decision
 as its pick stage), RV_MANY_CHAIN off (every job the ordinary way, the picker in host C++), and the built-in picker on the same jobs -- then
 `rem.align` per job over the first --rem-jobs jobs (default 1000), once: the route to these anchors without align_many.  --check compares the two
-picker sides job by job, and the jobs of the rem.align loop with it."""
+picker sides job by job, and the jobs of the rem.align loop with it.
+--picker --seqs K (K = 3 .. 16): the same for jobs of K sequences -- RV_MANY_CHAIN_MULTI on (the multi-sample leaf kernel with the picker as its pick
+stage), off (the ordinary path), and the built-in picker with RV_MANY_MULTI on (k_leaf_multi on the same jobs).  With RV_LIB_DIR set to a build from
+before the switch the first side is left out: the other two are that build's ordinary path and its k_leaf_multi, the baselines of the parent commit."""
 import argparse
 import ctypes
 import json
@@ -179,10 +182,18 @@ def main_picker(a, jobs, bases):
     from reveal_amd import many, rem, schemes
     args = schemes.PickerArgs(maxmums=10000)      # (rem.align's defaults)
     sides = {}
+    switch = "RV_MANY_CHAIN" if a.seqs == 2 else "RV_MANY_CHAIN_MULTI"
     for name, pk, chain in (("chain", args, 1), ("ordinary", args, 0), ("builtin", None, 0)):
         b = many.Batch(False)
         b.set_picker(pk)
-        b.option("RV_MANY_CHAIN", chain)
+        try:
+            b.option(switch, chain)
+        except many.error:      # (RV_LIB_DIR: a build from before the switch -- off is all it knows)
+            if chain:
+                print("%s is not known to this build: no chain side" % switch)
+                continue
+        if a.seqs > 2 and pk is None:
+            b.option("RV_MANY_MULTI", 1)
         if a.wave_max is not None:
             b.option("RV_MANY_WAVE_MAX", a.wave_max)
         run_many_c(b, jobs[:64], a.minlength)
@@ -190,7 +201,7 @@ def main_picker(a, jobs, bases):
     for rep in range(a.reps):
         for name, s in sides.items():
             t = time.perf_counter(); s["res"] = run_many_c(s["batch"], jobs, a.minlength); s["t"].append(time.perf_counter() - t)
-    out = dict(jobs=a.jobs, lmin=a.lmin, lmax=a.lmax, bases=bases, minlength=a.minlength, reps=a.reps, picker="graphmumpicker")
+    out = dict(jobs=a.jobs, seqs=a.seqs, lmin=a.lmin, lmax=a.lmax, bases=bases, minlength=a.minlength, reps=a.reps, picker="graphmumpicker", lib_dir=os.environ.get("RV_LIB_DIR", ""))
     for name, s in sides.items():
         t = s["t"]
         out[name + "_s"] = t; out[name + "_median_s"] = statistics.median(t); out[name + "_spread_s"] = max(t) - min(t); out[name + "_info"] = s["batch"].info()
@@ -200,10 +211,13 @@ def main_picker(a, jobs, bases):
     rem_res = []
     t = time.perf_counter()
     for job in jobs[:nrem]:
-        rem_res.append(rem.align([("a", job[0].decode()), ("b", job[1].decode())], minlength=a.minlength))
+        rem_res.append(rem.align([("s%d" % k, s.decode()) for k, s in enumerate(job)], minlength=a.minlength))
     out["rem_jobs"] = nrem; out["rem_s"] = time.perf_counter() - t
     out["rem_per_job_s"] = out["rem_s"] / max(nrem, 1)
     print("rem.align per job: %d jobs in %.2f s, %.2f ms a job, %.0f jobs/s" % (nrem, out["rem_s"], 1e3 * out["rem_per_job_s"], nrem / out["rem_s"]))
+    if "chain" not in sides:
+        print(json.dumps(out))
+        return 0
     out["chain_vs_rem"] = out["rem_per_job_s"] / (out["chain_median_s"] / a.jobs)
     out["ordinary_vs_chain"] = out["ordinary_median_s"] / out["chain_median_s"]
     out["chain_vs_builtin"] = out["chain_median_s"] / out["builtin_median_s"]
@@ -217,7 +231,7 @@ def main_picker(a, jobs, bases):
         # (the final text of rem.align's index says which positions its anchors cover)
         bad = 0
         for j, (G, idx) in enumerate(rem_res):
-            T = bytearray(jobs[j][0] + b"$" + jobs[j][1] + b"$")
+            T = bytearray(b"$".join(jobs[j]) + b"$")
             for l, pos in x[j]:
                 for p in pos:
                     T[p:p + l] = T[p:p + l].lower()
@@ -252,8 +266,8 @@ def main():
     ap.add_argument("--picker", action="store_true", help="the reference's default picker: RV_MANY_CHAIN on / off, the built-in picker, rem.align per job; no loop")
     ap.add_argument("--rem-jobs", type=int, default=1000, help="--picker: jobs of the rem.align loop")
     a = ap.parse_args()
-    if a.picker and a.seqs != 2:
-        ap.error("--picker times pair jobs")
+    if a.picker and not 2 <= a.seqs <= 16:
+        ap.error("--picker times jobs of 2 .. 16 sequences")
     if [a.multi, a.large, a.large_multi, a.wide].count("ab") > 1:
         ap.error("one switch at a time: --multi ab, --large ab, --large-multi ab or --wide ab")
     if a.wide is not None and not 17 <= a.seqs <= 64:
