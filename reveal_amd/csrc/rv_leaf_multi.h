@@ -30,14 +30,16 @@ struct RvLeafMultiArgs {
 // kmax: RV_MANY_KMAX or RV_MANY_WIDE_KMAX -- the form of the kernel; every job of the launch has at most that many samples
 int rv_leaf_multi_launch(hipStream_t q, const RvLeafMultiArgs &a, int njobs, int kmax);
 
-// k_leaf_multi_chain (rv_leaf_multi_chain.hip): the narrow form's job -- 3 .. RV_MANY_KMAX samples, at most RV_LEAF_N ranks -- with the reference's default
-// picker (schemes.graphmumpicker; rv_pick_chain for any number of samples) as the pick stage, for rv_many's RV_MANY_CHAIN_MULTI rounds.  What the caller
-// must have checked (rv_many.hip many_chain_multi_admits): trim on, minl > 0, no seeds, a --maxmums that cannot bite, weights within RV_LEAF_MCHAIN_WMAX.
-#define RV_LEAF_MCHAIN_WMAX 1024       // rv_leaf_multi_chain.hip derives it: scores of up to sixteen paths in 32 bits
+// k_leaf_multi_chain (rv_leaf_multi_chain.hip): the same jobs -- 3 .. RV_MANY_KMAX samples in the narrow form, up to RV_MANY_WIDE_KMAX in the wide one, at
+// most RV_LEAF_N ranks -- with the reference's default picker (schemes.graphmumpicker; rv_pick_chain for any number of samples) as the pick stage, for
+// rv_many's RV_MANY_CHAIN_MULTI and RV_MANY_CHAIN_WIDE rounds.  What the caller must have checked (rv_many.hip many_chain_multi_admits,
+// many_chain_wide_admits): trim on, minl > 0, no seeds, a --maxmums that cannot bite, weights within RV_LEAF_MCHAIN_WMAX.
+#define RV_LEAF_MCHAIN_WMAX 1024       // rv_leaf_multi_chain.hip derives it for both forms: scores of up to 16 / 64 paths in 32 bits
 struct RvLeafMultiChainArgs {
     int32_t wscore, wpen;                                    // 0 .. RV_LEAF_MCHAIN_WMAX
     int gcmodel;                                             // 0 sumofpairs, 1 star-avg, 2 star-med
     u32 *flags;                                              // one word per job, zeroed by the caller: != 0 -- the job was not finished here (1: the reference's own
                                                              // trim_overlap raises, 2: broken chain, 8: two matches share the split's offsets, 16: rv_many's test hook, 32: frame stack full)
 };
-int rv_leaf_multi_chain_launch(hipStream_t q, const RvLeafMultiArgs &a, const RvLeafMultiChainArgs &c, int njobs);
+// kmax: RV_MANY_KMAX or RV_MANY_WIDE_KMAX -- the form of the kernel, as for rv_leaf_multi_launch
+int rv_leaf_multi_chain_launch(hipStream_t q, const RvLeafMultiArgs &a, const RvLeafMultiChainArgs &c, int njobs, int kmax);

@@ -1,5 +1,7 @@
 // rv_leaf_multi_chain.hip -- the whole recursion of a job of 3 .. RV_MANY_KMAX samples inside one workgroup with the reference's default picker as the
-// pick stage (k_leaf_multi_chain), for rv_many's RV_MANY_CHAIN_MULTI rounds under picker kind 1.
+// pick stage (k_leaf_multi_chain), for rv_many's RV_MANY_CHAIN_MULTI rounds under picker kind 1; and, in its wide form, of a job of up to
+// RV_MANY_WIDE_KMAX = 64 samples (RV_MANY_CHAIN_WIDE: the jobs of 17 .. 64 sequences).  The kernel is a template over the sample bound KM, as k_leaf_multi
+// is; "The two forms" below says where they differ.
 //
 // The frame of the kernel is k_leaf_multi's (rv_leaf_multi.hip: one workgroup per job, the arrays in LDS in two copies, one wavefront per sub-index,
 // lane s owning sample s, a shared stack of frames); k_leaf_multi itself is untouched.  What differs is everything the picker decides.  The
@@ -20,9 +22,10 @@
 //             empty stack with matches left is where the reference raises: flag 1
 //   chain     rv_chain over the k paths of the set between the sentinels (interval begin - 1, interval end): matches by their coordinate on the
 //             lowest sample, then in rv_pick_chain's order (ascending l, trim's order).  Matches that share that coordinate share rv_chain's
-//             dictionary entry: the last one's score and link stand for all of them, and a link to one of them leads to the last; four predecessors a step, sixteen lanes (one per sample) each: ends-before by ballot, gapcost (sum of pairs of |d|,
-//             star-avg |sum d| / k, star-med sorted |d| at k / 2) by reductions inside the sixteen lanes; gain = wscore * l * n (n - 1) / 2.  Ties as in
-//             k_leaf_chain: candidate score, predecessor's score (descending), step of activation, sort order (ascending)
+//             dictionary entry: the last one's score and link stand for all of them, and a link to one of them leads to the last; 64 / KM predecessors
+//             a step, KM lanes (one per sample) each: ends-before by ballot, gapcost (sum of pairs of |d|, star-avg |sum d| / k, star-med sorted |d|
+//             at k / 2) by reductions inside the KM lanes; gain = wscore * l * n (n - 1) / 2.  Ties as in k_leaf_chain: candidate score, predecessor's
+//             score (descending), step of activation, sort order (ascending) -- one key, reduced once per match
 //   split     the largest match of the chain, of equal lengths the last; the anchor is the TRIMMED match, members in member (rank) order, as the
 //             ordinary path emits them.  Three children: lead and trail over the set's samples, rest = the other live samples with their whole
 //             intervals; running-minimum LCP per child; bubble_sort on the leading child.  A child is visited when at least max(2, minn) of its
@@ -31,7 +34,7 @@
 //   1   trim_overlap raises in the reference                     2   the chain finds no predecessor / a broken back-pointer chain
 //   8   another match of the list has the split's offsets member by member: rv_pick_chain's `mapping` would hand out that one
 //   16  rv_many's test hook                                     32  the frame stack is full
-// What the caller guarantees (rv_many.hip many_chain_multi_admits): trim on, minl > 0, no seed possible, a --maxmums of at least the job's ranks (a
+// What the caller guarantees (rv_many.hip many_chain_multi_admits, many_chain_wide_admits): trim on, minl > 0, no seed possible, a --maxmums of at least the job's ranks (a
 // sub-index has fewer candidates than ranks), gap model 0 .. 2, and
 //   0 <= wscore, wpen <= RV_LEAF_MCHAIN_WMAX = 2^10: scores in 32 bits.  A job has at most 2^11 ranks.  The lengths of a chain are disjoint on every
 //   path: they add up to at most 2^11, and n (n - 1) / 2 <= 120 < 2^7, so the gains of a chain add up to at most wscore * 2^18.  A gap cost is at most
@@ -39,12 +42,29 @@
 //   wscore * 2^18; a candidate score + gain - wpen * gap lies within 3 * 2^10 * 2^18 < 2^30.  k_leaf_chain's bound of 2^16 would need 2^36: the bound
 //   is tightened instead of widening the scores, because the tie order packs (candidate, predecessor's score) into one 64-bit key for ONE wave
 //   reduction per match, and the reference's defaults are 1 and 1.
+//   KM = 64: the same constant holds.  A match of n members and length l covers n * l ranks of the job, and the matches of a chain are disjoint on every
+//   path, so sum (n * l) <= 2^11; a gain is wscore * (n * l) * (n - 1) / 2 with (n - 1) / 2 < 2^5: the gains of a chain add up to less than wscore * 2^16.
+//   A sum-of-pairs gap is sum_{i<j} | |d_i| - |d_j| | <= (n - 1) * sum |d_i|, the |d_i| lie inside different sequences and add up to less than 2^11:
+//   a gap cost is below 63 * 2^11 < 2^17 (the star models: 2^11).  A score is >= -wpen * 2^17 (the left sentinel's offer) and < wscore * 2^16; a candidate
+//   score + gain - wpen * gap lies within 2^10 * (2^17 + 2^16 + 2^17) < 3 * 2^27 < 2^30.  RV_LEAF_MCHAIN_WMAX = 2^10 serves both forms (the same
+//   counting gives the 16-sample form 2^14 gains and 2^15 gaps: the bound above is not tight, and is kept).
 //   With weights >= 0 the early `break` of rv_chain never changes the choice.
 // Frame stack: a wave goes on with the smallest visited child and leaves the others to the stack -- two frames where the size falls to a third, one
 // where it halves: at most 2 log3(2048) < 14 frames wait per descent, four waves descend at once, and a frame taken from the stack starts a descent
 // no longer than its parent's: MAXSTACK = 96 as in k_leaf_multi.  A full stack flags the job (32), it does not fail the call.
-// LDS: k_leaf_multi<16>'s arrays + two lists of 8 B per rank + the chain's coordinate scratch: see the compiler remark; two workgroups
-// per CU.
+// The two forms (compiler remarks, gfx950):
+//   KM = 16   the kernel as it was before the template: four predecessors a chain step, sixteen lanes each (four exchanges for a sum, sixteen for the ranks
+//             of the |d|); sample sets in 16 bits beside the candidates (aux).  k_leaf_multi<16>'s arrays + two lists of 8 B per rank + the chain's
+//             coordinate scratch: 73 104 B of LDS, two workgroups per CU; 122 VGPRs, no scratch, 122 SGPRs spilled
+//   KM = 64   lane s owns path s through the whole chain step: ONE predecessor a step.  Ends-before is one 64-bit ballot; a sum is the wavefront's scan.
+//             Sum of pairs and star-med need every lane's |d| against every other path's: the paths of the set are taken in turn (a loop over the bits
+//             of the set, which sits in scalar registers), path j's |d| is read from lane j (v_readlane), and the lane adds | |d| - |d_j| | for j above
+//             it and counts the |d_j| below its own (ties by lane): its share of the 2016 pairs and its rank among 64, in two registers -- no per-lane
+//             array.  The tie key is unchanged, so the order in which predecessors are looked at does not show.  Sample sets are 64 bits: the
+//             candidates' sets lie in list B, which nothing else uses before trim.  Scan windows of 2 .. 64 ranks, trim over up to 64 member indices,
+//             FrameMT<64> of 264 B.  k_leaf_multi<64>'s 59 248 B + the two lists (32 768 B) + coordinate scratch: 93 168 B of LDS -- ONE workgroup
+//             per CU (of gfx950's 160 KiB); 123 VGPRs, no scratch, 39 SGPRs spilled.  Two per CU would need the lists inside the dead ranks of the
+//             other copy of the arrays, as k_leaf_chain keeps them: not done
 #include "rv_leaf_multi.h"
 
 namespace {
@@ -52,15 +72,17 @@ namespace {
 constexpr int NT = 256;
 constexpr int LN = RV_LEAF_N;
 constexpr int NW = NT / 64;
-constexpr int KM = RV_MANY_KMAX;
 constexpr int MAXSTACK = 96;
 constexpr int ACAP = 256;
 constexpr u32 INF = 0xFFFFFFFFu;
-constexpr uint8_t SMP_SEP = 0x40, SMP_DONE = 0x80, SMP_ID = (uint8_t)(KM - 1);
+constexpr uint8_t SMP_SEP = 0x40, SMP_DONE = 0x80;      // (the sample id lies below them: KM - 1, at most six bits)
 constexpr u32 LINK_L = 0xFFFFu, NOT_ACTIVE = 0xFFFFu;
-static_assert(LN <= 2048 && KM == 16, "positions and lengths in 12 bits of the sort keys, four groups of sixteen lanes in the chain");
+static_assert(LN <= 2048, "positions and lengths in 12 bits of the sort keys");
 
-struct FrameM { uint16_t start, len, depth, buf; uint16_t b[KM], e[KM]; };
+template <int KM>
+struct FrameMT { uint16_t start, len, depth, buf; uint16_t b[KM], e[KM]; };      // interval [b, e) of every sample, job-local; empty: b >= e
+template <int KM> struct Census { typedef u32 type; };      // a bit per sample: the samples of a match, of the picked set
+template <> struct Census<RV_MANY_WIDE_KMAX> { typedef u64 type; };
 
 #define WSYNC() do { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); __builtin_amdgcn_wave_barrier(); } while (0)
 
@@ -68,8 +90,16 @@ __device__ inline bool is_lower_c(uint8_t c) { return c >= 'a' && c <= 'z'; }
 __device__ inline u32 lanes_below(u64 mask) { return __builtin_amdgcn_mbcnt_hi((u32)(mask >> 32), __builtin_amdgcn_mbcnt_lo((u32)mask, 0u)); }
 __device__ inline u32 from_lane_below(u32 x, u32 first) { return (u32)__builtin_amdgcn_update_dpp((int)first, (int)x, 0x138 /* wave_shr:1 */, 0xf, 0xf, false); }
 __device__ inline int iabs(int x) { return x < 0 ? -x : x; }
-// sum over the sixteen lanes of a group
-__device__ inline int group_sum(int v) { v += __shfl_xor(v, 8, 16); v += __shfl_xor(v, 4, 16); v += __shfl_xor(v, 2, 16); v += __shfl_xor(v, 1, 16); return v; }
+// sum over the KM lanes of a group: sixteen lanes by four exchanges, the whole wavefront by its scan
+template <int KM>
+__device__ inline int group_sum(int v) {
+    if constexpr (KM == 64) return __builtin_amdgcn_readlane((int)rv_wave_incl_sum_u32((u32)v), 63);
+    else { v += __shfl_xor(v, 8, 16); v += __shfl_xor(v, 4, 16); v += __shfl_xor(v, 2, 16); v += __shfl_xor(v, 1, 16); return v; }
+}
+__device__ inline int cen_count(u32 m) { return __builtin_popcount(m); }
+__device__ inline int cen_count(u64 m) { return (int)__popcll(m); }
+__device__ inline int cen_first(u32 m) { return __builtin_ctz(m); }
+__device__ inline int cen_first(u64 m) { return (int)__builtin_ctzll(m); }
 
 // a match of the lists: length after trimming, first rank of its interval, how far trimming moved its members, members
 struct Mt { int l, lb, sh, n; };
@@ -97,7 +127,14 @@ __device__ inline MinSt3 wave_incl_ms3(MinSt3 m) {
     return m;
 }
 
+// KM: the sample bound of the form, RV_MANY_KMAX (16) or RV_MANY_WIDE_KMAX (64); a wavefront holds GRPS = 64 / KM predecessors of a chain step
+template <int KM>
 __global__ __launch_bounds__(NT) void k_leaf_multi_chain(RvLeafMultiArgs A, RvLeafMultiChainArgs C) {
+    static_assert(KM == RV_MANY_KMAX || KM == RV_MANY_WIDE_KMAX, "the sample in KM - 1 <= 0x3F of the smp byte, lane s owns sample s, groups of KM lanes in the chain");
+    constexpr uint8_t SMP_ID = (uint8_t)(KM - 1);
+    constexpr int GRPS = 64 / KM;
+    typedef typename Census<KM>::type cen_t;
+    typedef FrameMT<KM> FrameM;
     __shared__ uint16_t sa2[2][LN], lc2[2][LN];
     __shared__ uint8_t bw2[2][LN];
     __shared__ uint8_t smp[LN];
@@ -106,7 +143,7 @@ __global__ __launch_bounds__(NT) void k_leaf_multi_chain(RvLeafMultiArgs A, RvLe
     __shared__ FrameM stack[MAXSTACK];
     __shared__ FrameM cur[NW];
     __shared__ uint16_t wm[NW][KM];               // the picked match: its member on every sample of its set
-    __shared__ uint16_t cme[NW][KM], cpr[NW][4][KM];      // chain: the match's / four predecessors' coordinates per sample
+    __shared__ uint16_t cme[NW][KM], cpr[NW][GRPS][KM];      // chain: the match's / the step's predecessors' coordinates per sample
     __shared__ uint16_t seqb[KM];                 // where every sequence of the job begins
     __shared__ uint16_t an_l[ACAP], an_n[ACAP], an_mo[ACAP], an_pp[LN];
     __shared__ int s_top, s_pending, s_lock, s_bad;
@@ -163,7 +200,7 @@ __global__ __launch_bounds__(NT) void k_leaf_multi_chain(RvLeafMultiArgs A, RvLe
     const u32 acap = A.stage_cap < (u32)ACAP ? A.stage_cap : (u32)ACAP;
     const int wscore = C.wscore, wpen = C.wpen, model = C.gcmodel;
     u32 *const jflag = C.flags + blockIdx.x;
-    const int sl = lane & (KM - 1), grp = lane >> 4;
+    const int sl = lane & (KM - 1), grp = lane / KM;
     u32 my_steps = 0, my_splits = 0, my_maxdepth = 0; u64 my_bp = 0;
     bool have = wv == 0;
 
@@ -194,7 +231,7 @@ __global__ __launch_bounds__(NT) void k_leaf_multi_chain(RvLeafMultiArgs A, RvLe
         const int S = __builtin_amdgcn_readfirstlane((int)f->start), E = S + __builtin_amdgcn_readfirstlane((int)f->len);
         const int depth = __builtin_amdgcn_readfirstlane((int)f->depth), b = __builtin_amdgcn_readfirstlane((int)f->buf);
         const u32 myb = lane < KM ? (u32)f->b[sl] : 0u, mye = lane < KM ? (u32)f->e[sl] : 0u;      // lane s: the interval of sample s
-        const int gb = (int)f->b[sl], ge = (int)f->e[sl];                                           // lane: the interval of sample lane & 15 (the chain's groups)
+        const int gb = (int)f->b[sl], ge = (int)f->e[sl];                                           // lane: the interval of sample lane & (KM - 1) (the chain's groups)
         const bool lv = myb < mye;
         const u64 live = __ballot(lv);
         const int ns = (int)__popcll(live);
@@ -203,6 +240,9 @@ __global__ __launch_bounds__(NT) void k_leaf_multi_chain(RvLeafMultiArgs A, RvLe
         uint8_t *cb = bw2[b], *nb = bw2[b ^ 1];
         u64 *la = eA + S, *lbk = eB + S;
         uint16_t *aux = act + S;                       // candidate sample sets / sort keys / steps of activation, then bubble_sort's list
+        // the sample set of candidate i: sixteen bits in aux, 64 bits in list B (which nothing else uses before trim)
+        auto set_put = [&](int i, cen_t v) { if constexpr (KM == 64) lbk[i] = v; else aux[i] = (uint16_t)v; };
+        auto set_of = [&](int i) -> cen_t { if constexpr (KM == 64) return lbk[i]; else return (cen_t)aux[i]; };
         if (lane == 0) { my_steps++; if ((u32)depth > my_maxdepth) my_maxdepth = (u32)depth; }
 
         // the windows that close at rank u, by descending l
@@ -211,7 +251,7 @@ __global__ __launch_bounds__(NT) void k_leaf_multi_chain(RvLeafMultiArgs A, RvLe
             const u32 nxt = (u + 1 < E) ? (u32)cl[u + 1] : 0u;
             const uint8_t sb0 = smp[cs[u]];
             if (sb0 & SMP_SEP) return;
-            u32 seen = 1u << (sb0 & SMP_ID), l = INF;
+            cen_t seen = (cen_t)1 << (sb0 & SMP_ID); u32 l = INF;
             uint8_t cnext = cb[u];
             bool lm = false;
             for (int k = 2; k <= ns; k++) {
@@ -221,7 +261,7 @@ __global__ __launch_bounds__(NT) void k_leaf_multi_chain(RvLeafMultiArgs A, RvLe
                 l = v < l ? v : l;
                 if (l < need || l <= nxt) break;
                 const uint8_t sb = smp[cs[r]];
-                const u32 bit = 1u << (sb & SMP_ID);
+                const cen_t bit = (cen_t)1 << (sb & SMP_ID);
                 if ((sb & SMP_SEP) || (seen & bit)) break;
                 seen |= bit;
                 const uint8_t c = cb[r];
@@ -234,19 +274,19 @@ __global__ __launch_bounds__(NT) void k_leaf_multi_chain(RvLeafMultiArgs A, RvLe
         // ---- the pick stage -> picked, the match P and its sample set -------------------------------------------------------
         bool picked = false;
         Mt P; P.l = P.lb = P.sh = P.n = 0;
-        u32 setmask = 0;
+        cen_t setmask = 0;
         do {
             if (ns < 2 || ns < minn) break;
             // collect
             int m = 0, nfull = 0;
             for (int base = S; base < E; base += 64) {
                 int cnt = 0;
-                walk(base + lane, [&](int, int, int, u32) { cnt++; });
+                walk(base + lane, [&](int, int, int, cen_t) { cnt++; });
                 const u32 inc = rv_wave_incl_sum_u32((u32)cnt);
                 int at = m + (int)(inc - (u32)cnt), full = 0;
-                walk(base + lane, [&](int r, int k, int l, u32 seen) {
+                walk(base + lane, [&](int r, int k, int l, cen_t seen) {
                     Mt c; c.l = l; c.lb = r; c.sh = 0; c.n = k;
-                    if (at < E - S) { la[at] = mt_pack(c); aux[at] = (uint16_t)seen; }
+                    if (at < E - S) { la[at] = mt_pack(c); set_put(at, seen); }
                     at++;
                     full += k == ns ? 1 : 0;
                 });
@@ -257,32 +297,34 @@ __global__ __launch_bounds__(NT) void k_leaf_multi_chain(RvLeafMultiArgs A, RvLe
             if (m >= E - S) { if (lane == 0) atomicOr(jflag, 2u); break; }      // (cannot happen: fewer inner nodes than ranks)
             WSYNC();
             // the set: n == ns, or the best sample subset
-            u32 want_mask = 0;
-            if (nfull > 0) want_mask = (u32)live;
+            cen_t want_mask = 0;
+            if (nfull > 0) want_mask = (cen_t)live;
             else if (ns > 2) {
                 u64 best = 0;
                 for (int base = 0; base < m; base += 64) {
                     const int i = base + lane;
                     if (i < m) {
-                        const u32 mk = aux[i];
+                        const cen_t mk = set_of(i);
                         u32 z = 0; int first = -1;
-                        for (int j = 0; j < m; j++) if (aux[j] == mk) { z += (u32)(la[j] & 0xFFFFu); if (first < 0) first = j; }
-                        z *= (u32)__builtin_popcount(mk);
+                        for (int j = 0; j < m; j++) if (set_of(j) == mk) { z += (u32)(la[j] & 0xFFFFu); if (first < 0) first = j; }
+                        z *= (u32)cen_count(mk);
                         const u64 key = ((u64)z << 32) | (u64)(0xFFFFu - (u32)first);
                         best = key > best ? key : best;
                     }
                 }
                 best = rv_wave_max_u64(best);
                 if (best == 0) break;
-                want_mask = aux[0xFFFFu - (u32)(best & 0xFFFFu)];
+                want_mask = set_of((int)(0xFFFFu - (u32)(best & 0xFFFFu)));
             } else break;
+            if constexpr (KM == 64)                    // (the same word in every lane: in scalar registers for the loops over its bits)
+                want_mask = ((cen_t)(u32)__builtin_amdgcn_readfirstlane((int)(u32)(want_mask >> 32)) << 32) | (cen_t)(u32)__builtin_amdgcn_readfirstlane((int)(u32)want_mask);
             setmask = want_mask;
-            const int kset = __builtin_popcount(setmask);
+            const int kset = cen_count(setmask);
             {   // the chosen matches, in list order, to the front of list A
                 int w = 0;
                 for (int base = 0; base < m; base += 64) {
                     const int i = base + lane;
-                    const bool keep = i < m && aux[i] == (uint16_t)want_mask;
+                    const bool keep = i < m && set_of(i) == want_mask;
                     const u64 rec = i < m ? la[i] : 0ull;
                     WSYNC();
                     const u64 mask = __ballot(keep);
@@ -362,7 +404,7 @@ __global__ __launch_bounds__(NT) void k_leaf_multi_chain(RvLeafMultiArgs A, RvLe
             if (m == 1) { lbk[0] = la[0]; WSYNC(); }
             else {
                 // ---- rv_chain over the paths of the set ----------------------------------------------------------------------
-                const int s0 = __builtin_ctz(setmask);
+                const int s0 = cen_first(setmask);
                 for (int i = lane; i < m; i += 64) {      // the coordinate on the first path
                     const Mt x = mt_unpack(la[i]);
                     int p0 = 0;
@@ -384,7 +426,6 @@ __global__ __launch_bounds__(NT) void k_leaf_multi_chain(RvLeafMultiArgs A, RvLe
                 for (int i = lane; i < m; i += 64) aux[i] = (uint16_t)NOT_ACTIVE;
                 WSYNC();
                 const bool inset = (setmask >> sl) & 1u;
-                const u32 gmask = 0xFFFFu;
                 u32 linkR = LINK_L;
                 bool broken = false;
                 for (int e = 0; e <= m; e++) {
@@ -397,7 +438,7 @@ __global__ __launch_bounds__(NT) void k_leaf_multi_chain(RvLeafMultiArgs A, RvLe
                     const int mst = e < m ? (int)cme[wv][sl] : ge;           // where the match starts on this lane's sample; `right`: the interval's end
                     const int gain = wscore * me.l * ((me.n * (me.n - 1)) / 2);
                     u64 b1 = 0; u32 b2 = 0xFFFFFFFFu;
-                    for (int base = -1; base < e; base += 4) {
+                    for (int base = -1; base < e; base += GRPS) {
                         const int p = base + grp;                          // this group's predecessor; -1: the left sentinel
                         const bool on = p < e;
                         Mt o; o.l = 0; o.lb = 0; o.sh = 0; o.n = 0;
@@ -408,11 +449,24 @@ __global__ __launch_bounds__(NT) void k_leaf_multi_chain(RvLeafMultiArgs A, RvLe
                         WSYNC();
                         const int pend = p < 0 ? gb - 1 : (int)cpr[wv][grp][sl] + o.l;
                         const int d = (on && inset) ? pend - mst : 0;
-                        const u32 late = (u32)(__ballot(d > 0) >> (16 * grp)) & gmask;      // lanes where the predecessor does not end in front of the match
+                        u32 late;                                          // lanes where the predecessor does not end in front of the match
+                        if constexpr (KM == 64) late = __ballot(d > 0) ? 1u : 0u; else late = (u32)(__ballot(d > 0) >> (16 * grp)) & 0xFFFFu;
                         // utils.gapcost over the set's paths
                         const int D = iabs(d);
                         int acc = 0, rank = 0;
                         if (model != 1) {
+                            if constexpr (KM == 64) {
+                                // every path of the set in turn, its |d| read from its lane: the lane's share of the sum of pairs (the paths above it) and its
+                                // rank among the set's |d| (ties by lane) -- nothing is kept per lane beyond the two sums
+                                for (cen_t mm = setmask; mm; mm &= mm - 1) {
+                                    const int j = cen_first(mm);
+                                    const int od = __builtin_amdgcn_readlane(D, j);
+                                    if (inset) {
+                                        if (j > sl) acc += iabs(D - od);
+                                        rank += (od < D || (od == D && j < sl)) ? 1 : 0;
+                                    }
+                                }
+                            } else {
                             for (int j = 0; j < KM; j++) {
                                 const int od = __shfl(D, (lane & 48) | j);
                                 if (inset && ((setmask >> j) & 1u)) {
@@ -420,11 +474,12 @@ __global__ __launch_bounds__(NT) void k_leaf_multi_chain(RvLeafMultiArgs A, RvLe
                                     rank += (od < D || (od == D && j < sl)) ? 1 : 0;
                                 }
                             }
+                            }
                         }
                         int gap;
-                        if (model == 1) gap = iabs(group_sum(d)) / kset;
-                        else if (model == 2) gap = group_sum((inset && rank == kset / 2) ? D : 0);
-                        else gap = group_sum(acc);
+                        if (model == 1) gap = iabs(group_sum<KM>(d)) / kset;
+                        else if (model == 2) gap = group_sum<KM>((inset && rank == kset / 2) ? D : 0);
+                        else gap = group_sum<KM>(acc);
                         if (on && late == 0 && sl == 0) {
                             u32 st = 0; int sc = 0;
                             if (p >= 0) {
@@ -514,8 +569,8 @@ __global__ __launch_bounds__(NT) void k_leaf_multi_chain(RvLeafMultiArgs A, RvLe
                 } else if (lane == 0) atomicOr(A.err, 32u);
             }
         }
-        for (u32 mm = setmask; mm; mm &= mm - 1) {
-            const u32 Pm = wm[wv][__builtin_ctz(mm)];
+        for (cen_t mm = setmask; mm; mm &= mm - 1) {
+            const u32 Pm = wm[wv][cen_first(mm)];
             for (u32 j = lane; j < L; j += 64) if (Pm + j < (u32)n) smp[Pm + j] |= SMP_DONE;
         }
         // ---- graphalign, linear interval model: lead / trail on the set's samples, rest = the other live samples, whole -------
@@ -725,13 +780,15 @@ __global__ __launch_bounds__(NT) void k_leaf_multi_chain(RvLeafMultiArgs A, RvLe
 
 }  // namespace
 
-int rv_leaf_multi_chain_launch(hipStream_t q, const RvLeafMultiArgs &a, const RvLeafMultiChainArgs &c, int njobs) {
+int rv_leaf_multi_chain_launch(hipStream_t q, const RvLeafMultiArgs &a, const RvLeafMultiChainArgs &c, int njobs, int kmax) {
     if (njobs <= 0) return 0;
     if (!c.flags || c.wscore < 0 || c.wpen < 0 || c.wscore > RV_LEAF_MCHAIN_WMAX || c.wpen > RV_LEAF_MCHAIN_WMAX || c.gcmodel < 0 || c.gcmodel > 2 || a.minl < 1) {
         rv_set_error("rv_leaf_multi_chain_launch: arguments the chain form of the multi-sample leaf kernel does not take");
         return -1;
     }
-    hipLaunchKernelGGL(k_leaf_multi_chain, dim3((unsigned)njobs), dim3(NT), 0, q, a, c);
+    if (kmax == RV_MANY_KMAX) hipLaunchKernelGGL(k_leaf_multi_chain<RV_MANY_KMAX>, dim3((unsigned)njobs), dim3(NT), 0, q, a, c);
+    else if (kmax == RV_MANY_WIDE_KMAX) hipLaunchKernelGGL(k_leaf_multi_chain<RV_MANY_WIDE_KMAX>, dim3((unsigned)njobs), dim3(NT), 0, q, a, c);
+    else { rv_set_error("rv_leaf_multi_chain_launch: the kernel has forms for %d and %d samples, not %d", RV_MANY_KMAX, RV_MANY_WIDE_KMAX, kmax); return -1; }
     RV_LAUNCH_CHECK();
     return 0;
 }

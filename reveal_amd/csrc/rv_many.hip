@@ -62,6 +62,10 @@
 // sequences many_chain_multi_admits names share their launches too, in rounds of their own -- layout and index build of RV_MANY_MULTI (many_round_multi) and
 // ONE launch of k_leaf_multi_chain (rv_leaf_multi_chain.hip), the multi-sample leaf kernel with the whole picker as its pick stage: matches on sample
 // subsets, `segment`, trim and chain over k paths, a three-way split with a `rest` child.  Flags as for k_leaf_chain, per job.
+// RV_MANY_CHAIN_WIDE (off by default, independent of every other switch; it means something under kind 1 only): the jobs of 17 .. RV_MANY_WIDE_KMAX = 64
+// sequences many_chain_wide_admits names share their launches too, in rounds of their own -- layout and index build of the small RV_MANY_WIDE rounds
+// (many_round_multi with kmax = 64) and ONE launch of the 64-sample form of k_leaf_multi_chain.  Flags and test hooks as for RV_MANY_CHAIN_MULTI.  Under a
+// picker the jobs of 17 .. 64 sequences above RV_LEAF_N ranks, and every job of more than 64 sequences, stay ordinary.
 // Size classes (DESIGN.md "Many small alignments" has the measurements): up to `wave_max` ranks (default 512) a wavefront per job,
 // four jobs per workgroup, no workgroup barrier; above, a workgroup of 256 threads per job.  Both hold 22.6 KB of LDS per workgroup:
 // seven workgroups per CU.
@@ -259,6 +263,7 @@ struct rv_many {
     int picker = 0; rv_picker_args pargs{};     // rv_many_set_picker
     int64_t chain = 0, chain_flag = 0;          // RV_MANY_CHAIN, RV_MANY_CHAIN_FLAG (test hook)
     int64_t chain_multi = 0;                    // RV_MANY_CHAIN_MULTI
+    int64_t chain_wide = 0;                     // RV_MANY_CHAIN_WIDE
     std::vector<std::pair<std::string, int64_t>> fwd;      // switches for the internal handles
     // results of the last run
     bool ran = false;
@@ -302,17 +307,19 @@ bool many_chain_admits(const rv_many *m, const ManyJob &jb, int minl) {
     return true;
 }
 
-// The jobs of 3 .. RV_MANY_KMAX sequences k_leaf_multi_chain finishes under picker kind 1 (RV_MANY_CHAIN_MULTI): the rule, stated once
-// (many.takes_shared_launch(.., picker=, chain_multi=True) mirrors it).  As above, everything the kernel leaves out has to be impossible for the job:
+// The jobs of several sequences k_leaf_multi_chain finishes under picker kind 1: the rule, stated once for both forms of the kernel -- 3 .. RV_MANY_KMAX
+// sequences with RV_MANY_CHAIN_MULTI, RV_MANY_KMAX + 1 .. RV_MANY_WIDE_KMAX with RV_MANY_CHAIN_WIDE (many.takes_shared_launch(.., picker=, chain_multi=True /
+// chain_wide=True) mirrors it).  As above, everything the kernel leaves out has to be impossible for the job; none of the reasons depends on the number of
+// sequences:
 //   trim on, minl > 0, gap model 0 .. 2     no p-value cut, no untrimmed lists
-//   weights 0 .. RV_LEAF_MCHAIN_WMAX        scores of up to sixteen paths in 32 bits (rv_leaf_multi_chain.hip derives the bound)
+//   weights 0 .. RV_LEAF_MCHAIN_WMAX        scores of up to 16 / 64 paths in 32 bits (rv_leaf_multi_chain.hip derives the bound for both forms)
 //   seedsize <= 0 or above the longest sequence   no match is that long: no seeds for the children
 //   maxmums <= 0 or >= the job's ranks      the cut is made on the matches of ONE sub-index, every one of them an inner node of the LCP-interval tree over the
 //                                           sub-index' ranks: a tree over len leaves has fewer than len inner nodes, and len <= the job's ranks <= 2048, so
 //                                           rem.align's default of 10 000 passes whatever the job
-bool many_chain_multi_admits(const rv_many *m, const ManyJob &jb, int minl) {
-    if (m->picker != 1 || !m->chain_multi) return false;
-    if (jb.k < 3 || jb.k > RV_MANY_KMAX || !jb.clean || jb.ranks > RV_LEAF_N) return false;
+bool many_chain_k_admits(const rv_many *m, const ManyJob &jb, int minl, int kmin, int kmax, int64_t on) {
+    if (m->picker != 1 || !on) return false;
+    if (jb.k < kmin || jb.k > kmax || !jb.clean || jb.ranks > RV_LEAF_N) return false;
     const rv_picker_args &a = m->pargs;
     int64_t longest = 0;
     for (int q = 0; q < jb.k; q++) longest = std::max(longest, m->lens[jb.seq0 + (size_t)q]);
@@ -323,6 +330,8 @@ bool many_chain_multi_admits(const rv_many *m, const ManyJob &jb, int minl) {
     if (a.maxmums > 0 && a.maxmums < jb.ranks) return false;
     return true;
 }
+bool many_chain_multi_admits(const rv_many *m, const ManyJob &jb, int minl) { return many_chain_k_admits(m, jb, minl, 3, RV_MANY_KMAX, m->chain_multi); }
+bool many_chain_wide_admits(const rv_many *m, const ManyJob &jb, int minl) { return many_chain_k_admits(m, jb, minl, RV_MANY_KMAX + 1, RV_MANY_WIDE_KMAX, m->chain_wide); }
 
 // anchors of the handle's last run -> records of `job`, or (job < 0) of the job whose first sequence holds the first member
 int many_collect(rv_many *m, rv_index *h, int job, const std::vector<int> &order, const std::vector<int64_t> &abeg, const std::vector<int64_t> &bbeg) {
@@ -513,8 +522,8 @@ int many_round(rv_many *m, const std::vector<int> &order, size_t lo, size_t hi, 
 // nothing here); k_leaf_multi then finishes every job in one workgroup and lower-cases its text.  No handle is involved beyond
 // the stream and the read-back buffer of the shared one: the launches of a round do not depend on the number of jobs.
 // kmax: the sample bound of the round's class and the form of k_leaf_multi that takes it -- RV_MANY_KMAX, or RV_MANY_WIDE_KMAX for the
-// rounds of jobs of 17 .. 64 sequences (RV_MANY_WIDE).  redo != NULL: the round of picker kind 1 (RV_MANY_CHAIN_MULTI, kmax = RV_MANY_KMAX) -- its leaf
-// launch is k_leaf_multi_chain, and the jobs that kernel flags come back in *redo for the ordinary path: their anchors are dropped, their text is not taken
+// rounds of jobs of 17 .. 64 sequences (RV_MANY_WIDE).  redo != NULL: the round of picker kind 1 (RV_MANY_CHAIN_MULTI with kmax = RV_MANY_KMAX, RV_MANY_CHAIN_WIDE
+// with kmax = RV_MANY_WIDE_KMAX) -- its leaf launch is that form of k_leaf_multi_chain, and the jobs that kernel flags come back in *redo for the ordinary path: their anchors are dropped, their text is not taken
 int many_round_multi(rv_many *m, const std::vector<int> &order, size_t lo, size_t hi, int minl, int minn, rv_align_stats *total, int kmax, std::vector<int> *redo = nullptr) {
     RV_TRY(many_handle(m, &m->hs));
     rv_index *h = m->hs;
@@ -571,7 +580,6 @@ int many_round_multi(rv_many *m, const std::vector<int> &order, size_t lo, size_
     a.anchors = m->dAn.as<RvLeafMultiAnchor>(); a.an_pos = m->dAnPos.as<uint16_t>();
     a.stats = (unsigned long long *)(d_max + 6); a.err = d_max + 2;
     if (redo) {
-        if (kmax != RV_MANY_KMAX) { rv_set_error("rv_many_run: the chain form of the leaf kernel takes jobs of at most %d sequences", RV_MANY_KMAX); return -1; }
         for (auto &o : m->fwd) if (o.first == "RV_LEAF_ACAP" && o.second >= 0) a.stage_cap = (u32)std::min<int64_t>(a.stage_cap, o.second);      // (test hook, as for k_leaf_chain)
         std::vector<u32> pre(J, 0u);
         if (m->chain_flag > 0) for (size_t s = 0; s < J; s += (size_t)m->chain_flag) pre[s] = 16u;      // test hook: every chain_flag-th job of the round counts as flagged
@@ -580,7 +588,7 @@ int many_round_multi(rv_many *m, const std::vector<int> &order, size_t lo, size_
         RV_HIP(hipStreamSynchronize(q));
         RvLeafMultiChainArgs c;
         c.wscore = (int32_t)m->pargs.wscore; c.wpen = (int32_t)m->pargs.wpen; c.gcmodel = m->pargs.gcmodel; c.flags = m->dFlag.as<u32>();
-        RV_TRY(rv_leaf_multi_chain_launch(q, a, c, (int)J));
+        RV_TRY(rv_leaf_multi_chain_launch(q, a, c, (int)J, kmax));
     } else
     RV_TRY(rv_leaf_multi_launch(q, a, (int)J, kmax));
     m->info[4]++;
@@ -869,13 +877,14 @@ int many_run(rv_many *m, int minl, int minn, rv_align_stats *total) {
     int64_t nwlarge = 0;
     for (const ManyJob &jb : m->jobs) nwlarge += is_wide_large(jb) ? 1 : 0;
     const bool take_wide_large = nwlarge > 0 && nwlarge >= m->wide_large_min;
-    std::vector<int> worder, wlorder, cmorder;
-    const bool chain = m->picker == 1;      // the shared classes finish with built-in-picker kernels: under kind 1 only many_chain_admits' and
-                                            // many_chain_multi_admits' jobs share launches
+    std::vector<int> worder, wlorder, cmorder, cworder;
+    const bool chain = m->picker == 1;      // the shared classes finish with built-in-picker kernels: under kind 1 only many_chain_admits',
+                                            // many_chain_multi_admits' and many_chain_wide_admits' jobs share launches
     for (int j = 0; j < nj; j++) {
         ManyJob &jb = m->jobs[(size_t)j];
         jb.arr_off = -1;
-        if (chain) { if (many_chain_admits(m, jb, minl)) order.push_back(j); else if (many_chain_multi_admits(m, jb, minl)) cmorder.push_back(j); else rest.push_back(j); }
+        if (chain) { if (many_chain_admits(m, jb, minl)) order.push_back(j); else if (many_chain_multi_admits(m, jb, minl)) cmorder.push_back(j);
+                     else if (many_chain_wide_admits(m, jb, minl)) cworder.push_back(j); else rest.push_back(j); }
         else if (jb.k == 2 && jb.ranks <= RV_LEAF_N && jb.clean) order.push_back(j);
         else if (take_large && is_large(jb)) lorder.push_back(j);
         else if (take_large_multi && is_large_multi(jb)) lmorder.push_back(j);
@@ -892,6 +901,7 @@ int many_run(rv_many *m, int minl, int minn, rv_align_stats *total) {
     std::stable_sort(worder.begin(), worder.end(), by_size);
     std::stable_sort(wlorder.begin(), wlorder.end(), by_size);
     std::stable_sort(cmorder.begin(), cmorder.end(), by_size);
+    std::stable_sort(cworder.begin(), cworder.end(), by_size);
     for (size_t lo = 0; lo < order.size();) {
         size_t hi = lo; int64_t sum = 0;
         while (hi < order.size() && (hi == lo || sum + m->jobs[(size_t)order[hi]].ranks <= lim)) sum += m->jobs[(size_t)order[hi++]].ranks;
@@ -902,6 +912,12 @@ int many_run(rv_many *m, int minl, int minn, rv_align_stats *total) {
         size_t hi = lo; int64_t sum = 0;
         while (hi < cmorder.size() && (hi == lo || sum + m->jobs[(size_t)cmorder[hi]].ranks <= lim)) sum += m->jobs[(size_t)cmorder[hi++]].ranks;
         RV_TRY(many_round_multi(m, cmorder, lo, hi, minl, minn, total, RV_MANY_KMAX, &rest));
+        lo = hi;
+    }
+    for (size_t lo = 0; lo < cworder.size();) {     // picker kind 1, the jobs of 17 .. 64 sequences (RV_MANY_CHAIN_WIDE): rounds of their own
+        size_t hi = lo; int64_t sum = 0;
+        while (hi < cworder.size() && (hi == lo || sum + m->jobs[(size_t)cworder[hi]].ranks <= lim)) sum += m->jobs[(size_t)cworder[hi++]].ranks;
+        RV_TRY(many_round_multi(m, cworder, lo, hi, minl, minn, total, RV_MANY_WIDE_KMAX, &rest));
         lo = hi;
     }
     if (chain) std::sort(rest.begin(), rest.end());
@@ -994,6 +1010,7 @@ int rv_many_option(rv_many *m, const char *name, int64_t value) {
     if (strcmp(name, "RV_MANY_WIDE") == 0) { m->wide = value != 0; return 0; }
     if (strcmp(name, "RV_MANY_CHAIN") == 0) { m->chain = value != 0; return 0; }
     if (strcmp(name, "RV_MANY_CHAIN_MULTI") == 0) { m->chain_multi = value != 0; return 0; }
+    if (strcmp(name, "RV_MANY_CHAIN_WIDE") == 0) { m->chain_wide = value != 0; return 0; }
     if (strcmp(name, "RV_MANY_CHAIN_FLAG") == 0) { if (value < 0) { rv_set_error("RV_MANY_CHAIN_FLAG: negative"); return -1; } m->chain_flag = value; return 0; }
     if (strcmp(name, "RV_MANY_WIDE_LARGE_MIN") == 0) { if (value < 0) { rv_set_error("RV_MANY_WIDE_LARGE_MIN: negative"); return -1; } m->wide_large_min = value; return 0; }
     if (strcmp(name, "RV_MANY_LARGE_MAX") == 0) { if (value < 0) { rv_set_error("RV_MANY_LARGE_MAX: negative"); return -1; } m->large_max = value; return 0; }

@@ -9,7 +9,7 @@ inside the same call.  The built-in picker (as `index.align_builtin`) unless `pi
 (schemes.graphmumpicker: trim the overlaps, chain, split on the largest match of the chain) -- what `reveal refine` gets from
 `rem.align` for a bubble, and what `index.set_picker(args)` + `align_builtin` give a stand-alone index of the job.  The shared
 classes below all finish with built-in-picker kernels, so with a picker set none of them takes a job, whatever its switch says:
-the jobs run the ordinary way with the picker in host C++ (`info["ordinary"]`).  With the switch RV_MANY_CHAIN on
+without one of the three chain switches the jobs run the ordinary way with the picker in host C++ (`info["ordinary"]`).  With the switch RV_MANY_CHAIN on
 (`align_many(.., chain=True)`, `Batch.option("RV_MANY_CHAIN", 1)` or the environment variable; off by default, and it means
 something with a picker only) the pair jobs of at most 2048 ranks share their launches all the same, finished by the leaf kernel
 with the picker's decision for two samples as its pick stage (csrc/rv_leaf_chain.hip), when the options leave the picker nothing a
@@ -25,6 +25,13 @@ chain over k paths, a three-way split with a `rest` child), when trim is on, min
 seedsize and maxmums is at least the job's ranks (`takes_shared_launch(.., picker=args, chain_multi=True)`).  A job the kernel cannot finish
 (where the reference's trim_overlap raises) is flagged and runs the ordinary way
 inside the same call.  The results do not depend on the switch.
+
+With the switch RV_MANY_CHAIN_WIDE on (`align_many(.., chain_wide=True)`, `Batch.option("RV_MANY_CHAIN_WIDE", 1)` or the environment variable; off by
+default, independent of every other switch, and it means something with a picker only) the jobs of 17 .. 64 sequences and at most 2048 ranks share
+their launches under the picker too, in rounds of their own: layout and index build of the small RV_MANY_WIDE rounds and one launch of the 64-sample
+form of the same kernel (a wavefront holds one predecessor of a chain step, a lane per path; the gap costs over up to 64 paths by reductions over the
+wavefront), under the same conditions (`takes_shared_launch(.., picker=args, chain_wide=True)`); flagged jobs as above.  Under a picker the jobs of
+17 .. 64 sequences above 2048 ranks and the jobs of more than 64 sequences always run the ordinary way.  The results do not depend on the switch.
 
 Jobs of three and more sequences -- a bubble of a graph of N genomes carries up to N -- run the ordinary way unless the switch
 RV_MANY_MULTI is on (`align_many(.., multi=True)`, `Batch.option("RV_MANY_MULTI", 1)` or the environment variable; off by default).
@@ -71,7 +78,7 @@ MULTI_KMAX = 16            # RV_MANY_KMAX: sequences of a job the shared launche
 WIDE_KMAX = 64             # RV_MANY_WIDE_KMAX: sequences of a job the shared launches take with RV_MANY_WIDE (17 .. 64)
 WIDE_LARGE_MIN = 8         # default of RV_MANY_WIDE_LARGE_MIN: fewer jobs of 17 .. 64 sequences above 2048 ranks in a call stay ordinary
 CHAIN_WMAX = 65536         # RV_LEAF_CHAIN_WMAX: weights up to this keep the chain's scores in 32 bits on the device
-CHAIN_MULTI_WMAX = 1024    # RV_LEAF_MCHAIN_WMAX: the same for chains over up to sixteen paths (gain factor n (n - 1) / 2 <= 120)
+CHAIN_MULTI_WMAX = 1024    # RV_LEAF_MCHAIN_WMAX: the same for chains over up to 16 paths (gain factor n (n - 1) / 2 <= 120) and over up to 64 (csrc/rv_leaf_multi_chain.hip)
 LARGE_MAX = 1 << 17        # default of RV_MANY_LARGE_MAX: ranks of the largest pair job the shared launches take with RV_MANY_LARGE
 
 
@@ -115,14 +122,15 @@ def picker_struct(args):
 
 
 def takes_shared_launch(seqs, multi=False, large=False, large_max=LARGE_MAX, large_multi=False, wide=False, picker=None, chain=False, minlength=20,
-                        chain_multi=False):
+                        chain_multi=False, chain_wide=False):
     """whether the library builds and finishes this job in the shared launches; multi: with RV_MANY_MULTI on; large: with RV_MANY_LARGE
     on and RV_MANY_LARGE_MAX = large_max (in a call with at least RV_MANY_LARGE_MIN such jobs, and with rounds that hold the job);
     large_multi: with RV_MANY_LARGE_MULTI on (in a call with at least RV_MANY_LARGE_MULTI_MIN such jobs, and with rounds that hold the job);
     wide: with RV_MANY_WIDE on -- jobs of 17 .. 64 sequences, above 2048 ranks in a call with at least RV_MANY_WIDE_LARGE_MIN such jobs;
     picker: a schemes.PickerArgs -- with the reference's default picker set (the other switches then mean nothing); chain: with RV_MANY_CHAIN on;
     minlength: of the run (csrc/rv_many.hip many_chain_admits); chain_multi: with RV_MANY_CHAIN_MULTI on -- under a picker, the jobs of 3 .. 16
-    sequences (csrc/rv_many.hip many_chain_multi_admits)"""
+    sequences (csrc/rv_many.hip many_chain_multi_admits); chain_wide: with RV_MANY_CHAIN_WIDE on -- under a picker, the jobs of 17 .. 64 sequences
+    (csrc/rv_many.hip many_chain_wide_admits)"""
     k = len(seqs)
     ranks = sum(len(s) for s in seqs) + k
     if any(b"\0" in s for s in seqs):
@@ -131,8 +139,8 @@ def takes_shared_launch(seqs, multi=False, large=False, large_max=LARGE_MAX, lar
         if ranks > LEAF_RANKS:
             return False
         A = picker_struct(picker)
-        if 3 <= k <= MULTI_KMAX:
-            return bool(chain_multi and A.trim and int(minlength) > 0 and 0 <= A.wscore <= CHAIN_MULTI_WMAX and 0 <= A.wpen <= CHAIN_MULTI_WMAX
+        if 3 <= k <= MULTI_KMAX or (chain_wide and MULTI_KMAX < k <= WIDE_KMAX):
+            return bool((chain_multi if k <= MULTI_KMAX else chain_wide) and A.trim and int(minlength) > 0 and 0 <= A.wscore <= CHAIN_MULTI_WMAX and 0 <= A.wpen <= CHAIN_MULTI_WMAX
                         and (A.seedsize <= 0 or A.seedsize > max(len(s) for s in seqs)) and (A.maxmums <= 0 or A.maxmums >= ranks))
         if not chain or k != 2:
             return False
@@ -221,7 +229,7 @@ class Batch:
                     iv = 1
                 self.option(name, iv)
         for name in ("RV_MANY_KEEP", "RV_MANY_ROUND", "RV_MANY_WAVE_MAX", "RV_MANY_MULTI", "RV_MANY_LARGE", "RV_MANY_LARGE_MAX", "RV_MANY_LARGE_MIN",
-                     "RV_MANY_LARGE_MULTI", "RV_MANY_LARGE_MULTI_MIN", "RV_MANY_WIDE", "RV_MANY_WIDE_LARGE_MIN", "RV_MANY_CHAIN", "RV_MANY_CHAIN_MULTI"):
+                     "RV_MANY_LARGE_MULTI", "RV_MANY_LARGE_MULTI_MIN", "RV_MANY_WIDE", "RV_MANY_WIDE_LARGE_MIN", "RV_MANY_CHAIN", "RV_MANY_CHAIN_MULTI", "RV_MANY_CHAIN_WIDE"):
             v = os.environ.get(name)
             if v is not None and v.strip():
                 self.option(name, int(v))
@@ -304,7 +312,7 @@ class Batch:
 
 
 def align_many(jobs, minlength=20, minn=2, sa64=False, toupper=True, batch=None, multi=None, large=None, large_multi=None, wide=None, picker=None, chain=None,
-               chain_multi=None):
+               chain_multi=None, chain_wide=None):
     """jobs: a list of jobs, each a list of (name, seq) or of plain sequences (two or more, none empty; every sequence is a sample
     of its own, like the inputs of `reveal rem`).  -> (results, info): results[j] = dict(anchors=[(l, (pos, ..)), ..], T=final text
     `s0$s1$..` lower-cased where aligned), positions in the coordinates of the job's own text -- what index.align_builtin gives a
@@ -318,7 +326,8 @@ def align_many(jobs, minlength=20, minn=2, sa64=False, toupper=True, batch=None,
     index.set_picker(args) + align_builtin give a stand-alone index of it, the anchors `rem.align` chooses for a bubble; None: the built-in
     picker, as ever (a batch that is reused goes back to it).  `chain`: True / False sets RV_MANY_CHAIN (with a picker: the pair jobs of at most
     2048 ranks through the shared launches, see the module docstring) for this and later runs of the batch; None leaves it.  `chain_multi`: the
-    same for RV_MANY_CHAIN_MULTI (with a picker: the jobs of 3 .. 16 sequences and at most 2048 ranks through the shared launches)."""
+    same for RV_MANY_CHAIN_MULTI (with a picker: the jobs of 3 .. 16 sequences and at most 2048 ranks through the shared launches), `chain_wide`: the
+    same for RV_MANY_CHAIN_WIDE (with a picker: the jobs of 17 .. 64 sequences and at most 2048 ranks through the shared launches)."""
     if isinstance(jobs, (str, bytes, bytearray)) or not hasattr(jobs, "__iter__"):
         raise error("jobs is a list of jobs")
     if int(minlength) < 0 or int(minn) < 2:
@@ -332,6 +341,8 @@ def align_many(jobs, minlength=20, minn=2, sa64=False, toupper=True, batch=None,
         b.option("RV_MANY_CHAIN", 1 if chain else 0)
     if chain_multi is not None:
         b.option("RV_MANY_CHAIN_MULTI", 1 if chain_multi else 0)
+    if chain_wide is not None:
+        b.option("RV_MANY_CHAIN_WIDE", 1 if chain_wide else 0)
     if multi is not None:
         b.option("RV_MANY_MULTI", 1 if multi else 0)
     if large is not None:

@@ -7,7 +7,15 @@ sort order) without the `active` list, the entry of rv_chain's dictionaries that
 chains where that happens), and how often the kernel's give-ups would fire (1: trim_overlap raises, 2: no predecessor, 8: another match carries the
 split's offsets) -- a call that gives up falls back to the reference's picker here, as a flagged job reruns the ordinary way.  The scan's order is
 pinned separately (many_chain_multi_cases.kernel_scan, tests/test_cpu_many_chain_multi.py).  CPU only.  Prints per set: jobs equal to the golden file,
-picker calls, calls per give-up."""
+picker calls, calls per give-up.
+
+`--cases wide`: the same over tests/many_chain_wide_cases.py and tests/golden/many_chain_wide.json -- jobs of 17 .. 64 sequences, the 64-sample form of
+the kernel.  That form holds ONE predecessor of a chain step per wavefront where the 16-sample form holds four; the predecessors are still taken by
+ascending sort order, the step of activation is the match at which a predecessor first ends in front, and the choice is the maximum of the one key,
+whatever the order the candidates are looked at in.  What it does differently is the gap cost over up to 64 paths, and `gapcost_lanes` restates that
+arithmetic lane by lane -- a lane per sample, the set's paths taken in turn, two sums per lane, wave sums with the lanes outside the set contributing
+zero -- and is what the picker uses under `--cases wide` (tests/test_cpu_many_chain_wide.py also holds it against `gapcost` on random gaps with ties)."""
+import argparse
 import os
 import sys
 
@@ -29,7 +37,32 @@ def gapcost(d, model):
     return sum(abs(D[i] - D[j]) for i in range(k) for j in range(i + 1, k))
 
 
-def make_picker(seqs, args, stat, orig):
+def gapcost_lanes(d_by_sample, model, lanes=64):
+    """the gap cost as the 64-sample form of the kernel computes it: d_by_sample = {sample: d} over the set's paths.  Lane s holds d of sample s (0
+    outside the set) and D = |d|; for every path j of the set in ascending order the lane reads D[j] (readlane) and, if it is in the set itself, adds
+    |D - D[j]| for j above it (its share of the pairs) and counts the D[j] below its own, ties by lane (its rank).  star-avg: |wave sum of d| / k with C's
+    truncation; star-med: wave sum of D over the lanes whose rank is k / 2 (exactly one); sum of pairs: wave sum of the shares"""
+    inset = [s in d_by_sample for s in range(lanes)]
+    d = [d_by_sample.get(s, 0) for s in range(lanes)]
+    D = [abs(x) for x in d]
+    k = sum(inset)
+    acc, rank = [0] * lanes, [0] * lanes
+    if model != 1:
+        for j in (s for s in range(lanes) if inset[s]):
+            od = D[j]
+            for lane in range(lanes):
+                if inset[lane]:
+                    if j > lane:
+                        acc[lane] += abs(D[lane] - od)
+                    rank[lane] += 1 if (od < D[lane] or (od == D[lane] and j < lane)) else 0
+    if model == 1:
+        return int(abs(sum(d)) / k)
+    if model == 2:
+        return sum(D[lane] if inset[lane] and rank[lane] == k // 2 else 0 for lane in range(lanes))
+    return sum(acc)
+
+
+def make_picker(seqs, args, stat, orig, wide=False):
     ends, at = [], 0
     for s in seqs:
         at += len(s) + 1
@@ -120,7 +153,8 @@ def make_picker(seqs, args, stat, orig):
                     if p >= 0 and step[p] is None:
                         step[p] = e
                     sc = 0 if p < 0 else score[p]
-                    tmpw = sc + gain - args.wpen * gapcost(d, GCMODEL[args.gcmodel])
+                    gap = gapcost_lanes(dict(zip(order, d)), GCMODEL[args.gcmodel]) if wide else gapcost(d, GCMODEL[args.gcmodel])
+                    tmpw = sc + gain - args.wpen * gap
                     key = (tmpw, sc, -(0 if p < 0 else ((step[p] + 1) << 12) | p))
                     if best is None or key > best[0]:
                         best = (key, p)
@@ -153,7 +187,15 @@ def make_picker(seqs, args, stat, orig):
 
 
 def main():
-    import many_chain_multi_cases as cm
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--cases", choices=("multi", "wide"), default="multi", help="multi: jobs of 3 .. 16 sequences (many_chain_multi_cases); wide: 17 .. 64 (many_chain_wide_cases)")
+    opt = ap.parse_args()
+    if opt.cases == "wide":
+        import many_chain_wide_cases as cm
+        matches = lambda rec, an, T: cm.same(rec, an, cm.sha(T))
+    else:
+        import many_chain_multi_cases as cm
+        matches = lambda rec, an, T: (an, cm.sha(T)) == rec
     import pin_oracle
     from reveal_amd import schemes
     refmod = pin_oracle.load_refmod(False)
@@ -165,12 +207,12 @@ def main():
     for name, kw in cm.SETS:
         stat, same = {}, 0
         for j, (cls, seqs) in enumerate(jobs):
-            schemes.GraphPicker.graphmumpicker = make_picker([s.upper() for s in seqs], cm.picker_args(kw), stat, orig)
+            schemes.GraphPicker.graphmumpicker = make_picker([s.upper() for s in seqs], cm.picker_args(kw), stat, orig, wide=opt.cases == "wide")
             try:
                 an, T = cm.rem_align_job(seqs, indexmod=refmod, **kw)
             finally:
                 schemes.GraphPicker.graphmumpicker = orig
-            ok = (an, cm.sha(T)) == golden[name][j]
+            ok = matches(golden[name][j], an, T)
             same += ok
             if not ok:
                 print("  %s job %d (%s) differs" % (name, j, cls))

@@ -4,6 +4,7 @@
     python tools/time_many.py [--jobs 10000] [--lmin 50] [--lmax 1000] [--reps 5] [--minlength 20] [--wave-max N] [--only loop|many] [--check]
                               [--seqs K] [--multi 0|1|ab] [--large 0|1|ab] [--large-multi 0|1|ab] [--large-max R] [--large-min J]
                               [--wide 0|1|ab] [--wide-large-min J] [--no-cut] [--sites] [--picker [--rem-jobs N]]
+                              [--chain-wide [--save-digests FILE] [--compare-digests FILE]]
 
 Workload: J jobs of 2 x L bases, L uniform in lmin .. lmax, 1 % substitutions.  The two sides run alternately, `reps` times each:
   loop   rv_reset, rv_add_sample / rv_add_sequence x 2, rv_construct, rv_align_builtin, rv_fetch_anchors, the text -- per job, straight at
@@ -29,9 +30,15 @@ as its pick stage), RV_MANY_CHAIN off (every job the ordinary way, the picker in
 picker sides job by job, and the jobs of the rem.align loop with it.
 --picker --seqs K (K = 3 .. 16): the same for jobs of K sequences -- RV_MANY_CHAIN_MULTI on (the multi-sample leaf kernel with the picker as its pick
 stage), off (the ordinary path), and the built-in picker with RV_MANY_MULTI on (k_leaf_multi on the same jobs).  With RV_LIB_DIR set to a build from
-before the switch the first side is left out: the other two are that build's ordinary path and its k_leaf_multi, the baselines of the parent commit."""
+before the switch the first side is left out: the other two are that build's ordinary path and its k_leaf_multi, the baselines of the parent commit.
+--chain-wide (with --seqs K, K = 17 .. 64; implies --picker; use --sites): the same for jobs of K sequences -- RV_MANY_CHAIN_WIDE on (the 64-sample form of
+that kernel), off (the ordinary path), and the built-in picker with RV_MANY_WIDE on (k_leaf_multi<64> on the same jobs).  The chain side's
+info["ordinary"] is the number of jobs the kernel flagged.  --save-digests FILE writes a digest per job of the picker side's anchors (the chain side, or
+the ordinary side where the build has none); --compare-digests FILE counts the jobs whose digest differs from that file's: two builds run in a process
+each, and this is how their results are compared."""
 import argparse
 import ctypes
+import hashlib
 import json
 import os
 import statistics
@@ -182,7 +189,7 @@ def main_picker(a, jobs, bases):
     from reveal_amd import many, rem, schemes
     args = schemes.PickerArgs(maxmums=10000)      # (rem.align's defaults)
     sides = {}
-    switch = "RV_MANY_CHAIN" if a.seqs == 2 else "RV_MANY_CHAIN_MULTI"
+    switch = "RV_MANY_CHAIN" if a.seqs == 2 else ("RV_MANY_CHAIN_MULTI" if a.seqs <= 16 else "RV_MANY_CHAIN_WIDE")
     for name, pk, chain in (("chain", args, 1), ("ordinary", args, 0), ("builtin", None, 0)):
         b = many.Batch(False)
         b.set_picker(pk)
@@ -193,7 +200,7 @@ def main_picker(a, jobs, bases):
                 print("%s is not known to this build: no chain side" % switch)
                 continue
         if a.seqs > 2 and pk is None:
-            b.option("RV_MANY_MULTI", 1)
+            b.option("RV_MANY_MULTI" if a.seqs <= 16 else "RV_MANY_WIDE", 1)
         if a.wave_max is not None:
             b.option("RV_MANY_WAVE_MAX", a.wave_max)
         run_many_c(b, jobs[:64], a.minlength)
@@ -207,6 +214,17 @@ def main_picker(a, jobs, bases):
         out[name + "_s"] = t; out[name + "_median_s"] = statistics.median(t); out[name + "_spread_s"] = max(t) - min(t); out[name + "_info"] = s["batch"].info()
         print("%-8s: runs %s s; median %.4f s, spread (max - min) %.4f s, %.0f jobs/s; info %r"
               % (name, " ".join("%.4f" % x for x in t), out[name + "_median_s"], out[name + "_spread_s"], a.jobs / out[name + "_median_s"], out[name + "_info"]))
+    if a.save_digests or a.compare_digests:
+        side = "chain" if "chain" in sides else "ordinary"
+        dig = [hashlib.sha256(repr(x).encode()).hexdigest()[:12] for x in as_lists(*sides[side]["res"])]
+        if a.save_digests:
+            with open(a.save_digests, "w") as f:
+                json.dump(dig, f)
+        if a.compare_digests:
+            with open(a.compare_digests) as f:
+                other = json.load(f)
+            out["digest_bad_jobs"] = sum(1 for p, q in zip(dig, other) if p != q) + abs(len(dig) - len(other))
+            print("digests: %d of %d jobs of the %s side differ from %s" % (out["digest_bad_jobs"], a.jobs, side, a.compare_digests))
     nrem = min(a.rem_jobs, len(jobs))
     rem_res = []
     t = time.perf_counter()
@@ -217,7 +235,8 @@ def main_picker(a, jobs, bases):
     print("rem.align per job: %d jobs in %.2f s, %.2f ms a job, %.0f jobs/s" % (nrem, out["rem_s"], 1e3 * out["rem_per_job_s"], nrem / out["rem_s"]))
     if "chain" not in sides:
         print(json.dumps(out))
-        return 0
+        return 1 if out.get("digest_bad_jobs") else 0
+    out["flagged"] = out["chain_info"]["ordinary"]
     out["chain_vs_rem"] = out["rem_per_job_s"] / (out["chain_median_s"] / a.jobs)
     out["ordinary_vs_chain"] = out["ordinary_median_s"] / out["chain_median_s"]
     out["chain_vs_builtin"] = out["chain_median_s"] / out["builtin_median_s"]
@@ -240,7 +259,7 @@ def main_picker(a, jobs, bases):
         print("check : %d of %d jobs differ between chain and ordinary (%d anchors; %d jobs differ from the built-in picker); %d of %d differ from rem.align's final text"
               % (out["check_bad_jobs"], a.jobs, out["anchors"], out["differ_from_builtin"], bad, nrem))
     print(json.dumps(out))
-    return 1 if out.get("check_bad_jobs") or out.get("check_bad_rem_jobs") else 0
+    return 1 if out.get("check_bad_jobs") or out.get("check_bad_rem_jobs") or out.get("digest_bad_jobs") else 0
 
 
 def main():
@@ -265,9 +284,16 @@ def main():
     ap.add_argument("--no-cut", action="store_true", help="leave lmax as given when jobs of --seqs K sequences pass 2048 ranks")
     ap.add_argument("--picker", action="store_true", help="the reference's default picker: RV_MANY_CHAIN on / off, the built-in picker, rem.align per job; no loop")
     ap.add_argument("--rem-jobs", type=int, default=1000, help="--picker: jobs of the rem.align loop")
+    ap.add_argument("--chain-wide", action="store_true", help="--picker for jobs of --seqs K = 17 .. 64 sequences: RV_MANY_CHAIN_WIDE on / off, the built-in picker with RV_MANY_WIDE")
+    ap.add_argument("--save-digests", default=None, help="--picker: write a digest per job of the picker side's anchors to this file")
+    ap.add_argument("--compare-digests", default=None, help="--picker: count the jobs whose digest differs from this file's")
     a = ap.parse_args()
-    if a.picker and not 2 <= a.seqs <= 16:
-        ap.error("--picker times jobs of 2 .. 16 sequences")
+    if a.chain_wide:
+        if not 17 <= a.seqs <= 64:
+            ap.error("--chain-wide wants jobs of 17 .. 64 sequences: --seqs K")
+        a.picker = True
+    elif a.picker and not 2 <= a.seqs <= 16:
+        ap.error("--picker times jobs of 2 .. 16 sequences (17 .. 64: --chain-wide)")
     if [a.multi, a.large, a.large_multi, a.wide].count("ab") > 1:
         ap.error("one switch at a time: --multi ab, --large ab, --large-multi ab or --wide ab")
     if a.wide is not None and not 17 <= a.seqs <= 64:
