@@ -230,6 +230,10 @@ struct Align {
     // (builtin_cascade); builtin_finish copies the rest when they still belong there
     size_t early_sent = 0; u32 *early_l = nullptr; int64_t *early_pos = nullptr;
     bool leaf_chain = false; RvLeafChainArgs chain_args{}; int64_t chain_roots = 0;      // rv_leaf_chain_route
+    // ... the round's jobs (text begins of their first / second sequences, ascending: 2 x chain_njobs), on the host and on the device; what the chain pick of
+    // the level pipeline (k_pick_chain) took; the jobs the host flagged; whether the level's records are the device's picks (one per sub-index) or its whole list
+    std::vector<int64_t> chain_begin; const int64_t *d_chain_begin = nullptr; int chain_njobs = 0;
+    int64_t chain_pick_subs = 0; std::vector<int> chain_host_flags; bool recs_are_picks = false;
     size_t leaf_na = 0;          // anchors of the leaf launches of the last run: they stay in the pinned staging buffer (hLeafOut: pos[2 na], l[na]) until fetched
     void release() {
         // (the side streams may still be writing pinned buffers that go back to the process-wide pool below: after an aborted run nothing else waits for them)
@@ -461,12 +465,13 @@ int rv_set_preselect(rv_index *h, int64_t maxmums) {
 
 }  // extern "C"
 
-int rv_leaf_chain_route(rv_index *h, const rv_picker_args *args, u32 *flags) {
-    if (!h || (args && !flags)) { rv_set_error("rv_leaf_chain_route: bad arguments"); return -1; }
+int rv_leaf_chain_route(rv_index *h, const rv_picker_args *args, u32 *flags, const int64_t *job_begin, const int64_t *d_job_begin, int njobs) {
+    if (!h || (args && (!flags || !job_begin || !d_job_begin || njobs <= 0))) { rv_set_error("rv_leaf_chain_route: bad arguments"); return -1; }
     if (!h->al) h->al = new Align();
     Align *a = h->al;
     a->leaf_chain = args != nullptr;
-    a->chain_roots = 0;
+    a->chain_roots = 0; a->chain_pick_subs = 0; a->chain_host_flags.clear();
+    a->chain_begin.clear(); a->d_chain_begin = nullptr; a->chain_njobs = 0;
     if (args) {
         if (a->picker != 0 || args->wscore < 0 || args->wpen < 0 || args->wscore > RV_LEAF_CHAIN_WMAX || args->wpen > RV_LEAF_CHAIN_WMAX || args->gcmodel < 0 || args->gcmodel > 2) {
             rv_set_error("rv_leaf_chain_route: options the chain form of the leaf kernel does not take");
@@ -474,10 +479,25 @@ int rv_leaf_chain_route(rv_index *h, const rv_picker_args *args, u32 *flags) {
             return -1;
         }
         a->chain_args.wscore = (int32_t)args->wscore; a->chain_args.wpen = (int32_t)args->wpen; a->chain_args.gcmodel = args->gcmodel; a->chain_args.flags = flags;
+        a->chain_args.root_job = nullptr;
+        a->pargs = *args;
+        a->chain_begin.assign(job_begin, job_begin + 2 * (size_t)njobs); a->d_chain_begin = d_job_begin; a->chain_njobs = njobs;
     }
     return 0;
 }
+// the job (of the routed round) that holds text position p of sample `side`
+static int chain_job_of(const Align *a, int side, int64_t p) {
+    const int64_t *beg = a->chain_begin.data() + (side ? a->chain_njobs : 0);
+    const int j = (int)(std::upper_bound(beg, beg + a->chain_njobs, p) - beg) - 1;
+    return j < 0 ? 0 : j;
+}
 int64_t rv_leaf_chain_roots(const rv_index *h) { return h && h->al ? h->al->chain_roots : 0; }
+int64_t rv_pick_chain_subs(const rv_index *h) { return h && h->al ? h->al->chain_pick_subs : 0; }
+int rv_leaf_chain_host_flags(const rv_index *h, const int **jobs) {
+    if (!h || !h->al) { if (jobs) *jobs = nullptr; return 0; }
+    if (jobs) *jobs = h->al->chain_host_flags.data();
+    return (int)h->al->chain_host_flags.size();
+}
 
 int rv_run_multi_scan(rv_index *h, const sa_t *SA, const lcp_t *LCP, const uint8_t *BWT, int64_t m, int minl, int minn, int mems,
                       std::vector<u32> &l, std::vector<int32_t> &n, std::vector<int64_t> &off, std::vector<uint16_t> &so,
@@ -496,13 +516,23 @@ static int leaf_launch(rv_index *h) {
     hipStream_t ls = leaf_flip ? a->leaf_stream2 : a->leaf_stream;
     const int slot = (a->level == 0) ? RV_LEVEL_BUFS : a->cur;
     if (a->leaf_pending[slot]) RV_HIP(hipEventSynchronize(a->ev_leaf[slot]));     // (cannot happen: commit waits first)
-    RV_TRY(droots.reserve(roots.size() * sizeof(RvLeafRoot)));
+    // (the chain form: the job of every root behind the roots, in the same copy)
+    const size_t roots_bytes = roots.size() * sizeof(RvLeafRoot), table_bytes = roots_bytes + (a->leaf_chain ? roots.size() * sizeof(u32) : 0);
+    RV_TRY(droots.reserve(table_bytes));
     // pinned staging (one per ping-pong slot): a pageable copy would make the host wait for the leaf stream to drain
     HBuf &hroots = a->hLeafRoots[leaf_flip];
     if (a->roots_inflight[leaf_flip]) RV_HIP(hipEventSynchronize(a->ev_roots[leaf_flip]));     // copy of two levels ago (long done)
-    RV_TRY(hroots.reserve(roots.size() * sizeof(RvLeafRoot)));
-    memcpy(hroots.p, roots.data(), roots.size() * sizeof(RvLeafRoot));
-    RV_HIP(hipMemcpyAsync(droots.p, hroots.p, roots.size() * sizeof(RvLeafRoot), hipMemcpyHostToDevice, ls));
+    RV_TRY(hroots.reserve(table_bytes));
+    memcpy(hroots.p, roots.data(), roots_bytes);
+    if (a->leaf_chain) {
+        u32 *rj = (u32 *)(hroots.as<uint8_t>() + roots_bytes);
+        for (size_t r = 0; r < roots.size(); r++) {
+            const bool on_a = roots[r].a0 < roots[r].a1;
+            rj[r] = (u32)chain_job_of(a, on_a ? 0 : 1, on_a ? roots[r].a0 : roots[r].b0);
+        }
+        a->chain_args.root_job = (const u32 *)(droots.as<uint8_t>() + roots_bytes);
+    }
+    RV_HIP(hipMemcpyAsync(droots.p, hroots.p, table_bytes, hipMemcpyHostToDevice, ls));
     RV_HIP(hipEventRecord(a->ev_roots[leaf_flip], ls));
     a->roots_inflight[leaf_flip] = true;
     RvLeafArgs la;
@@ -516,7 +546,7 @@ static int leaf_launch(rv_index *h) {
     la.err = a->lf_counters + 2;
     {
         Workspace lw; lw.stream = ls;
-        if (a->leaf_chain) { RV_TRY(rv_leaf_chain_launch(lw, la, a->chain_args, (int)roots.size())); a->chain_roots = (int64_t)roots.size(); }
+        if (a->leaf_chain) { RV_TRY(rv_leaf_chain_launch(lw, la, a->chain_args, (int)roots.size())); a->chain_roots += (int64_t)roots.size(); }
         else RV_TRY(rv_leaf_launch(lw, la, (int)roots.size()));
     }
     RV_HIP(hipEventRecord(a->ev_leaf[slot], ls));
@@ -793,7 +823,18 @@ int rv_frontier_scan(rv_index *h) {
         // built-in picker without tracing: the device keeps only the record the picker would take.  The sub-index starts of this
         // level came with the previous commit's table upload (a pageable H2D copy here would wait for the stream to drain and
         // expose the launch latency of the whole scan).
-        const int64_t *d_ss = (a->full_only && (a->level > 0 || a->cur_dev_ok)) ? a->d_next_ss : nullptr;
+        // (the chain route: the device's pick needs the level's intervals and flag bytes as well; a level without them sends its whole list to the host)
+        const int64_t *d_ss = (a->full_only && (a->level > 0 || a->cur_dev_ok) && (!a->leaf_chain || a->cur_dev_ok)) ? a->d_next_ss : nullptr;
+        RvPickChainArgs pc;
+        memset(&pc, 0, sizeof pc);
+        if (a->leaf_chain && d_ss) {
+            pc.nodes = a->d_next_nodes; pc.flags = a->d_next_flags;
+            pc.wscore = a->chain_args.wscore; pc.wpen = a->chain_args.wpen; pc.gcmodel = a->chain_args.gcmodel;
+            pc.cap = (u32)std::max<int64_t>(0, std::min<int64_t>(h->ws.opt.pick_chain_cap, RV_PICK_CHAIN_CAP_MAX));
+            pc.job_flags = a->chain_args.flags; pc.job_begin = a->d_chain_begin; pc.njobs = a->chain_njobs;
+            for (int s2 = 0; s2 < ns; s2++) if (!(a->use_leaf && a->lv.n[(size_t)s2] <= RV_LEAF_N)) a->chain_pick_subs++;
+        }
+        a->recs_are_picks = d_ss != nullptr;
         a->early_done = false; a->early_bubble = false;
         const bool early = d_ss && a->cur_dev_ok && !h->ws.opt.no_early_split;
         a->hook_early = early;
@@ -816,7 +857,7 @@ int rv_frontier_scan(rv_index *h) {
             d_ps = (const int64_t *)(buf.as<uint8_t>() + o1);
         }
         RV_TRY(rv_run_pair_scan(h, cur_sa(h), cur_lcp(h), cur_bwt(h), a->lv.m, a->minl, a->recs, a->dErr.as<u32>(), &err, d_ss, ns, level_hook, early || a->leaf_launch_due,
-                                (d_ss && a->cur_dev_ok) ? a->d_next_tsub : nullptr, d_ps, ns, a->presel));
+                                (d_ss && a->cur_dev_ok) ? a->d_next_tsub : nullptr, d_ps, ns, a->presel, (a->leaf_chain && d_ss) ? &pc : nullptr));
         if (a->presel_on && !a->full_only) a->presel_d2h += (int64_t)a->recs.size();
         RV_TRY(report_dev_err(err));
         int si = 0;
@@ -1096,11 +1137,12 @@ static bool pair_intervals(const rv_index *h, const Level &lv, int s, int64_t ou
 //  - more than two samples: tile -> sub-index table (the multi-sample picker looks sub-indices up per candidate)
 //  - two samples, untraced: the level's split can be decided on the device if each of its sub-indices owns at most one
 //    interval per sample (rv_decide.hip): node intervals, "finished by the leaf kernel" flags, tiles.
+static_assert(RV_DECIDE_MAX_SUBS == 65536, "the default of the option RV_DECIDE_MAX_SUBS (rv_common.h)");
 static void prep_level_tables(rv_index *h, const Level &nx, int64_t m_next, bool tsub_on_device = false) {
     Align *a = h->al;
     const int nsn = nx.size();
     a->next_ss.assign(nx.off.begin(), nx.off.end()); a->next_ss.push_back(m_next);
-    a->next_dev_ok = a->full_only && nsn > 0 && nsn <= RV_DECIDE_MAX_SUBS && m_next > 0;
+    a->next_dev_ok = a->full_only && nsn > 0 && nsn <= std::min<int64_t>(RV_DECIDE_MAX_SUBS, h->ws.opt.decide_max_subs) && m_next > 0;      // (RV_DECIDE_MAX_SUBS: test hook, lowers the bound)
     if (a->next_dev_ok && a->multi) {
         // more than two samples: one (begin, end) slot per sample and sub-index; a sub-index with two intervals of one sample
         // (multi-contig inputs) sends the level to the host path
@@ -1727,6 +1769,42 @@ static void pick_one(rv_index *h, int s, PickScratch &X, PickRes &R, RvGraphIv g
                                                  (int)(X.pk_soff[(size_t)k + 1] - X.pk_soff[(size_t)k]), X.pk_ssc[(size_t)k]);
     }
 }
+// the chain route of rv_many's handle (picker 0, rv_leaf_chain_route) at a level whose whole match list came to the host: rv_pick_chain's decision for
+// sub-index s of two samples -> 1 and the pick (the trimmed match), 0 none, < 0 the picker failed (the caller flags the job).  The shared text holds many
+// sequences per sample; the picker only ever looks at differences of positions on a path, so every path is taken relative to 0.
+static int chain_host_pick(rv_index *h, int s, PickScratch &X, RvPairRec &out) {
+    Align *a = h->al;
+    const Level &lv = a->lv;
+    int64_t ab[4];
+    if (!pair_intervals(h, lv, s, ab)) return -1;
+    const int64_t first = a->mum_first[(size_t)s], cnt = a->nmums[(size_t)s];
+    X.pk_l.clear(); X.pk_n.clear(); X.pk_off.assign(1, 0); X.pk_mso.clear(); X.pk_mpos.clear();
+    for (int64_t k = first; k < first + cnt; k++) {
+        const RvPairRec &r = a->recs[(size_t)k];
+        X.pk_l.push_back(r.l); X.pk_n.push_back(2);
+        X.pk_mso.push_back(0); X.pk_mpos.push_back((int64_t)r.a); X.pk_mso.push_back(1); X.pk_mpos.push_back((int64_t)r.b);
+        X.pk_off.push_back((int64_t)X.pk_mpos.size());
+    }
+    const int64_t sb[2] = {0, 0}, ib[2] = {ab[0], ab[2]}, ie[2] = {ab[1], ab[3]};
+    const size_t scap = X.pk_l.size(), mcap = X.pk_mpos.size();
+    X.pk_sl.resize(scap); X.pk_sn.resize(scap); X.pk_soff.resize(scap + 1); X.pk_sso.resize(std::max<size_t>(mcap, 1)); X.pk_spos.resize(std::max<size_t>(mcap, 1));
+    X.pk_ssc.resize(scap); X.pk_srt.resize(scap);
+    uint16_t pso[2] = {0, 0}; int64_t ppos[2] = {0, 0};
+    rv_picker_out po;
+    memset(&po, 0, sizeof po);
+    po.pick_so = pso; po.pick_pos = ppos; po.member_cap = 2;
+    po.seed_cap = (int64_t)scap; po.seed_member_cap = (int64_t)std::max<size_t>(mcap, 1);
+    po.seed_l = X.pk_sl.data(); po.seed_n = X.pk_sn.data(); po.seed_off = X.pk_soff.data(); po.seed_so = X.pk_sso.data(); po.seed_pos = X.pk_spos.data();
+    po.seed_score = X.pk_ssc.data(); po.seed_right = X.pk_srt.data();
+    const int pr = rv_pick_chain(&a->pargs, 2, (int64_t)X.pk_l.size(), X.pk_l.data(), X.pk_n.data(), X.pk_off.data(), X.pk_mso.data(), X.pk_mpos.data(), 2,
+                                 sb, ib, ie, a->minl, &po);
+    if (pr < 0) return -1;
+    if (pr == 0 || po.pick_members != 2 || po.nleft + po.nright > 0) return pr == 0 ? 0 : -1;      // (a seed: the admission rule excludes it)
+    out.l = po.pick_l; out.rank = a->recs[(size_t)first].rank;
+    for (int q2 = 0; q2 < 2; q2++) (pso[q2] == 0 ? out.a : out.b) = (sa_t)ppos[q2];
+    return 1;
+}
+
 // every not-seeded sub-index of the level with matches; on several threads when the level holds enough of them (RV_PICK_THREADS: 0 = up to eight, 1 = none)
 static void pick_level(rv_index *h, std::vector<PickRes> &res) {
     Align *a = h->al;
@@ -1898,6 +1976,23 @@ static int builtin_levels(rv_index *h, int stop_subs) {
                     }
                 }
                 if (chain_pick) { sp.assign(pk_pos.begin(), pk_pos.begin() + members); best = 0; pk_members = members; }
+            } else
+            if (!a->multi && a->leaf_chain) {
+                // the chain route (rv_leaf_chain_route): no sub-index is decided by the longest-match rule.  The level's records are the device's chain picks
+                // (k_pick_chain: at most one per sub-index, the trimmed match) -- or, for a level without device tables, the sub-index' whole list: the
+                // host's picker on it (rv_pick_chain, as pick_one calls it); what it cannot decide flags the job
+                if (!a->recs_are_picks) a->chain_pick_subs++;      // (rv_frontier_scan counts the ones the device was asked for)
+                if (want == 2 && cnt > 0) {
+                    if (a->recs_are_picks) {
+                        if (cnt != 1) { rv_set_error("chain route: %lld picks for sub-index %d", (long long)cnt, s); return -1; }
+                        best = first; bl = a->recs[(size_t)first].l;
+                    } else {
+                        RvPairRec pk;
+                        const int pr = chain_host_pick(h, s, gpx, pk);
+                        if (pr < 0) a->chain_host_flags.push_back(chain_job_of(a, 0, (int64_t)a->recs[(size_t)first].a));
+                        else if (pr == 1) { a->recs[(size_t)first] = pk; best = first; bl = pk.l; }
+                    }
+                }
             } else
             if (!a->multi) {
                 if (want == 2)

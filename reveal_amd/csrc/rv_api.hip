@@ -705,7 +705,7 @@ static int pair_topk(rv_index *h, const RvPairRec *recs, u32 total, const int64_
 
 int rv_run_pair_scan(rv_index *h, const sa_t *SA, const lcp_t *LCP, const uint8_t *BWT, int64_t m, int minl, std::vector<RvPairRec> &out,
                      const u32 *d_err, u32 *err_out, const int64_t *d_sub_start, int nsubs, int (*after_pick)(rv_index *), bool use_hook,
-                     const int *d_tile_sub, const int64_t *d_presel_start, int presel_subs, int64_t presel) {
+                     const int *d_tile_sub, const int64_t *d_presel_start, int presel_subs, int64_t presel, const RvPickChainArgs *chain) {
     out.clear();
     if (err_out) *err_out = 0;
     if (m <= 1) {
@@ -741,6 +741,10 @@ int rv_run_pair_scan(rv_index *h, const sa_t *SA, const lcp_t *LCP, const uint8_
                                    bbest.as<unsigned long long>(), picks, d_sub_start ? nsubs : 0, ev_a, ev_b));
         if (d_sub_start) {
             // the built-in picker only wants the best record of each sub-index: pick on the device straight from the slots
+            // (the chain route of rv_many's handle: the reference's default picker's choice instead, one wavefront per sub-index -- rv_pick_chain.hip)
+            if (chain) RV_TRY(rv_pick_chain_launch(h->ws, bslot.as<RvPairRec>(), bovf.as<RvPairRec>(), (u32)std::min<size_t>(vcap, 0xffffffffu), tilecnt, tileovf, ntile,
+                                                   d_sub_start, nsubs, picks, bcnt.as<u32>(), d_err, *chain));
+            else
             RV_TRY(rv_pick_slots_launch(h->ws, bslot.as<RvPairRec>(), bovf.as<RvPairRec>(), (u32)std::min<size_t>(vcap, 0xffffffffu), tilecnt, tileovf, ntile,
                                         d_sub_start, nsubs, bbest.as<unsigned long long>(), picks, bcnt.as<u32>(), d_err, d_tile_sub, ceil_div(m, RV_TSUB_TILE)));
             // The one host round trip of a level.  The host waits for the picks only (an event behind the picker kernels), not for

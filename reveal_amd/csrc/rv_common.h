@@ -110,7 +110,9 @@ void rv_set_error(const char *fmt, ...);
     X(cas_witness_pass, "RV_CAS_WITNESS_PASS", 0) \
     X(cap_limit, "RV_CAP_LIMIT", 0) \
     X(cap_sites, "RV_CAP_SITES", -1) \
-    X(many_chain_multi, "RV_MANY_CHAIN_MULTI", 0)
+    X(many_chain_multi, "RV_MANY_CHAIN_MULTI", 0) \
+    X(pick_chain_cap, "RV_PICK_CHAIN_CAP", 1024) \
+    X(decide_max_subs, "RV_DECIDE_MAX_SUBS", 65536)
 struct RvOptions {
 #define RV_X_(f, name, def) int64_t f = def;
     RV_OPTION_LIST(RV_X_)

@@ -172,7 +172,8 @@ int rv_run_pair_scan(rv_index *h, const sa_t *SA, const lcp_t *LCP, const uint8_
                      const u32 *d_err, u32 *err_out, const int64_t *d_sub_start, int nsubs,   // d_sub_start != NULL: only the best record per sub-index
                      int (*after_pick)(rv_index *), bool use_hook,
                      const int *d_tile_sub = nullptr,                                        // ... tile -> sub-index table of the level (optional, speeds the picker's look-ups)
-                     const int64_t *d_presel_start = nullptr, int presel_subs = 0, int64_t presel = 0);   // rv_set_preselect: of every sub-index (starts on the device, presel_subs + 1 of them) only the `presel` longest records come back                        // ... and a hook called once the picker kernels are queued
+                     const int64_t *d_presel_start = nullptr, int presel_subs = 0, int64_t presel = 0,
+                     const struct RvPickChainArgs *chain = nullptr);      // chain != NULL (with d_sub_start): the chain pick of k_pick_chain (rv_pick_chain.hip) per sub-index instead of the longest record;    // rv_set_preselect: of every sub-index (starts on the device, presel_subs + 1 of them) only the `presel` longest records come back                        // ... and a hook called once the picker kernels are queued
 
 // text, shared inverse and separators in HBM without an index (rv_api.hip); maxlcp = window size of bubble_sort
 int rv_text_only(rv_index *h, u32 maxlcp);
@@ -190,9 +191,16 @@ int rv_ensure_working_text(rv_index *h);
 int rv_working_text_begin(rv_index *h, hipStream_t side);
 
 // rv_align.hip
-// rv_many's own handle only (not part of the ABI, and not rv_set_picker): the leaf launches of the handle's next runs use k_leaf_chain
-// (rv_leaf_chain.hip) with these picker options, flags = one zeroed word per root of the frontier on the device; args == NULL: k_leaf again.
-// rv_leaf_chain_roots: the roots of the last such launch, in frontier order (root r = word r of flags).
-int rv_leaf_chain_route(rv_index *h, const rv_picker_args *args, u32 *flags);
+// rv_many's own handle only (not part of the ABI, and not rv_set_picker): the handle's next runs make the reference's default picker's decisions for two
+// samples on the device, with these picker options -- their leaf launches use k_leaf_chain (rv_leaf_chain.hip), and the sub-indices above RV_LEAF_N ranks
+// of a level get their pick from k_pick_chain (rv_pick_chain.hip) in place of the longest-match kernel; a->picker stays 0.  flags = one zeroed word per
+// JOB on the device; job_begin / d_job_begin = the text begins of the jobs' first sequences, then of their second ones (2 x njobs, each half ascending),
+// on the host (copied) and on the device (kept by the caller until the run ends): a root or sub-index of any level sets the word of the job that holds
+// it.  args == NULL: k_leaf and the longest match again.
+// rv_leaf_chain_roots: the roots of the chain leaf launches since the route was set; rv_pick_chain_subs: the sub-indices above RV_LEAF_N ranks a chain pick was asked for (k_pick_chain, or the host's picker at a level without device tables);
+// rv_leaf_chain_host_flags: the jobs the host flagged (a level without device tables whose sub-index the host's picker could not decide).
+int rv_leaf_chain_route(rv_index *h, const rv_picker_args *args, u32 *flags, const int64_t *job_begin = nullptr, const int64_t *d_job_begin = nullptr, int njobs = 0);
+int64_t rv_pick_chain_subs(const rv_index *h);
+int rv_leaf_chain_host_flags(const rv_index *h, const int **jobs);
 int64_t rv_leaf_chain_roots(const rv_index *h);
 void rv_align_free(rv_index *h);

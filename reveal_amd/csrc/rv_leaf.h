@@ -37,8 +37,10 @@ int rv_leaf_launch(Workspace &ws, const RvLeafArgs &a, int nroots);
 struct RvLeafChainArgs {
     int32_t wscore, wpen;                                    // 0 .. RV_LEAF_CHAIN_WMAX
     int gcmodel;                                             // 0 sumofpairs, 1 star-avg, 2 star-med
-    u32 *flags;                                              // one word per root, zeroed by the caller: != 0 -- the root was not finished here (1: the reference's own
-                                                             // trim_overlap raises, 2: broken chain, 4 / 8: k_leaf's error bits, 16: rv_many's test hook); its anchors are to be dropped
+    u32 *flags;                                              // one word per JOB, zeroed by the caller: != 0 -- a root of the job was not finished here (1: the reference's own
+                                                             // trim_overlap raises, 2: broken chain, 4 / 8: k_leaf's error bits, 16: rv_many's test hook; 32 / 64: k_pick_chain's,
+                                                             // rv_scan.h); the job's anchors are to be dropped
+    const u32 *root_job;                                     // the job of every root of the launch: a whole job in a small round, a sub-index of one, at any level, in a large one
 };
 int rv_leaf_chain_launch(Workspace &ws, const RvLeafArgs &a, const RvLeafChainArgs &c, int nroots);
 // lower-cases the matched text of the anchors the leaf launches wrote (reveal.c:1230-1234), once, when the run ends

@@ -1,4 +1,5 @@
-// rv_leaf_chain.hip -- the leaf kernel with the reference's default picker as its pick stage (k_leaf_chain), for rv_many's small pair jobs.
+// rv_leaf_chain.hip -- the leaf kernel with the reference's default picker as its pick stage (k_leaf_chain), for rv_many's pair jobs: the whole job where it has at
+// most RV_LEAF_N ranks (RV_MANY_CHAIN), and the sub-indices of larger jobs once they are leaf-sized (RV_MANY_CHAIN_LARGE; the picks above are rv_pick_chain.hip's).
 //
 // `reveal refine --method reveal_rem` aligns a bubble with schemes.graphmumpicker (reveal/schemes.py:197-361): trim the overlaps of the sub-index'
 // matches, chain them, split on the largest match of the chain.  rv_pick_chain (rv_chain.hip, with pk_trim_overlap of rv_pick.h and rv_chain) is that
@@ -54,8 +55,13 @@ __device__ inline int gap2(int d0, int d1, int model) {
     return D0 > D1 ? D0 - D1 : D1 - D0;
 }
 
+// the flag word of the root's JOB (the cold path: a root that cannot be finished).  The roots of a launch are whole jobs in a small round and sub-indices of
+// jobs, at any level, in a large one: the host ships the job of every root with the launch (found among the round's text begins, rv_align.hip leaf_launch).
+// (Searched here instead, inlined, the begins cost a VGPR and seven spilled SGPRs; out of line, 48 B of scratch.)
+__device__ inline u32 *job_flag(const RvLeafChainArgs &P) { return P.flags + P.root_job[blockIdx.x]; }
+
 struct PickChain {
-    static __device__ __forceinline__ void fail(const RvLeafArgs &, const RvLeafChainArgs &P, u32 bits) { atomicOr(&P.flags[blockIdx.x], bits); }
+    static __device__ __forceinline__ void fail(const RvLeafArgs &, const RvLeafChainArgs &P, u32 bits) { atomicOr(job_flag(P), bits); }
 
     static __device__ __forceinline__ bool pick(const RvLeafArgs &, const RvLeafChainArgs &P, const LeafSub &X, u32 &L, int64_t &pa, int64_t &pb) {
         __shared__ u64 eA[LN];
@@ -152,7 +158,7 @@ struct PickChain {
                 }
                 WSYNC();
             }
-            if (raised) { if (lane == 0) atomicOr(&P.flags[blockIdx.x], 1u); return false; }
+            if (raised) { if (lane == 0) atomicOr(job_flag(P), 1u); return false; }
             m = top + 1;
         }
         if (m == 0) return false;
@@ -194,7 +200,7 @@ struct PickChain {
                 }
             }
             const u64 w1 = wave_max_u64(b1);
-            if (w1 == 0) { if (lane == 0) atomicOr(&P.flags[blockIdx.x], 2u); return false; }      // (a match that does not lie behind `left`: rv_chain fails)
+            if (w1 == 0) { if (lane == 0) atomicOr(job_flag(P), 2u); return false; }      // (a match that does not lie behind `left`: rv_chain fails)
             const u32 w2 = 0xFFFFFFFFu - (u32)wave_max_u64((u64)(0xFFFFFFFFu - (b1 == w1 ? b2 : 0xFFFFFFFFu)));
             const u32 link = w2 < 4096u ? LINK_L : (w2 & 0xFFFu);
             const u32 score = (u32)(w1 >> 32) ^ 0x80000000u;
@@ -205,7 +211,7 @@ struct PickChain {
         // back from `right`: the largest of the chain, of equal lengths the last in chain order = the first met on the way back
         int split = -1, bl = 0, guard = 0;
         for (u32 c = linkR; c != LINK_L; c = (u32)(la[c] >> 32) & 0xFFFFu) {
-            if (c >= (u32)m || ++guard > m) { if (lane == 0) atomicOr(&P.flags[blockIdx.x], 2u); return false; }      // (broken back-pointer chain)
+            if (c >= (u32)m || ++guard > m) { if (lane == 0) atomicOr(job_flag(P), 2u); return false; }      // (broken back-pointer chain)
             const int l = getB((int)c).l;
             if (l > bl) { bl = l; split = (int)c; }
         }
@@ -220,7 +226,7 @@ __global__ __launch_bounds__(NT) void k_leaf_chain(RvLeafArgs A, RvLeafChainArgs
 
 int rv_leaf_chain_launch(Workspace &ws, const RvLeafArgs &a, const RvLeafChainArgs &c, int nroots) {
     if (nroots <= 0) return 0;
-    if (a.trace || !c.flags || c.wscore < 0 || c.wpen < 0 || c.wscore > RV_LEAF_CHAIN_WMAX || c.wpen > RV_LEAF_CHAIN_WMAX || c.gcmodel < 0 || c.gcmodel > 2) {
+    if (a.trace || !c.flags || !c.root_job || c.wscore < 0 || c.wpen < 0 || c.wscore > RV_LEAF_CHAIN_WMAX || c.wpen > RV_LEAF_CHAIN_WMAX || c.gcmodel < 0 || c.gcmodel > 2) {
         rv_set_error("rv_leaf_chain_launch: arguments the chain form of the leaf kernel does not take");
         return -1;
     }

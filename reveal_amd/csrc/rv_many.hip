@@ -66,6 +66,12 @@
 // sequences many_chain_wide_admits names share their launches too, in rounds of their own -- layout and index build of the small RV_MANY_WIDE rounds
 // (many_round_multi with kmax = 64) and ONE launch of the 64-sample form of k_leaf_multi_chain.  Flags and test hooks as for RV_MANY_CHAIN_MULTI.  Under a
 // picker the jobs of 17 .. 64 sequences above RV_LEAF_N ranks, and every job of more than 64 sequences, stay ordinary.
+// RV_MANY_CHAIN_LARGE (off by default, independent of every other switch; it means something under kind 1 only): the pair jobs many_chain_large_admits names
+// -- more than RV_LEAF_N and at most min(RV_MANY_LARGE_MAX, 2^17) ranks -- share their launches too, in rounds of their own, from RV_MANY_CHAIN_LARGE_MIN such
+// jobs in a call on: layout, segmented index build and frontier of the RV_MANY_LARGE rounds (many_round with `large` and `redo`), and the level pipeline under
+// the chain route -- every sub-index above RV_LEAF_N ranks gets its pick from k_pick_chain (rv_pick_chain.hip: the picker's decision for two samples, a
+// wavefront per sub-index, in place of the longest-match kernel; k_decide and the early split as they are), the others drop into k_leaf_chain as they shrink.
+// The flag words are the jobs': a flag set by any launch of any level drops all of the job's anchors, leaves its text untaken and sends it to the ordinary path.
 // Size classes (DESIGN.md "Many small alignments" has the measurements): up to `wave_max` ranks (default 512) a wavefront per job,
 // four jobs per workgroup, no workgroup barrier; above, a workgroup of 256 threads per job.  Both hold 22.6 KB of LDS per workgroup:
 // seven workgroups per CU.
@@ -264,6 +270,7 @@ struct rv_many {
     int64_t chain = 0, chain_flag = 0;          // RV_MANY_CHAIN, RV_MANY_CHAIN_FLAG (test hook)
     int64_t chain_multi = 0;                    // RV_MANY_CHAIN_MULTI
     int64_t chain_wide = 0;                     // RV_MANY_CHAIN_WIDE
+    int64_t chain_large = 0, chain_large_min = RV_MANY_CHAIN_LARGE_MIN_DEFAULT;      // RV_MANY_CHAIN_LARGE, RV_MANY_CHAIN_LARGE_MIN
     std::vector<std::pair<std::string, int64_t>> fwd;      // switches for the internal handles
     // results of the last run
     bool ran = false;
@@ -274,6 +281,7 @@ struct rv_many {
     int64_t info[5] = {0, 0, 0, 0, 0};
     DBuf dJobs, dKJobs, dSA, dLCP, dBWT, dCnt;
     DBuf dFlag;                                 // rounds of k_leaf_chain: a word per job
+    DBuf dBeg;                                  // ... and the text begins of the jobs' first / second sequences
     DBuf dTxt, dMJobs, dAn, dAnPos;             // rounds of multi-sequence jobs: their text, jobs, anchors
     RvManyLargeBufs large_bufs;                      // rounds of large pair jobs: the scratch of their index build
     // scratch of a run
@@ -301,6 +309,26 @@ bool many_chain_admits(const rv_many *m, const ManyJob &jb, int minl) {
     const int64_t la = m->lens[jb.seq0], lb = m->lens[jb.seq0 + 1];
     if (!a.trim || minl <= 0) return false;
     if (a.wscore < 0 || a.wpen < 0 || a.wscore > RV_LEAF_CHAIN_WMAX || a.wpen > RV_LEAF_CHAIN_WMAX) return false;
+    if (a.gcmodel < 0 || a.gcmodel > 2) return false;
+    if (a.seedsize > 0 && a.seedsize <= std::max(la, lb)) return false;
+    if (a.maxmums > 0 && a.maxmums < std::min(la, lb)) return false;
+    return true;
+}
+
+// The pair jobs above RV_LEAF_N ranks the level pipeline finishes under picker kind 1 (RV_MANY_CHAIN_LARGE), its picks made by k_pick_chain and k_leaf_chain:
+// the rule, stated once (many.takes_shared_launch(.., picker=, chain_large=True) mirrors it).  It is many_chain_admits' with
+//   RV_LEAF_N < ranks <= min(RV_MANY_LARGE_MAX, 2^17)      positions and lengths of a sub-index in 17 bits, whatever RV_MANY_LARGE_MAX says
+//   weights 0 .. RV_LEAF_MCHAIN_WMAX = 1024               scores in 32 bits at 2^17 ranks (rv_pick_chain.hip derives the bound)
+//   seedsize <= 0 or above the longer sequence, maxmums <= 0 or at least the shorter one: as there
+// rem.align's defaults (10 000 / 10 000) admit every bubble `reveal refine` produces (alleles below 10 000 bases) and nothing with an allele of 10 000 or more.
+static_assert(RV_PICK_CHAIN_WMAX == RV_LEAF_MCHAIN_WMAX && RV_PICK_CHAIN_WMAX <= RV_LEAF_CHAIN_WMAX, "one weight bound for the class");
+bool many_chain_large_admits(const rv_many *m, const ManyJob &jb, int minl) {
+    if (m->picker != 1 || !m->chain_large) return false;
+    if (jb.k != 2 || !jb.clean || jb.ranks <= RV_LEAF_N || jb.ranks > std::min<int64_t>(m->large_max, RV_PICK_CHAIN_RANKS)) return false;
+    const rv_picker_args &a = m->pargs;
+    const int64_t la = m->lens[jb.seq0], lb = m->lens[jb.seq0 + 1];
+    if (!a.trim || minl <= 0) return false;
+    if (a.wscore < 0 || a.wpen < 0 || a.wscore > RV_LEAF_MCHAIN_WMAX || a.wpen > RV_LEAF_MCHAIN_WMAX) return false;
     if (a.gcmodel < 0 || a.gcmodel > 2) return false;
     if (a.seedsize > 0 && a.seedsize <= std::max(la, lb)) return false;
     if (a.maxmums > 0 && a.maxmums < std::min(la, lb)) return false;
@@ -387,7 +415,8 @@ int many_build(rv_many *m, hipStream_t q, const ManyDevJob *djobs, size_t J, siz
 }
 
 // one round of the shared launches: the jobs order[lo .. hi) (ascending size); large: jobs above RV_LEAF_N ranks (RV_MANY_LARGE); redo != NULL: the
-// round of picker kind 1 (RV_MANY_CHAIN) -- its leaf launch is k_leaf_chain, and the jobs that kernel flags come back in *redo for the ordinary path
+// round of picker kind 1 (RV_MANY_CHAIN; with large: RV_MANY_CHAIN_LARGE) -- its leaf launches are k_leaf_chain's, the picks of the level pipeline k_pick_chain's, and
+// the jobs a launch of any level flags come back in *redo for the ordinary path
 int many_round(rv_many *m, const std::vector<int> &order, size_t lo, size_t hi, int minl, int minn, rv_align_stats *total, bool large, std::vector<int> *redo = nullptr) {
     RV_TRY(many_handle(m, &m->hs));
     rv_index *h = m->hs;
@@ -403,7 +432,7 @@ int many_round(rv_many *m, const std::vector<int> &order, size_t lo, size_t hi, 
             RV_HIP(hipStreamSynchronize(h->ws.stream));
         }
     }
-    RV_TRY(rv_leaf_chain_route(h, redo ? &m->pargs : nullptr, redo ? m->dFlag.as<u32>() : nullptr));
+    if (!redo) RV_TRY(rv_leaf_chain_route(h, nullptr, nullptr));
     // text: every first sequence, then every second one
     std::vector<int> ord(order.begin() + (ptrdiff_t)lo, order.begin() + (ptrdiff_t)hi);
     std::vector<int64_t> abeg(J), bbeg(J), la(J), lb(J);
@@ -429,6 +458,14 @@ int many_round(rv_many *m, const std::vector<int> &order, size_t lo, size_t hi, 
     for (size_t s = 0; s < J; s++) bbeg[s] += ta;
     const int64_t n = ta + tb;
     RV_TRY(rv_upload(h));
+    if (redo) {      // the chain route: flags per job, a root or sub-index of any level finds its job among the text begins
+        std::vector<int64_t> beg(abeg);
+        beg.insert(beg.end(), bbeg.begin(), bbeg.end());
+        RV_TRY(m->dBeg.reserve(2 * J * sizeof(int64_t)));
+        RV_HIP(hipMemcpyAsync(m->dBeg.p, beg.data(), 2 * J * sizeof(int64_t), hipMemcpyHostToDevice, h->ws.stream));
+        RV_HIP(hipStreamSynchronize(h->ws.stream));
+        RV_TRY(rv_leaf_chain_route(h, &m->pargs, m->dFlag.as<u32>(), beg.data(), m->dBeg.as<int64_t>(), (int)J));
+    }
     // jobs, segment offsets, frontier tables
     std::vector<ManyDevJob> dj(J);
     std::vector<int64_t> meta(6 * J), node_first(J + 1), nodes(4 * J);
@@ -492,9 +529,15 @@ int many_round(rv_many *m, const std::vector<int> &order, size_t lo, size_t hi, 
     size_t nflag = 0;
     if (redo) {
         // the jobs the kernel did not finish: their anchors are dropped, their text is not taken from the round
-        if (rv_leaf_chain_roots(h) != (int64_t)J) { rv_set_error("rv_many_run: the chain leaf launch took %lld of the round's %lld jobs", (long long)rv_leaf_chain_roots(h), (long long)J); return -1; }
+        // (every job of a small round is a root of its one chain leaf launch; every job of a large round is above RV_LEAF_N ranks, so the level pipeline's
+        // chain pick was asked for each of the J roots at least -- or the host's picker, at a level without device tables -- and never the longest match)
+        if (!large && rv_leaf_chain_roots(h) != (int64_t)J) { rv_set_error("rv_many_run: the chain leaf launch took %lld of the round's %lld jobs", (long long)rv_leaf_chain_roots(h), (long long)J); return -1; }
+        const int *hflag = nullptr;
+        const int nhflag = rv_leaf_chain_host_flags(h, &hflag);
+        if (large && rv_pick_chain_subs(h) < (int64_t)J) { rv_set_error("rv_many_run: the chain pick took %lld sub-indices of a round of %lld jobs", (long long)rv_pick_chain_subs(h), (long long)J); return -1; }
         flag.resize(J);
         RV_HIP(hipMemcpy(flag.data(), m->dFlag.p, J * sizeof(u32), hipMemcpyDeviceToHost));
+        for (int k = 0; k < nhflag; k++) if (hflag[k] >= 0 && (size_t)hflag[k] < J) flag[(size_t)hflag[k]] |= 128u;
         std::vector<char> out((size_t)m->jobs.size(), 0);
         for (size_t s = 0; s < J; s++) if (flag[s]) { out[(size_t)ord[s]] = 1; redo->push_back(ord[s]); nflag++; }
         if (nflag) m->recs.erase(std::remove_if(m->recs.begin() + (ptrdiff_t)rec0, m->recs.end(), [&](const ManyRec &r) { return out[(size_t)r.job] != 0; }), m->recs.end());
@@ -877,13 +920,19 @@ int many_run(rv_many *m, int minl, int minn, rv_align_stats *total) {
     int64_t nwlarge = 0;
     for (const ManyJob &jb : m->jobs) nwlarge += is_wide_large(jb) ? 1 : 0;
     const bool take_wide_large = nwlarge > 0 && nwlarge >= m->wide_large_min;
-    std::vector<int> worder, wlorder, cmorder, cworder;
+    std::vector<int> worder, wlorder, cmorder, cworder, clorder;
+    // (picker kind 1, the pair jobs above RV_LEAF_N ranks: counted on their own against a threshold of their own)
+    const auto is_chain_large = [&](const ManyJob &jb) { return many_chain_large_admits(m, jb, minl) && jb.ranks <= lim; };
+    int64_t nclarge = 0;
+    for (const ManyJob &jb : m->jobs) nclarge += is_chain_large(jb) ? 1 : 0;
+    const bool take_chain_large = nclarge > 0 && nclarge >= m->chain_large_min;
     const bool chain = m->picker == 1;      // the shared classes finish with built-in-picker kernels: under kind 1 only many_chain_admits',
                                             // many_chain_multi_admits' and many_chain_wide_admits' jobs share launches
     for (int j = 0; j < nj; j++) {
         ManyJob &jb = m->jobs[(size_t)j];
         jb.arr_off = -1;
-        if (chain) { if (many_chain_admits(m, jb, minl)) order.push_back(j); else if (many_chain_multi_admits(m, jb, minl)) cmorder.push_back(j);
+        if (chain) { if (many_chain_admits(m, jb, minl)) order.push_back(j); else if (take_chain_large && is_chain_large(jb)) clorder.push_back(j);
+                     else if (many_chain_multi_admits(m, jb, minl)) cmorder.push_back(j);
                      else if (many_chain_wide_admits(m, jb, minl)) cworder.push_back(j); else rest.push_back(j); }
         else if (jb.k == 2 && jb.ranks <= RV_LEAF_N && jb.clean) order.push_back(j);
         else if (take_large && is_large(jb)) lorder.push_back(j);
@@ -902,6 +951,7 @@ int many_run(rv_many *m, int minl, int minn, rv_align_stats *total) {
     std::stable_sort(wlorder.begin(), wlorder.end(), by_size);
     std::stable_sort(cmorder.begin(), cmorder.end(), by_size);
     std::stable_sort(cworder.begin(), cworder.end(), by_size);
+    std::stable_sort(clorder.begin(), clorder.end(), by_size);
     for (size_t lo = 0; lo < order.size();) {
         size_t hi = lo; int64_t sum = 0;
         while (hi < order.size() && (hi == lo || sum + m->jobs[(size_t)order[hi]].ranks <= lim)) sum += m->jobs[(size_t)order[hi++]].ranks;
@@ -918,6 +968,12 @@ int many_run(rv_many *m, int minl, int minn, rv_align_stats *total) {
         size_t hi = lo; int64_t sum = 0;
         while (hi < cworder.size() && (hi == lo || sum + m->jobs[(size_t)cworder[hi]].ranks <= lim)) sum += m->jobs[(size_t)cworder[hi++]].ranks;
         RV_TRY(many_round_multi(m, cworder, lo, hi, minl, minn, total, RV_MANY_WIDE_KMAX, &rest));
+        lo = hi;
+    }
+    for (size_t lo = 0; lo < clorder.size();) {     // picker kind 1, the pair jobs above RV_LEAF_N ranks (RV_MANY_CHAIN_LARGE): rounds of their own
+        size_t hi = lo; int64_t sum = 0;
+        while (hi < clorder.size() && (hi == lo || sum + m->jobs[(size_t)clorder[hi]].ranks <= lim)) sum += m->jobs[(size_t)clorder[hi++]].ranks;
+        RV_TRY(many_round(m, clorder, lo, hi, minl, minn, total, true, &rest));
         lo = hi;
     }
     if (chain) std::sort(rest.begin(), rest.end());
@@ -994,7 +1050,7 @@ void rv_many_free(rv_many *m) {
     if (m->hs) rv_free(m->hs);
     if (m->ho) rv_free(m->ho);
     m->dJobs.release(); m->dKJobs.release(); m->dSA.release(); m->dLCP.release(); m->dBWT.release(); m->dCnt.release();
-    m->dTxt.release(); m->dMJobs.release(); m->dAn.release(); m->dAnPos.release(); m->dFlag.release();
+    m->dTxt.release(); m->dMJobs.release(); m->dAn.release(); m->dAnPos.release(); m->dFlag.release(); m->dBeg.release();
     m->large_bufs.release();
     delete m;
 }
@@ -1011,6 +1067,8 @@ int rv_many_option(rv_many *m, const char *name, int64_t value) {
     if (strcmp(name, "RV_MANY_CHAIN") == 0) { m->chain = value != 0; return 0; }
     if (strcmp(name, "RV_MANY_CHAIN_MULTI") == 0) { m->chain_multi = value != 0; return 0; }
     if (strcmp(name, "RV_MANY_CHAIN_WIDE") == 0) { m->chain_wide = value != 0; return 0; }
+    if (strcmp(name, "RV_MANY_CHAIN_LARGE") == 0) { m->chain_large = value != 0; return 0; }
+    if (strcmp(name, "RV_MANY_CHAIN_LARGE_MIN") == 0) { if (value < 0) { rv_set_error("RV_MANY_CHAIN_LARGE_MIN: negative"); return -1; } m->chain_large_min = value; return 0; }
     if (strcmp(name, "RV_MANY_CHAIN_FLAG") == 0) { if (value < 0) { rv_set_error("RV_MANY_CHAIN_FLAG: negative"); return -1; } m->chain_flag = value; return 0; }
     if (strcmp(name, "RV_MANY_WIDE_LARGE_MIN") == 0) { if (value < 0) { rv_set_error("RV_MANY_WIDE_LARGE_MIN: negative"); return -1; } m->wide_large_min = value; return 0; }
     if (strcmp(name, "RV_MANY_LARGE_MAX") == 0) { if (value < 0) { rv_set_error("RV_MANY_LARGE_MAX: negative"); return -1; } m->large_max = value; return 0; }

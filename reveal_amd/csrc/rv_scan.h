@@ -38,6 +38,24 @@ int rv_scan_pair_launch(Workspace &ws, const sa_t *SA, const lcp_t *LCP, int64_t
 int rv_pick_slots_launch(Workspace &ws, const RvPairRec *slots, const RvPairRec *ovf, u32 ovf_cap, const u32 *tilecnt, const u32 *tileovf, int64_t ntile,
                          const int64_t *sub_start, int nsubs, unsigned long long *best, RvPairRec *picks, u32 *ovf_counter, const u32 *err,
                          const int *tile_sub, int64_t ntsub);      // tile_sub (optional): sub-index of the first rank of every RV_TSUB_TILE ranks
+// The reference's default picker in place of the longest record (k_pick_chain, rv_pick_chain.hip; rv_many's handle under the chain route): picks[1 + s] =
+// the TRIMMED match schemes.graphmumpicker splits sub-index s on (its rank field: the sub-index' first rank), for every sub-index whose flag byte has
+// bit 0 clear; same header, same reset of *ovf_counter.  nodes: a0, a1, b0, b1 per sub-index and flags: one byte per sub-index, as k_decide reads them.
+// A sub-index the kernel cannot decide sets bits in the flag word of its JOB (job_begin: the ascending begins of the jobs' first sequences in the text,
+// njobs of them) and gets no pick: 1 the reference's own trim_overlap raises, 2 broken chain or a match outside the intervals, 32 more than `cap`
+// candidates, 64 an interval of 2^17 positions or more.  cap: at most RV_PICK_CHAIN_CAP_MAX (RV_PICK_CHAIN_CAP lowers it: test hook).
+#define RV_PICK_CHAIN_CAP_MAX 1024
+#define RV_PICK_CHAIN_WMAX 1024
+#define RV_PICK_CHAIN_RANKS (1 << 17)
+struct RvPickChainArgs {
+    const sa_t *nodes; const uint8_t *flags;
+    int32_t wscore, wpen;                                    // 0 .. RV_PICK_CHAIN_WMAX
+    int gcmodel;                                             // 0 sumofpairs, 1 star-avg, 2 star-med
+    u32 cap;
+    u32 *job_flags; const int64_t *job_begin; int njobs;
+};
+int rv_pick_chain_launch(Workspace &ws, const RvPairRec *slots, const RvPairRec *ovf, u32 ovf_cap, const u32 *tilecnt, const u32 *tileovf, int64_t ntile,
+                         const int64_t *sub_start, int nsubs, RvPairRec *picks, u32 *ovf_counter, const u32 *err, const RvPickChainArgs &c);
 // out holds RV_PAIR_HDR header records ({total, overflow count, *err, 0} as u32) followed by the packed records.
 // Resets *ovf_counter for the next scan.
 #define RV_PAIR_HDR 1

@@ -33,7 +33,11 @@ stage), off (the ordinary path), and the built-in picker with RV_MANY_MULTI on (
 before the switch the first side is left out: the other two are that build's ordinary path and its k_leaf_multi, the baselines of the parent commit.
 --chain-wide (with --seqs K, K = 17 .. 64; implies --picker; use --sites): the same for jobs of K sequences -- RV_MANY_CHAIN_WIDE on (the 64-sample form of
 that kernel), off (the ordinary path), and the built-in picker with RV_MANY_WIDE on (k_leaf_multi<64> on the same jobs).  The chain side's
-info["ordinary"] is the number of jobs the kernel flagged.  --save-digests FILE writes a digest per job of the picker side's anchors (the chain side, or
+--picker --chain-large (pair jobs; choose --lmin / --lmax above 1023, e.g. 1100 / 9999): the same for pair jobs above 2048 ranks -- RV_MANY_CHAIN_LARGE on (the
+level pipeline with the picker's decision made by k_pick_chain and k_leaf_chain), off (the ordinary path), and the built-in picker with RV_MANY_LARGE on (the
+same rounds with the longest-match kernel).  --chain-large-min J sets RV_MANY_CHAIN_LARGE_MIN.  With RV_LIB_DIR set to a build from before the switch the
+ordinary side alone is timed, on the same jobs: the yardstick.
+The chain side's info["ordinary"] is the number of jobs the kernel flagged.  --save-digests FILE writes a digest per job of the picker side's anchors (the chain side, or
 the ordinary side where the build has none); --compare-digests FILE counts the jobs whose digest differs from that file's: two builds run in a process
 each, and this is how their results are compared."""
 import argparse
@@ -190,6 +194,8 @@ def main_picker(a, jobs, bases):
     args = schemes.PickerArgs(maxmums=10000)      # (rem.align's defaults)
     sides = {}
     switch = "RV_MANY_CHAIN" if a.seqs == 2 else ("RV_MANY_CHAIN_MULTI" if a.seqs <= 16 else "RV_MANY_CHAIN_WIDE")
+    if a.chain_large:
+        switch = "RV_MANY_CHAIN_LARGE"
     for name, pk, chain in (("chain", args, 1), ("ordinary", args, 0), ("builtin", None, 0)):
         b = many.Batch(False)
         b.set_picker(pk)
@@ -201,6 +207,10 @@ def main_picker(a, jobs, bases):
                 continue
         if a.seqs > 2 and pk is None:
             b.option("RV_MANY_MULTI" if a.seqs <= 16 else "RV_MANY_WIDE", 1)
+        if a.chain_large and pk is None:
+            b.option("RV_MANY_LARGE", 1)
+        if a.chain_large and chain and a.chain_large_min is not None:
+            b.option("RV_MANY_CHAIN_LARGE_MIN", a.chain_large_min)
         if a.wave_max is not None:
             b.option("RV_MANY_WAVE_MAX", a.wave_max)
         run_many_c(b, jobs[:64], a.minlength)
@@ -285,12 +295,18 @@ def main():
     ap.add_argument("--picker", action="store_true", help="the reference's default picker: RV_MANY_CHAIN on / off, the built-in picker, rem.align per job; no loop")
     ap.add_argument("--rem-jobs", type=int, default=1000, help="--picker: jobs of the rem.align loop")
     ap.add_argument("--chain-wide", action="store_true", help="--picker for jobs of --seqs K = 17 .. 64 sequences: RV_MANY_CHAIN_WIDE on / off, the built-in picker with RV_MANY_WIDE")
+    ap.add_argument("--chain-large", action="store_true", help="--picker for pair jobs above 2048 ranks: RV_MANY_CHAIN_LARGE on / off, the built-in picker with RV_MANY_LARGE")
+    ap.add_argument("--chain-large-min", type=int, default=None, help="RV_MANY_CHAIN_LARGE_MIN")
     ap.add_argument("--save-digests", default=None, help="--picker: write a digest per job of the picker side's anchors to this file")
     ap.add_argument("--compare-digests", default=None, help="--picker: count the jobs whose digest differs from this file's")
     a = ap.parse_args()
     if a.chain_wide:
         if not 17 <= a.seqs <= 64:
             ap.error("--chain-wide wants jobs of 17 .. 64 sequences: --seqs K")
+        a.picker = True
+    elif a.chain_large:
+        if a.seqs != 2:
+            ap.error("--chain-large times pair jobs")
         a.picker = True
     elif a.picker and not 2 <= a.seqs <= 16:
         ap.error("--picker times jobs of 2 .. 16 sequences (17 .. 64: --chain-wide)")
