@@ -519,6 +519,15 @@ void rv_batch_free(rv_batch *b);
  * them (default 4), under the conditions of RV_MANY_CHAIN with the weights bounded by 1024: the rounds of RV_MANY_LARGE, the pick of every sub-index above 2048
  * ranks made by k_pick_chain (rv_pick_chain.hip) in place of the longest-match kernel, the smaller sub-indices finished by k_leaf_chain.  A job that a kernel
  * of any level flags (more than 1024 matches in a sub-index, or where the reference's trim_overlap raises) is dropped from the round and runs the ordinary way.
+ * With RV_MANY_CHAIN_LARGE_MULTI set (off by default, independent of every other switch; it means something under kind 1 only) the jobs of 3 .. 16 sequences and
+ * more than 2048, at most min(RV_MANY_LARGE_MAX, 2^17) ranks without a NUL byte share their launches under the picker too, in a call with at least
+ * RV_MANY_CHAIN_LARGE_MULTI_MIN of them (default 4), under the conditions of RV_MANY_CHAIN_MULTI with the weights bounded by 512 (2^17 ranks x 120 pairs of
+ * paths do not keep the scores in 32 bits at 1024): the rounds of RV_MANY_LARGE_MULTI, the scan of every level unfiltered, the pick of every sub-index made by
+ * k_pick_multi_chain (rv_pick_multi_chain.hip) in place of the longest-match kernels -- a match of a sample subset leaves a `rest` child --, or by the host's
+ * picker at a level without device tables.  maxmums has to be at least the job's ranks: rem.align's default of 10 000 admits jobs of up to 10 000 ranks only.
+ * A job that a kernel of any level flags (more than 512 candidates in a sub-index, where the reference's trim_overlap raises, twin offsets) is dropped from
+ * the round and runs the ordinary way.  Under kind 1 the jobs of 17 .. 64 sequences above 2048 ranks and the jobs of more than 64 sequences always run the
+ * ordinary way.
  *   rv_many_set_picker  kind 0: the built-in picker (the default); kind 1: the reference's default picker with *args (copied).  Holds for later runs,
  *                   like an option.  -1 with an error text: args == NULL with kind 1, an unknown gap cost model, any other kind
  *   rv_many_add     a job of k >= 2 non-empty sequences -> its id (0, 1, ..), < 0 on error (an empty sequence, k < 2, non-ASCII bytes)
@@ -546,7 +555,8 @@ void rv_batch_free(rv_batch *b);
  *                   shared launches; they count in out[1] then), RV_MANY_CHAIN_MULTI (0 / 1: under picker kind 1, the jobs of 3 .. 16 sequences named above
  *                   through shared launches; they count in out[1] then), RV_MANY_CHAIN_WIDE (0 / 1: the same for the jobs of 17 .. 64 sequences named
  *                   above), RV_MANY_CHAIN_LARGE (0 / 1: the same for the pair jobs above 2048 ranks named above), RV_MANY_CHAIN_LARGE_MIN (fewer such jobs
- *                   than this in a call stay ordinary, default 4), RV_MANY_CHAIN_FLAG (test hook: every n-th job of such a round is treated as flagged by the kernel --
+ *                   than this in a call stay ordinary, default 4), RV_MANY_CHAIN_LARGE_MULTI (0 / 1: the same for the jobs of 3 .. 16 sequences above 2048 ranks
+ *                   named above), RV_MANY_CHAIN_LARGE_MULTI_MIN (fewer such jobs than this in a call stay ordinary, default 4), RV_MANY_CHAIN_FLAG (test hook: every n-th job of such a round is treated as flagged by the kernel --
  *                   dropped from the round and run the ordinary way; 0: off); any other name: rv_set_option on the internal handles
  *   rv_many_arrays  test hook: which = RV_SA / RV_LCP of a shared-launch job in job-local positions, native element width; -2: not kept */
 typedef struct rv_many rv_many;

@@ -234,6 +234,10 @@ struct Align {
     // the level pipeline (k_pick_chain) took; the jobs the host flagged; whether the level's records are the device's picks (one per sub-index) or its whole list
     std::vector<int64_t> chain_begin; const int64_t *d_chain_begin = nullptr; int chain_njobs = 0;
     int64_t chain_pick_subs = 0; std::vector<int> chain_host_flags; bool recs_are_picks = false;
+    // rv_multi_chain_route: the same for more than two samples (k_pick_multi_chain).  mchain_begin[q * chain_njobs + j]: where sequence q of job j begins in
+    // the text, every row ascending (mchain_rows of them); the flag words, the picker's options and the counters are the fields above
+    bool multi_chain = false; std::vector<int64_t> mchain_begin; const int64_t *d_mchain_begin = nullptr; int mchain_rows = 0;
+    std::vector<u32> pick_n;
     size_t leaf_na = 0;          // anchors of the leaf launches of the last run: they stay in the pinned staging buffer (hLeafOut: pos[2 na], l[na]) until fetched
     void release() {
         // (the side streams may still be writing pinned buffers that go back to the process-wide pool below: after an aborted run nothing else waits for them)
@@ -308,20 +312,22 @@ static int count_samples(rv_index *h, const RvIntv *iv, size_t cnt) {
 }
 
 /* can the sub-index made of these intervals (sorted by begin) still hold a match of minl bases present in each of its samples? */
-static bool child_is_dead(const rv_index *h, const RvIntv *iv, size_t cnt, int minl, int minn) {
+// subsets: the rule of the reference's default picker instead (the multi-sample chain route) -- a match of a sample SUBSET anchors too, so a child is dead
+// only when fewer than max(minn, 2) of its samples own an interval of minl bases (k_leaf_multi_chain visits its children by the same rule)
+static bool child_is_dead(const rv_index *h, const RvIntv *iv, size_t cnt, int minl, int minn, bool subsets = false) {
     const int64_t need = std::max(minl, 1);
-    int ns = 0; size_t sp = 0; int last = -1; int64_t best = 0;
+    int ns = 0, nlong = 0; size_t sp = 0; int last = -1; int64_t best = 0;
     for (size_t k = 0; k < cnt; k++) {
         if (k && iv[k].begin < iv[k - 1].begin) return false;          // (not sorted: no shortcut)
         while (sp < h->nsep.size() && h->nsep[sp] < iv[k].begin) sp++;
         if ((int)sp != last) {
-            if (last >= 0 && best < need) return true;
+            if (last >= 0 && best < need) { if (!subsets) return true; } else if (last >= 0) nlong++;
             ns++; last = (int)sp; best = 0;
         }
         best = std::max(best, iv[k].end - iv[k].begin);
     }
-    if (last >= 0 && best < need) return true;
-    return ns < std::max(minn, 2);
+    if (last >= 0 && best < need) { if (!subsets) return true; } else if (last >= 0) nlong++;
+    return (subsets ? nlong : ns) < std::max(minn, 2);
 }
 
 static int need_align(rv_index *h) {
@@ -488,6 +494,35 @@ int rv_leaf_chain_route(rv_index *h, const rv_picker_args *args, u32 *flags, con
 // the job (of the routed round) that holds text position p of sample `side`
 static int chain_job_of(const Align *a, int side, int64_t p) {
     const int64_t *beg = a->chain_begin.data() + (side ? a->chain_njobs : 0);
+    const int j = (int)(std::upper_bound(beg, beg + a->chain_njobs, p) - beg) - 1;
+    return j < 0 ? 0 : j;
+}
+int rv_multi_chain_route(rv_index *h, const rv_picker_args *args, u32 *flags, const int64_t *job_begin, const int64_t *d_job_begin, int njobs, int rows) {
+    if (!h || (args && (!flags || !job_begin || !d_job_begin || njobs <= 0 || rows < 2 || rows > RV_PICK_MCHAIN_KMAX))) { rv_set_error("rv_multi_chain_route: bad arguments"); return -1; }
+    if (!h->al) h->al = new Align();
+    Align *a = h->al;
+    a->multi_chain = args != nullptr;
+    a->chain_pick_subs = 0; a->chain_host_flags.clear();
+    a->mchain_begin.clear(); a->d_mchain_begin = nullptr; a->chain_njobs = 0; a->mchain_rows = 0;
+    if (args) {
+        a->leaf_chain = false;      // (the pair route of an earlier round of the handle: one route at a time)
+        if (a->picker != 0 || args->wscore < 0 || args->wpen < 0 || args->wscore > RV_PICK_MCHAIN_WMAX || args->wpen > RV_PICK_MCHAIN_WMAX || args->gcmodel < 0 ||
+            args->gcmodel > 2) {
+            rv_set_error("rv_multi_chain_route: options the chain pick of the multi-sample level pipeline does not take");
+            a->multi_chain = false;
+            return -1;
+        }
+        a->chain_args.wscore = (int32_t)args->wscore; a->chain_args.wpen = (int32_t)args->wpen; a->chain_args.gcmodel = args->gcmodel; a->chain_args.flags = flags;
+        a->chain_args.root_job = nullptr;
+        a->pargs = *args;
+        a->mchain_begin.assign(job_begin, job_begin + (size_t)rows * (size_t)njobs); a->d_mchain_begin = d_job_begin; a->chain_njobs = njobs; a->mchain_rows = rows;
+    }
+    return 0;
+}
+// the job (of the routed round) whose sequence of sample q holds text position p
+static int mchain_job_of(const Align *a, int q, int64_t p) {
+    if (q < 0 || q >= a->mchain_rows) return 0;
+    const int64_t *beg = a->mchain_begin.data() + (size_t)q * (size_t)a->chain_njobs;
     const int j = (int)(std::upper_bound(beg, beg + a->chain_njobs, p) - beg) - 1;
     return j < 0 ? 0 : j;
 }
@@ -869,6 +904,53 @@ int rv_frontier_scan(rv_index *h) {
             a->nmums[(size_t)si]++;
         }
     } else {
+        if (a->multi_chain && a->full_only) {
+            // the multi-sample chain route (rv_multi_chain_route): the scan runs unfiltered -- the picker looks at the matches of sample subsets where no
+            // match lies in every sample -- and the reference's default picker decides every sub-index: on the device (k_pick_multi_chain, one pick per
+            // sub-index comes back) where the level's tables are there -- an imported frontier counts as level 1 and ships them, so rv_many's roots are
+            // picked there too --, on the host (rv_pick_chain on the whole list, builtin_levels) at level 0 of a run of its own and at any other level
+            // without them (more sub-indices than RV_DECIDE_MAX_SUBS, two intervals of one sample).  The device-side early split (early_split,
+            // k_decide_multi) is written for picks present in every sample of their sub-index: it stays off under this route, the commit splits from
+            // the host's tables.
+            const bool dev = a->level > 0 && a->cur_dev_ok;
+            a->recs_are_picks = dev;
+            a->early_done = false; a->early_bubble = false;
+            a->ml.clear(); a->mn.clear(); a->moff.assign(1, 0); a->mso.clear(); a->mpos.clear();
+            if (dev) {
+                const int W = h->nsamples;
+                RvPickMultiChainArgs pc;
+                memset(&pc, 0, sizeof pc);
+                pc.nodes = a->d_next_nodes; pc.W = W;
+                pc.wscore = a->chain_args.wscore; pc.wpen = a->chain_args.wpen; pc.gcmodel = a->chain_args.gcmodel;
+                pc.cap = (u32)std::max<int64_t>(0, std::min<int64_t>(h->ws.opt.pick_mchain_cap, RV_PICK_MCHAIN_CAP_MAX));
+                pc.job_flags = a->chain_args.flags; pc.job_begin = a->d_mchain_begin; pc.njobs = a->chain_njobs;
+                if (W > a->mchain_rows) { rv_set_error("chain route: %d samples, a job table of %d", W, a->mchain_rows); return -1; }
+                a->chain_pick_subs += ns;
+                RV_TRY(rv_run_multi_chain_pick(h, cur_sa(h), cur_lcp(h), cur_bwt(h), a->lv.m, a->minl, a->minn, a->d_next_ss, ns, pc, a->pick_l, a->pick_n, a->pick_pos));
+                for (int s2 = 0; s2 < ns; s2++) {
+                    if (a->pick_l[(size_t)s2] == 0) continue;
+                    const int pn = (int)a->pick_n[(size_t)s2];
+                    if (pn < 2 || pn > a->lv.nsamples[(size_t)s2]) { rv_set_error("chain route: a pick of %d members for sub-index %d", pn, s2); return -1; }
+                    a->mum_first[(size_t)s2] = (int64_t)a->ml.size(); a->nmums[(size_t)s2] = 1;
+                    a->ml.push_back(a->pick_l[(size_t)s2]); a->mn.push_back(pn);
+                    for (int k = 0; k < pn; k++) {
+                        const int64_t p = (int64_t)a->pick_pos[(size_t)s2 * W + k];
+                        a->mso.push_back((uint16_t)sample_of(h, p)); a->mpos.push_back(p);
+                    }
+                    a->moff.push_back((int64_t)a->mpos.size());
+                }
+            } else {
+                std::vector<int64_t> ub;
+                RV_TRY(rv_run_multi_scan(h, cur_sa(h), cur_lcp(h), cur_bwt(h), a->lv.m, a->minl, a->minn, 0, a->ml, a->mn, a->moff, a->mso, a->mpos, &ub, nullptr, nullptr, 0));
+                int si = 0;
+                for (size_t k = 0; k < a->ml.size(); k++) {
+                    while (si < ns && ub[k] >= a->lv.off[(size_t)si] + a->lv.n[(size_t)si]) si++;
+                    if (si >= ns) { rv_set_error("scan record outside the frontier"); return -1; }
+                    if (a->nmums[(size_t)si] == 0) a->mum_first[(size_t)si] = (int64_t)k;
+                    a->nmums[(size_t)si]++;
+                }
+            }
+        } else
         if (a->full_only && a->level > 0) {
             // built-in picker without tracing: the device returns, per sub-index, the match the picker would take (the tables
             // came with the previous commit's upload)
@@ -1257,7 +1339,7 @@ static int commit_tables(rv_index *h, int32_t *children, Commit &cm) {
         // sub-indices visited is smaller than the reference's.
         bool dead[3] = {false, false, false};
         if (a->multi && a->full_only && !dc.host_lists && !h->ws.opt.keep_dead)
-            for (int c = 0; c < 3; c++) dead[c] = cnts[c] > 0 && child_is_dead(h, lists[c], cnts[c], a->minl, a->minn);
+            for (int c = 0; c < 3; c++) dead[c] = cnts[c] > 0 && child_is_dead(h, lists[c], cnts[c], a->minl, a->minn, a->multi_chain);
         if (dc.drop_lead) dead[0] = cnts[0] > 0;
         // class table of this sub: lead/trail/rest merged by begin (the split's tables: not needed when the split of this level ran
         // already, from the same tables built on the device -- early_split; those decisions come from the built-in picker, whose
@@ -1805,6 +1887,49 @@ static int chain_host_pick(rv_index *h, int s, PickScratch &X, RvPairRec &out) {
     return 1;
 }
 
+// ... and of more than two samples (rv_multi_chain_route): the sub-index' whole unfiltered list, its intervals per sample, the begins of its job's sequences
+// (what `mapping` takes the offsets relative to) -> members of the pick (its length in *l, the positions in the picker's member order in pos[0 ..]),
+// 0 none, < 0 the picker failed or raised (the caller flags the job)
+static int mchain_host_pick(rv_index *h, int s, int job, PickScratch &X, u32 *l, std::vector<int64_t> &pos) {
+    Align *a = h->al;
+    const Level &lv = a->lv;
+    const int W = h->nsamples, want = lv.nsamples[(size_t)s];
+    const RvIntv *nodes = lv.nodes.data() + lv.node_first[(size_t)s];
+    const size_t nn = (size_t)(lv.node_first[(size_t)s + 1] - lv.node_first[(size_t)s]);
+    const int64_t first = a->mum_first[(size_t)s], cnt = a->nmums[(size_t)s];
+    X.pk_l.clear(); X.pk_n.clear(); X.pk_off.assign(1, 0); X.pk_mso.clear(); X.pk_mpos.clear();
+    for (int64_t k = first; k < first + cnt; k++) {
+        X.pk_l.push_back(a->ml[(size_t)k]); X.pk_n.push_back(a->mn[(size_t)k]);
+        for (int64_t qq = a->moff[(size_t)k]; qq < a->moff[(size_t)k + 1]; qq++) { X.pk_mso.push_back(a->mso[(size_t)qq]); X.pk_mpos.push_back(a->mpos[(size_t)qq]); }
+        X.pk_off.push_back((int64_t)X.pk_mpos.size());
+    }
+    X.pk_sb.assign((size_t)W, 0); X.pk_ib.assign((size_t)W, -1); X.pk_ie.assign((size_t)W, -1);
+    for (size_t k = 0; k < nn; k++) {
+        const int sm = sample_of(h, nodes[k].begin);
+        if (sm >= W || sm >= a->mchain_rows || X.pk_ib[(size_t)sm] >= 0) return -1;      // (one interval per sample and sub-index)
+        X.pk_ib[(size_t)sm] = nodes[k].begin; X.pk_ie[(size_t)sm] = nodes[k].end;
+        X.pk_sb[(size_t)sm] = a->mchain_begin[(size_t)sm * (size_t)a->chain_njobs + (size_t)job];
+    }
+    const size_t scap = X.pk_l.size(), mcap = X.pk_mpos.size();
+    X.pk_sl.resize(scap); X.pk_sn.resize(scap); X.pk_soff.resize(scap + 1); X.pk_sso.resize(std::max<size_t>(mcap, 1)); X.pk_spos.resize(std::max<size_t>(mcap, 1));
+    X.pk_ssc.resize(scap); X.pk_srt.resize(scap);
+    std::vector<uint16_t> pso((size_t)W, 0);
+    pos.assign((size_t)W, 0);
+    rv_picker_out po;
+    memset(&po, 0, sizeof po);
+    po.pick_so = pso.data(); po.pick_pos = pos.data(); po.member_cap = W;
+    po.seed_cap = (int64_t)scap; po.seed_member_cap = (int64_t)std::max<size_t>(mcap, 1);
+    po.seed_l = X.pk_sl.data(); po.seed_n = X.pk_sn.data(); po.seed_off = X.pk_soff.data(); po.seed_so = X.pk_sso.data(); po.seed_pos = X.pk_spos.data();
+    po.seed_score = X.pk_ssc.data(); po.seed_right = X.pk_srt.data();
+    const int pr = rv_pick_chain(&a->pargs, want, (int64_t)X.pk_l.size(), X.pk_l.data(), X.pk_n.data(), X.pk_off.data(), X.pk_mso.data(), X.pk_mpos.data(), W,
+                                 X.pk_sb.data(), X.pk_ib.data(), X.pk_ie.data(), a->minl, &po);
+    if (pr < 0) return -1;
+    if (pr == 0) return 0;
+    if (po.pick_members < 2 || po.nleft + po.nright > 0) return -1;      // (a seed: the admission rule excludes it)
+    *l = po.pick_l;
+    return po.pick_members;
+}
+
 // every not-seeded sub-index of the level with matches; on several threads when the level holds enough of them (RV_PICK_THREADS: 0 = up to eight, 1 = none)
 static void pick_level(rv_index *h, std::vector<PickRes> &res) {
     Align *a = h->al;
@@ -1976,6 +2101,25 @@ static int builtin_levels(rv_index *h, int stop_subs) {
                     }
                 }
                 if (chain_pick) { sp.assign(pk_pos.begin(), pk_pos.begin() + members); best = 0; pk_members = members; }
+            } else
+            if (a->multi && a->multi_chain) {
+                // the multi-sample chain route (rv_multi_chain_route): the level's records are the device's chain picks (k_pick_multi_chain: at most one per
+                // sub-index, the trimmed match, possibly of fewer samples than the sub-index holds -- the untouched intervals become the `rest` child below)
+                // -- or, for a level without device tables, the sub-index' whole list: the host's picker on it; what it cannot decide flags the job
+                if (!a->recs_are_picks) a->chain_pick_subs++;      // (rv_frontier_scan counts the ones the device was asked for)
+                if (cnt > 0) {
+                    int members = 0;
+                    if (a->recs_are_picks) {
+                        if (cnt != 1) { rv_set_error("chain route: %lld picks for sub-index %d", (long long)cnt, s); return -1; }
+                        bl = a->ml[(size_t)first]; members = (int)(a->moff[(size_t)first + 1] - a->moff[(size_t)first]);
+                        pk_pos.assign(a->mpos.begin() + a->moff[(size_t)first], a->mpos.begin() + a->moff[(size_t)first + 1]);
+                    } else if (nn > 0) {
+                        const int job = mchain_job_of(a, sample_of(h, nodes[0].begin), nodes[0].begin);
+                        members = mchain_host_pick(h, s, job, gpx, &bl, pk_pos);
+                        if (members < 0) { a->chain_host_flags.push_back(job); members = 0; }
+                    }
+                    if (members > 0) { sp.assign(pk_pos.begin(), pk_pos.begin() + members); best = 0; chain_pick = true; pk_members = members; }
+                }
             } else
             if (!a->multi && a->leaf_chain) {
                 // the chain route (rv_leaf_chain_route): no sub-index is decided by the longest-match rule.  The level's records are the device's chain picks

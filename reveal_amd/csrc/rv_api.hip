@@ -962,6 +962,49 @@ int rv_run_multi_pick(rv_index *h, const sa_t *SA, const lcp_t *LCP, const uint8
     return -1;
 }
 
+// The multi-sample chain route of rv_many's handle (rv_multi_chain_route, rv_align.hip): the UNFILTERED multi-MUM scan of the level, its records and tile
+// table left in device memory (no member lists: a capacity of 0 -- the pick reads the members from SA), then k_pick_multi_chain, one wavefront per
+// sub-index, and one (l, n, positions) per sub-index back to the host.  The host looks at the record count between the two launches: a list that did not
+// fit is scanned again into a larger buffer before anything picks from it.
+int rv_run_multi_chain_pick(rv_index *h, const sa_t *SA, const lcp_t *LCP, const uint8_t *BWT, int64_t m, int minl, int minn, const int64_t *d_sub_start, int nsubs,
+                            const RvPickMultiChainArgs &pc, std::vector<u32> &pick_l, std::vector<u32> &pick_n, std::vector<sa_t> &pick_pos) {
+    pick_l.assign((size_t)std::max(nsubs, 0), 0); pick_n.assign((size_t)std::max(nsubs, 0), 0); pick_pos.clear();
+    if (m <= 1 || nsubs <= 0) return 0;
+    hipStream_t q = h->ws.stream;
+    const int W = h->nsamples;
+    if (W != pc.W) { rv_set_error("multi chain pick: %d samples, arguments for %d", W, pc.W); return -1; }
+    const int64_t ntile = ceil_div(m, RV_MULTI_TILE);
+    DBuf &bcnt = h->ws.misc[1], &btab = h->ws.misc[2], &brec = h->ws.misc[8], &bso = h->ws.misc[6], &bpos = h->ws.misc[7], &bl = h->ws.misc[13], &bn = h->ws.misc[12];
+    RV_TRY(bcnt.reserve(64));
+    RV_TRY(btab.reserve((size_t)ntile * sizeof(uint4)));
+    if (brec.cap < 4096 * sizeof(RvMultiRec)) RV_TRY(brec.reserve(sizeof(RvMultiRec) * (size_t)std::max<int64_t>(4096, m / 32)));
+    RV_TRY(bso.reserve(64));
+    RV_TRY(bl.reserve((size_t)nsubs * 4)); RV_TRY(bn.reserve((size_t)nsubs * 4)); RV_TRY(bpos.reserve((size_t)nsubs * W * sizeof(sa_t) + 64));
+    for (int attempt = 0; attempt < 2; attempt++) {
+        const size_t rcap = brec.cap / sizeof(RvMultiRec);
+        RV_HIP(hipMemsetAsync(bcnt.p, 0, 8, q));
+        int id = h->prof.begin(q, RV_K_SCAN_MULTI, (double)m * (sizeof(sa_t) + sizeof(lcp_t)));
+        RV_TRY(rv_scan_multi_launch(h->ws, SA, LCP, m, BWT, h->dNsep.as<sa_t>(), W, minl, minn, brec.as<RvMultiRec>(), bso.as<uint16_t>(), bpos.as<sa_t>(),
+                                    (u32)std::min<size_t>(rcap, 0xffffffffu), 0u, bcnt.as<u32>(), btab.as<uint4>(), nullptr, nullptr, 0));
+        h->prof.end(q, id);
+        u32 tot[2] = {0, 0};
+        RV_TRY(rv_read_back(h->ws, tot, bcnt.p, 8));
+        if (tot[0] > rcap) { h->ws.cap_events[RV_CE_MULTI_REC]++; RV_TRY(brec.reserve((size_t)tot[0] * sizeof(RvMultiRec))); continue; }
+        RV_HIP(hipMemsetAsync(bl.p, 0, (size_t)nsubs * 4, q));
+        RV_HIP(hipMemsetAsync(bn.p, 0, (size_t)nsubs * 4, q));
+        RV_TRY(rv_pick_multi_chain_launch(h->ws, SA, brec.as<RvMultiRec>(), (u32)std::min<size_t>(rcap, 0xffffffffu), btab.as<uint4>(), ntile, d_sub_start, nsubs,
+                                          bl.as<u32>(), bn.as<u32>(), bpos.as<sa_t>(), pc));
+        pick_pos.resize((size_t)nsubs * W);
+        RV_HIP(hipMemcpyAsync(pick_l.data(), bl.p, (size_t)nsubs * 4, hipMemcpyDeviceToHost, q));
+        RV_HIP(hipMemcpyAsync(pick_n.data(), bn.p, (size_t)nsubs * 4, hipMemcpyDeviceToHost, q));
+        RV_HIP(hipMemcpyAsync(pick_pos.data(), bpos.p, (size_t)nsubs * W * sizeof(sa_t), hipMemcpyDeviceToHost, q));
+        RV_HIP(hipStreamSynchronize(q));
+        return 0;
+    }
+    rv_set_error("multi chain pick: record buffer sizing failed");
+    return -1;
+}
+
 extern "C" {
 
 /* reveal.c:436-580 / 292-434 */

@@ -72,6 +72,14 @@
 // the chain route -- every sub-index above RV_LEAF_N ranks gets its pick from k_pick_chain (rv_pick_chain.hip: the picker's decision for two samples, a
 // wavefront per sub-index, in place of the longest-match kernel; k_decide and the early split as they are), the others drop into k_leaf_chain as they shrink.
 // The flag words are the jobs': a flag set by any launch of any level drops all of the job's anchors, leaves its text untaken and sends it to the ordinary path.
+// RV_MANY_CHAIN_LARGE_MULTI (off by default, independent of every other switch; it means something under kind 1 only): the jobs of 3 .. RV_MANY_KMAX sequences
+// many_chain_large_multi_admits names -- more than RV_LEAF_N and at most min(RV_MANY_LARGE_MAX, 2^17) ranks -- share their launches too, in rounds of their own,
+// from RV_MANY_CHAIN_LARGE_MULTI_MIN such jobs in a call on: sample-major layout, index build and frontier of the RV_MANY_LARGE_MULTI rounds
+// (many_round_large_multi with `redo`), and the multi-sample level pipeline under its chain route (rv_multi_chain_route) -- every level's scan unfiltered, every
+// sub-index picked by k_pick_multi_chain (rv_pick_multi_chain.hip: the picker's decision for up to 16 samples, a wavefront per sub-index) in place of
+// k_multi_pick1 / k_multi_pick2, the early split off; a pick of a sample subset leaves a `rest` child.  There is no leaf kernel for multi-sample sub-indices of
+// a handle: sub-indices of every size are picked this way.  Flag words per job as above.  Under a picker the jobs of 17 .. 64 sequences above RV_LEAF_N ranks
+// stay ordinary.
 // Size classes (DESIGN.md "Many small alignments" has the measurements): up to `wave_max` ranks (default 512) a wavefront per job,
 // four jobs per workgroup, no workgroup barrier; above, a workgroup of 256 threads per job.  Both hold 22.6 KB of LDS per workgroup:
 // seven workgroups per CU.
@@ -271,6 +279,7 @@ struct rv_many {
     int64_t chain_multi = 0;                    // RV_MANY_CHAIN_MULTI
     int64_t chain_wide = 0;                     // RV_MANY_CHAIN_WIDE
     int64_t chain_large = 0, chain_large_min = RV_MANY_CHAIN_LARGE_MIN_DEFAULT;      // RV_MANY_CHAIN_LARGE, RV_MANY_CHAIN_LARGE_MIN
+    int64_t chain_large_multi = 0, chain_large_multi_min = RV_MANY_CHAIN_LARGE_MULTI_MIN_DEFAULT;      // RV_MANY_CHAIN_LARGE_MULTI, RV_MANY_CHAIN_LARGE_MULTI_MIN
     std::vector<std::pair<std::string, int64_t>> fwd;      // switches for the internal handles
     // results of the last run
     bool ran = false;
@@ -332,6 +341,27 @@ bool many_chain_large_admits(const rv_many *m, const ManyJob &jb, int minl) {
     if (a.gcmodel < 0 || a.gcmodel > 2) return false;
     if (a.seedsize > 0 && a.seedsize <= std::max(la, lb)) return false;
     if (a.maxmums > 0 && a.maxmums < std::min(la, lb)) return false;
+    return true;
+}
+
+// The jobs of 3 .. RV_MANY_KMAX sequences above RV_LEAF_N ranks the multi-sample level pipeline finishes under picker kind 1 (RV_MANY_CHAIN_LARGE_MULTI), its
+// picks made by k_pick_multi_chain: the rule, stated once (many.takes_shared_launch(.., picker=, chain_large_multi=True) mirrors it).  It is
+// many_chain_multi_admits' with
+//   RV_LEAF_N < ranks <= min(RV_MANY_LARGE_MAX, 2^17)      positions and lengths of a sub-index in 17 bits, whatever RV_MANY_LARGE_MAX says
+//   weights 0 .. RV_PICK_MCHAIN_WMAX = 512                scores in 32 bits at 2^17 ranks x 120 pairs (rv_pick_multi_chain.hip derives the bound: 1024 does not hold)
+//   seedsize <= 0 or above the longest sequence, maxmums <= 0 or at least the job's ranks: as there
+// rem.align's default maxmums of 10 000 therefore admits jobs of up to 10 000 ranks only (and its seedsize no sequence of 10 000 bases or more).
+bool many_chain_large_multi_admits(const rv_many *m, const ManyJob &jb, int minl) {
+    if (m->picker != 1 || !m->chain_large_multi) return false;
+    if (jb.k < 3 || jb.k > RV_MANY_KMAX || !jb.clean || jb.ranks <= RV_LEAF_N || jb.ranks > std::min<int64_t>(m->large_max, RV_PICK_CHAIN_RANKS)) return false;
+    const rv_picker_args &a = m->pargs;
+    if (!a.trim || minl <= 0) return false;
+    if (a.wscore < 0 || a.wpen < 0 || a.wscore > RV_PICK_MCHAIN_WMAX || a.wpen > RV_PICK_MCHAIN_WMAX) return false;
+    if (a.gcmodel < 0 || a.gcmodel > 2) return false;
+    int64_t longest = 0;
+    for (int q = 0; q < jb.k; q++) longest = std::max(longest, m->lens[jb.seq0 + (size_t)q]);
+    if (a.seedsize > 0 && a.seedsize <= longest) return false;
+    if (a.maxmums > 0 && a.maxmums < jb.ranks) return false;
     return true;
 }
 
@@ -710,7 +740,9 @@ struct ManyRoundK {
 // anchors of the handle's last run over a sample-major round -> records of their jobs.  An anchor's job comes from its first member (search among
 // the begins of that member's sample), every member maps back to the job's stand-alone coordinate.  The map is strictly increasing, so the members
 // stay in the (sorted) order rv_fetch_anchors gives a stand-alone index.
-int many_collect_k(rv_many *m, rv_index *h, const ManyRoundK &R) {
+// picker_order: the round of picker kind 1 -- the members come in the picker's order (the scan's member order), which the map keeps as well; they only
+// have to differ
+int many_collect_k(rv_many *m, rv_index *h, const ManyRoundK &R, bool picker_order = false) {
     int64_t members = 0;
     const int64_t na = rv_anchor_count(h, &members);
     if (na < 0) return -1;
@@ -728,12 +760,13 @@ int many_collect_k(rv_many *m, rv_index *h, const ManyRoundK &R) {
         if (at == 0) { rv_set_error("rv_many_run: an anchor outside the text"); return -1; }
         const size_t s = (size_t)R.sslot[(size_t)q0][at - 1];
         const ManyDevJobK &J = R.dj[s];
-        int64_t last = -1;
+        int64_t last = -1; u64 seen = 0;
         for (int x = 0; x < r.np; x++) {
             const int q = R.sample_of(p[x]);
             if (q >= J.k) { rv_set_error("rv_many_run: an anchor outside its job"); return -1; }
             const int64_t lo = q ? J.pend[q - 1] : 0, loc = R.local(s, q, p[x]);
-            if (loc < lo || loc + r.l > J.pend[q] - 1 || loc <= last) { rv_set_error("rv_many_run: an anchor outside its job"); return -1; }
+            if (loc < lo || loc + r.l > J.pend[q] - 1 || (picker_order ? ((seen >> q) & 1ull) != 0 : loc <= last)) { rv_set_error("rv_many_run: an anchor outside its job"); return -1; }
+            seen |= 1ull << q;
             m->rpos.push_back(loc);
             last = loc;
         }
@@ -747,11 +780,24 @@ int many_collect_k(rv_many *m, rv_index *h, const ManyRoundK &R) {
 // The sample-major text goes into the shared handle (K samples, K the widest job), the index of every job is built at once
 // (rv_many_large_build_k), the segments become a level-0 frontier of J roots of k samples each, and the level pipeline finishes them together.
 // kmax: the sample bound of the round's class (RV_MANY_KMAX; RV_MANY_WIDE_KMAX for the rounds of jobs of 17 .. 64 sequences, RV_MANY_WIDE).
-int many_round_large_multi(rv_many *m, const std::vector<int> &order, size_t lo, size_t hi, int minl, int minn, rv_align_stats *total, int kmax) {
+// redo != NULL: the round of picker kind 1 (RV_MANY_CHAIN_LARGE_MULTI, kmax = RV_MANY_KMAX) -- the level pipeline runs under the multi-sample chain route
+// (rv_multi_chain_route: every sub-index picked by k_pick_multi_chain, or by the host's picker at a level without device tables), and the jobs a launch of
+// any level flags come back in *redo for the ordinary path: their anchors are dropped, their text is not taken
+int many_round_large_multi(rv_many *m, const std::vector<int> &order, size_t lo, size_t hi, int minl, int minn, rv_align_stats *total, int kmax, std::vector<int> *redo = nullptr) {
     RV_TRY(many_handle(m, &m->hs));
     rv_index *h = m->hs;
     const size_t J = hi - lo;
     RV_TRY(rv_reset(h));
+    if (redo) {
+        RV_TRY(m->dFlag.reserve(J * sizeof(u32)));
+        RV_HIP(hipMemsetAsync(m->dFlag.p, 0, J * sizeof(u32), h->ws.stream));
+        if (m->chain_flag > 0) {      // test hook: every chain_flag-th job of the round counts as flagged by the kernel, whatever the kernel does with it
+            std::vector<u32> pre(J, 0u);
+            for (size_t s = 0; s < J; s += (size_t)m->chain_flag) pre[s] = 16u;
+            RV_HIP(hipMemcpyAsync(m->dFlag.p, pre.data(), J * sizeof(u32), hipMemcpyHostToDevice, h->ws.stream));
+            RV_HIP(hipStreamSynchronize(h->ws.stream));
+        }
+    } else RV_TRY(rv_multi_chain_route(h, nullptr, nullptr));
     ManyRoundK R;
     R.ord.assign(order.begin() + (ptrdiff_t)lo, order.begin() + (ptrdiff_t)hi);
     R.dj.resize(J);
@@ -782,6 +828,23 @@ int many_round_large_multi(rv_many *m, const std::vector<int> &order, size_t lo,
         R.send[(size_t)q] = n - 1;
     }
     RV_TRY(rv_upload(h));
+    if (redo) {
+        // the chain route: flags per job; a sub-index of any level finds its job in the row of its lowest live sample -- where sequence q of every job
+        // begins, ascending (a job without a q-th sequence stands at the begin of the next one that has it)
+        if (K > RV_PICK_MCHAIN_KMAX) { rv_set_error("rv_many_run: a chain round of jobs of %d sequences", K); return -1; }
+        std::vector<int64_t> beg((size_t)K * J);
+        for (int q2 = 0; q2 < K; q2++) {
+            int64_t nxt = R.send[(size_t)q2];
+            for (size_t s = J; s-- > 0;) {
+                if (q2 < m->jobs[(size_t)R.ord[s]].k) nxt = R.dj[s].beg[q2];
+                beg[(size_t)q2 * J + s] = nxt;
+            }
+        }
+        RV_TRY(m->dBeg.reserve(beg.size() * sizeof(int64_t)));
+        RV_HIP(hipMemcpyAsync(m->dBeg.p, beg.data(), beg.size() * sizeof(int64_t), hipMemcpyHostToDevice, h->ws.stream));
+        RV_HIP(hipStreamSynchronize(h->ws.stream));
+        RV_TRY(rv_multi_chain_route(h, &m->pargs, m->dFlag.as<u32>(), beg.data(), m->dBeg.as<int64_t>(), (int)J, K));
+    }
     // jobs, segment offsets, frontier tables
     std::vector<int64_t> meta(6 * J), node_first(J + 1);
     int64_t off = 0;
@@ -847,14 +910,30 @@ int many_round_large_multi(rv_many *m, const std::vector<int> &order, size_t lo,
     RV_TRY(rv_align_builtin_resume(h, &st));
     many_add_stats(total, st);
     const size_t rec0 = m->recs.size();
-    RV_TRY(many_collect_k(m, h, R));
+    RV_TRY(many_collect_k(m, h, R, redo != nullptr));
     m->info[4] += st.levels + (m->recs.size() > rec0 ? 2 : 0);      // one per level, and the two of the lower-casing when there are anchors
+    std::vector<u32> flag;
+    size_t nflag = 0;
+    if (redo) {
+        // the jobs a kernel (or the host's picker) did not finish: their anchors are dropped, their text is not taken from the round.  Every job is a root of
+        // level 0 at least: the picker -- never the longest match -- was asked for each of them
+        const int *hflag = nullptr;
+        const int nhflag = rv_leaf_chain_host_flags(h, &hflag);
+        if (rv_pick_chain_subs(h) < (int64_t)J) { rv_set_error("rv_many_run: the chain pick took %lld sub-indices of a round of %lld jobs", (long long)rv_pick_chain_subs(h), (long long)J); return -1; }
+        flag.resize(J);
+        RV_HIP(hipMemcpy(flag.data(), m->dFlag.p, J * sizeof(u32), hipMemcpyDeviceToHost));
+        for (int k = 0; k < nhflag; k++) if (hflag[k] >= 0 && (size_t)hflag[k] < J) flag[(size_t)hflag[k]] |= 128u;
+        std::vector<char> out((size_t)m->jobs.size(), 0);
+        for (size_t s = 0; s < J; s++) if (flag[s]) { out[(size_t)R.ord[s]] = 1; redo->push_back(R.ord[s]); nflag++; }
+        if (nflag) m->recs.erase(std::remove_if(m->recs.begin() + (ptrdiff_t)rec0, m->recs.end(), [&](const ManyRec &r) { return out[(size_t)r.job] != 0; }), m->recs.end());
+    }
     // final text of every job, gathered from its k places
     std::vector<char> txt((size_t)n);
     RV_TRY(rv_ensure_working_text(h));
     RV_HIP(hipStreamSynchronize(h->ws.stream));
     RV_HIP(hipMemcpy(txt.data(), h->dT.p, (size_t)n, hipMemcpyDeviceToHost));
     for (size_t s = 0; s < J; s++) {
+        if (nflag && flag[s]) continue;
         ManyJob &jb = m->jobs[(size_t)R.ord[s]];
         jb.text_off = (int64_t)m->out_text.size();
         jb.shared = true;
@@ -863,7 +942,7 @@ int many_round_large_multi(rv_many *m, const std::vector<int> &order, size_t lo,
             m->out_text.insert(m->out_text.end(), txt.begin() + (ptrdiff_t)b, txt.begin() + (ptrdiff_t)(b + len1));
         }
     }
-    m->info[1] += (int64_t)J; m->info[3]++;
+    m->info[1] += (int64_t)(J - nflag); m->info[3]++;
     return 0;
 }
 
@@ -926,6 +1005,12 @@ int many_run(rv_many *m, int minl, int minn, rv_align_stats *total) {
     int64_t nclarge = 0;
     for (const ManyJob &jb : m->jobs) nclarge += is_chain_large(jb) ? 1 : 0;
     const bool take_chain_large = nclarge > 0 && nclarge >= m->chain_large_min;
+    // (... and the jobs of 3 .. 16 sequences above RV_LEAF_N ranks: the same, RV_MANY_CHAIN_LARGE_MULTI_MIN)
+    const auto is_chain_large_multi = [&](const ManyJob &jb) { return many_chain_large_multi_admits(m, jb, minl) && jb.ranks <= lim; };
+    int64_t nclmulti = 0;
+    for (const ManyJob &jb : m->jobs) nclmulti += is_chain_large_multi(jb) ? 1 : 0;
+    const bool take_chain_large_multi = nclmulti > 0 && nclmulti >= m->chain_large_multi_min;
+    std::vector<int> clmorder;
     const bool chain = m->picker == 1;      // the shared classes finish with built-in-picker kernels: under kind 1 only many_chain_admits',
                                             // many_chain_multi_admits' and many_chain_wide_admits' jobs share launches
     for (int j = 0; j < nj; j++) {
@@ -933,6 +1018,7 @@ int many_run(rv_many *m, int minl, int minn, rv_align_stats *total) {
         jb.arr_off = -1;
         if (chain) { if (many_chain_admits(m, jb, minl)) order.push_back(j); else if (take_chain_large && is_chain_large(jb)) clorder.push_back(j);
                      else if (many_chain_multi_admits(m, jb, minl)) cmorder.push_back(j);
+                     else if (take_chain_large_multi && is_chain_large_multi(jb)) clmorder.push_back(j);
                      else if (many_chain_wide_admits(m, jb, minl)) cworder.push_back(j); else rest.push_back(j); }
         else if (jb.k == 2 && jb.ranks <= RV_LEAF_N && jb.clean) order.push_back(j);
         else if (take_large && is_large(jb)) lorder.push_back(j);
@@ -952,6 +1038,7 @@ int many_run(rv_many *m, int minl, int minn, rv_align_stats *total) {
     std::stable_sort(cmorder.begin(), cmorder.end(), by_size);
     std::stable_sort(cworder.begin(), cworder.end(), by_size);
     std::stable_sort(clorder.begin(), clorder.end(), by_size);
+    std::stable_sort(clmorder.begin(), clmorder.end(), by_size);
     for (size_t lo = 0; lo < order.size();) {
         size_t hi = lo; int64_t sum = 0;
         while (hi < order.size() && (hi == lo || sum + m->jobs[(size_t)order[hi]].ranks <= lim)) sum += m->jobs[(size_t)order[hi++]].ranks;
@@ -974,6 +1061,12 @@ int many_run(rv_many *m, int minl, int minn, rv_align_stats *total) {
         size_t hi = lo; int64_t sum = 0;
         while (hi < clorder.size() && (hi == lo || sum + m->jobs[(size_t)clorder[hi]].ranks <= lim)) sum += m->jobs[(size_t)clorder[hi++]].ranks;
         RV_TRY(many_round(m, clorder, lo, hi, minl, minn, total, true, &rest));
+        lo = hi;
+    }
+    for (size_t lo = 0; lo < clmorder.size();) {    // picker kind 1, the jobs of 3 .. 16 sequences above RV_LEAF_N ranks (RV_MANY_CHAIN_LARGE_MULTI): rounds of their own
+        size_t hi = lo; int64_t sum = 0;
+        while (hi < clmorder.size() && (hi == lo || sum + m->jobs[(size_t)clmorder[hi]].ranks <= lim)) sum += m->jobs[(size_t)clmorder[hi++]].ranks;
+        RV_TRY(many_round_large_multi(m, clmorder, lo, hi, minl, minn, total, RV_MANY_KMAX, &rest));
         lo = hi;
     }
     if (chain) std::sort(rest.begin(), rest.end());
@@ -1068,6 +1161,8 @@ int rv_many_option(rv_many *m, const char *name, int64_t value) {
     if (strcmp(name, "RV_MANY_CHAIN_MULTI") == 0) { m->chain_multi = value != 0; return 0; }
     if (strcmp(name, "RV_MANY_CHAIN_WIDE") == 0) { m->chain_wide = value != 0; return 0; }
     if (strcmp(name, "RV_MANY_CHAIN_LARGE") == 0) { m->chain_large = value != 0; return 0; }
+    if (strcmp(name, "RV_MANY_CHAIN_LARGE_MULTI") == 0) { m->chain_large_multi = value != 0; return 0; }
+    if (strcmp(name, "RV_MANY_CHAIN_LARGE_MULTI_MIN") == 0) { if (value < 0) { rv_set_error("RV_MANY_CHAIN_LARGE_MULTI_MIN: negative"); return -1; } m->chain_large_multi_min = value; return 0; }
     if (strcmp(name, "RV_MANY_CHAIN_LARGE_MIN") == 0) { if (value < 0) { rv_set_error("RV_MANY_CHAIN_LARGE_MIN: negative"); return -1; } m->chain_large_min = value; return 0; }
     if (strcmp(name, "RV_MANY_CHAIN_FLAG") == 0) { if (value < 0) { rv_set_error("RV_MANY_CHAIN_FLAG: negative"); return -1; } m->chain_flag = value; return 0; }
     if (strcmp(name, "RV_MANY_WIDE_LARGE_MIN") == 0) { if (value < 0) { rv_set_error("RV_MANY_WIDE_LARGE_MIN: negative"); return -1; } m->wide_large_min = value; return 0; }

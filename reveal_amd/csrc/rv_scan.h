@@ -71,6 +71,27 @@ int rv_scan_multi_launch(Workspace &ws, const sa_t *SA, const lcp_t *LCP, int64_
                          int minl, int minn, RvMultiRec *rec, uint16_t *so, sa_t *pos, u32 rec_cap, u32 mem_cap, u32 *counters, uint4 *tiletab,
                          const int64_t *sub_start, const int *sub_want, int nsubs);   // sub_want != NULL: keep only matches with n == sub_want[sub of ub]
 
+// The reference's default picker in place of the longest full match (k_pick_multi_chain, rv_pick_multi_chain.hip; rv_many's handle under the multi-sample
+// chain route): for every sub-index s, from the records an UNFILTERED k_scan_multi left in rec / tiletab, pick_l[s] = the length of the TRIMMED match
+// schemes.graphmumpicker splits on (left as it is where nothing is picked: the caller zeroes it), pick_n[s] = its members, pick_pos[s * W ..] = their
+// positions in member (rank) order.  nodes: (begin, end) per sample and sub-index (2 W per sub-index, as k_decide_multi reads them).  A sub-index the
+// kernel cannot decide sets bits in the flag word of its JOB and gets no pick: 1 the reference's own trim_overlap raises, 2 broken chain or a match
+// outside the intervals, 8 twin offsets, 32 more than `cap` candidates, 64 an interval of 2^17 positions or more.  job_begin[q * njobs + j]: where
+// sequence q of job j begins in the text, every row ascending (a job without a q-th sequence: the begin of the next one that has it).  cap: at most
+// RV_PICK_MCHAIN_CAP_MAX (RV_PICK_MCHAIN_CAP lowers it: test hook).
+#define RV_PICK_MCHAIN_CAP_MAX 512
+#define RV_PICK_MCHAIN_WMAX 512        // (rv_pick_multi_chain.hip derives it: 2^17 ranks x 120 pairs do not keep the scores in 32 bits at RV_LEAF_MCHAIN_WMAX)
+#define RV_PICK_MCHAIN_KMAX 16
+struct RvPickMultiChainArgs {
+    const sa_t *nodes; int W;
+    int32_t wscore, wpen;                                    // 0 .. RV_PICK_MCHAIN_WMAX
+    int gcmodel;                                             // 0 sumofpairs, 1 star-avg, 2 star-med
+    u32 cap;
+    u32 *job_flags; const int64_t *job_begin; int njobs;
+};
+int rv_pick_multi_chain_launch(Workspace &ws, const sa_t *SA, const RvMultiRec *rec, u32 rec_cap, const uint4 *tiletab, int64_t ntile, const int64_t *sub_start,
+                               int nsubs, u32 *pick_l, u32 *pick_n, sa_t *pick_pos, const RvPickMultiChainArgs &c);
+
 // getmultimems (reveal.c:292-434), a stack machine per run of LCP values of minl and more (rv_mems.hip); counts beyond the capacities are still counted.
 // Any number of samples a record's 16-bit sample field can name
 #define RV_MEMS_MAX_SAMPLES 65536

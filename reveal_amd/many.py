@@ -43,6 +43,16 @@ trim is on, minlength > 0, the weights are 0 .. 1024, no match can reach seedsiz
 RV_MANY_CHAIN_LARGE_MIN such jobs (default 4) leaves them on the ordinary path; a job a kernel of any level cannot finish (more candidates than the cap,
 or where the reference's trim_overlap raises) is flagged and runs the ordinary way inside the same call.  The results do not depend on the switch.
 
+With the switch RV_MANY_CHAIN_LARGE_MULTI on (`align_many(.., chain_large_multi=True)`, `Batch.option("RV_MANY_CHAIN_LARGE_MULTI", 1)` or the environment
+variable; off by default, independent of every other switch, and it means something with a picker only) the jobs of 3 .. 16 sequences and 2049 ..
+min(RV_MANY_LARGE_MAX, 2^17) ranks share their launches under the picker too, in rounds of their own: layout, index build and level pipeline of the
+RV_MANY_LARGE_MULTI rounds, the scan of every level unfiltered, and the pick of every sub-index made on the device by a kernel that takes the picker's
+decision for up to 16 samples (csrc/rv_pick_multi_chain.hip: a wavefront per sub-index, up to 512 candidates; a match of a sample subset leaves a `rest`
+child) in place of the longest-match kernels -- when trim is on, minlength > 0, the weights are 0 .. 512, no match can reach seedsize and maxmums is at
+least the job's ranks (`takes_shared_launch(.., picker=args, chain_large_multi=True)`): `rem.align`'s default maxmums of 10 000 admits jobs of up to
+10 000 ranks only.  A call with fewer than RV_MANY_CHAIN_LARGE_MULTI_MIN such jobs (default 4) leaves them on the ordinary path; a flagged job runs the
+ordinary way inside the same call.  Jobs of 17 .. 64 sequences above 2048 ranks stay ordinary under a picker.  The results do not depend on the switch.
+
 Jobs of three and more sequences -- a bubble of a graph of N genomes carries up to N -- run the ordinary way unless the switch
 RV_MANY_MULTI is on (`align_many(.., multi=True)`, `Batch.option("RV_MANY_MULTI", 1)` or the environment variable; off by default).
 With it the jobs of 3 .. 16 sequences and at most 2048 ranks share their launches as well, in rounds of their own: every job
@@ -91,6 +101,8 @@ CHAIN_WMAX = 65536         # RV_LEAF_CHAIN_WMAX: weights up to this keep the cha
 CHAIN_MULTI_WMAX = 1024    # RV_LEAF_MCHAIN_WMAX: the same for chains over up to 16 paths (gain factor n (n - 1) / 2 <= 120) and over up to 64 (csrc/rv_leaf_multi_chain.hip)
 LARGE_MAX = 1 << 17        # default of RV_MANY_LARGE_MAX: ranks of the largest pair job the shared launches take with RV_MANY_LARGE
 CHAIN_LARGE_RANKS = 1 << 17  # RV_PICK_CHAIN_RANKS: ranks of the largest pair job RV_MANY_CHAIN_LARGE takes, whatever RV_MANY_LARGE_MAX says (17-bit positions)
+CHAIN_LARGE_MULTI_WMAX = 512  # RV_PICK_MCHAIN_WMAX: weights up to this keep the chain's scores in 32 bits over up to 16 paths of a job of 2^17 ranks (csrc/rv_pick_multi_chain.hip)
+CHAIN_LARGE_MULTI_MIN = 4  # default of RV_MANY_CHAIN_LARGE_MULTI_MIN: fewer admitted jobs of 3 .. 16 sequences above 2048 ranks in a call under a picker stay ordinary
 CHAIN_LARGE_MIN = 4        # default of RV_MANY_CHAIN_LARGE_MIN: fewer admitted pair jobs above 2048 ranks in a call under a picker stay ordinary
 
 
@@ -134,7 +146,7 @@ def picker_struct(args):
 
 
 def takes_shared_launch(seqs, multi=False, large=False, large_max=LARGE_MAX, large_multi=False, wide=False, picker=None, chain=False, minlength=20,
-                        chain_multi=False, chain_wide=False, chain_large=False):
+                        chain_multi=False, chain_wide=False, chain_large=False, chain_large_multi=False):
     """whether the library builds and finishes this job in the shared launches; multi: with RV_MANY_MULTI on; large: with RV_MANY_LARGE
     on and RV_MANY_LARGE_MAX = large_max (in a call with at least RV_MANY_LARGE_MIN such jobs, and with rounds that hold the job);
     large_multi: with RV_MANY_LARGE_MULTI on (in a call with at least RV_MANY_LARGE_MULTI_MIN such jobs, and with rounds that hold the job);
@@ -143,13 +155,20 @@ def takes_shared_launch(seqs, multi=False, large=False, large_max=LARGE_MAX, lar
     minlength: of the run (csrc/rv_many.hip many_chain_admits); chain_multi: with RV_MANY_CHAIN_MULTI on -- under a picker, the jobs of 3 .. 16
     sequences (csrc/rv_many.hip many_chain_multi_admits); chain_wide: with RV_MANY_CHAIN_WIDE on -- under a picker, the jobs of 17 .. 64 sequences
     (csrc/rv_many.hip many_chain_wide_admits); chain_large: with RV_MANY_CHAIN_LARGE on -- under a picker, the pair jobs of 2049 .. min(large_max, 2^17)
-    ranks (csrc/rv_many.hip many_chain_large_admits), in a call with at least RV_MANY_CHAIN_LARGE_MIN such jobs and with rounds that hold the job"""
+    ranks (csrc/rv_many.hip many_chain_large_admits), in a call with at least RV_MANY_CHAIN_LARGE_MIN such jobs and with rounds that hold the job;
+    chain_large_multi: with RV_MANY_CHAIN_LARGE_MULTI on -- under a picker, the jobs of 3 .. 16 sequences and 2049 .. min(large_max, 2^17) ranks
+    (csrc/rv_many.hip many_chain_large_multi_admits), in a call with at least RV_MANY_CHAIN_LARGE_MULTI_MIN such jobs and with rounds that hold the job"""
     k = len(seqs)
     ranks = sum(len(s) for s in seqs) + k
     if any(b"\0" in s for s in seqs):
         return False
     if picker is not None:
         A = picker_struct(picker)
+        if ranks > LEAF_RANKS and 3 <= k <= MULTI_KMAX:
+            if not chain_large_multi or ranks > min(int(large_max), CHAIN_LARGE_RANKS):
+                return False
+            return bool(A.trim and int(minlength) > 0 and 0 <= A.wscore <= CHAIN_LARGE_MULTI_WMAX and 0 <= A.wpen <= CHAIN_LARGE_MULTI_WMAX
+                        and (A.seedsize <= 0 or A.seedsize > max(len(s) for s in seqs)) and (A.maxmums <= 0 or A.maxmums >= ranks))
         if ranks > LEAF_RANKS:
             if not chain_large or k != 2 or ranks > min(int(large_max), CHAIN_LARGE_RANKS):
                 return False
@@ -247,7 +266,7 @@ class Batch:
                 self.option(name, iv)
         for name in ("RV_MANY_KEEP", "RV_MANY_ROUND", "RV_MANY_WAVE_MAX", "RV_MANY_MULTI", "RV_MANY_LARGE", "RV_MANY_LARGE_MAX", "RV_MANY_LARGE_MIN",
                      "RV_MANY_LARGE_MULTI", "RV_MANY_LARGE_MULTI_MIN", "RV_MANY_WIDE", "RV_MANY_WIDE_LARGE_MIN", "RV_MANY_CHAIN", "RV_MANY_CHAIN_MULTI", "RV_MANY_CHAIN_WIDE",
-                     "RV_MANY_CHAIN_LARGE", "RV_MANY_CHAIN_LARGE_MIN"):
+                     "RV_MANY_CHAIN_LARGE", "RV_MANY_CHAIN_LARGE_MIN", "RV_MANY_CHAIN_LARGE_MULTI", "RV_MANY_CHAIN_LARGE_MULTI_MIN"):
             v = os.environ.get(name)
             if v is not None and v.strip():
                 self.option(name, int(v))
@@ -330,7 +349,7 @@ class Batch:
 
 
 def align_many(jobs, minlength=20, minn=2, sa64=False, toupper=True, batch=None, multi=None, large=None, large_multi=None, wide=None, picker=None, chain=None,
-               chain_multi=None, chain_wide=None, chain_large=None):
+               chain_multi=None, chain_wide=None, chain_large=None, chain_large_multi=None):
     """jobs: a list of jobs, each a list of (name, seq) or of plain sequences (two or more, none empty; every sequence is a sample
     of its own, like the inputs of `reveal rem`).  -> (results, info): results[j] = dict(anchors=[(l, (pos, ..)), ..], T=final text
     `s0$s1$..` lower-cased where aligned), positions in the coordinates of the job's own text -- what index.align_builtin gives a
@@ -346,7 +365,8 @@ def align_many(jobs, minlength=20, minn=2, sa64=False, toupper=True, batch=None,
     2048 ranks through the shared launches, see the module docstring) for this and later runs of the batch; None leaves it.  `chain_multi`: the
     same for RV_MANY_CHAIN_MULTI (with a picker: the jobs of 3 .. 16 sequences and at most 2048 ranks through the shared launches), `chain_wide`: the
     same for RV_MANY_CHAIN_WIDE (with a picker: the jobs of 17 .. 64 sequences and at most 2048 ranks through the shared launches), `chain_large`: the
-    same for RV_MANY_CHAIN_LARGE (with a picker: the pair jobs of 2049 .. 2^17 ranks through the shared launches)."""
+    same for RV_MANY_CHAIN_LARGE (with a picker: the pair jobs of 2049 .. 2^17 ranks through the shared launches), `chain_large_multi`: the same for
+    RV_MANY_CHAIN_LARGE_MULTI (with a picker: the jobs of 3 .. 16 sequences and 2049 .. 2^17 ranks through the shared launches)."""
     if isinstance(jobs, (str, bytes, bytearray)) or not hasattr(jobs, "__iter__"):
         raise error("jobs is a list of jobs")
     if int(minlength) < 0 or int(minn) < 2:
@@ -364,6 +384,8 @@ def align_many(jobs, minlength=20, minn=2, sa64=False, toupper=True, batch=None,
         b.option("RV_MANY_CHAIN_WIDE", 1 if chain_wide else 0)
     if chain_large is not None:
         b.option("RV_MANY_CHAIN_LARGE", 1 if chain_large else 0)
+    if chain_large_multi is not None:
+        b.option("RV_MANY_CHAIN_LARGE_MULTI", 1 if chain_large_multi else 0)
     if multi is not None:
         b.option("RV_MANY_MULTI", 1 if multi else 0)
     if large is not None:

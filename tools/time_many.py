@@ -37,6 +37,10 @@ that kernel), off (the ordinary path), and the built-in picker with RV_MANY_WIDE
 level pipeline with the picker's decision made by k_pick_chain and k_leaf_chain), off (the ordinary path), and the built-in picker with RV_MANY_LARGE on (the
 same rounds with the longest-match kernel).  --chain-large-min J sets RV_MANY_CHAIN_LARGE_MIN.  With RV_LIB_DIR set to a build from before the switch the
 ordinary side alone is timed, on the same jobs: the yardstick.
+--picker --chain-large-multi (with --seqs K, K = 3 .. 16; choose --lmin / --lmax so that the jobs lie above 2048 ranks, and --maxmums / --seedsize above their
+ranks / sequences so that all are admitted): the same for jobs of K sequences above 2048 ranks -- RV_MANY_CHAIN_LARGE_MULTI on (the multi-sample level pipeline
+with the picker's decision made by k_pick_multi_chain), off (the ordinary path), and the built-in picker with RV_MANY_LARGE_MULTI on (the same rounds with the
+longest-match kernels).  --chain-large-multi-min J sets RV_MANY_CHAIN_LARGE_MULTI_MIN.
 The chain side's info["ordinary"] is the number of jobs the kernel flagged.  --save-digests FILE writes a digest per job of the picker side's anchors (the chain side, or
 the ordinary side where the build has none); --compare-digests FILE counts the jobs whose digest differs from that file's: two builds run in a process
 each, and this is how their results are compared."""
@@ -191,11 +195,13 @@ def main_ab(a, jobs, bases, switch="RV_MANY_MULTI"):
 def main_picker(a, jobs, bases):
     """the reference's default picker: RV_MANY_CHAIN on / off, the built-in picker beside them, rem.align per job"""
     from reveal_amd import many, rem, schemes
-    args = schemes.PickerArgs(maxmums=10000)      # (rem.align's defaults)
+    args = schemes.PickerArgs(maxmums=a.maxmums, seedsize=a.seedsize)      # (10 000 / 10 000: rem.align's defaults)
     sides = {}
     switch = "RV_MANY_CHAIN" if a.seqs == 2 else ("RV_MANY_CHAIN_MULTI" if a.seqs <= 16 else "RV_MANY_CHAIN_WIDE")
     if a.chain_large:
         switch = "RV_MANY_CHAIN_LARGE"
+    if a.chain_large_multi:
+        switch = "RV_MANY_CHAIN_LARGE_MULTI"
     for name, pk, chain in (("chain", args, 1), ("ordinary", args, 0), ("builtin", None, 0)):
         b = many.Batch(False)
         b.set_picker(pk)
@@ -207,6 +213,11 @@ def main_picker(a, jobs, bases):
                 continue
         if a.seqs > 2 and pk is None:
             b.option("RV_MANY_MULTI" if a.seqs <= 16 else "RV_MANY_WIDE", 1)
+        if a.chain_large_multi and pk is None:
+            b.option("RV_MANY_LARGE_MULTI", 1)
+            b.option("RV_MANY_LARGE_MULTI_MIN", 1)
+        if a.chain_large_multi and chain and a.chain_large_multi_min is not None:
+            b.option("RV_MANY_CHAIN_LARGE_MULTI_MIN", a.chain_large_multi_min)
         if a.chain_large and pk is None:
             b.option("RV_MANY_LARGE", 1)
         if a.chain_large and chain and a.chain_large_min is not None:
@@ -239,7 +250,7 @@ def main_picker(a, jobs, bases):
     rem_res = []
     t = time.perf_counter()
     for job in jobs[:nrem]:
-        rem_res.append(rem.align([("s%d" % k, s.decode()) for k, s in enumerate(job)], minlength=a.minlength))
+        rem_res.append(rem.align([("s%d" % k, s.decode()) for k, s in enumerate(job)], minlength=a.minlength, maxmums=a.maxmums, seedsize=a.seedsize))
     out["rem_jobs"] = nrem; out["rem_s"] = time.perf_counter() - t
     out["rem_per_job_s"] = out["rem_s"] / max(nrem, 1)
     print("rem.align per job: %d jobs in %.2f s, %.2f ms a job, %.0f jobs/s" % (nrem, out["rem_s"], 1e3 * out["rem_per_job_s"], nrem / out["rem_s"]))
@@ -297,6 +308,10 @@ def main():
     ap.add_argument("--chain-wide", action="store_true", help="--picker for jobs of --seqs K = 17 .. 64 sequences: RV_MANY_CHAIN_WIDE on / off, the built-in picker with RV_MANY_WIDE")
     ap.add_argument("--chain-large", action="store_true", help="--picker for pair jobs above 2048 ranks: RV_MANY_CHAIN_LARGE on / off, the built-in picker with RV_MANY_LARGE")
     ap.add_argument("--chain-large-min", type=int, default=None, help="RV_MANY_CHAIN_LARGE_MIN")
+    ap.add_argument("--chain-large-multi", action="store_true", help="--picker for jobs of --seqs K = 3 .. 16 sequences above 2048 ranks: RV_MANY_CHAIN_LARGE_MULTI on / off, the built-in picker with RV_MANY_LARGE_MULTI")
+    ap.add_argument("--chain-large-multi-min", type=int, default=None, help="RV_MANY_CHAIN_LARGE_MULTI_MIN")
+    ap.add_argument("--maxmums", type=int, default=10000, help="--picker: the picker's maxmums (rem.align's default)")
+    ap.add_argument("--seedsize", type=int, default=10000, help="--picker: the picker's seedsize (rem.align's default)")
     ap.add_argument("--save-digests", default=None, help="--picker: write a digest per job of the picker side's anchors to this file")
     ap.add_argument("--compare-digests", default=None, help="--picker: count the jobs whose digest differs from this file's")
     a = ap.parse_args()
@@ -308,6 +323,11 @@ def main():
         if a.seqs != 2:
             ap.error("--chain-large times pair jobs")
         a.picker = True
+    elif a.chain_large_multi:
+        if not 3 <= a.seqs <= 16:
+            ap.error("--chain-large-multi times jobs of 3 .. 16 sequences: --seqs K")
+        a.picker = True
+        a.no_cut = True
     elif a.picker and not 2 <= a.seqs <= 16:
         ap.error("--picker times jobs of 2 .. 16 sequences (17 .. 64: --chain-wide)")
     if [a.multi, a.large, a.large_multi, a.wide].count("ab") > 1:
