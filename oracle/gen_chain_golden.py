@@ -9,7 +9,11 @@ imports of those files (intervaltree, matplotlib ...) are never executed, so not
 Python-2 semantics the converted code would otherwise lose are restored explicitly, as SURVEY.md Appendix A lists them:
 `/` on ints is floor division (schemes.py:71, utils.py:166-168) and `x > None` is True for any number (schemes.py:84).
 
-    python oracle/gen_chain_golden.py        # rewrites tests/golden/chain_vectors.json
+    python oracle/gen_chain_golden.py        # rewrites tests/golden/chain_vectors.json and tests/golden/chain_vectors_wide.json
+
+chain_vectors_wide.json (wide_vectors) holds chain() alone where the device pickers' bounds lie: 2, 16 and 64 paths, coordinates up to 2^17, weights
+512, 1024 and 65536, the three gap models, far-path shapes among the cases -- rv_chain supplies the picks of every golden file of the align_many
+tests, and the first file pins it at weights <= 4, k <= 7 and spans <= 30 000 only.
 """
 import ast
 import json
@@ -101,6 +105,69 @@ def random_case(rng, m, k, span, collinear):
     return mums, left, right
 
 
+WIDE_K = (2, 16, 64)
+WIDE_W = (512, 1024, 65536)            # the weight bounds of the device pickers (RV_PICK_MCHAIN_WMAX, RV_LEAF_MCHAIN_WMAX, RV_LEAF_CHAIN_WMAX)
+WIDE_MODELS = ("sumofpairs", "star-avg", "star-med")
+WIDE_TOP = 1 << 17                     # coordinates up to here: the ranks of the largest job a device picker takes
+
+
+def wide_case(rng, m, k, far, spread):
+    """m matches over k paths with coordinates up to 2^17.  far: None -- a collinear backbone over all of (0, 2^17) plus noise, as random_case; 0 or
+    k - 1 -- the far-path shape: every path but this one keeps its matches within a few thousand bases, a few bases apart from path to path, and this
+    one spreads them over all of 2^17 -- one path far away, the others at hand, the shape that reaches the gap bounds of the device pickers.  A share
+    of the matches (spread) lies off the backbone on some of its paths, so that the chain has something to leave out"""
+    keys = list(range(k))
+    near = sorted(rng.sample(range(10, 4000 if far is not None else WIDE_TOP - 200), m))
+    wide = sorted(rng.sample(range(10, WIDE_TOP - 200), m))
+    mums = []
+    jitter = max(1, 30 // k)           # (sum of pairs adds the jitter up over k (k - 1) / 2 pairs: kept small against the gains)
+    for i in range(m):
+        l = rng.randint(1, 60)
+        noise = rng.random() < spread
+        crd = {}
+        for q in keys:
+            if q == far:
+                crd[q] = wide[i]
+            elif q == 0 or (far == 0 and q == 1):
+                crd[q] = near[i]
+            elif noise and rng.random() < 0.3:
+                crd[q] = rng.randint(5, 4000 if far is not None else WIDE_TOP - 200)
+            else:
+                crd[q] = max(0, near[i] + rng.randint(-jitter, jitter))
+        mums.append((l, k, crd))
+    left = (0, 0, {q: -1 for q in keys})
+    right = (0, 0, {q: WIDE_TOP if q == far or far is None else 4100 for q in keys})
+    return mums, left, right
+
+
+def wide_vectors(chain):
+    """tests/golden/chain_vectors_wide.json: the reference's chain() where the device pickers' bounds lie -- k of 2, 16 and 64 paths, coordinates up to
+    2^17, weights 512, 1024 and 65536 as (W, W), (1, W) and (W, 1), the three gap models, up to 40 matches; a far-path case per k, weight and model (the
+    far path first or last) and a backbone case per k and weight"""
+    rng = random.Random(20261019)
+    out = []
+
+    def add(k, wscore, wpen, model, m, far, spread):
+        Args.wscore, Args.wpen = wscore, wpen
+        mums, left, right = wide_case(rng, m, k, far, spread)
+        res = chain([(l, n, dict(c)) for l, n, c in mums], left, right, gcmodel=model)
+        keys = sorted(left[2])
+        out.append({"wscore": wscore, "wpen": wpen, "gcmodel": model, "keys": keys, "left": [left[2][q] for q in keys], "right": [right[2][q] for q in keys],
+                    "mums": [[l, n] + [c[q] for q in keys] for l, n, c in mums],
+                    "path": [[mm[0], mm[1]] + [mm[2][q] for q in keys] + [sc] for mm, sc in res]})
+    x = 0
+    for k in WIDE_K:
+        m = {2: 40, 16: 32, 64: 14}[k]
+        for wi, W in enumerate(WIDE_W):
+            for mi, model in enumerate(WIDE_MODELS):
+                wscore, wpen = ((W, W), (1, W), (W, 1))[(wi + mi) % 3]       # (every model meets each of the three forms, once per weight)
+                add(k, wscore, wpen, model, m, (0, k - 1)[x % 2], 0.15)
+                x += 1
+            add(k, W, W, "sumofpairs", m, None, 0.25)
+    Args.wscore, Args.wpen = 1, 1
+    return {"_generator": "oracle/gen_chain_golden.py: reveal/schemes.py chain + reveal/utils.py gapcost, converted in memory (lib2to3) and executed", "chain": out}
+
+
 def main():
     gapcost, env = load()
     chain, trim_overlap, segment = env["chain"], env["trim_overlap"], env["segment"]
@@ -150,6 +217,11 @@ def main():
     with open(os.path.join(ROOT, "tests", "golden", "chain_vectors.json"), "w") as f:
         json.dump(out, f, sort_keys=True)
     print("wrote tests/golden/chain_vectors.json: %d gapcost, %d chain, %d trim_overlap, %d segment cases" % (len(out["gapcost"]), len(out["chain"]), len(out["trim_overlap"]), len(out["segment"])))
+    wide = wide_vectors(chain)
+    with open(os.path.join(ROOT, "tests", "golden", "chain_vectors_wide.json"), "w") as f:
+        json.dump(wide, f, sort_keys=True, separators=(",", ":"))
+        f.write("\n")
+    print("wrote tests/golden/chain_vectors_wide.json: %d chain cases, scores up to 2^%.1f" % (len(wide["chain"]), math.log2(max(abs(r[-1]) for c in wide["chain"] for r in c["path"]))))
 
 
 if __name__ == "__main__":

@@ -2,7 +2,9 @@
 checks the list and the golden file, tests/test_gpu_many_chain_large.py runs it): the large class jobs of many_large_cases, a class of its own whose alleles
 carry swapped, dropped or duplicated blocks of a few hundred bases -- where trimming and chaining choose other anchors than the longest match --, a class of
 long alleles 1 % apart with more than 64 matches at the root, and the corners: the first size above the leaf kernel's, alleles of 9 999 bases (1 % apart,
-and identical), and one job of 80 002 ranks whose positions do not fit 16 bits.  Deterministic.  The expected results (tests/golden/many_chain_large.json,
+and identical), and one job of 80 002 ranks (2 x 40 000 bases) whose TEXT positions do not fit 16 bits -- the positions k_pick_chain packs are relative
+to the interval begins and stay below 40 000 there, bit 16 of neither field is set; tests/many_chain_limits_cases.py has the jobs of 2^17 ranks that set
+it on either path (tests/test_gpu_many_chain_limits.py test_the_jobs_of_2_17_ranks).  Deterministic.  The expected results (tests/golden/many_chain_large.json,
 written by tools/gen_many_chain_large_golden.py) come from `rem.align` on the REFERENCE's own index module."""
 import hashlib
 import json
@@ -55,7 +57,7 @@ def corner_jobs():
 
 
 def big_job():
-    """the job of 80 002 ranks (positions beyond 16 bits)"""
+    """the job of 80 002 ranks (text positions beyond 16 bits; the kernel's positions, relative to the interval begins, stay below 2^16)"""
     a, b = lc.corner_jobs()[7]
     assert len(a) + len(b) + 2 == 80002
     return a, b

@@ -69,7 +69,8 @@ def test_every_job_equals_the_reference_on_the_ordinary_path(jobs, golden, name,
 @pytest.mark.parametrize("sa64", [False, True])
 def test_positions_beyond_16_bits(golden, sa64):
     """the job of 80 002 ranks under its own set (a seedsize and a maxmums that admit it), with three small fillers so that the call reaches
-    RV_MANY_CHAIN_LARGE_MIN"""
+    RV_MANY_CHAIN_LARGE_MIN.  Its TEXT positions go beyond 16 bits; the positions k_pick_chain packs, relative to the interval begins, stay below
+    40 000 < 2^16 -- bit 16 of the packed fields is set by the jobs of 2^17 ranks of tests/test_gpu_many_chain_limits.py test_the_jobs_of_2_17_ranks"""
     name, kw = cl.BIG_SET
     batch = [list(cl.big_job())] + [list(p) for p in cl.fillers()]
     args = cl.picker_args(kw)
