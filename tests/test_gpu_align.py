@@ -27,8 +27,10 @@ def oracle_run(inputs, minl, minn, sa64=False):
     return O.align_bench(c, nodes, minl, minn, trace_cap=4 * len(T) // max(minl, 1) + 1000), T
 
 
-def compare(inputs, minl=20, minn=2, sa64=False):
-    ref, T = oracle_run(inputs, minl, minn, sa64)
+def compare(inputs, minl=20, minn=2, sa64=False, ref=None):
+    """ref: what oracle_run gives for these arguments, where the caller has it already"""
+    if ref is None:
+        ref, T = oracle_run(inputs, minl, minn, sa64)
     idx = feed(mod(sa64).index(), inputs)
     idx.construct()
     got = idx.align_builtin(minl, minn, trace=True)
@@ -216,7 +218,8 @@ def test_parallel_bubble_rounds(monkeypatch, par_min, name, inputs, minl, sa64):
     ("5way", fa("1a", "1b", "1c", "1d", "1e"), 20),
     ("synth12", (30000, 12), 20),       # picker windows from LDS (up to 16 samples)
     ("synth20", (20000, 20), 20),       # more than 16 samples: the picker's general form
-    ("synth70", (4000, 70), 15),        # more than 64 samples: sample sets no longer fit a bit mask
+    ("synth70", (4000, 70), 15),        # more than 64 samples -- but one sub-index and NO anchor: every window of 15 bases differs in some member
+    ("wide65", "wide", 12),             # more than 64 samples with anchors: sample sets no longer fit a bit mask (tests/wide_sample_cases.py)
 ])
 @pytest.mark.parametrize("cascade", [False, True])
 def test_untraced_run_same_anchors(monkeypatch, name, inputs, minl, cascade):
@@ -229,6 +232,9 @@ def test_untraced_run_same_anchors(monkeypatch, name, inputs, minl, cascade):
         inputs = [g.decode() for g in synth.genomes(400000, 2)]
     elif isinstance(inputs, tuple):
         inputs = [g.decode() for g in synth.genomes(inputs[0], inputs[1], seed=3)]
+    elif inputs == "wide":
+        import wide_sample_cases as wc
+        inputs = wc.family(65, wc.SEEDS[65])
     ref, T = oracle_run(inputs, minl, 2)
     idx = feed(mod(False).index(), inputs)
     idx.construct()
@@ -238,6 +244,7 @@ def test_untraced_run_same_anchors(monkeypatch, name, inputs, minl, cascade):
     gl, goff, gpos = got["anchors"]
     ga = sorted((int(gl[k]), tuple(int(x) for x in gpos[goff[k]:goff[k + 1]])) for k in range(len(gl)))
     assert ra == ga
+    assert (len(ra) == 0) == (name == "synth70")
     assert idx.T.encode("latin-1") == ref["T"]
     assert got["stats"]["splits"] == ref["stats"]["nsplits"]
     if len(inputs) == 2:      # two samples: every sub-index the reference visits is counted (the leaf kernel counts the ones it does not scan)

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Randomised parity soak: the GPU recursion (traced and untraced, default and forced code paths) against the CPU oracle
 on random inputs -- SNPs, indels, tandem repeats, N runs, several contigs, 2-4 samples.  Test infrastructure.
-usage: python tools/fuzz.py [seconds] [seed]      (FUZZ_BIG=1 adds inputs of 1 and 2.5 Mbp per sample; FUZZ_CASES=N stops after N cases whatever
-the time; FUZZ_ENVS=3,27 runs those entries of ENVS only)"""
+usage: python tools/fuzz.py [--wide] [seconds] [seed]      (FUZZ_BIG=1 adds inputs of 1 and 2.5 Mbp per sample; FUZZ_CASES=N stops after N cases
+whatever the time; FUZZ_ENVS=3,27 runs those entries of ENVS only; --wide: families of 5 .. 130 samples from tests/wide_sample_cases.py, and
+without FUZZ_ENVS the entries WIDE_ENVS, the switches the multi-sample path reads)"""
 import os
 import random
 import sys
@@ -49,6 +50,7 @@ ENVS = [
     {"RV_CAS_WITNESS_PASS": "1"},                         # the cascade's witnesses from a pass of their own (k_cas_witness), not from the top-level pair scan
     {"RV_CAP_LIMIT": "48", "RV_CAP_SITES": "511"},        # every estimated capacity RV_CAP_LIMIT reaches starts at 48: the cascades give up on a full list, the multi picker goes round again
 ]
+WIDE_ENVS = (0, 1, 5, 11, 12, 24, 27)
 
 
 def mutate(rng, base, snp, indel):
@@ -85,6 +87,14 @@ def make_case(rng):
     if rng.random() < 0.2:      # identical copy
         seqs[-1] = seqs[0]
     return seqs, rng.choice([10, 20, 20, 30])
+
+
+def make_wide_case(rng):
+    """a family of 5 .. 130 samples on the variant-sites model (tests/wide_sample_cases.py): sub-indices of 2 .. k samples, matches on subsets"""
+    import wide_sample_cases      # (tests/: only this mode needs it, and make_case's callers need nothing but make_case)
+    k = rng.randint(5, 130)
+    seqs = wide_sample_cases.family(k, rng.randrange(1, 1 << 20))
+    return seqs, rng.choice([10, 12, 20])
 
 
 def maybe_contigs(rng, seqs):
@@ -146,15 +156,17 @@ def divided(M, seqs, minl, stop, nparts, trace):
 
 
 def main():
-    budget = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
-    seed = int(sys.argv[2]) if len(sys.argv) > 2 else int(time.time())
+    args = [a for a in sys.argv[1:] if a != "--wide"]
+    wide = "--wide" in sys.argv[1:]
+    budget = float(args[0]) if len(args) > 0 else 60.0
+    seed = int(args[1]) if len(args) > 1 else int(time.time())
     rng = random.Random(seed)
     t_end = time.time() + budget
     max_cases = int(os.environ.get("FUZZ_CASES", "0"))
-    envs = [ENVS[int(k)] for k in os.environ["FUZZ_ENVS"].split(",")] if os.environ.get("FUZZ_ENVS") else ENVS
+    envs = [ENVS[int(k)] for k in os.environ["FUZZ_ENVS"].split(",")] if os.environ.get("FUZZ_ENVS") else [ENVS[k] for k in WIDE_ENVS] if wide else ENVS
     ncase = 0
     while time.time() < t_end and not (max_cases and ncase >= max_cases):
-        seqs, minl = make_case(rng)
+        seqs, minl = make_wide_case(rng) if wide else make_case(rng)
         seqs = maybe_contigs(rng, seqs)
         sa64 = rng.random() < 0.2
         if ONLY >= 0 and ncase != ONLY:      # replay the generator up to one case (FUZZ_ONLY=<case>)
@@ -207,7 +219,7 @@ def main():
                 for f in FIELDS:
                     assert len(gd[f]) == len(rd[f]) and (gd[f] == rd[f]).all(), "trace field %s %s" % (f, tag)
         ncase += 1
-    print("fuzz: %d cases x (%d configurations + divided run) x 2 (traced / untraced) identical to the oracle (seed %d)" % (ncase, len(envs), seed))
+    print("fuzz%s: %d cases x (%d configurations + divided run) x 2 (traced / untraced) identical to the oracle (seed %d)" % (" --wide (5 .. 130 samples)" if wide else "", ncase, len(envs), seed))
 
 
 if __name__ == "__main__":
