@@ -593,6 +593,13 @@ int rv_sa_diag_table(rv_index *h);      /* 1: two samples on piecewise diagonals
 /* what finished the suffixes the first key and the text round left tied (agreement beyond 4 KB: near-identical inputs, repeats): out[0] = tied
  * pairs of partners ordered from the diagonal's marks, out[1] = ranks whose LCP / BWT came from the text after the doubling rounds */
 int rv_sa_tail(rv_index *h, int64_t *out);
+/* which side of each host decision the SA build of the last rv_construct took (read-only; nothing of it is computed for this call).
+ * Up to `count` values, in this order; returns how many were written (RV_SA_PATHS_FIELDS = 27 exist) or -1:
+ *   tiny, short_alphabet, ends_with_sep, g, K, bits, fused_asked, fused_final, hint_ns, nd_bits, collapse, diag_table_tried,
+ *   diag_table_kept, heads_kernel (0 k_heads + k_publish0, 1 k_heads_publish, 2 k_heads_publish_tc), text_round, text_mode,
+ *   packed_text, text_big, far_ran, nd_table, doubling_rounds, slow_class, text_jump, lcp_list_overflow, defer_max, defer_cap,
+ *   lcp_by_rank.  The counting build of short texts (tiny) sets tiny and the fused pair and leaves the rest 0. */
+int rv_sa_paths(rv_index *h, int64_t *out, int count);
 
 /* ---- self-test hooks for the device primitives (tests/ only) ------------------ */
 int rv_test_exclusive_sum_u32(const uint32_t *in, uint32_t *out, int64_t n);

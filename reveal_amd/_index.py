@@ -209,6 +209,14 @@ def make_index_type(sa64, error):
             return dict(sigma=v[0].value, bits=v[1].value, k0=v[2].value, rounds=v[3].value, sorted_elems=se.value, radix_passes=rp.value,
                         diag_table=int(self._dll.rv_sa_diag_table(self._h)), far_pairs=int(tail[0]), lcp_list=int(tail[1]))
 
+        def sa_paths(self):
+            """which side of each host decision the SA build of the last construct() took (rv_sa_paths): {field: int}"""
+            out = (ctypes.c_int64 * len(_lib.SA_PATHS))()
+            got = self._dll.rv_sa_paths(self._h, out, len(_lib.SA_PATHS))
+            if got != len(_lib.SA_PATHS):
+                raise error("rv_sa_paths: %d of %d fields" % (got, len(_lib.SA_PATHS)))
+            return {name: int(out[k]) for k, name in enumerate(_lib.SA_PATHS)}
+
         # ---- construct --------------------------------------------------------
         def construct(self, rc=0):                          # interface.c:160-291
             if self._sx:

@@ -22,6 +22,11 @@ CAPACITY_EVENTS = ("pair_ovf", "pair_out", "pair_pick_ovf", "pair_second_copy", 
 CAP_SITES = {"multi_cand": 1, "cas_wit": 2, "cas_tables": 4, "casm_matches": 8, "casm_wit": 16, "casm_tables": 32,
              "mems_rec": 64, "mems_mem": 128, "mems_long": 256}
 
+# rv_sa_paths: the order of RvSaPaths (rv_common.h)
+SA_PATHS = ("tiny", "short_alphabet", "ends_with_sep", "g", "K", "bits", "fused_asked", "fused_final", "hint_ns", "nd_bits", "collapse",
+            "diag_table_tried", "diag_table_kept", "heads_kernel", "text_round", "text_mode", "packed_text", "text_big", "far_ran", "nd_table",
+            "doubling_rounds", "slow_class", "text_jump", "lcp_list_overflow", "defer_max", "defer_cap", "lcp_by_rank")
+
 c_i64p = ctypes.POINTER(ctypes.c_int64)
 V = ctypes.c_void_p
 
@@ -136,6 +141,7 @@ SYMBOLS = {
     "rv_sa_stats": (_I, [V] + [ctypes.POINTER(_I)] * 4 + [c_i64p, ctypes.POINTER(_I)]),
     "rv_sa_diag_table": (_I, [V]),
     "rv_sa_tail": (_I, [V, c_i64p]),
+    "rv_sa_paths": (_I, [V, c_i64p, _I]),
     "rv_set_picker": (_I, [V, _I, V]),
     "rv_picker_info": (_I, [V, c_i64p]),
     "rv_pick_chain": (_I, [V, _I, _L, V, V, V, V, V, _I, V, V, V, _I, V]),

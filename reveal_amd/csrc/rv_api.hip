@@ -497,6 +497,7 @@ int rv_construct(rv_index *h, int rc, const char *safile, const char *lcpfile, i
             int id = h->prof.begin(q, RV_K_LCP, 13.0 * (double)n);
             RV_TRY(rv_build_lcp(h->ws, h->dT0.as<uint8_t>(), h->dSA.as<sa_t>(), false, h->dLCP.as<lcp_t>(), n, d_max, h->dBWT.as<uint8_t>(), side_sep));
             h->prof.end(q, id);
+            h->sa_stats.paths.lcp_by_rank = h->ws.opt.lcp_by_rank ? 1 : 0;
         }
         RV_TRY(rv_read_back(h->ws, &h->maxlcp, d_max, 4));
     } else {
@@ -1080,6 +1081,17 @@ int rv_sa_stats(rv_index *h, int *sigma, int *bits, int *k0, int *rounds, int64_
 int rv_sa_diag_table(rv_index *h) { return h->sa_stats.diag_table; }
 /* what finished the suffixes the first key and the text round left tied in the last construct(): out[0] tied pairs of partners ordered from the
  * diagonal's marks (k_far_twins), out[1] ranks whose LCP / BWT came from the text after the doubling rounds (k_lcp_list) */
+int rv_sa_paths(rv_index *h, int64_t *out, int count) {
+    if (!h || !out || count < 0) return -1;
+    const RvSaPaths &p = h->sa_stats.paths;
+    const int64_t v[RV_SA_PATHS_FIELDS] = {
+        p.tiny, p.short_alphabet, p.ends_with_sep, p.g, p.K, p.bits, p.fused_asked, p.fused_final, p.hint_ns, p.nd_bits, p.collapse,
+        p.diag_table_tried, p.diag_table_kept, p.heads_kernel, p.text_round, p.text_mode, p.packed_text, p.text_big, p.far_ran, p.nd_table,
+        p.doubling_rounds, p.slow_class, p.text_jump, p.lcp_list_overflow, p.defer_max, p.defer_cap, p.lcp_by_rank };
+    const int m = count < RV_SA_PATHS_FIELDS ? count : RV_SA_PATHS_FIELDS;
+    for (int k = 0; k < m; k++) out[k] = v[k];
+    return m;
+}
 int rv_sa_tail(rv_index *h, int64_t *out) { if (!h || !out) return -1; out[0] = h->sa_stats.far_pairs; out[1] = h->sa_stats.lcp_list; return 0; }
 
 /* ---- the node's practical HBM ceiling (SURVEY 8(d) "Roofline": measured copy-kernel bandwidth beside the 8 TB/s spec) ---- */

@@ -426,6 +426,25 @@ int rv_read_back2(Workspace &ws, void *dst_a, const void *dsrc_a, size_t bytes_a
 int rv_h2d_copy(Workspace &ws, const void *pinned_src, void *dst, size_t bytes);
 
 // ---- construct (rv_construct.hip) ------------------------------------------
+// which side of each of rv_build_sa's host decisions a build took (read-only census: rv_sa_paths hands the fields out in this order)
+struct RvSaPaths {
+    int tiny;                                   // the counting build ran (k_sa_tiny_rank / k_sa_tiny_emit); everything below but the fused pair stays 0
+    int short_alphabet, ends_with_sep;          // "past the end" spells the separator when both are set
+    int g, K, bits;                             // key layout: digits per field, symbols and bits of the first key
+    int fused_asked, fused_final;               // LCP / BWT from the build itself: requested / kept to the end
+    int hint_ns, nd_bits;                       // samples the diagonal hint knows / hint bits in the key
+    int collapse;                               // twins of the second sample leave before the sort
+    int diag_table_tried, diag_table_kept;      // piecewise diagonals
+    int heads_kernel;                           // 0 k_heads + k_publish0, 1 k_heads_publish, 2 k_heads_publish_tc
+    int text_round, text_mode, packed_text;     // the text round ran, the work division that ran (0 when it did not), the 2-bit text was used
+    int text_big;                               // a group above MEDIUM_GROUP went through the radix path in the text round
+    int far_ran, nd_table;                      // k_far_twins ran, with the table of k_far_nd
+    int doubling_rounds, slow_class, text_jump; // rounds ordered by ranks (k_round_small), classes made, h jumped to TEXT_LIM
+    int lcp_list_overflow;                      // k_lcp_list met a common prefix it gave up on
+    int64_t defer_max, defer_cap;               // k_round_text3: largest per-region count of its work list, and reg_cap
+    int lcp_by_rank;                            // rv_build_lcp ran rank by rank (k_lcp) after the build (set by rv_construct)
+};
+#define RV_SA_PATHS_FIELDS 27
 struct RvSaStats {
     int    sigma, bits, k0;     // alphabet size, bits per symbol, symbols in the first key
     int    rounds;              // doubling rounds after the initial sort
@@ -434,6 +453,7 @@ struct RvSaStats {
     int    diag_table;          // two samples: the hint and the twins' leaving follow piecewise diagonals from seeds (k_diag_bits_tab)
     int64_t far_pairs;          // tied pairs of partners ordered from the diagonal's marks (k_far_twins)
     int64_t lcp_list;           // ranks whose LCP / BWT came from the text after the doubling rounds (k_lcp_list)
+    RvSaPaths paths;
 };
 // SA of T[0..n) (device pointers).  T must be readable up to n+15 (zero padded).
 // LCP / BWT / d_maxlcp given: the build also leaves LCP (interface.c:97-114), the BWT bytes (side_sep as for rv_build_lcp) and

@@ -2511,6 +2511,7 @@ int rv_build_sa(Workspace &ws, const uint8_t *T, int64_t n, sa_t *SA, RvSaStats 
         hipLaunchKernelGGL(k_sa_tiny_emit, dim3(nb), dim3(TB), 0, q, T, (int)n, (const uint16_t *)ws.sa[0].as<uint16_t>(), SA, LCP, BWT, side_sep, d_maxlcp);
         RV_LAUNCH_CHECK();
         s.rounds = 0; s.sorted_elems = 0;
+        s.paths.tiny = 1; s.paths.fused_asked = 1; s.paths.fused_final = 1;
         if (st) *st = s;
         if (fused_done) *fused_done = true;
         return 0;
@@ -2593,6 +2594,8 @@ int rv_build_sa(Workspace &ws, const uint8_t *T, int64_t n, sa_t *SA, RvSaStats 
         }
     }
     s.sigma = sigma; s.bits = bits; s.k0 = K;        // (bits: of the whole first key)
+    s.paths.short_alphabet = short_alphabet ? 1 : 0; s.paths.ends_with_sep = ends_with_sep ? 1 : 0;
+    s.paths.g = kp.g; s.paths.K = K; s.paths.bits = bits;
     RV_HIP(hipMemcpyAsync(d_lut.p, lut, 256, hipMemcpyHostToDevice, q));
     // Fused LCP / BWT (interface.c:97-114 folded into the build).  Related genomes are finished by the first key plus the text
     // round, and both already hold what LCP needs: two suffixes of different groups share less than K symbols -- their LCP is the
@@ -2623,6 +2626,7 @@ int rv_build_sa(Workspace &ws, const uint8_t *T, int64_t n, sa_t *SA, RvSaStats 
     }
     const bool want_hint = fused && kd.D > 0 && kd.ns >= 2 && kd.ly.at_shift - kd.ly.nd_shift >= 8 && !ws.opt.no_diag && !ws.opt.no_packed_text;
     if (want_hint) kd.ly.nd_bits = std::min(kd.ly.at_shift - kd.ly.nd_shift - 1, 11);
+    s.paths.fused_asked = fused ? 1 : 0; s.paths.hint_ns = kd.ns; s.paths.nd_bits = kd.ly.nd_bits;
     kd.K = K; kd.kp = kp; kd.stop0 = lut[(uint8_t)'$']; kd.stop1 = lut[(uint8_t)'N'];
     if (fused) RV_HIP(hipMemsetAsync(d_maxlcp, 0, sizeof(u32), q));
 
@@ -2663,6 +2667,7 @@ int rv_build_sa(Workspace &ws, const uint8_t *T, int64_t n, sa_t *SA, RvSaStats 
                           && (sizeof(sav_t) > 4 || n < ((int64_t)1 << 31));
     int64_t nsort = n;
     const u32 *tw_off = nullptr;
+    s.paths.collapse = collapse ? 1 : 0;
     if (collapse) {
         const int64_t ntiles = ceil_div(n, KEY_TILE);
         DBuf &btw = ws.sa[23];
@@ -2683,6 +2688,7 @@ int rv_build_sa(Workspace &ws, const uint8_t *T, int64_t n, sa_t *SA, RvSaStats 
         const int64_t n2 = n - kd.D;
         if (dt_mode != 0 && n >= 4096 && (dt_mode == 1 || (int64_t)kept * 10 > n2 * 3)) {
             const int64_t mseeds = nw * SEED_SLOTS;
+            s.paths.diag_table_tried = 1;
             DBuf &bdt = ws.sa[25];
             const int64_t ndt = (n >> DT_SHIFT) + 1;
             SA_TRY(bdt.reserve((size_t)ndt * 8 + 64));
@@ -2713,7 +2719,7 @@ int rv_build_sa(Workspace &ws, const uint8_t *T, int64_t n, sa_t *SA, RvSaStats 
         }
         nsort = kd.D + (int64_t)kept;
         tw_off = tc;
-        s.diag_table = dg.tab;
+        s.diag_table = dg.tab; s.paths.diag_table_kept = dg.tab;
     }
     uint8_t *dig0 = nullptr;
     {
@@ -2756,7 +2762,9 @@ int rv_build_sa(Workspace &ws, const uint8_t *T, int64_t n, sa_t *SA, RvSaStats 
         ws.prof_end(pbid);
         SA_HIP(hipGetLastError());
         keys_by_rank = kt; vals_by_rank = vexp;
+        s.paths.heads_kernel = 2;
     } else if (fused && kd.ly.nd_bits > 0 && !ws.opt.no_heads_fusion) {
+        s.paths.heads_kernel = 1;
         hipLaunchKernelGGL(k_heads_publish, dim3((unsigned)ceil_div(n, (int64_t)HP_ITEMS * TB)), dim3(TB), 0, q, (const u64 *)ks, (const sav_t *)vs, n, head, seed, LCP, SA, BWT, side_sep, kd, d_maxlcp,
                            ws.opt.no_pub_twins ? 0 : 1);
         SA_HIP(hipGetLastError());
@@ -2902,7 +2910,7 @@ int rv_build_sa(Workspace &ws, const uint8_t *T, int64_t n, sa_t *SA, RvSaStats 
         const bool text_round = !far_round && s.rounds == 1 && h <= 64 && !ws.opt.sa_no_text;
         bool text_big = false;
         if (far_round) {
-            far_ran = true;
+            far_ran = true; s.paths.far_ran = 1;
             DBuf &bR = ws.sa[27], &bM = ws.sa[28];
             const int64_t nw1 = ceil_div(kd.D - 1, (int64_t)64);      // words of the first sample
             SA_TRY(bR.reserve(std::max((size_t)nw * 4 + 64, (size_t)(nw1 * 64 + 64) * 4))); SA_TRY(bM.reserve((size_t)nw * 4 + 64));      // (bR: the reversed words, then the table of k_far_nd)
@@ -2912,6 +2920,7 @@ int rv_build_sa(Workspace &ws, const uint8_t *T, int64_t n, sa_t *SA, RvSaStats 
             FarTwins ft; ft.stop = dg.stop; ft.exc = dg.exc; ft.lt = dg.lt; ft.M = bM.as<u32>(); ft.nw = nw; ft.n = n; ft.S2 = kd.D; ft.D = kd.D; ft.dtab = kd.dtab;
             // (the table pays for itself from about a million pairs on: 0.6 ms at 2 x 250 Mbp; the few pairs of a 1 % pair walk the marks themselves)
             const bool nd_table = m >= ((int64_t)1 << 21) || ws.opt.far_table == 1;
+            s.paths.nd_table = nd_table ? 1 : 0;
             if (nd_table) {
                 hipLaunchKernelGGL(k_far_nd, dim3((unsigned)ceil_div(nw1, TB)), dim3(TB), 0, q, ft, bR.as<u32>(), nw1);
                 SA_HIP(hipGetLastError());
@@ -2922,7 +2931,7 @@ int rv_build_sa(Workspace &ws, const uint8_t *T, int64_t n, sa_t *SA, RvSaStats 
         // groups of up to SMALL_GROUP members: sorted by their first thread, in place
         else if (text_round)
         {
-            text_round_ran = true;
+            text_round_ran = true; s.paths.text_round = 1;
             FusedOut fo;
             fo.pk.Tp = nullptr; fo.pk.blk = nullptr;
             if (!ws.opt.no_packed_text) {       // 2-bit copy of the text for the comparisons (n/4 bytes + a flag per 128 bases)
@@ -2934,6 +2943,7 @@ int rv_build_sa(Workspace &ws, const uint8_t *T, int64_t n, sa_t *SA, RvSaStats 
                 hipLaunchKernelGGL(k_pack2, dim3((unsigned)ceil_div(nwords, TB)), dim3(TB), 0, q, T, n, bTp.as<u64>(), bBlk.as<uint8_t>(), nwords);
                 SA_HIP(hipGetLastError());
                 fo.pk.Tp = bTp.as<u64>(); fo.pk.blk = bBlk.as<uint8_t>();
+                s.paths.packed_text = 1;
             }
             fo.LCP = fused ? LCP : (lcp_t *)nullptr; fo.BWT = BWT; fo.keys = keys_by_rank; fo.maxlcp = d_maxlcp; fo.side_sep = side_sep; fo.kd = kd;
             fo.h = (int)h;
@@ -2946,6 +2956,7 @@ int rv_build_sa(Workspace &ws, const uint8_t *T, int64_t n, sa_t *SA, RvSaStats 
             // length of its dependent-load chains); 16-byte steps: +4 / -1 / +0.03.  RV_TEXT_MODE: test hook for the other two.
             // (with the diagonal hint: groups of up to four by their first thread, twins from their keys -- mode 3)
             const int tmode = ws.opt.text_mode >= 0 ? (int)ws.opt.text_mode : (kd.ly.nd_bits > 0 ? 3 : 1);
+            s.paths.text_mode = (tmode == 3 && fused) ? 3 : (tmode == 0 || tmode == 2) ? tmode : 1;      // (the kernel that runs, as chosen below)
 #define RT_LAUNCH(M_) hipLaunchKernelGGL((k_round_text<4, M_>), dim3(mb), dim3(TB), 0, q, T, S, (const u32 *)G, (const u32 *)P, m, head, bigflag, SA, Sfree, fo)
             // (bytes: the list entries in -- group rank, position, suffix, key -- and SA / LCP / BWT / heads / suffix out)
             const int tid = ws.prof_begin(9 /* RV_K_TEXT_ROUND */, (double)m * (4 + 4 + sizeof(sav_t) + 8) + (double)m * (sizeof(sav_t) + sizeof(sa_t) + sizeof(lcp_t) + 2));
@@ -2960,6 +2971,7 @@ int rv_build_sa(Workspace &ws, const uint8_t *T, int64_t n, sa_t *SA, RvSaStats 
                 SA_TRY(rv_read_back(ws, cnt, work_count, sizeof cnt));
                 u32 mx = 0;
                 for (int r = 0; r < RT_REGIONS; r++) mx = std::max(mx, cnt[r]);
+                s.paths.defer_max = mx; s.paths.defer_cap = reg_cap;
                 if (mx) {
                     const u32 bpr = (u32)ceil_div((int64_t)mx, TB);
                     hipLaunchKernelGGL((k_round_text3b<4>), dim3(bpr * RT_REGIONS), dim3(TB), 0, q, T, S, (const u32 *)G, m, n, head, SA, fo, (const u32 *)work,
@@ -2977,6 +2989,7 @@ int rv_build_sa(Workspace &ws, const uint8_t *T, int64_t n, sa_t *SA, RvSaStats 
             if (!list_in_todo) { SA_TRY(leave_fused(P, m)); list_in_todo = true; }
             SA_TRY(need_isa());
             const uint8_t *slow = (cls && 2 * h <= TEXT_LIM) ? cls : nullptr;
+            s.paths.doubling_rounds++;
             hipLaunchKernelGGL(k_round_small, dim3(mb), dim3(TB), 0, q, S, (const u32 *)G, (const u32 *)P, m, n, h, (const u32 *)ISA, head, bigflag, SA, slow);
         }
         SA_HIP(hipGetLastError());
@@ -2990,6 +3003,7 @@ int rv_build_sa(Workspace &ws, const uint8_t *T, int64_t n, sa_t *SA, RvSaStats 
             SA_TRY(rv_read_back(ws, &mbig, tile + nt, 4));
             if (mbig > 0) {
                 text_big = text_round;
+                if (text_big) s.paths.text_big = 1;
                 SA_TRY(need_isa());
                 u32 *Pb = bPb.as<u32>(), *Qb = bQb.as<u32>();
                 hipLaunchKernelGGL(k_flag_emit, dim3((unsigned)nt), dim3(TB), 0, q, (const uint8_t *)bigflag, m, (const u32 *)tile, (const u32 *)P, (const sav_t *)S,
@@ -3032,6 +3046,7 @@ int rv_build_sa(Workspace &ws, const uint8_t *T, int64_t n, sa_t *SA, RvSaStats 
         // (classes: made when the text round had groups above MEDIUM_GROUP -- its flag 1 --, carried along afterwards)
         const bool want_cls = (text_round && text_big && !ws.opt.no_slow_class && n > 2 * TEXT_LIM) || cls != nullptr;
         if (want_cls) {
+            s.paths.slow_class = 1;
             SA_TRY(bcls0.reserve((size_t)m2 + 64)); SA_TRY(bcls1.reserve((size_t)m2 + 64));
             cls_next = (cls == bcls0.as<uint8_t>()) ? bcls1.as<uint8_t>() : bcls0.as<uint8_t>();
             SA_TRY(emit_unsorted(head, m, P, S, grp, Pn, Sfree, Gn, text_round ? (const uint8_t *)bigflag : (const uint8_t *)cls, cls_next, text_round ? 1 : 0));
@@ -3043,7 +3058,7 @@ int rv_build_sa(Workspace &ws, const uint8_t *T, int64_t n, sa_t *SA, RvSaStats 
         m = m2;
         // (what the text round leaves tied agrees for TEXT_LIM symbols -- unless groups above MEDIUM_GROUP went through the radix path on
         //  the rank of suffix + K: then the list is only 2 K-ordered)
-        if (text_round && !text_big && !ws.opt.no_text_jump && h < TEXT_LIM && n > 2 * TEXT_LIM) h = TEXT_LIM;
+        if (text_round && !text_big && !ws.opt.no_text_jump && h < TEXT_LIM && n > 2 * TEXT_LIM) { h = TEXT_LIM; s.paths.text_jump = 1; }
         else if (!far_round) h *= 2;
     }
     if (fused && partial) {
@@ -3056,12 +3071,13 @@ int rv_build_sa(Workspace &ws, const uint8_t *T, int64_t n, sa_t *SA, RvSaStats 
         SA_HIP(hipGetLastError());
         u32 ov = 0;
         SA_TRY(rv_read_back(ws, &ov, bov.p, 4));
-        if (ov) fused = false;
+        if (ov) { fused = false; s.paths.lcp_list_overflow = 1; }
         s.lcp_list = ntodo;
     }
 #undef SA_TRY
 #undef SA_HIP
     freeall();
+    s.paths.fused_final = fused ? 1 : 0;
     if (st) *st = s;
     if (fused_done) *fused_done = fused;
     return 0;

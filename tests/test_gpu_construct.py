@@ -352,8 +352,11 @@ def test_piecewise_diagonals(monkeypatch, mode, sa64):
         ["ACGTACGTACGTTTACGTACGT" * 300, "ACGTACGTACGTTACGTACGT" * 300],    # repeats: every seed is ambiguous
         [base[:5000], base[1:5000]], ["ACGTA", "ACGA"],
     ]
-    used = 0
-    for seqs in cases:
+    # (tried, kept) of the table per case when the build decides by itself (rv_construct.hip:2689, :2713): tried when more than 30 % of the second
+    # sample stays in the sort along the fixed diagonal -- not for samples that stay on it (ends early, identical) nor below 4096 positions --,
+    # kept when a fifth more leaves along the table's -- not without seeds that occur once per sample (unrelated, the period-22 repeats)
+    auto = [(1, 1), (1, 1), (1, 1), (1, 1), (1, 1), (1, 1), (0, 0), (1, 1), (1, 0), (0, 0), (1, 1), (1, 0), (1, 1), (0, 0)]
+    for case_no, seqs in enumerate(cases):
         T, nsep, nodes = assemble(seqs, toupper=False)
         O = oracle(sa64)
         c = O.construct(T, nsep, 2)
@@ -368,11 +371,13 @@ def test_piecewise_diagonals(monkeypatch, mode, sa64):
         assert idx.maxlcp == int(c["LCP"].max()), tag
         l, a, b = O.getmums(c["tbuf"], c["SA"], c["LCP"], nsep, 20)
         assert idx.getmums(20) == [(int(l[k]), (int(a[k]), int(b[k])), 0) for k in range(len(l))], tag
-        used += idx.sa_stats()["diag_table"]
+        p = idx.sa_paths()
+        want = (0, 0) if (mode == "off" or idx.n < 4096) else (1, 1) if mode == "forced" else auto[case_no]
+        assert (p["diag_table_tried"], p["diag_table_kept"]) == want and p["diag_table_kept"] == idx.sa_stats()["diag_table"], (case_no, mode, tag, p)
+        assert p["collapse"] == (0 if idx.n <= 1024 else 1) and p["tiny"] == (1 if idx.n <= 1024 else 0), (case_no, p)
         if seqs is sim and mode != "off":
             st = idx.sa_stats()
             assert st["diag_table"] == 1 and st["sorted_elems"] < 0.8 * idx.n, st      # the table was used and most twins left
-    assert (used > 0) == (mode != "off")
 
 
 @pytest.mark.parametrize("sa64", [False, True])
@@ -435,6 +440,13 @@ def test_text_round_of_many_samples(count, L, seed, sa64):
     idx.construct()
     assert np.array_equal(idx.array("SA"), c["SA"])
     assert np.array_equal(idx.array("LCP"), c["LCP"])
+    # which side ran (rv_construct.hip:2618-2628, :2763-2787, :2958): up to HINT_K = 16 samples the hint knows them all -- k_heads_publish and the
+    # staged text round --, from 17 on there is no hint: k_heads + k_publish0 and every member ranks itself on the text
+    p = idx.sa_paths()
+    hint = count <= 16
+    assert p["hint_ns"] == (count if hint else 0) and (p["nd_bits"] > 0) == hint and p["collapse"] == 0, p
+    assert p["heads_kernel"] == (1 if hint else 0) and p["text_round"] == 1 and p["text_mode"] == (3 if hint else 1) and p["packed_text"] == 1, p
+    assert p["defer_max"] <= p["defer_cap"] and (p["defer_cap"] > 0) == hint, p
 
 
 def test_reset_reuses_the_handle():
