@@ -216,6 +216,24 @@ __device__ inline u32 rv_wave_incl_sum_u32(u32 v) {
 #undef RV_STEP_
     return v;
 }
+// Where ONE wavefront works on a piece of LDS by itself (a sub-index of the leaf kernels, a job of the small build class): what its lanes wrote is
+// visible to its other lanes behind this -- a fence and a wave barrier, no workgroup barrier
+#define RV_WSYNC() do { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); __builtin_amdgcn_wave_barrier(); } while (0)
+// how many lanes below this one have their bit set in a ballot
+__device__ inline u32 rv_lanes_below(u64 mask) { return __builtin_amdgcn_mbcnt_hi((u32)(mask >> 32), __builtin_amdgcn_mbcnt_lo((u32)mask, 0u)); }
+__device__ inline int rv_iabs(int x) { return x < 0 ? -x : x; }
+// sum over the KM lanes of a group: sixteen lanes by four exchanges, the whole wavefront by its scan
+template <int KM>
+__device__ inline int rv_group_sum(int v) {
+    if constexpr (KM == 64) return __builtin_amdgcn_readlane((int)rv_wave_incl_sum_u32((u32)v), 63);
+    else { v += __shfl_xor(v, 8, 16); v += __shfl_xor(v, 4, 16); v += __shfl_xor(v, 2, 16); v += __shfl_xor(v, 1, 16); return v; }
+}
+// the job whose sequence holds text position p, among the ascending begins of a round's jobs: the last begin at or in front of it
+__device__ inline int rv_job_of(const int64_t *__restrict__ beg, int njobs, int64_t p) {
+    int lo = 0, hi = njobs;
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (beg[mid] <= p) lo = mid + 1; else hi = mid; }
+    return lo > 0 ? lo - 1 : 0;
+}
 #endif
 
 // When a device allocation fails: give back the SA-build scratch of every handle that is not inside a construct() right now

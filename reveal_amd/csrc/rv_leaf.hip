@@ -59,7 +59,7 @@ struct PickBuiltin {
                          (s1 < s0 ? left_maximal(cb[i], cb[i - 1]) : left_maximal(cb[i - 1], cb[i]));
                 }
                 const u64 mask = __ballot(ok);
-                const u32 k = run + lanes_below(mask);
+                const u32 k = run + rv_lanes_below(mask);
                 if (ok) {
                     const int64_t a = (int64_t)(s1 < s0 ? s1 : s0), bb = (int64_t)(s1 < s0 ? s0 : s1);
                     const u64 o = (u64)k * 6;                  // the candidate as the oracle hashes it: l, n = 2, (0, a), (1, b)

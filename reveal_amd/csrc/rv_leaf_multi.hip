@@ -39,10 +39,8 @@ struct FrameMT { uint16_t start, len, depth, buf; uint16_t b[KM], e[KM]; };     
 template <int KM> struct Census { typedef u32 type; };      // a bit per sample of the window the scan looks at
 template <> struct Census<RV_MANY_WIDE_KMAX> { typedef u64 type; };
 
-#define WSYNC() do { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); __builtin_amdgcn_wave_barrier(); } while (0)
 
 __device__ inline bool is_lower_c(uint8_t c) { return c >= 'a' && c <= 'z'; }
-__device__ inline u32 lanes_below(u64 mask) { return __builtin_amdgcn_mbcnt_hi((u32)(mask >> 32), __builtin_amdgcn_mbcnt_lo((u32)mask, 0u)); }
 __device__ inline u32 from_lane_below(u32 x, u32 first) { return (u32)__builtin_amdgcn_update_dpp((int)first, (int)x, 0x138 /* wave_shr:1 */, 0xf, 0xf, false); }
 
 // running minimum of the LCP values since the last rank of the leading / trailing child (rv_leaf.hip MinSt2)
@@ -157,7 +155,7 @@ __global__ __launch_bounds__(NT) void k_leaf_multi(RvLeafMultiArgs A) {
             got = __builtin_amdgcn_readfirstlane(got);
             if (got < 0) break;
         }
-        WSYNC();
+        RV_WSYNC();
         const FrameM *f = &cur[wv];
         have = false;
         const int S = __builtin_amdgcn_readfirstlane((int)f->start), E = S + __builtin_amdgcn_readfirstlane((int)f->len);
@@ -203,7 +201,7 @@ __global__ __launch_bounds__(NT) void k_leaf_multi(RvLeafMultiArgs A) {
         const u32 L = (u32)(best >> 32);
         const int lb = (int)(best & 0xFFFFu);
         if (lane < ns) { const u32 p = cs[lb + lane]; wm[wv][smp[p] & SMP_ID] = (uint16_t)p; }
-        WSYNC();
+        RV_WSYNC();
         const u32 myp = wm[wv][lane & (KM - 1)];       // the member on this lane's sample (lanes with an interval)
         if (lv && (myp < myb || myp + L > mye)) atomicOr(A.err, 8u);
         // ---- the anchor: members ascending = in sample order ---------------------------------------------------------------
@@ -289,7 +287,7 @@ __global__ __launch_bounds__(NT) void k_leaf_multi(RvLeafMultiArgs A) {
             MinSt2 tot; tot.has = (u32)__builtin_amdgcn_readlane((int)inc.has, 63); tot.v0 = (u32)__builtin_amdgcn_readlane((int)inc.v0, 63); tot.v1 = (u32)__builtin_amdgcn_readlane((int)inc.v1, 63);
             car = ms2_combine(car, tot);
         }
-        WSYNC();
+        RV_WSYNC();
         const int nl = (int)nlead, ntr = (int)ntrail;
         if (lane == 0 && (cnt0 != nlead || cnt1 != ntrail)) atomicOr(A.err, 8u);      // (a sub-index that is not the suffixes of its intervals)
         const int cdepth = depth + 1;
@@ -319,10 +317,10 @@ __global__ __launch_bounds__(NT) void k_leaf_multi(RvLeafMultiArgs A) {
                     }
                 }
                 const u64 mask = __ballot(on);
-                if (on) act[S + nact + lanes_below(mask)] = (uint16_t)e;
+                if (on) act[S + nact + rv_lanes_below(mask)] = (uint16_t)e;
                 nact += (u32)__popcll(mask);
             }
-            WSYNC();
+            RV_WSYNC();
             for (u32 ai = 0; ai < nact; ai++) {
                 const int e = (int)act[S + ai];
                 const int p = (int)nsa[S + e], l0 = (int)nl_[S + e];
@@ -340,9 +338,9 @@ __global__ __launch_bounds__(NT) void k_leaf_multi(RvLeafMultiArgs A) {
                         const int r = hi - lane;
                         uint16_t vs = 0, vl = 0; uint8_t vb = 0;
                         if (r > x) { vs = nsa[S + r - 1]; vl = nl_[S + r - 1]; vb = nb[S + r - 1]; }
-                        WSYNC();
+                        RV_WSYNC();
                         if (r > x) { nsa[S + r] = vs; nl_[S + r] = vl; nb[S + r] = vb; }
-                        WSYNC();
+                        RV_WSYNC();
                     }
                     if (lane == 0) {
                         nsa[S + x] = (uint16_t)p; nb[S + x] = tB;
@@ -353,7 +351,7 @@ __global__ __launch_bounds__(NT) void k_leaf_multi(RvLeafMultiArgs A) {
                     const int l1 = (int)nl_[S + e + 1];
                     if (lane == 0 && p < B && p + l1 > B && l1 > l0) nl_[S + e + 1] = (uint16_t)(B - p);
                 }
-                WSYNC();
+                RV_WSYNC();
             }
         }
         // ---- children: this wave goes on with the smaller one, the larger one goes to the stack for any wave -------------------
@@ -374,7 +372,7 @@ __global__ __launch_bounds__(NT) void k_leaf_multi(RvLeafMultiArgs A) {
                 if (lane == 0) { o->start = (uint16_t)(keep_lead ? S + nl : S); o->len = (uint16_t)(keep_lead ? ntr : nl); o->depth = (uint16_t)cdepth; o->buf = (uint16_t)(b ^ 1); }
                 if (lane < KM) { o->b[lane] = keep_lead ? tb_ : lb_; o->e[lane] = keep_lead ? te_ : le_; }
             }
-            WSYNC();
+            RV_WSYNC();
             if (lane == 0) { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); atomicExch(&s_lock, 0); }
         }
         if (do_lead || do_trail) {

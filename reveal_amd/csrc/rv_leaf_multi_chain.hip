@@ -16,17 +16,9 @@
 //             is handed out when it closes; of those that close at one rank the innermost first) -- the order `segment` breaks its tie by.  An
 //             LCP-interval tree over len ranks has fewer than len inner nodes: the lists are indexed from the sub-index' first rank and cannot
 //             overflow.  A record is (l, first rank, shift, n): member q is cs[first + q] + shift, the members are never copied (PkItem).
-//   set       the matches with n == ns; none and ns > 2: `segment` -- group by sample set, z = (sum of l) x (members), strict > in first-seen order
-//   trim      pk_trim_overlap over every coordinate c = member index (NOT sample: member c of two matches may lie in different samples, as in the
-//             reference): stable rank sort by (position, -l), the containment filter with Python's index -1, the sequential cut-back on a stack.  An
-//             empty stack with matches left is where the reference raises: flag 1
-//   chain     rv_chain over the k paths of the set between the sentinels (interval begin - 1, interval end): matches by their coordinate on the
-//             lowest sample, then in rv_pick_chain's order (ascending l, trim's order).  Matches that share that coordinate share rv_chain's
-//             dictionary entry: the last one's score and link stand for all of them, and a link to one of them leads to the last; 64 / KM predecessors
-//             a step, KM lanes (one per sample) each: ends-before by ballot, gapcost (sum of pairs of |d|, star-avg |sum d| / k, star-med sorted |d|
-//             at k / 2) by reductions inside the KM lanes; gain = wscore * l * n (n - 1) / 2.  Ties as in k_leaf_chain: candidate score, predecessor's
-//             score (descending), step of activation, sort order (ascending) -- one key, reduced once per match
-//   split     the largest match of the chain, of equal lengths the last; the anchor is the TRIMMED match, members in member (rank) order, as the
+//   pick      set, trim, chain and the choice of the split are rv_chain_stage_multi<KM> (rv_chain_stage.h), between the sentinels (interval begin - 1,
+//             interval end) of every sample; MultiLeafStage says where its lists live
+//   split     on the largest match of the chain, of equal lengths the last; the anchor is the TRIMMED match, members in member (rank) order, as the
 //             ordinary path emits them.  Three children: lead and trail over the set's samples, rest = the other live samples with their whole
 //             intervals; running-minimum LCP per child; bubble_sort on the leading child.  A child is visited when at least max(2, minn) of its
 //             samples are at least minl long (a match of a sample SUBSET needs no more; k_leaf_multi's "every interval" rule would be wrong here)
@@ -36,26 +28,24 @@
 //   16  rv_many's test hook                                     32  the frame stack is full
 // What the caller guarantees (rv_many.hip many_chain_multi_admits, many_chain_wide_admits): trim on, minl > 0, no seed possible, a --maxmums of at least the job's ranks (a
 // sub-index has fewer candidates than ranks), gap model 0 .. 2, and
-//   0 <= wscore, wpen <= RV_LEAF_MCHAIN_WMAX = 2^10: scores in 32 bits.  A job has at most 2^11 ranks.  The lengths of a chain are disjoint on every
+//   0 <= wscore, wpen <= RV_LEAF_MCHAIN_WMAX = 2^10: scores in 32 bits (rv_chain_stage.h).  A job has at most 2^11 ranks.  The lengths of a chain are disjoint on every
 //   path: they add up to at most 2^11, and n (n - 1) / 2 <= 120 < 2^7, so the gains of a chain add up to at most wscore * 2^18.  A gap cost is at most
 //   120 * 2^11 < 2^18 (sum of pairs; the star models: 2^11).  A score is at least what the left sentinel offers, >= -wpen * 2^18, and at most
 //   wscore * 2^18; a candidate score + gain - wpen * gap lies within 3 * 2^10 * 2^18 < 2^30.  k_leaf_chain's bound of 2^16 would need 2^36: the bound
-//   is tightened instead of widening the scores, because the tie order packs (candidate, predecessor's score) into one 64-bit key for ONE wave
-//   reduction per match, and the reference's defaults are 1 and 1.
+//   is tightened instead of widening the scores; the reference's defaults are 1 and 1.
 //   KM = 64: the same constant holds.  A match of n members and length l covers n * l ranks of the job, and the matches of a chain are disjoint on every
 //   path, so sum (n * l) <= 2^11; a gain is wscore * (n * l) * (n - 1) / 2 with (n - 1) / 2 < 2^5: the gains of a chain add up to less than wscore * 2^16.
 //   A sum-of-pairs gap is sum_{i<j} | |d_i| - |d_j| | <= (n - 1) * sum |d_i|, the |d_i| lie inside different sequences and add up to less than 2^11:
 //   a gap cost is below 63 * 2^11 < 2^17 (the star models: 2^11).  A score is >= -wpen * 2^17 (the left sentinel's offer) and < wscore * 2^16; a candidate
 //   score + gain - wpen * gap lies within 2^10 * (2^17 + 2^16 + 2^17) < 3 * 2^27 < 2^30.  RV_LEAF_MCHAIN_WMAX = 2^10 serves both forms (the same
 //   counting gives the 16-sample form 2^14 gains and 2^15 gaps: the bound above is not tight, and is kept).
-//   With weights >= 0 the early `break` of rv_chain never changes the choice.
 // Frame stack: a wave goes on with the smallest visited child and leaves the others to the stack -- two frames where the size falls to a third, one
 // where it halves: at most 2 log3(2048) < 14 frames wait per descent, four waves descend at once, and a frame taken from the stack starts a descent
 // no longer than its parent's: MAXSTACK = 96 as in k_leaf_multi.  A full stack flags the job (32), it does not fail the call.
 // The two forms (compiler remarks, gfx950):
 //   KM = 16   the kernel as it was before the template: four predecessors a chain step, sixteen lanes each (four exchanges for a sum, sixteen for the ranks
 //             of the |d|); sample sets in 16 bits beside the candidates (aux).  k_leaf_multi<16>'s arrays + two lists of 8 B per rank + the chain's
-//             coordinate scratch: 73 104 B of LDS, two workgroups per CU; 122 VGPRs, no scratch, 122 SGPRs spilled
+//             coordinate scratch: 73 104 B of LDS, two workgroups per CU; 122 VGPRs, no scratch, 116 SGPRs spilled
 //   KM = 64   lane s owns path s through the whole chain step: ONE predecessor a step.  Ends-before is one 64-bit ballot; a sum is the wavefront's scan.
 //             Sum of pairs and star-med need every lane's |d| against every other path's: the paths of the set are taken in turn (a loop over the bits
 //             of the set, which sits in scalar registers), path j's |d| is read from lane j (v_readlane), and the lane adds | |d| - |d_j| | for j above
@@ -63,9 +53,10 @@
 //             array.  The tie key is unchanged, so the order in which predecessors are looked at does not show.  Sample sets are 64 bits: the
 //             candidates' sets lie in list B, which nothing else uses before trim.  Scan windows of 2 .. 64 ranks, trim over up to 64 member indices,
 //             FrameMT<64> of 264 B.  k_leaf_multi<64>'s 59 248 B + the two lists (32 768 B) + coordinate scratch: 93 168 B of LDS -- ONE workgroup
-//             per CU (of gfx950's 160 KiB); 123 VGPRs, no scratch, 39 SGPRs spilled.  Two per CU would need the lists inside the dead ranks of the
+//             per CU (of gfx950's 160 KiB); 121 VGPRs, no scratch, 34 SGPRs spilled.  Two per CU would need the lists inside the dead ranks of the
 //             other copy of the arrays, as k_leaf_chain keeps them: not done
 #include "rv_leaf_multi.h"
+#include "rv_chain_stage.h"
 
 namespace {
 
@@ -76,35 +67,47 @@ constexpr int MAXSTACK = 96;
 constexpr int ACAP = 256;
 constexpr u32 INF = 0xFFFFFFFFu;
 constexpr uint8_t SMP_SEP = 0x40, SMP_DONE = 0x80;      // (the sample id lies below them: KM - 1, at most six bits)
-constexpr u32 LINK_L = 0xFFFFu, NOT_ACTIVE = 0xFFFFu;
-static_assert(LN <= 2048, "positions and lengths in 12 bits of the sort keys");
 
 template <int KM>
 struct FrameMT { uint16_t start, len, depth, buf; uint16_t b[KM], e[KM]; };      // interval [b, e) of every sample, job-local; empty: b >= e
 template <int KM> struct Census { typedef u32 type; };      // a bit per sample: the samples of a match, of the picked set
 template <> struct Census<RV_MANY_WIDE_KMAX> { typedef u64 type; };
 
-#define WSYNC() do { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); __builtin_amdgcn_wave_barrier(); } while (0)
-
 __device__ inline bool is_lower_c(uint8_t c) { return c >= 'a' && c <= 'z'; }
-__device__ inline u32 lanes_below(u64 mask) { return __builtin_amdgcn_mbcnt_hi((u32)(mask >> 32), __builtin_amdgcn_mbcnt_lo((u32)mask, 0u)); }
 __device__ inline u32 from_lane_below(u32 x, u32 first) { return (u32)__builtin_amdgcn_update_dpp((int)first, (int)x, 0x138 /* wave_shr:1 */, 0xf, 0xf, false); }
-__device__ inline int iabs(int x) { return x < 0 ? -x : x; }
-// sum over the KM lanes of a group: sixteen lanes by four exchanges, the whole wavefront by its scan
-template <int KM>
-__device__ inline int group_sum(int v) {
-    if constexpr (KM == 64) return __builtin_amdgcn_readlane((int)rv_wave_incl_sum_u32((u32)v), 63);
-    else { v += __shfl_xor(v, 8, 16); v += __shfl_xor(v, 4, 16); v += __shfl_xor(v, 2, 16); v += __shfl_xor(v, 1, 16); return v; }
-}
-__device__ inline int cen_count(u32 m) { return __builtin_popcount(m); }
-__device__ inline int cen_count(u64 m) { return (int)__popcll(m); }
-__device__ inline int cen_first(u32 m) { return __builtin_ctz(m); }
-__device__ inline int cen_first(u64 m) { return (int)__builtin_ctzll(m); }
 
-// a match of the lists: length after trimming, first rank of its interval, how far trimming moved its members, members
-struct Mt { int l, lb, sh, n; };
-__device__ inline u64 mt_pack(const Mt &m) { return (u64)(u32)m.l | ((u64)(u32)m.lb << 16) | ((u64)(u32)m.sh << 32) | ((u64)(u32)m.n << 48); }
-__device__ inline Mt mt_unpack(u64 w) { Mt m; m.l = (int)(w & 0xFFFFu); m.lb = (int)((w >> 16) & 0xFFFFu); m.sh = (int)((w >> 32) & 0xFFFFu); m.n = (int)((w >> 48) & 0xFFu); return m; }
+// the stage's storage (rv_chain_stage.h), all from the sub-index' first rank: the two lists in eA / eB; the 16-bit words of act[] hold the sample sets
+// of the candidates (KM = 64: 64 bits, in list B, which nothing else uses before trim), then the first-path positions, then the steps; the sorted
+// first-path positions lie in the other copy of the suffix array, which is free until the split.  The row of a match is the first rank of its interval:
+// member q is cs[row + q] (job-local position; the members are never copied), its sample the smp byte of that position
+template <int KM_>
+struct MultiLeafStage {
+    typedef RvMtK Mt; typedef u32 key_t; typedef typename Census<KM_>::type cen_t; typedef uint16_t crd_t;
+    static constexpr int KM = KM_, POS_BITS = 16, ROW_BITS = 16, N_BITS = 8, ROWS = LN, CAP = LN, LMAX = LN;
+    static constexpr int COORD_BITS = 12, LKEY_BITS = 12, ORDER_BITS = 12;
+    static constexpr bool SUBSETS_LISTED = true;           // (the scan lists every window, whatever its sample set)
+    static_assert(LN <= (1 << (COORD_BITS - 1)), "a job-local position, shifted by less than a match's length, in COORD_BITS");
+    const uint16_t *cs; const uint8_t *smp; const uint16_t *seqb; u64 *la, *lb; uint16_t *aux, *skey, *cme, *cpr;
+    int wscore, wpen, model;
+    __device__ __forceinline__ Mt getA(int i) const { return rv_mtk_unpack<MultiLeafStage>(la[i]); }
+    __device__ __forceinline__ void putA(int i, const Mt &m) { la[i] = rv_mtk_pack<MultiLeafStage>(m); }
+    __device__ __forceinline__ Mt getB(int i) const { return rv_mtk_unpack<MultiLeafStage>(lb[i]); }
+    __device__ __forceinline__ void putB(int i, const Mt &m) { lb[i] = rv_mtk_pack<MultiLeafStage>(m); }
+    __device__ __forceinline__ u64 getE(int i) const { return la[i]; }
+    __device__ __forceinline__ void putE(int i, u64 w) { la[i] = w; }
+    __device__ __forceinline__ u32 getStep(int i) const { return aux[i]; }
+    __device__ __forceinline__ void putStep(int i, u32 v) { aux[i] = (uint16_t)v; }
+    __device__ __forceinline__ cen_t getSet(int i) const { if constexpr (KM == 64) return lb[i]; else return (cen_t)aux[i]; }
+    __device__ __forceinline__ void putSet(int i, cen_t v) { if constexpr (KM == 64) lb[i] = v; else aux[i] = (uint16_t)v; }
+    __device__ __forceinline__ u32 getPun(int i) const { return aux[i]; }
+    __device__ __forceinline__ void putPun(int i, u32 v) { aux[i] = (uint16_t)v; }
+    __device__ __forceinline__ u32 getKey(int i) const { return skey[i]; }
+    __device__ __forceinline__ void putKey(int i, u32 v) { skey[i] = (uint16_t)v; }
+    __device__ __forceinline__ int pos(const Mt &m, int c) const { return (int)cs[m.row + c] + m.sh; }
+    static __device__ __forceinline__ void cut(Mt &m, int overlap) { m.l -= overlap; m.sh += overlap; }
+    __device__ __forceinline__ void member(const Mt &m, int q, int &s, int &p) const { p = (int)cs[m.row + q]; s = (int)(smp[p] & (uint8_t)(KM - 1)); }
+    __device__ __forceinline__ int seq_off(int s) const { return -(int)seqb[s]; }
+};
 
 // running minimum of the LCP values since the last rank of the leading / trailing / rest child (rv_leaf_multi.hip MinSt2, one class more)
 struct MinSt3 { u32 has, v0, v1, v2; };
@@ -198,9 +201,8 @@ __global__ __launch_bounds__(NT) void k_leaf_multi_chain(RvLeafMultiArgs A, RvLe
     const u32 need = A.minl > 1 ? (u32)A.minl : 1u;
     const int minn = A.minn, nmin = minn > 2 ? minn : 2;
     const u32 acap = A.stage_cap < (u32)ACAP ? A.stage_cap : (u32)ACAP;
-    const int wscore = C.wscore, wpen = C.wpen, model = C.gcmodel;
     u32 *const jflag = C.flags + blockIdx.x;
-    const int sl = lane & (KM - 1), grp = lane / KM;
+    const int sl = lane & (KM - 1);
     u32 my_steps = 0, my_splits = 0, my_maxdepth = 0; u64 my_bp = 0;
     bool have = wv == 0;
 
@@ -225,7 +227,7 @@ __global__ __launch_bounds__(NT) void k_leaf_multi_chain(RvLeafMultiArgs A, RvLe
             got = __builtin_amdgcn_readfirstlane(got);
             if (got < 0) break;
         }
-        WSYNC();
+        RV_WSYNC();
         const FrameM *f = &cur[wv];
         have = false;
         const int S = __builtin_amdgcn_readfirstlane((int)f->start), E = S + __builtin_amdgcn_readfirstlane((int)f->len);
@@ -238,11 +240,9 @@ __global__ __launch_bounds__(NT) void k_leaf_multi_chain(RvLeafMultiArgs A, RvLe
         uint16_t *cs = sa2[b], *nsa = sa2[b ^ 1];
         uint16_t *cl = lc2[b], *nl_ = lc2[b ^ 1];
         uint8_t *cb = bw2[b], *nb = bw2[b ^ 1];
-        u64 *la = eA + S, *lbk = eB + S;
-        uint16_t *aux = act + S;                       // candidate sample sets / sort keys / steps of activation, then bubble_sort's list
-        // the sample set of candidate i: sixteen bits in aux, 64 bits in list B (which nothing else uses before trim)
-        auto set_put = [&](int i, cen_t v) { if constexpr (KM == 64) lbk[i] = v; else aux[i] = (uint16_t)v; };
-        auto set_of = [&](int i) -> cen_t { if constexpr (KM == 64) return lbk[i]; else return (cen_t)aux[i]; };
+        MultiLeafStage<KM> st;
+        st.cs = cs; st.smp = smp; st.seqb = seqb; st.la = eA + S; st.lb = eB + S; st.aux = act + S; st.skey = nsa + S;
+        st.cme = cme[wv]; st.cpr = &cpr[wv][0][0]; st.wscore = C.wscore; st.wpen = C.wpen; st.model = C.gcmodel;
         if (lane == 0) { my_steps++; if ((u32)depth > my_maxdepth) my_maxdepth = (u32)depth; }
 
         // the windows that close at rank u, by descending l
@@ -273,7 +273,7 @@ __global__ __launch_bounds__(NT) void k_leaf_multi_chain(RvLeafMultiArgs A, RvLe
 
         // ---- the pick stage -> picked, the match P and its sample set -------------------------------------------------------
         bool picked = false;
-        Mt P; P.l = P.lb = P.sh = P.n = 0;
+        RvMtK P = RvMtK();
         cen_t setmask = 0;
         do {
             if (ns < 2 || ns < minn) break;
@@ -285,8 +285,8 @@ __global__ __launch_bounds__(NT) void k_leaf_multi_chain(RvLeafMultiArgs A, RvLe
                 const u32 inc = rv_wave_incl_sum_u32((u32)cnt);
                 int at = m + (int)(inc - (u32)cnt), full = 0;
                 walk(base + lane, [&](int r, int k, int l, cen_t seen) {
-                    Mt c; c.l = l; c.lb = r; c.sh = 0; c.n = k;
-                    if (at < E - S) { la[at] = mt_pack(c); set_put(at, seen); }
+                    RvMtK c; c.l = l; c.row = r; c.sh = 0; c.n = k;
+                    if (at < E - S) { st.putA(at, c); st.putSet(at, seen); }
                     at++;
                     full += k == ns ? 1 : 0;
                 });
@@ -295,247 +295,10 @@ __global__ __launch_bounds__(NT) void k_leaf_multi_chain(RvLeafMultiArgs A, RvLe
             }
             if (m == 0) break;
             if (m >= E - S) { if (lane == 0) atomicOr(jflag, 2u); break; }      // (cannot happen: fewer inner nodes than ranks)
-            WSYNC();
-            // the set: n == ns, or the best sample subset
-            cen_t want_mask = 0;
-            if (nfull > 0) want_mask = (cen_t)live;
-            else if (ns > 2) {
-                u64 best = 0;
-                for (int base = 0; base < m; base += 64) {
-                    const int i = base + lane;
-                    if (i < m) {
-                        const cen_t mk = set_of(i);
-                        u32 z = 0; int first = -1;
-                        for (int j = 0; j < m; j++) if (set_of(j) == mk) { z += (u32)(la[j] & 0xFFFFu); if (first < 0) first = j; }
-                        z *= (u32)cen_count(mk);
-                        const u64 key = ((u64)z << 32) | (u64)(0xFFFFu - (u32)first);
-                        best = key > best ? key : best;
-                    }
-                }
-                best = rv_wave_max_u64(best);
-                if (best == 0) break;
-                want_mask = set_of((int)(0xFFFFu - (u32)(best & 0xFFFFu)));
-            } else break;
-            if constexpr (KM == 64)                    // (the same word in every lane: in scalar registers for the loops over its bits)
-                want_mask = ((cen_t)(u32)__builtin_amdgcn_readfirstlane((int)(u32)(want_mask >> 32)) << 32) | (cen_t)(u32)__builtin_amdgcn_readfirstlane((int)(u32)want_mask);
-            setmask = want_mask;
-            const int kset = cen_count(setmask);
-            {   // the chosen matches, in list order, to the front of list A
-                int w = 0;
-                for (int base = 0; base < m; base += 64) {
-                    const int i = base + lane;
-                    const bool keep = i < m && set_of(i) == want_mask;
-                    const u64 rec = i < m ? la[i] : 0ull;
-                    WSYNC();
-                    const u64 mask = __ballot(keep);
-                    if (keep) la[w + (int)lanes_below(mask)] = rec;
-                    w += (int)__popcll(mask);
-                    WSYNC();
-                }
-                m = w;
-            }
-            if (m == 0) break;
-            auto posc = [&](const Mt &x, int c) { return (int)cs[x.lb + c] + x.sh; };
-            // list A -> list B in the stable order of (position of member c, -l)
-            auto sort_AB = [&](int c, int cnt) {
-                for (int base = 0; base < cnt; base += 64) {
-                    const int i = base + lane;
-                    u32 key = 0; u64 me = 0;
-                    if (i < cnt) { me = la[i]; const Mt x = mt_unpack(me); key = ((u32)posc(x, c) << 12) | (u32)(4095 - x.l); }
-                    int r = 0;
-                    for (int j = 0; j < cnt; j++) {
-                        const Mt o = mt_unpack(la[j]);
-                        const u32 ko = ((u32)posc(o, c) << 12) | (u32)(4095 - o.l);
-                        r += (ko < key || (ko == key && j < i)) ? 1 : 0;
-                    }
-                    if (i < cnt) lbk[r] = me;
-                }
-                WSYNC();
-            };
-            // ---- pk_trim_overlap -------------------------------------------------------------------------------------------
-            bool raised = false;
-            for (int c = 0; c < kset && m > 1; c++) {
-                sort_AB(c, m);
-                const Mt b0 = mt_unpack(lbk[0]), b1 = mt_unpack(lbk[1]);
-                const int end0 = posc(b0, c) + b0.l, end1 = posc(b1, c) + b1.l;
-                int w = 0;
-                for (int base = 0; base < m; base += 64) {
-                    const int i = base + lane;
-                    bool keep = false; u64 me = 0;
-                    if (i < m) {
-                        me = lbk[i];
-                        const Mt x = mt_unpack(me), pv = mt_unpack(lbk[i == 0 ? m - 1 : i - 1]);
-                        const int en = posc(x, c) + x.l, ep = posc(pv, c) + pv.l;
-                        keep = (i == 0 && end1 > end0) || ep < en;
-                    }
-                    const u64 mask = __ballot(keep);
-                    if (keep) la[w + (int)lanes_below(mask)] = me;
-                    w += (int)__popcll(mask);
-                }
-                m = w;
-                WSYNC();
-                if (m <= 1) break;
-                int top = 0;
-                for (int i = 1; i < m; i++) {
-                    if (top < 0) { raised = true; break; }
-                    const Mt mum = mt_unpack(la[i]);
-                    Mt pm = mt_unpack(la[top]);
-                    const int overlap = posc(pm, c) + pm.l - posc(mum, c);
-                    if (overlap > 0) {
-                        if (pm.l - overlap > 0) { pm.l -= overlap; if (lane == 0) la[top] = mt_pack(pm); }
-                        else top--;
-                        if (mum.l - overlap > 0) {
-                            Mt t = mum; t.l -= overlap; t.sh += overlap;
-                            top++;
-                            if (lane == 0) la[top] = mt_pack(t);
-                        }
-                    } else {
-                        top++;
-                        if (lane == 0) la[top] = mt_pack(mum);
-                    }
-                    WSYNC();
-                }
-                if (raised) break;
-                m = top + 1;
-            }
-            if (raised) { if (lane == 0) atomicOr(jflag, 1u); break; }
-            if (m == 0) break;
-            int split = 0;
-            if (m == 1) { lbk[0] = la[0]; WSYNC(); }
-            else {
-                // ---- rv_chain over the paths of the set ----------------------------------------------------------------------
-                const int s0 = cen_first(setmask);
-                for (int i = lane; i < m; i += 64) {      // the coordinate on the first path
-                    const Mt x = mt_unpack(la[i]);
-                    int p0 = 0;
-                    for (int q = 0; q < x.n; q++) { const int p = (int)cs[x.lb + q]; if ((smp[p] & SMP_ID) == s0) p0 = p + x.sh; }
-                    aux[i] = (uint16_t)p0;
-                }
-                WSYNC();
-                // rv_chain's stable sort by that coordinate over rv_pick_chain's list: ascending l, equal lengths in trim's order
-                uint16_t *skey = nsa + S;                      // the sorted coordinates (the other copy of the arrays is free until the split)
-                for (int base = 0; base < m; base += 64) {
-                    const int i = base + lane;
-                    u32 key = 0;
-                    if (i < m) key = ((u32)aux[i] << 12) | (u32)(la[i] & 0xFFFu);
-                    int r = 0;
-                    for (int j = 0; j < m; j++) { const u32 ko = ((u32)aux[j] << 12) | (u32)(la[j] & 0xFFFu); r += (ko < key || (ko == key && j < i)) ? 1 : 0; }
-                    if (i < m) { lbk[r] = la[i]; skey[r] = aux[i]; }
-                }
-                WSYNC();
-                for (int i = lane; i < m; i += 64) aux[i] = (uint16_t)NOT_ACTIVE;
-                WSYNC();
-                const bool inset = (setmask >> sl) & 1u;
-                u32 linkR = LINK_L;
-                bool broken = false;
-                for (int e = 0; e <= m; e++) {
-                    Mt me; me.l = 0; me.lb = 0; me.sh = 0; me.n = 0;
-                    if (e < m) {
-                        me = mt_unpack(lbk[e]);
-                        if (lane < me.n) { const int p = (int)cs[me.lb + lane]; cme[wv][smp[p] & SMP_ID] = (uint16_t)(p + me.sh); }
-                    }
-                    WSYNC();
-                    const int mst = e < m ? (int)cme[wv][sl] : ge;           // where the match starts on this lane's sample; `right`: the interval's end
-                    const int gain = wscore * me.l * ((me.n * (me.n - 1)) / 2);
-                    u64 b1 = 0; u32 b2 = 0xFFFFFFFFu;
-                    for (int base = -1; base < e; base += GRPS) {
-                        const int p = base + grp;                          // this group's predecessor; -1: the left sentinel
-                        const bool on = p < e;
-                        Mt o; o.l = 0; o.lb = 0; o.sh = 0; o.n = 0;
-                        if (on && p >= 0) {
-                            o = mt_unpack(lbk[p]);
-                            if (sl < o.n) { const int q = (int)cs[o.lb + sl]; cpr[wv][grp][smp[q] & SMP_ID] = (uint16_t)(q + o.sh); }
-                        }
-                        WSYNC();
-                        const int pend = p < 0 ? gb - 1 : (int)cpr[wv][grp][sl] + o.l;
-                        const int d = (on && inset) ? pend - mst : 0;
-                        u32 late;                                          // lanes where the predecessor does not end in front of the match
-                        if constexpr (KM == 64) late = __ballot(d > 0) ? 1u : 0u; else late = (u32)(__ballot(d > 0) >> (16 * grp)) & 0xFFFFu;
-                        // utils.gapcost over the set's paths
-                        const int D = iabs(d);
-                        int acc = 0, rank = 0;
-                        if (model != 1) {
-                            if constexpr (KM == 64) {
-                                // every path of the set in turn, its |d| read from its lane: the lane's share of the sum of pairs (the paths above it) and its
-                                // rank among the set's |d| (ties by lane) -- nothing is kept per lane beyond the two sums
-                                for (cen_t mm = setmask; mm; mm &= mm - 1) {
-                                    const int j = cen_first(mm);
-                                    const int od = __builtin_amdgcn_readlane(D, j);
-                                    if (inset) {
-                                        if (j > sl) acc += iabs(D - od);
-                                        rank += (od < D || (od == D && j < sl)) ? 1 : 0;
-                                    }
-                                }
-                            } else {
-                            for (int j = 0; j < KM; j++) {
-                                const int od = __shfl(D, (lane & 48) | j);
-                                if (inset && ((setmask >> j) & 1u)) {
-                                    if (j > sl) acc += iabs(D - od);
-                                    rank += (od < D || (od == D && j < sl)) ? 1 : 0;
-                                }
-                            }
-                            }
-                        }
-                        int gap;
-                        if (model == 1) gap = iabs(group_sum<KM>(d)) / kset;
-                        else if (model == 2) gap = group_sum<KM>((inset && rank == kset / 2) ? D : 0);
-                        else gap = group_sum<KM>(acc);
-                        if (on && late == 0 && sl == 0) {
-                            u32 st = 0; int sc = 0;
-                            if (p >= 0) {
-                                st = aux[p];
-                                if (st == NOT_ACTIVE) { st = (u32)e; aux[p] = (uint16_t)e; }
-                                st += 1u;
-                                sc = (int)(u32)(la[p] & 0xFFFFFFFFull);
-                            }
-                            const int tmpw = sc + gain - wpen * gap;
-                            const u64 k1 = ((u64)((u32)tmpw ^ 0x80000000u) << 32) | (u64)((u32)sc ^ 0x80000000u);
-                            const u32 k2 = p < 0 ? 0u : ((st << 12) | (u32)p);
-                            if (k1 > b1 || (k1 == b1 && k2 < b2)) { b1 = k1; b2 = k2; }
-                        }
-                        WSYNC();
-                    }
-                    const u64 w1 = rv_wave_max_u64(b1);
-                    if (w1 == 0) { broken = true; break; }
-                    const u32 w2 = 0xFFFFFFFFu - (u32)rv_wave_max_u64((u64)(0xFFFFFFFFu - (b1 == w1 ? b2 : 0xFFFFFFFFu)));
-                    // rv_chain keeps score and link per first-path coordinate: matches that share it share the entry (they stand side by side here, and none
-                    // of them is a predecessor before the last of them is through), the last one's values stand, and a link leads to the last match of
-                    // the predecessor's coordinate
-                    u32 link = w2 < 4096u ? LINK_L : (w2 & 0xFFFu);
-                    if (link != LINK_L) while ((int)link + 1 < m && skey[link + 1] == skey[link]) link++;
-                    const u32 score = (u32)(w1 >> 32) ^ 0x80000000u;
-                    if (e < m) { if (lane == 0) for (int j = e; j >= 0 && skey[j] == skey[e]; j--) la[j] = (u64)score | ((u64)link << 32); }
-                    else linkR = link;
-                    WSYNC();
-                }
-                split = -1;
-                int bl = 0, guard = 0;
-                if (!broken)
-                    for (u32 c = linkR; c != LINK_L; c = (u32)(la[c] >> 32) & 0xFFFFu) {
-                        if (c >= (u32)m || ++guard > m) { broken = true; break; }
-                        const int l = (int)(lbk[c] & 0xFFFFu);
-                        if (l > bl) { bl = l; split = (int)c; }
-                    }
-                if (broken) { if (lane == 0) atomicOr(jflag, 2u); break; }
-                if (split < 0) break;                          // `right` links to `left`: an empty chain, nothing picked
-            }
-            P = mt_unpack(lbk[split]);
-            // rv_pick_chain's `mapping`: keyed by the offsets member by member -- another match with the split's offsets would replace it
-            bool twin = false;
-            for (int base = 0; base < m; base += 64) {
-                const int i = base + lane;
-                if (i < m && i != split) {
-                    const Mt x = mt_unpack(lbk[i]);
-                    bool same = x.n == P.n;
-                    for (int q = 0; same && q < P.n; q++) {
-                        const int pa = (int)cs[x.lb + q], pb = (int)cs[P.lb + q];
-                        same = pa + x.sh - (int)seqb[smp[pa] & SMP_ID] == pb + P.sh - (int)seqb[smp[pb] & SMP_ID];
-                    }
-                    twin |= same;
-                }
-            }
-            if (__ballot(twin)) { if (lane == 0) atomicOr(jflag, 8u); break; }
-            picked = true;
+            // set, trim, chain, split (rv_chain_stage.h)
+            const int res = rv_chain_stage_multi<KM>(st, lane, m, nfull, ns, live, gb - 1, ge, P, setmask);
+            if (res > 0 && lane == 0) atomicOr(jflag, (u32)res);
+            picked = res == RV_STAGE_PICK;
         } while (0);
         if (!picked) {
             if (lane == 0) atomicSub(&s_pending, 1);
@@ -544,8 +307,8 @@ __global__ __launch_bounds__(NT) void k_leaf_multi_chain(RvLeafMultiArgs A, RvLe
         const u32 L = (u32)P.l;
         const int pn = P.n;
         u32 mem = 0;                                   // lane q < pn: member q, in member order
-        if (lane < pn) { const u32 p = cs[P.lb + lane]; mem = p + (u32)P.sh; wm[wv][smp[p] & SMP_ID] = (uint16_t)mem; }
-        WSYNC();
+        if (lane < pn) { const u32 p = cs[P.row + lane]; mem = p + (u32)P.sh; wm[wv][smp[p] & SMP_ID] = (uint16_t)mem; }
+        RV_WSYNC();
         const bool inset = lane < KM && ((setmask >> lane) & 1u);
         const u32 myp = wm[wv][sl];
         if (inset && (!lv || myp < myb || myp + L > mye)) atomicOr(A.err, 8u);
@@ -570,7 +333,7 @@ __global__ __launch_bounds__(NT) void k_leaf_multi_chain(RvLeafMultiArgs A, RvLe
             }
         }
         for (cen_t mm = setmask; mm; mm &= mm - 1) {
-            const u32 Pm = wm[wv][cen_first(mm)];
+            const u32 Pm = wm[wv][rv_cen_first(mm)];
             for (u32 j = lane; j < L; j += 64) if (Pm + j < (u32)n) smp[Pm + j] |= SMP_DONE;
         }
         // ---- graphalign, linear interval model: lead / trail on the set's samples, rest = the other live samples, whole -------
@@ -646,7 +409,7 @@ __global__ __launch_bounds__(NT) void k_leaf_multi_chain(RvLeafMultiArgs A, RvLe
             tot.v1 = (u32)__builtin_amdgcn_readlane((int)inc.v1, 63); tot.v2 = (u32)__builtin_amdgcn_readlane((int)inc.v2, 63);
             car = ms3_combine(car, tot);
         }
-        WSYNC();
+        RV_WSYNC();
         const int nl = (int)nlead, ntr = (int)ntrail, nrs = (int)nrest;
         if (lane == 0 && (cnt0 != nlead || cnt1 != ntrail || cnt2 != nrest)) atomicOr(A.err, 8u);      // (a sub-index that is not the suffixes of its intervals)
         const int cdepth = depth + 1;
@@ -675,10 +438,10 @@ __global__ __launch_bounds__(NT) void k_leaf_multi_chain(RvLeafMultiArgs A, RvLe
                     }
                 }
                 const u64 mask = __ballot(on);
-                if (on) act[S + nact + lanes_below(mask)] = (uint16_t)e;
+                if (on) act[S + nact + rv_lanes_below(mask)] = (uint16_t)e;
                 nact += (u32)__popcll(mask);
             }
-            WSYNC();
+            RV_WSYNC();
             for (u32 ai = 0; ai < nact; ai++) {
                 const int e = (int)act[S + ai];
                 const int p = (int)nsa[S + e], l0 = (int)nl_[S + e];
@@ -695,9 +458,9 @@ __global__ __launch_bounds__(NT) void k_leaf_multi_chain(RvLeafMultiArgs A, RvLe
                         const int r = hi - lane;
                         uint16_t vs = 0, vl = 0; uint8_t vb = 0;
                         if (r > x) { vs = nsa[S + r - 1]; vl = nl_[S + r - 1]; vb = nb[S + r - 1]; }
-                        WSYNC();
+                        RV_WSYNC();
                         if (r > x) { nsa[S + r] = vs; nl_[S + r] = vl; nb[S + r] = vb; }
-                        WSYNC();
+                        RV_WSYNC();
                     }
                     if (lane == 0) {
                         nsa[S + x] = (uint16_t)p; nb[S + x] = tB;
@@ -708,7 +471,7 @@ __global__ __launch_bounds__(NT) void k_leaf_multi_chain(RvLeafMultiArgs A, RvLe
                     const int l1 = (int)nl_[S + e + 1];
                     if (lane == 0 && p < B && p + l1 > B && l1 > l0) nl_[S + e + 1] = (uint16_t)(B - p);
                 }
-                WSYNC();
+                RV_WSYNC();
             }
         }
         // ---- children: this wave goes on with the smallest one, the others go to the stack for any wave ----------------------
@@ -738,7 +501,7 @@ __global__ __launch_bounds__(NT) void k_leaf_multi_chain(RvLeafMultiArgs A, RvLe
                     if (lane < KM) { o->b[lane] = cbeg[c]; o->e[lane] = cend[c]; }
                 }
             }
-            WSYNC();
+            RV_WSYNC();
             if (lane == 0) { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); atomicExch(&s_lock, 0); }
         }
         if (keepc >= 0) {
@@ -746,7 +509,7 @@ __global__ __launch_bounds__(NT) void k_leaf_multi_chain(RvLeafMultiArgs A, RvLe
             uint16_t kb = 0, ke = 0; int ks = 0, kl = 0;
 #pragma unroll
             for (int c = 0; c < 3; c++) if (c == keepc) { kb = cbeg[c]; ke = cend[c]; ks = cstart[c]; kl = clen[c]; }
-            WSYNC();
+            RV_WSYNC();
             if (lane == 0) { o->start = (uint16_t)ks; o->len = (uint16_t)kl; o->depth = (uint16_t)cdepth; o->buf = (uint16_t)(b ^ 1); }
             if (lane < KM) { o->b[lane] = kb; o->e[lane] = ke; }
         } else if (lane == 0) {

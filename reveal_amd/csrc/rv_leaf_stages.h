@@ -35,14 +35,12 @@ __device__ inline u64 hash_step(u64 acc, u64 i, int64_t v) {      // oracle/reve
 // ---- wave-level collectives (DPP, rv_common.h) ------------------------------------------
 // Every sub-index is processed by ONE wavefront: no workgroup barrier inside the recursion, the four waves of a workgroup
 // work on different sub-indices of the same root (disjoint rank ranges of the LDS arrays).
-#define WSYNC() do { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); __builtin_amdgcn_wave_barrier(); } while (0)
 
 __device__ inline u64 wave_max_u64(u64 v) { return rv_wave_max_u64(v); }
 __device__ inline u64 wave_sum_u64(u64 v) {       // trace mode only
     for (int d = 32; d >= 1; d >>= 1) v += ((u64)__shfl_xor((u32)(v >> 32), d, 64) << 32) | __shfl_xor((u32)v, d, 64);
     return v;
 }
-__device__ inline u32 lanes_below(u64 mask) { return __builtin_amdgcn_mbcnt_hi((u32)(mask >> 32), __builtin_amdgcn_mbcnt_lo((u32)mask, 0u)); }
 // the value of the lane below (lane 0: `first`)
 __device__ inline u32 from_lane_below(u32 x, u32 first) { return (u32)__builtin_amdgcn_update_dpp((int)first, (int)x, 0x138 /* wave_shr:1 */, 0xf, 0xf, false); }
 
@@ -146,7 +144,7 @@ __device__ __forceinline__ void leaf_run(const RvLeafArgs &A, const PARGS &P) {
             got = __builtin_amdgcn_readfirstlane(got);
             if (got < 0) break;
         }
-        WSYNC();
+        RV_WSYNC();
         const Frame f = cur[wv];
         have = false;
         LF_PROF(p_idle)
@@ -236,7 +234,7 @@ __device__ __forceinline__ void leaf_run(const RvLeafArgs &A, const PARGS &P) {
             MinSt2 tot; tot.has = (u32)__builtin_amdgcn_readlane((int)inc.has, 63); tot.v0 = (u32)__builtin_amdgcn_readlane((int)inc.v0, 63); tot.v1 = (u32)__builtin_amdgcn_readlane((int)inc.v1, 63);
             car = ms2_combine(car, tot);
         }
-        WSYNC();
+        RV_WSYNC();
         LF_PROF(p_split)
         const int nl = (int)cnt0, ntr = (int)cnt1;
         if (lane == 0 && (cnt0 != nlead || cnt1 != (u32)(TAn + TBn))) PICK::fail(A, P, 8u);      // (a sub-index that is not the suffixes of its intervals)
@@ -268,10 +266,10 @@ __device__ __forceinline__ void leaf_run(const RvLeafArgs &A, const PARGS &P) {
                     }
                 }
                 const u64 mask = __ballot(on);
-                if (on) act[S + nact + lanes_below(mask)] = (uint16_t)e;
+                if (on) act[S + nact + rv_lanes_below(mask)] = (uint16_t)e;
                 nact += (u32)__popcll(mask);
             }
-            WSYNC();
+            RV_WSYNC();
             for (u32 ai = 0; ai < nact; ai++) {
                 const int e = (int)act[S + ai];
                 const int64_t p = (int64_t)ns[S + e], l0 = (int64_t)nl_[S + e];          // (the same address for every lane: one broadcast read)
@@ -290,9 +288,9 @@ __device__ __forceinline__ void leaf_run(const RvLeafArgs &A, const PARGS &P) {
                         const int r = hi - lane;
                         sa_t vs = 0; u32 vl = 0; uint8_t vb = 0;
                         if (r > x) { vs = ns[S + r - 1]; vl = nl_[S + r - 1]; vb = nb[S + r - 1]; }
-                        WSYNC();
+                        RV_WSYNC();
                         if (r > x) { ns[S + r] = vs; nl_[S + r] = vl; nb[S + r] = vb; }
-                        WSYNC();
+                        RV_WSYNC();
                     }
                     if (lane == 0) {
                         ns[S + x] = (sa_t)p; nb[S + x] = tB;
@@ -303,7 +301,7 @@ __device__ __forceinline__ void leaf_run(const RvLeafArgs &A, const PARGS &P) {
                     const int64_t l1 = (int64_t)nl_[S + e + 1];
                     if (lane == 0 && p < B && p + l1 > B && l1 > l0) nl_[S + e + 1] = (u32)(B - p);
                 }
-                WSYNC();
+                RV_WSYNC();
             }
         }
         // ---- children (reveal.c:1296-1324); their order is free: this wave goes on with the smaller one, the larger one goes to

@@ -99,8 +99,6 @@ constexpr int CAP_L = RV_LEAF_N;           // ranks of the largest job a workgro
 constexpr int CAP_S = 512;                 // ... a wavefront builds
 static_assert(CAP_L <= 2048, "local ranks are packed in 12 bits, positions in 16");
 
-#define MANY_WSYNC() do { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); __builtin_amdgcn_wave_barrier(); } while (0)
-
 __device__ inline u32 many_wave_incl_max(u32 v) {
     const int lane = threadIdx.x & 63;
 #define MANY_STEP_(CTRL, RM, TAKE) { const u32 o = rv_dpp_u32<CTRL, RM>(v); v = ((TAKE) && o > v) ? o : v; }
@@ -132,7 +130,7 @@ __global__ __launch_bounds__(MT) void k_many_build(const ManyDevJob *__restrict_
     u64 *key = s_key[slot];
     uint8_t *txt = s_txt[slot];
     uint16_t *rank = s_rank[slot];
-#define MANY_SYNC() do { if (TPJ == 64) MANY_WSYNC(); else __syncthreads(); } while (0)
+#define MANY_SYNC() do { if (TPJ == 64) RV_WSYNC(); else __syncthreads(); } while (0)
     int N2 = 2;
     while (N2 < n) N2 <<= 1;               // size of the sorting network (<= CAP)
 

@@ -4,9 +4,9 @@
 // The level pipeline picks on the device: k_pick_slots (rv_scan.hip) writes the longest survivor of the pair scan of every sub-index into picks[1 + s],
 // k_decide (rv_decide.hip) turns that into the split's tables.  Under the chain route of rv_many's handle (rv_leaf_chain_route, rv_align.hip) this kernel
 // is launched in place of k_pick_slots and writes what schemes.graphmumpicker (reveal/schemes.py:197-361) picks into the same slot: trim the overlaps of
-// the sub-index' matches, chain them, split on the largest match of the chain -- the TRIMMED match, which may be shorter than minl.  rv_pick_chain
-// (rv_chain.hip, with pk_trim_overlap of rv_pick.h and rv_chain) is the specification; the stage is PickChain::pick of rv_leaf_chain.hip with wider fields
-// and the scan's survivors instead of a scan of its own.  k_decide, the early split and the host's bookkeeping stay as they are: to them a pick is a pick.
+// the sub-index' matches, chain them, split on the largest match of the chain -- the TRIMMED match, which may be shorter than minl.  The decision is
+// rv_chain_stage_pair (rv_chain_stage.h); what is here: collecting the scan's survivors, the lists, the flags and writing the pick.  k_decide, the early
+// split and the host's bookkeeping stay as they are: to them a pick is a pick.
 // Sub-indices whose flag byte says "finished elsewhere" (bit 0: the leaf kernel takes them) are left alone.
 //
 // What the caller guarantees (rv_many.hip many_chain_large_admits) is what k_leaf_chain asks for, with other bounds:
@@ -14,21 +14,13 @@
 //   a job of at most 2^17 ranks          a sub-index' intervals are pieces of its job's two sequences: lengths and positions relative to the interval begins
 //                                        lie in [0, 2^17) -- 17 bits each (the kernel flags a job whose interval is longer instead of packing garbage)
 //   0 <= wscore, wpen <= RV_LEAF_MCHAIN_WMAX = 2^10
-//                                        scores in 32 bits: the lengths of a chain (disjoint on path 0) add up to at most 2^17, and a gap cost is at most 2^17
-//                                        (for every model it is bounded by the larger per-path distance, which lies inside the interval + the sentinels); a
-//                                        score is at least what the left sentinel offers, gain - wpen * gap >= -2^27, and at most wscore * 2^17 = 2^27; a
-//                                        candidate score + gain - wpen * gap therefore lies within 3 * 2^27 < 2^30
-//   with weights >= 0 the early `break` of rv_chain never changes the choice (rv_leaf_chain.hip)
+//                                        scores in 32 bits (rv_chain_stage.h): the lengths of a chain (disjoint on path 0) add up to at most 2^17, and a gap
+//                                        cost is at most 2^17 (for every model it is bounded by the larger per-path distance, which lies inside the interval +
+//                                        the sentinels); a score is at least what the left sentinel offers, gain - wpen * gap >= -2^27, and at most wscore *
+//                                        2^17 = 2^27; a candidate score + gain - wpen * gap therefore lies within 3 * 2^27 < 2^30
 //
-// Packed fields (all re-derived for 17-bit positions; rv_leaf_chain.hip has 16-bit ones):
-//   a match      u64: l (17 bits, 0 .. 16) | a << 17 (17 bits) | b << 34 (17 bits): 51 bits
-//   sort key     u64: position << 18 | (2^18 - 1 - l): l <= 2^17 keeps the low field in 18 bits, 35 bits in all; smaller key = in front (position
-//                ascending, longer first)
-//   chain entry  u64: score (32 bits, two's complement) | link << 32 (16 bits; 0xFFFF = the left sentinel)
-//   tie order    k1 (ONE 64-bit key, larger wins) = (candidate score ^ 2^31) << 32 | (predecessor's score ^ 2^31); among equal k1 the smaller
-//                k2 = (step of activation + 1) << 16 | sort order (16 + 16 bits; the left sentinel, active from the start: 0)
-//   the step at which a match became active: 16 bits, 0xFFFF = not yet
-// so the candidate cap must stay below 2^16 - 1; the LDS budget sets it far lower:
+// Packed fields (PairPickStage; the header checks that they fit): a match is l | a << 17 | b << 34, the length field of a sort key has 18 bits (l <= 2^17),
+// the sort order in the tie key 16.  The candidate cap must stay below 2^16 - 1; the LDS budget sets it far lower:
 //
 // Lists in LDS, PC_CAP = 1024 candidates per sub-index: two lists of 8 B and the step numbers of 2 B = 18 B per entry, 18 432 B per workgroup: eight
 // workgroups per CU (160 KiB).  At 1 % divergence a pair of 2 x 10 000 bases has about 100 matches of 20 and more bases, a rearranged one a few hundred.
@@ -45,39 +37,30 @@
 // ascending text begins, ManyDevJob::abeg).
 // No scratch, no VGPR spill (compiler remarks; DESIGN.md 3j quotes them).
 #include "rv_scan.h"
+#include "rv_chain_stage.h"
 
 namespace {
 
 constexpr int PC_CAP = RV_PICK_CHAIN_CAP_MAX;
-constexpr u32 LINK_L = 0xFFFFu;        // predecessor: the left sentinel
-constexpr u32 NOT_ACTIVE = 0xFFFFu;
-constexpr int POS_BITS = 17;
-constexpr u64 POS_MASK = (1ull << POS_BITS) - 1;
-static_assert(PC_CAP < 0xFFFF, "links, sort order and activation steps are 16-bit fields");
 static_assert(PC_CAP * 18 <= 160 * 1024 / 8, "eight workgroups per CU");
 
-#define PC_WSYNC() do { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); __builtin_amdgcn_wave_barrier(); } while (0)
-
-struct Mt { int l, a, b; };            // a match: length, position on path 0 / 1 (relative to the sub-index' interval begins)
-__device__ inline u64 mt_pack(const Mt &m) { return (u64)(u32)m.l | ((u64)(u32)m.a << POS_BITS) | ((u64)(u32)m.b << (2 * POS_BITS)); }
-__device__ inline Mt mt_unpack(u64 w) { Mt m; m.l = (int)(w & POS_MASK); m.a = (int)((w >> POS_BITS) & POS_MASK); m.b = (int)((w >> (2 * POS_BITS)) & POS_MASK); return m; }
-__device__ inline u64 sort_key(const Mt &m, int c) { return ((u64)(u32)(c ? m.b : m.a) << 18) | (u64)(262143u - (u32)m.l); }
-__device__ inline u32 pc_lanes_below(u64 mask) { return __builtin_amdgcn_mbcnt_hi((u32)(mask >> 32), __builtin_amdgcn_mbcnt_lo((u32)mask, 0u)); }
-
-// utils.gapcost for two paths (rv_chain.hip gapcost): d0, d1 = end of the predecessor - start of the match
-__device__ inline int gap2(int d0, int d1, int model) {
-    if (model == 1) { const int s = d0 + d1; return (s < 0 ? -s : s) / 2; }
-    const int D0 = d0 < 0 ? -d0 : d0, D1 = d1 < 0 ? -d1 : d1;
-    if (model == 2) return D0 > D1 ? D0 : D1;
-    return D0 > D1 ? D0 - D1 : D1 - D0;
-}
-
-// the job whose first sequence holds text position p: the last begin at or in front of it
-__device__ inline int job_of(const int64_t *__restrict__ beg, int njobs, int64_t p) {
-    int lo = 0, hi = njobs;
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if (beg[mid] <= p) lo = mid + 1; else hi = mid; }
-    return lo > 0 ? lo - 1 : 0;
-}
+// the stage's storage (rv_chain_stage.h): the kernel's own LDS lists; positions relative to the sub-index' interval begins, so `left` is -1 on both paths
+struct PairPickStage {
+    typedef RvMt2 Mt; typedef u64 key_t;
+    static constexpr int POS_BITS = 17, CAP = PC_CAP, LMAX = (1 << POS_BITS) - 1, COORD_BITS = POS_BITS, LKEY_BITS = 18, ORDER_BITS = 16;
+    u64 *la, *lb; uint16_t *act;
+    int aL, bL, aR, bR, wscore, wpen, model;
+    __device__ __forceinline__ Mt getA(int i) const { return rv_mt2_unpack<POS_BITS>(la[i]); }
+    __device__ __forceinline__ void putA(int i, const Mt &m) { la[i] = rv_mt2_pack<POS_BITS>(m); }
+    __device__ __forceinline__ Mt getB(int i) const { return rv_mt2_unpack<POS_BITS>(lb[i]); }
+    __device__ __forceinline__ void putB(int i, const Mt &m) { lb[i] = rv_mt2_pack<POS_BITS>(m); }
+    __device__ __forceinline__ u64 getE(int i) const { return la[i]; }
+    __device__ __forceinline__ void putE(int i, u64 w) { la[i] = w; }
+    __device__ __forceinline__ u32 getStep(int i) const { return act[i]; }
+    __device__ __forceinline__ void putStep(int i, u32 v) { act[i] = (uint16_t)v; }
+    __device__ __forceinline__ int pos(const Mt &m, int c) const { return c ? m.b : m.a; }
+    static __device__ __forceinline__ void cut(Mt &m, int overlap) { m.l -= overlap; m.a += overlap; m.b += overlap; }
+};
 
 __global__ __launch_bounds__(64) void k_pick_chain(const RvPairRec *__restrict__ slots, const RvPairRec *__restrict__ ovf, u32 ovf_cap,
                                                    const u32 *__restrict__ tilecnt, const u32 *__restrict__ tileovf, int64_t ntile,
@@ -97,26 +80,24 @@ __global__ __launch_bounds__(64) void k_pick_chain(const RvPairRec *__restrict__
     const int64_t b0 = (int64_t)P.nodes[4 * (size_t)s + 2], b1 = (int64_t)P.nodes[4 * (size_t)s + 3];
     if (!(a0 < a1 && b0 < b1)) return;                           // one sample only: no match, no pick (k_decide decides nothing either)
     const int64_t r0 = sub_start[s], r1 = sub_start[s + 1];
-    auto flag_job = [&](u32 bits) { if (lane == 0) atomicOr(&P.job_flags[job_of(P.job_begin, P.njobs, a0)], bits); };
-    if (a1 - a0 >= ((int64_t)1 << POS_BITS) || b1 - b0 >= ((int64_t)1 << POS_BITS)) { flag_job(64u); return; }
+    auto flag_job = [&](u32 bits) { if (lane == 0) atomicOr(&P.job_flags[rv_job_of(P.job_begin, P.njobs, a0)], bits); };
+    if (a1 - a0 > PairPickStage::LMAX || b1 - b0 > PairPickStage::LMAX) { flag_job(64u); return; }
     const int cap = (int)(P.cap < (u32)PC_CAP ? P.cap : (u32)PC_CAP);
-    auto getB = [&](int i) { return mt_unpack(lb[i]); };
-    auto done = [&](const Mt &m) {
-        if (lane == 0) { RvPairRec r; r.a = (sa_t)(a0 + m.a); r.b = (sa_t)(b0 + m.b); r.l = (u32)m.l; r.rank = (u32)r0; picks[RV_PAIR_HDR + s] = r; }
-    };
+    PairPickStage t;
+    t.la = la; t.lb = lb; t.act = act;
 
     // ---- collect: the survivors of the pair scan with a rank of this sub-index, in rank order (tiles straddle sub-indices) ----
     int m = 0;
     bool bad = false;
     const int64_t t1 = (r1 - 1) / RV_PAIR_TILE;
-    for (int64_t t = r0 / RV_PAIR_TILE; t <= t1 && t < ntile; t++) {
-        const u32 cnt = tilecnt[t], ob = tileovf[t];
+    for (int64_t tl = r0 / RV_PAIR_TILE; tl <= t1 && tl < ntile; tl++) {
+        const u32 cnt = tilecnt[tl], ob = tileovf[tl];
         for (u32 q0 = 0; q0 < cnt; q0 += 64) {
             const u32 q = q0 + (u32)lane;
-            bool ok = false; Mt c; c.l = c.a = c.b = 0;
+            bool ok = false; RvMt2 c; c.l = c.a = c.b = 0;
             if (q < cnt) {
                 RvPairRec r; r.a = r.b = 0; r.l = 0; r.rank = 0xFFFFFFFFu;
-                if (q < RV_PAIR_SLOTS) r = slots[(size_t)t * RV_PAIR_SLOTS + q];
+                if (q < RV_PAIR_SLOTS) r = slots[(size_t)tl * RV_PAIR_SLOTS + q];
                 else { const u32 o = ob + (q - RV_PAIR_SLOTS); if (o < ovf_cap) r = ovf[o]; }      // (an overflow list that was too small: the host repeats the scan)
                 ok = r.rank != 0xFFFFFFFFu && (int64_t)r.rank >= r0 && (int64_t)r.rank < r1;
                 if (ok) {
@@ -126,137 +107,23 @@ __global__ __launch_bounds__(64) void k_pick_chain(const RvPairRec *__restrict__
                 }
             }
             const u64 mask = __ballot(ok);
-            const int at = m + (int)pc_lanes_below(mask);
-            if (ok && at < cap) la[at] = mt_pack(c);
+            const int at = m + (int)rv_lanes_below(mask);
+            if (ok && at < cap) t.putA(at, c);
             m += (int)__popcll(mask);
         }
     }
     if (__ballot(bad)) { flag_job(2u); return; }
     if (m == 0) return;
     if (m > cap) { flag_job(32u); return; }
-    PC_WSYNC();
-    if (m == 1) { done(mt_unpack(la[0])); return; }
 
-    // list A -> list B in the stable order of (position on path c, -l): every match counts the ones in front of it
-    auto sort_AB = [&](int c, int cnt) {
-        for (int base = 0; base < cnt; base += 64) {
-            const int i = base + lane;
-            Mt me; me.l = me.a = me.b = 0;
-            if (i < cnt) me = mt_unpack(la[i]);
-            const u64 key = sort_key(me, c);
-            int r = 0;
-            for (int j = 0; j < cnt; j++) {
-                const u64 ko = sort_key(mt_unpack(la[j]), c);      // (the same address for every lane: one broadcast read)
-                r += (ko < key || (ko == key && j < i)) ? 1 : 0;
-            }
-            if (i < cnt) lb[r] = mt_pack(me);
-        }
-        PC_WSYNC();
-    };
-
-    // ---- pk_trim_overlap (rv_pick.h; schemes.py:160-193) ----
-    for (int c = 0; c < 2 && m > 1; c++) {
-        sort_AB(c, m);
-        // the containment filter, B -> A
-        const Mt f0 = getB(0), f1 = getB(1);
-        const int end0 = (c ? f0.b : f0.a) + f0.l, end1 = (c ? f1.b : f1.a) + f1.l;
-        int w = 0;
-        for (int base = 0; base < m; base += 64) {
-            const int i = base + lane;
-            bool keep = false; Mt me; me.l = me.a = me.b = 0;
-            if (i < m) {
-                me = getB(i);
-                const Mt pv = getB(i == 0 ? m - 1 : i - 1);      // (i - 1 == -1: the last one)
-                const int en = (c ? me.b : me.a) + me.l, ep = (c ? pv.b : pv.a) + pv.l;
-                keep = (i == 0 && end1 > end0) || ep < en;
-            }
-            const u64 mask = __ballot(keep);
-            if (keep) la[w + (int)pc_lanes_below(mask)] = mt_pack(me);
-            w += (int)__popcll(mask);
-        }
-        m = w;
-        PC_WSYNC();
-        if (m <= 1) break;
-        // the cut-back: `trimmed` is the stack la[0 .. top], written in place (it never holds more than the i matches read so far).  Every lane
-        // follows the same values (broadcast reads), lane 0 writes.
-        int top = 0;
-        bool raised = false;
-        for (int i = 1; i < m; i++) {
-            if (top < 0) { raised = true; break; }            // trimmed[-1] of an empty list: the reference raises IndexError
-            const Mt mum = mt_unpack(la[i]);
-            Mt pm = mt_unpack(la[top]);
-            const int overlap = (c ? pm.b : pm.a) + pm.l - (c ? mum.b : mum.a);
-            if (overlap > 0) {
-                if (pm.l - overlap > 0) { pm.l -= overlap; if (lane == 0) la[top] = mt_pack(pm); }
-                else top--;
-                if (mum.l - overlap > 0) {
-                    Mt t = mum; t.l -= overlap; t.a += overlap; t.b += overlap;
-                    top++;
-                    if (lane == 0) la[top] = mt_pack(t);
-                }
-            } else {
-                top++;
-                if (lane == 0) la[top] = mt_pack(mum);
-            }
-            PC_WSYNC();
-        }
-        if (raised) { flag_job(1u); return; }
-        m = top + 1;
-    }
-    if (m == 0) return;
-    if (m == 1) { done(mt_unpack(la[0])); return; }
-
-    // ---- rv_chain for two paths ----
-    sort_AB(0, m);                                          // the order of path 0 (distinct coordinates)
-    for (int i = lane; i < m; i += 64) act[i] = (uint16_t)NOT_ACTIVE;
-    PC_WSYNC();
-    const int aL = -1, bL = -1;                             // `left`: right in front of the intervals
-    const int aR = (int)(a1 - a0), bR = (int)(b1 - b0);     // `right`: right behind them
-    const int wscore = P.wscore, wpen = P.wpen, model = P.gcmodel;
-    u32 linkR = LINK_L;
-    for (int e = 0; e <= m; e++) {
-        Mt me; me.l = 0; me.a = aR; me.b = bR;
-        if (e < m) me = getB(e);
-        const int gain = wscore * me.l;                     // n (n - 1) / 2 = 1 for two members; `right` has none
-        u64 b1k = 0; u32 b2k = 0xFFFFFFFFu;
-        if (lane == 0 && aL <= me.a && bL <= me.b) {
-            const int tmpw = gain - wpen * gap2(aL - me.a, bL - me.b, model);
-            b1k = ((u64)((u32)tmpw ^ 0x80000000u) << 32) | (u64)(0u ^ 0x80000000u);
-            b2k = 0;
-        }
-        for (int base = 0; base < e; base += 64) {
-            const int p = base + lane;
-            if (p < e) {
-                const Mt o = getB(p);
-                if (o.a + o.l <= me.a && o.b + o.l <= me.b) {      // ends at or in front of the match on both paths
-                    u32 st = act[p];
-                    if (st == NOT_ACTIVE) { st = (u32)e; act[p] = (uint16_t)e; }
-                    const int sc = (int)(u32)(la[p] & 0xFFFFFFFFull);
-                    const int tmpw = sc + gain - wpen * gap2(o.a + o.l - me.a, o.b + o.l - me.b, model);
-                    const u64 k1 = ((u64)((u32)tmpw ^ 0x80000000u) << 32) | (u64)((u32)sc ^ 0x80000000u);
-                    const u32 k2 = ((st + 1u) << 16) | (u32)p;
-                    if (k1 > b1k || (k1 == b1k && k2 < b2k)) { b1k = k1; b2k = k2; }
-                }
-            }
-        }
-        const u64 w1 = rv_wave_max_u64(b1k);
-        if (w1 == 0) { flag_job(2u); return; }              // (a match that does not lie behind `left`: rv_chain fails)
-        const u32 w2 = 0xFFFFFFFFu - (u32)rv_wave_max_u64((u64)(0xFFFFFFFFu - (b1k == w1 ? b2k : 0xFFFFFFFFu)));
-        const u32 link = w2 < 65536u ? LINK_L : (w2 & 0xFFFFu);
-        const u32 score = (u32)(w1 >> 32) ^ 0x80000000u;
-        if (e < m) { if (lane == 0) la[e] = (u64)score | ((u64)link << 32); }
-        else linkR = link;
-        PC_WSYNC();
-    }
-    // back from `right`: the largest of the chain, of equal lengths the last in chain order = the first met on the way back
-    int split = -1, bl = 0, guard = 0;
-    for (u32 c = linkR; c != LINK_L; c = (u32)(la[c] >> 32) & 0xFFFFu) {
-        if (c >= (u32)m || ++guard > m) { flag_job(2u); return; }      // (broken back-pointer chain)
-        const int l = getB((int)c).l;
-        if (l > bl) { bl = l; split = (int)c; }
-    }
-    if (split < 0) return;                                  // `right` links to `left`: an empty chain, nothing picked
-    done(getB(split));
+    t.aL = -1; t.bL = -1;                                        // `left`: right in front of the intervals
+    t.aR = (int)(a1 - a0); t.bR = (int)(b1 - b0);                // `right`: right behind them
+    t.wscore = P.wscore; t.wpen = P.wpen; t.model = P.gcmodel;
+    RvMt2 pk;
+    const int res = rv_chain_stage_pair(t, lane, m, pk);
+    if (res > 0) { flag_job((u32)res); return; }
+    if (res != RV_STAGE_PICK) return;
+    if (lane == 0) { RvPairRec r; r.a = (sa_t)(a0 + pk.a); r.b = (sa_t)(b0 + pk.b); r.l = (u32)pk.l; r.rank = (u32)r0; picks[RV_PAIR_HDR + s] = r; }
 }
 
 }  // namespace
