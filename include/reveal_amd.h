@@ -525,8 +525,12 @@ void rv_batch_free(rv_batch *b);
  * paths do not keep the scores in 32 bits at 1024): the rounds of RV_MANY_LARGE_MULTI, the scan of every level unfiltered, the pick of every sub-index made by
  * k_pick_multi_chain (rv_pick_multi_chain.hip) in place of the longest-match kernels -- a match of a sample subset leaves a `rest` child --, or by the host's
  * picker at a level without device tables.  maxmums has to be at least the job's ranks: rem.align's default of 10 000 admits jobs of up to 10 000 ranks only.
- * A job that a kernel of any level flags (more than 512 candidates in a sub-index, where the reference's trim_overlap raises, twin offsets) is dropped from
- * the round and runs the ordinary way.  Under kind 1 the jobs of 17 .. 64 sequences above 2048 ranks and the jobs of more than 64 sequences always run the
+ * With RV_MANY_CHAIN_WIDE_LARGE set (off by default, independent of every other switch; it means something under kind 1 only) the jobs of 17 .. 64 sequences of
+ * that size share their launches under the picker too, in a call with at least RV_MANY_CHAIN_WIDE_LARGE_MIN of them (default 2), under the same conditions with
+ * the weights bounded by 128 (2^17 ranks x 2016 pairs of paths do not keep the scores in 32 bits at 256): the same rounds with up to 64 samples, every sub-index
+ * picked by the 64-sample form of k_pick_multi_chain, which holds 256 candidates a sub-index.
+ * A job that a kernel of any level flags (more than 512 candidates in a sub-index -- 256 in a round of jobs of 17 .. 64 sequences --, where the reference's
+ * trim_overlap raises, twin offsets) is dropped from the round and runs the ordinary way.  Under kind 1 the jobs of more than 64 sequences always run the
  * ordinary way.
  *   rv_many_set_picker  kind 0: the built-in picker (the default); kind 1: the reference's default picker with *args (copied).  Holds for later runs,
  *                   like an option.  -1 with an error text: args == NULL with kind 1, an unknown gap cost model, any other kind
@@ -541,6 +545,10 @@ void rv_batch_free(rv_batch *b);
  *                   out[4] kernel launches of the shared part of the last run (index build, leaf kernel, lower-casing; copies not counted).  A round
  *                   of large jobs adds every kernel of its index build (those of the radix sorts and scans included), one per level of its finish
  *                   (rv_align_stats.levels: a level is a handful of launches whatever the number of jobs) and the two of the lower-casing
+ *   rv_many_flagged out[b], b = 0 .. 7: the jobs of the last run that a round under rv_many_set_picker(1) gave back to the ordinary path with bit 1 << b
+ *                   of their flag word set (1 the reference's trim_overlap raises, 2 a broken chain, 8 twin offsets, 16 the RV_MANY_CHAIN_FLAG hook,
+ *                   32 more candidates than the kernel's cap or a full frame stack, 64 an interval of 2^17 positions, 128 the host's picker gave up);
+ *                   a job with several bits counts under each
  *   rv_many_option  RV_MANY_KEEP (test hook: keep SA / LCP of the shared-launch jobs for rv_many_arrays), RV_MANY_ROUND (positions per round),
  *                   RV_MANY_WAVE_MAX (ranks up to which a wavefront builds a job, at most 512; above: a workgroup), RV_MANY_MULTI (0 / 1: jobs of
  *                   3 .. 16 sequences through shared launches; they count in out[1] then), RV_MANY_STAGE (test hook: anchors such a job stages in LDS,
@@ -556,7 +564,9 @@ void rv_batch_free(rv_batch *b);
  *                   through shared launches; they count in out[1] then), RV_MANY_CHAIN_WIDE (0 / 1: the same for the jobs of 17 .. 64 sequences named
  *                   above), RV_MANY_CHAIN_LARGE (0 / 1: the same for the pair jobs above 2048 ranks named above), RV_MANY_CHAIN_LARGE_MIN (fewer such jobs
  *                   than this in a call stay ordinary, default 4), RV_MANY_CHAIN_LARGE_MULTI (0 / 1: the same for the jobs of 3 .. 16 sequences above 2048 ranks
- *                   named above), RV_MANY_CHAIN_LARGE_MULTI_MIN (fewer such jobs than this in a call stay ordinary, default 4), RV_MANY_CHAIN_FLAG (test hook: every n-th job of such a round is treated as flagged by the kernel --
+ *                   named above), RV_MANY_CHAIN_LARGE_MULTI_MIN (fewer such jobs than this in a call stay ordinary, default 4), RV_MANY_CHAIN_WIDE_LARGE (0 / 1: the
+ *                   same for the jobs of 17 .. 64 sequences above 2048 ranks named above), RV_MANY_CHAIN_WIDE_LARGE_MIN (fewer such jobs than this in a call stay
+ *                   ordinary, default 2), RV_MANY_CHAIN_FLAG (test hook: every n-th job of such a round is treated as flagged by the kernel --
  *                   dropped from the round and run the ordinary way; 0: off); any other name: rv_set_option on the internal handles
  *   rv_many_arrays  test hook: which = RV_SA / RV_LCP of a shared-launch job in job-local positions, native element width; -2: not kept */
 typedef struct rv_many rv_many;
@@ -571,6 +581,7 @@ int64_t rv_many_anchor_count(rv_many *m, int64_t *first, int64_t *members);
 int rv_many_fetch(rv_many *m, uint32_t *l, int64_t *off, int64_t *pos);
 int64_t rv_many_text(rv_many *m, int64_t job, char *out, int64_t cap);
 int rv_many_info(const rv_many *m, int64_t *out);
+int rv_many_flagged(const rv_many *m, int64_t *out);
 int64_t rv_many_arrays(rv_many *m, int64_t job, int which, void *out, int64_t cap);
 /* ---- device memory for the frontier hand-off between processes ("child SA/LCP shipped once to the owner GPU, peer copy over
  * xGMI") -- what reveal_amd/shard.py's own transport uses instead of a tensor library: the owner packs the segments it hands out into buffers of its

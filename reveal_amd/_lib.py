@@ -182,6 +182,7 @@ SYMBOLS = {
     "rv_many_fetch": (_I, [V, V, V, V]),
     "rv_many_text": (_L, [V, _L, V, _L]),
     "rv_many_info": (_I, [V, V]),
+    "rv_many_flagged": (_I, [V, V]),
     "rv_many_arrays": (_L, [V, _L, _I, V, _L]),
     "rv_test_exclusive_sum_u32": (_I, [V, V, _L]),
     "rv_test_inclusive_max_u32": (_I, [V, V, _L]),

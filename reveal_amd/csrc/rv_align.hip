@@ -497,8 +497,12 @@ static int chain_job_of(const Align *a, int side, int64_t p) {
     const int j = (int)(std::upper_bound(beg, beg + a->chain_njobs, p) - beg) - 1;
     return j < 0 ? 0 : j;
 }
-int rv_multi_chain_route(rv_index *h, const rv_picker_args *args, u32 *flags, const int64_t *job_begin, const int64_t *d_job_begin, int njobs, int rows) {
-    if (!h || (args && (!flags || !job_begin || !d_job_begin || njobs <= 0 || rows < 2 || rows > RV_PICK_MCHAIN_KMAX))) { rv_set_error("rv_multi_chain_route: bad arguments"); return -1; }
+int rv_multi_chain_route(rv_index *h, const rv_picker_args *args, u32 *flags, const int64_t *job_begin, const int64_t *d_job_begin, int njobs, int rows, int kmax) {
+    // (rows up to the bound of the round's class: more than RV_PICK_MCHAIN_KMAX only for the class of the kernel's 64-sample form)
+    if (!h || (args && (!flags || !job_begin || !d_job_begin || njobs <= 0 || (kmax != RV_PICK_MCHAIN_KMAX && kmax != RV_PICK_WCHAIN_KMAX) || rows < 2 || rows > kmax))) {
+        rv_set_error("rv_multi_chain_route: bad arguments");
+        return -1;
+    }
     if (!h->al) h->al = new Align();
     Align *a = h->al;
     a->multi_chain = args != nullptr;
@@ -506,8 +510,8 @@ int rv_multi_chain_route(rv_index *h, const rv_picker_args *args, u32 *flags, co
     a->mchain_begin.clear(); a->d_mchain_begin = nullptr; a->chain_njobs = 0; a->mchain_rows = 0;
     if (args) {
         a->leaf_chain = false;      // (the pair route of an earlier round of the handle: one route at a time)
-        if (a->picker != 0 || args->wscore < 0 || args->wpen < 0 || args->wscore > RV_PICK_MCHAIN_WMAX || args->wpen > RV_PICK_MCHAIN_WMAX || args->gcmodel < 0 ||
-            args->gcmodel > 2) {
+        const int wmax = kmax == RV_PICK_WCHAIN_KMAX ? RV_PICK_WCHAIN_WMAX : RV_PICK_MCHAIN_WMAX;
+        if (a->picker != 0 || args->wscore < 0 || args->wpen < 0 || args->wscore > wmax || args->wpen > wmax || args->gcmodel < 0 || args->gcmodel > 2) {
             rv_set_error("rv_multi_chain_route: options the chain pick of the multi-sample level pipeline does not take");
             a->multi_chain = false;
             return -1;
@@ -922,7 +926,8 @@ int rv_frontier_scan(rv_index *h) {
                 memset(&pc, 0, sizeof pc);
                 pc.nodes = a->d_next_nodes; pc.W = W;
                 pc.wscore = a->chain_args.wscore; pc.wpen = a->chain_args.wpen; pc.gcmodel = a->chain_args.gcmodel;
-                pc.cap = (u32)std::max<int64_t>(0, std::min<int64_t>(h->ws.opt.pick_mchain_cap, RV_PICK_MCHAIN_CAP_MAX));
+                // (the cap of the form the launch takes: RV_PICK_MCHAIN_CAP lowers either)
+                pc.cap = (u32)std::max<int64_t>(0, std::min<int64_t>(h->ws.opt.pick_mchain_cap, W > RV_PICK_MCHAIN_KMAX ? RV_PICK_WCHAIN_CAP_MAX : RV_PICK_MCHAIN_CAP_MAX));
                 pc.job_flags = a->chain_args.flags; pc.job_begin = a->d_mchain_begin; pc.njobs = a->chain_njobs;
                 if (W > a->mchain_rows) { rv_set_error("chain route: %d samples, a job table of %d", W, a->mchain_rows); return -1; }
                 a->chain_pick_subs += ns;

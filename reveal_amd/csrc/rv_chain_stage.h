@@ -5,7 +5,7 @@
 //   k_leaf_chain (rv_leaf_chain.hip)                     rv_chain_stage_pair    lists in the dead ranks of the leaf kernel's arrays, 16-bit positions
 //   k_pick_chain (rv_pick_chain.hip)                     rv_chain_stage_pair    own LDS lists, 17-bit positions
 //   k_leaf_multi_chain<16 / 64> (rv_leaf_multi_chain.hip) rv_chain_stage_multi   up to 16 / 64 samples, positions below 2^11
-//   k_pick_multi_chain<16> (rv_pick_multi_chain.hip)     rv_chain_stage_multi   up to 16 samples, 17-bit positions
+//   k_pick_multi_chain<16 / 64> (rv_pick_multi_chain.hip) rv_chain_stage_multi  up to 16 / 64 samples, 17-bit positions
 // A kernel collects its matches into list A, hands the stage a traits object (storage accessors + field widths) and acts on the outcome:
 //   RV_STAGE_NONE   nothing to pick          RV_STAGE_PICK   the pick is the TRIMMED match handed back          > 0   flag bits for the job:
 //   1  trim_overlap raises in the reference      2  the chain finds no predecessor / a broken back-pointer chain

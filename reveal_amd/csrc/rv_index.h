@@ -200,14 +200,16 @@ int rv_working_text_begin(rv_index *h, hipStream_t side);
 // rv_leaf_chain_roots: the roots of the chain leaf launches since the route was set; rv_pick_chain_subs: the sub-indices above RV_LEAF_N ranks a chain pick was asked for (k_pick_chain, or the host's picker at a level without device tables);
 // rv_leaf_chain_host_flags: the jobs the host flagged (a level without device tables whose sub-index the host's picker could not decide).
 int rv_leaf_chain_route(rv_index *h, const rv_picker_args *args, u32 *flags, const int64_t *job_begin = nullptr, const int64_t *d_job_begin = nullptr, int njobs = 0);
-// The multi-sample counterpart (rv_many's rounds of jobs of 3 .. 16 sequences above RV_LEAF_N ranks, RV_MANY_CHAIN_LARGE_MULTI): under the route the level
+// The multi-sample counterpart (rv_many's rounds of jobs of 3 .. 16 sequences above RV_LEAF_N ranks, RV_MANY_CHAIN_LARGE_MULTI, and of 17 .. 64, RV_MANY_CHAIN_WIDE_LARGE): under the route the level
 // pipeline of more than two samples scans unfiltered and every sub-index gets the reference's default picker's decision -- from k_pick_multi_chain
 // (rv_pick_multi_chain.hip) in place of k_multi_pick1 / k_multi_pick2 where the level's tables are on the device (an imported frontier ships them), from
 // rv_pick_chain on the host at a level without them; never the longest match.  The device-side early split stays off.  a->picker stays 0.  flags: one zeroed word
 // per JOB on the device; job_begin / d_job_begin: rows x njobs text begins, row q = where sequence q of every job begins, ascending (a job without a q-th
-// sequence: the begin of the next job that has one), rows >= the handle's samples.  args == NULL: the built-in picker again.  rv_pick_chain_subs and
-// rv_leaf_chain_host_flags count for this route as for the other.
-int rv_multi_chain_route(rv_index *h, const rv_picker_args *args, u32 *flags, const int64_t *job_begin = nullptr, const int64_t *d_job_begin = nullptr, int njobs = 0, int rows = 0);
+// sequence: the begin of the next job that has one), rows >= the handle's samples.  kmax: the sample bound of the round's class -- RV_PICK_MCHAIN_KMAX (16), or
+// RV_PICK_WCHAIN_KMAX (64) for rv_many's rounds of jobs of 17 .. 64 sequences (RV_MANY_CHAIN_WIDE_LARGE): rows <= kmax, and the weights within the bound of that
+// form of the kernel.  args == NULL: the built-in picker again.  rv_pick_chain_subs and rv_leaf_chain_host_flags count for this route as for the other.
+int rv_multi_chain_route(rv_index *h, const rv_picker_args *args, u32 *flags, const int64_t *job_begin = nullptr, const int64_t *d_job_begin = nullptr, int njobs = 0, int rows = 0,
+                         int kmax = 0);
 // the scan and the pick of a level under that route (rv_api.hip): pick_l[s] = 0 where sub-index s gets none
 int rv_run_multi_chain_pick(rv_index *h, const sa_t *SA, const lcp_t *LCP, const uint8_t *BWT, int64_t m, int minl, int minn, const int64_t *d_sub_start, int nsubs,
                             const struct RvPickMultiChainArgs &pc, std::vector<u32> &pick_l, std::vector<u32> &pick_n, std::vector<sa_t> &pick_pos);

@@ -65,7 +65,7 @@
 // RV_MANY_CHAIN_WIDE (off by default, independent of every other switch; it means something under kind 1 only): the jobs of 17 .. RV_MANY_WIDE_KMAX = 64
 // sequences many_chain_wide_admits names share their launches too, in rounds of their own -- layout and index build of the small RV_MANY_WIDE rounds
 // (many_round_multi with kmax = 64) and ONE launch of the 64-sample form of k_leaf_multi_chain.  Flags and test hooks as for RV_MANY_CHAIN_MULTI.  Under a
-// picker the jobs of 17 .. 64 sequences above RV_LEAF_N ranks, and every job of more than 64 sequences, stay ordinary.
+// picker the jobs of 17 .. 64 sequences above RV_LEAF_N ranks are RV_MANY_CHAIN_WIDE_LARGE's (below); every job of more than 64 sequences stays ordinary.
 // RV_MANY_CHAIN_LARGE (off by default, independent of every other switch; it means something under kind 1 only): the pair jobs many_chain_large_admits names
 // -- more than RV_LEAF_N and at most min(RV_MANY_LARGE_MAX, 2^17) ranks -- share their launches too, in rounds of their own, from RV_MANY_CHAIN_LARGE_MIN such
 // jobs in a call on: layout, segmented index build and frontier of the RV_MANY_LARGE rounds (many_round with `large` and `redo`), and the level pipeline under
@@ -78,8 +78,12 @@
 // (many_round_large_multi with `redo`), and the multi-sample level pipeline under its chain route (rv_multi_chain_route) -- every level's scan unfiltered, every
 // sub-index picked by k_pick_multi_chain (rv_pick_multi_chain.hip: the picker's decision for up to 16 samples, a wavefront per sub-index) in place of
 // k_multi_pick1 / k_multi_pick2, the early split off; a pick of a sample subset leaves a `rest` child.  There is no leaf kernel for multi-sample sub-indices of
-// a handle: sub-indices of every size are picked this way.  Flag words per job as above.  Under a picker the jobs of 17 .. 64 sequences above RV_LEAF_N ranks
-// stay ordinary.
+// a handle: sub-indices of every size are picked this way.  Flag words per job as above.
+// RV_MANY_CHAIN_WIDE_LARGE (off by default, independent of every other switch; it means something under kind 1 only): the jobs of 17 .. RV_MANY_WIDE_KMAX = 64
+// sequences many_chain_wide_large_admits names -- more than RV_LEAF_N and at most min(RV_MANY_LARGE_MAX, 2^17) ranks -- share their launches too, in rounds of
+// their own, from RV_MANY_CHAIN_WIDE_LARGE_MIN such jobs in a call on: the rounds of RV_MANY_CHAIN_LARGE_MULTI with kmax = RV_MANY_WIDE_KMAX
+// (many_round_large_multi with `redo`), every sub-index picked by the 64-sample form of k_pick_multi_chain.  That form holds 256 candidates a sub-index, not
+// 512, and its weight bound is 128: a sub-index with more flags its job (32), which finishes on the ordinary path.  Jobs of more than 64 sequences stay ordinary.
 // Size classes (DESIGN.md "Many small alignments" has the measurements): up to `wave_max` ranks (default 512) a wavefront per job,
 // four jobs per workgroup, no workgroup barrier; above, a workgroup of 256 threads per job.  Both hold 22.6 KB of LDS per workgroup:
 // seven workgroups per CU.
@@ -278,6 +282,7 @@ struct rv_many {
     int64_t chain_wide = 0;                     // RV_MANY_CHAIN_WIDE
     int64_t chain_large = 0, chain_large_min = RV_MANY_CHAIN_LARGE_MIN_DEFAULT;      // RV_MANY_CHAIN_LARGE, RV_MANY_CHAIN_LARGE_MIN
     int64_t chain_large_multi = 0, chain_large_multi_min = RV_MANY_CHAIN_LARGE_MULTI_MIN_DEFAULT;      // RV_MANY_CHAIN_LARGE_MULTI, RV_MANY_CHAIN_LARGE_MULTI_MIN
+    int64_t chain_wide_large = 0, chain_wide_large_min = RV_MANY_CHAIN_WIDE_LARGE_MIN_DEFAULT;        // RV_MANY_CHAIN_WIDE_LARGE, RV_MANY_CHAIN_WIDE_LARGE_MIN
     std::vector<std::pair<std::string, int64_t>> fwd;      // switches for the internal handles
     // results of the last run
     bool ran = false;
@@ -286,6 +291,7 @@ struct rv_many {
     std::vector<char> out_text;
     std::vector<sa_t> keep_sa; std::vector<lcp_t> keep_lcp;
     int64_t info[5] = {0, 0, 0, 0, 0};
+    int64_t flagged[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // rv_many_flagged: the jobs of the last run a chain round sent to the ordinary path, per bit of their flag word
     DBuf dJobs, dKJobs, dSA, dLCP, dBWT, dCnt;
     DBuf dFlag;                                 // rounds of k_leaf_chain: a word per job
     DBuf dBeg;                                  // ... and the text begins of the jobs' first / second sequences
@@ -296,6 +302,11 @@ struct rv_many {
 };
 
 namespace {
+
+// a job a chain round gives back: which bits its flag word holds (1, 2, 4, .. 128 -> flagged[0 .. 7])
+void many_count_flags(rv_many *m, u32 word) {
+    for (int b = 0; b < 8; b++) if (word >> b & 1u) m->flagged[b]++;
+}
 
 int many_handle(rv_many *m, rv_index **h) {
     if (*h) return 0;
@@ -342,25 +353,33 @@ bool many_chain_large_admits(const rv_many *m, const ManyJob &jb, int minl) {
     return true;
 }
 
-// The jobs of 3 .. RV_MANY_KMAX sequences above RV_LEAF_N ranks the multi-sample level pipeline finishes under picker kind 1 (RV_MANY_CHAIN_LARGE_MULTI), its
-// picks made by k_pick_multi_chain: the rule, stated once (many.takes_shared_launch(.., picker=, chain_large_multi=True) mirrors it).  It is
-// many_chain_multi_admits' with
+// The jobs of several sequences above RV_LEAF_N ranks the multi-sample level pipeline finishes under picker kind 1, its picks made by k_pick_multi_chain:
+// the rule, stated once for both forms of the kernel -- 3 .. RV_MANY_KMAX sequences with RV_MANY_CHAIN_LARGE_MULTI, RV_MANY_KMAX + 1 .. RV_MANY_WIDE_KMAX with
+// RV_MANY_CHAIN_WIDE_LARGE (many.takes_shared_launch(.., picker=, chain_large_multi=True / chain_wide_large=True) mirrors it).  It is many_chain_k_admits' with
 //   RV_LEAF_N < ranks <= min(RV_MANY_LARGE_MAX, 2^17)      positions and lengths of a sub-index in 17 bits, whatever RV_MANY_LARGE_MAX says
-//   weights 0 .. RV_PICK_MCHAIN_WMAX = 512                scores in 32 bits at 2^17 ranks x 120 pairs (rv_pick_multi_chain.hip derives the bound: 1024 does not hold)
+//   weights 0 .. wmax                                     scores in 32 bits at 2^17 ranks: RV_PICK_MCHAIN_WMAX = 512 over 120 pairs (1024 does not hold),
+//                                                         RV_PICK_WCHAIN_WMAX = 128 over 2016 pairs (256 does not hold); rv_pick_multi_chain.hip derives both
 //   seedsize <= 0 or above the longest sequence, maxmums <= 0 or at least the job's ranks: as there
 // rem.align's default maxmums of 10 000 therefore admits jobs of up to 10 000 ranks only (and its seedsize no sequence of 10 000 bases or more).
-bool many_chain_large_multi_admits(const rv_many *m, const ManyJob &jb, int minl) {
-    if (m->picker != 1 || !m->chain_large_multi) return false;
-    if (jb.k < 3 || jb.k > RV_MANY_KMAX || !jb.clean || jb.ranks <= RV_LEAF_N || jb.ranks > std::min<int64_t>(m->large_max, RV_PICK_CHAIN_RANKS)) return false;
+bool many_chain_large_k_admits(const rv_many *m, const ManyJob &jb, int minl, int kmin, int kmax, int wmax, int64_t on) {
+    if (m->picker != 1 || !on) return false;
+    if (jb.k < kmin || jb.k > kmax || !jb.clean || jb.ranks <= RV_LEAF_N || jb.ranks > std::min<int64_t>(m->large_max, RV_PICK_CHAIN_RANKS)) return false;
     const rv_picker_args &a = m->pargs;
     if (!a.trim || minl <= 0) return false;
-    if (a.wscore < 0 || a.wpen < 0 || a.wscore > RV_PICK_MCHAIN_WMAX || a.wpen > RV_PICK_MCHAIN_WMAX) return false;
+    if (a.wscore < 0 || a.wpen < 0 || a.wscore > wmax || a.wpen > wmax) return false;
     if (a.gcmodel < 0 || a.gcmodel > 2) return false;
     int64_t longest = 0;
     for (int q = 0; q < jb.k; q++) longest = std::max(longest, m->lens[jb.seq0 + (size_t)q]);
     if (a.seedsize > 0 && a.seedsize <= longest) return false;
     if (a.maxmums > 0 && a.maxmums < jb.ranks) return false;
     return true;
+}
+static_assert(RV_PICK_MCHAIN_KMAX == RV_MANY_KMAX && RV_PICK_WCHAIN_KMAX == RV_MANY_WIDE_KMAX, "the two forms of k_pick_multi_chain take the two classes");
+bool many_chain_large_multi_admits(const rv_many *m, const ManyJob &jb, int minl) {
+    return many_chain_large_k_admits(m, jb, minl, 3, RV_MANY_KMAX, RV_PICK_MCHAIN_WMAX, m->chain_large_multi);
+}
+bool many_chain_wide_large_admits(const rv_many *m, const ManyJob &jb, int minl) {
+    return many_chain_large_k_admits(m, jb, minl, RV_MANY_KMAX + 1, RV_MANY_WIDE_KMAX, RV_PICK_WCHAIN_WMAX, m->chain_wide_large);
 }
 
 // The jobs of several sequences k_leaf_multi_chain finishes under picker kind 1: the rule, stated once for both forms of the kernel -- 3 .. RV_MANY_KMAX
@@ -567,7 +586,7 @@ int many_round(rv_many *m, const std::vector<int> &order, size_t lo, size_t hi, 
         RV_HIP(hipMemcpy(flag.data(), m->dFlag.p, J * sizeof(u32), hipMemcpyDeviceToHost));
         for (int k = 0; k < nhflag; k++) if (hflag[k] >= 0 && (size_t)hflag[k] < J) flag[(size_t)hflag[k]] |= 128u;
         std::vector<char> out((size_t)m->jobs.size(), 0);
-        for (size_t s = 0; s < J; s++) if (flag[s]) { out[(size_t)ord[s]] = 1; redo->push_back(ord[s]); nflag++; }
+        for (size_t s = 0; s < J; s++) if (flag[s]) { out[(size_t)ord[s]] = 1; redo->push_back(ord[s]); nflag++; many_count_flags(m, flag[s]); }
         if (nflag) m->recs.erase(std::remove_if(m->recs.begin() + (ptrdiff_t)rec0, m->recs.end(), [&](const ManyRec &r) { return out[(size_t)r.job] != 0; }), m->recs.end());
     }
     // final text of every job: a$b$
@@ -687,7 +706,7 @@ int many_round_multi(rv_many *m, const std::vector<int> &order, size_t lo, size_
     m->out_text.resize(tbase + (size_t)n);
     RV_HIP(hipMemcpyAsync(m->out_text.data() + tbase, m->dTxt.p, (size_t)n, hipMemcpyDeviceToHost, q));
     RV_HIP(hipStreamSynchronize(q));
-    if (redo) for (size_t s = 0; s < J; s++) if (flag[s]) { redo->push_back(order[lo + s]); nflag++; }
+    if (redo) for (size_t s = 0; s < J; s++) if (flag[s]) { redo->push_back(order[lo + s]); nflag++; many_count_flags(m, flag[s]); }
     for (size_t k = 0; k < na; k++) {
         const RvLeafMultiAnchor &r = an[k];
         if (r.job >= J || r.n < 2 || r.n > (u32)kmax || (size_t)r.moff + r.n > nm) { rv_set_error("rv_many_run: a malformed anchor"); return -1; }
@@ -778,7 +797,8 @@ int many_collect_k(rv_many *m, rv_index *h, const ManyRoundK &R, bool picker_ord
 // The sample-major text goes into the shared handle (K samples, K the widest job), the index of every job is built at once
 // (rv_many_large_build_k), the segments become a level-0 frontier of J roots of k samples each, and the level pipeline finishes them together.
 // kmax: the sample bound of the round's class (RV_MANY_KMAX; RV_MANY_WIDE_KMAX for the rounds of jobs of 17 .. 64 sequences, RV_MANY_WIDE).
-// redo != NULL: the round of picker kind 1 (RV_MANY_CHAIN_LARGE_MULTI, kmax = RV_MANY_KMAX) -- the level pipeline runs under the multi-sample chain route
+// redo != NULL: the round of picker kind 1 (RV_MANY_CHAIN_LARGE_MULTI with kmax = RV_MANY_KMAX, RV_MANY_CHAIN_WIDE_LARGE with kmax = RV_MANY_WIDE_KMAX: the
+// form of k_pick_multi_chain that takes it) -- the level pipeline runs under the multi-sample chain route
 // (rv_multi_chain_route: every sub-index picked by k_pick_multi_chain, or by the host's picker at a level without device tables), and the jobs a launch of
 // any level flags come back in *redo for the ordinary path: their anchors are dropped, their text is not taken
 int many_round_large_multi(rv_many *m, const std::vector<int> &order, size_t lo, size_t hi, int minl, int minn, rv_align_stats *total, int kmax, std::vector<int> *redo = nullptr) {
@@ -829,7 +849,8 @@ int many_round_large_multi(rv_many *m, const std::vector<int> &order, size_t lo,
     if (redo) {
         // the chain route: flags per job; a sub-index of any level finds its job in the row of its lowest live sample -- where sequence q of every job
         // begins, ascending (a job without a q-th sequence stands at the begin of the next one that has it)
-        if (K > RV_PICK_MCHAIN_KMAX) { rv_set_error("rv_many_run: a chain round of jobs of %d sequences", K); return -1; }
+        // (K <= kmax was checked above: a chain round of more than RV_MANY_KMAX rows exists for the class of the kernel's 64-sample form only)
+        if (kmax != RV_MANY_KMAX && kmax != RV_MANY_WIDE_KMAX) { rv_set_error("rv_many_run: a chain round of a class of %d sequences", kmax); return -1; }
         std::vector<int64_t> beg((size_t)K * J);
         for (int q2 = 0; q2 < K; q2++) {
             int64_t nxt = R.send[(size_t)q2];
@@ -841,7 +862,7 @@ int many_round_large_multi(rv_many *m, const std::vector<int> &order, size_t lo,
         RV_TRY(m->dBeg.reserve(beg.size() * sizeof(int64_t)));
         RV_HIP(hipMemcpyAsync(m->dBeg.p, beg.data(), beg.size() * sizeof(int64_t), hipMemcpyHostToDevice, h->ws.stream));
         RV_HIP(hipStreamSynchronize(h->ws.stream));
-        RV_TRY(rv_multi_chain_route(h, &m->pargs, m->dFlag.as<u32>(), beg.data(), m->dBeg.as<int64_t>(), (int)J, K));
+        RV_TRY(rv_multi_chain_route(h, &m->pargs, m->dFlag.as<u32>(), beg.data(), m->dBeg.as<int64_t>(), (int)J, K, kmax));
     }
     // jobs, segment offsets, frontier tables
     std::vector<int64_t> meta(6 * J), node_first(J + 1);
@@ -922,7 +943,7 @@ int many_round_large_multi(rv_many *m, const std::vector<int> &order, size_t lo,
         RV_HIP(hipMemcpy(flag.data(), m->dFlag.p, J * sizeof(u32), hipMemcpyDeviceToHost));
         for (int k = 0; k < nhflag; k++) if (hflag[k] >= 0 && (size_t)hflag[k] < J) flag[(size_t)hflag[k]] |= 128u;
         std::vector<char> out((size_t)m->jobs.size(), 0);
-        for (size_t s = 0; s < J; s++) if (flag[s]) { out[(size_t)R.ord[s]] = 1; redo->push_back(R.ord[s]); nflag++; }
+        for (size_t s = 0; s < J; s++) if (flag[s]) { out[(size_t)R.ord[s]] = 1; redo->push_back(R.ord[s]); nflag++; many_count_flags(m, flag[s]); }
         if (nflag) m->recs.erase(std::remove_if(m->recs.begin() + (ptrdiff_t)rec0, m->recs.end(), [&](const ManyRec &r) { return out[(size_t)r.job] != 0; }), m->recs.end());
     }
     // final text of every job, gathered from its k places
@@ -975,6 +996,7 @@ int many_run(rv_many *m, int minl, int minn, rv_align_stats *total) {
     m->ran = false;
     m->recs.clear(); m->rpos.clear(); m->out_text.clear(); m->keep_sa.clear(); m->keep_lcp.clear();
     for (int k = 0; k < 5; k++) m->info[k] = 0;
+    for (int k = 0; k < 8; k++) m->flagged[k] = 0;
     if (total) memset(total, 0, sizeof *total);
     const int nj = (int)m->jobs.size();
     m->info[0] = nj;
@@ -1008,7 +1030,12 @@ int many_run(rv_many *m, int minl, int minn, rv_align_stats *total) {
     int64_t nclmulti = 0;
     for (const ManyJob &jb : m->jobs) nclmulti += is_chain_large_multi(jb) ? 1 : 0;
     const bool take_chain_large_multi = nclmulti > 0 && nclmulti >= m->chain_large_multi_min;
-    std::vector<int> clmorder;
+    // (... and the jobs of 17 .. 64 sequences above RV_LEAF_N ranks: the same, RV_MANY_CHAIN_WIDE_LARGE_MIN)
+    const auto is_chain_wide_large = [&](const ManyJob &jb) { return many_chain_wide_large_admits(m, jb, minl) && jb.ranks <= lim; };
+    int64_t ncwlarge = 0;
+    for (const ManyJob &jb : m->jobs) ncwlarge += is_chain_wide_large(jb) ? 1 : 0;
+    const bool take_chain_wide_large = ncwlarge > 0 && ncwlarge >= m->chain_wide_large_min;
+    std::vector<int> clmorder, cwlorder;
     const bool chain = m->picker == 1;      // the shared classes finish with built-in-picker kernels: under kind 1 only many_chain_admits',
                                             // many_chain_multi_admits' and many_chain_wide_admits' jobs share launches
     for (int j = 0; j < nj; j++) {
@@ -1017,7 +1044,8 @@ int many_run(rv_many *m, int minl, int minn, rv_align_stats *total) {
         if (chain) { if (many_chain_admits(m, jb, minl)) order.push_back(j); else if (take_chain_large && is_chain_large(jb)) clorder.push_back(j);
                      else if (many_chain_multi_admits(m, jb, minl)) cmorder.push_back(j);
                      else if (take_chain_large_multi && is_chain_large_multi(jb)) clmorder.push_back(j);
-                     else if (many_chain_wide_admits(m, jb, minl)) cworder.push_back(j); else rest.push_back(j); }
+                     else if (many_chain_wide_admits(m, jb, minl)) cworder.push_back(j);
+                     else if (take_chain_wide_large && is_chain_wide_large(jb)) cwlorder.push_back(j); else rest.push_back(j); }
         else if (jb.k == 2 && jb.ranks <= RV_LEAF_N && jb.clean) order.push_back(j);
         else if (take_large && is_large(jb)) lorder.push_back(j);
         else if (take_large_multi && is_large_multi(jb)) lmorder.push_back(j);
@@ -1037,6 +1065,7 @@ int many_run(rv_many *m, int minl, int minn, rv_align_stats *total) {
     std::stable_sort(cworder.begin(), cworder.end(), by_size);
     std::stable_sort(clorder.begin(), clorder.end(), by_size);
     std::stable_sort(clmorder.begin(), clmorder.end(), by_size);
+    std::stable_sort(cwlorder.begin(), cwlorder.end(), by_size);
     for (size_t lo = 0; lo < order.size();) {
         size_t hi = lo; int64_t sum = 0;
         while (hi < order.size() && (hi == lo || sum + m->jobs[(size_t)order[hi]].ranks <= lim)) sum += m->jobs[(size_t)order[hi++]].ranks;
@@ -1065,6 +1094,12 @@ int many_run(rv_many *m, int minl, int minn, rv_align_stats *total) {
         size_t hi = lo; int64_t sum = 0;
         while (hi < clmorder.size() && (hi == lo || sum + m->jobs[(size_t)clmorder[hi]].ranks <= lim)) sum += m->jobs[(size_t)clmorder[hi++]].ranks;
         RV_TRY(many_round_large_multi(m, clmorder, lo, hi, minl, minn, total, RV_MANY_KMAX, &rest));
+        lo = hi;
+    }
+    for (size_t lo = 0; lo < cwlorder.size();) {    // picker kind 1, the jobs of 17 .. 64 sequences above RV_LEAF_N ranks (RV_MANY_CHAIN_WIDE_LARGE): rounds of their own
+        size_t hi = lo; int64_t sum = 0;
+        while (hi < cwlorder.size() && (hi == lo || sum + m->jobs[(size_t)cwlorder[hi]].ranks <= lim)) sum += m->jobs[(size_t)cwlorder[hi++]].ranks;
+        RV_TRY(many_round_large_multi(m, cwlorder, lo, hi, minl, minn, total, RV_MANY_WIDE_KMAX, &rest));
         lo = hi;
     }
     if (chain) std::sort(rest.begin(), rest.end());
@@ -1161,6 +1196,8 @@ int rv_many_option(rv_many *m, const char *name, int64_t value) {
     if (strcmp(name, "RV_MANY_CHAIN_LARGE") == 0) { m->chain_large = value != 0; return 0; }
     if (strcmp(name, "RV_MANY_CHAIN_LARGE_MULTI") == 0) { m->chain_large_multi = value != 0; return 0; }
     if (strcmp(name, "RV_MANY_CHAIN_LARGE_MULTI_MIN") == 0) { if (value < 0) { rv_set_error("RV_MANY_CHAIN_LARGE_MULTI_MIN: negative"); return -1; } m->chain_large_multi_min = value; return 0; }
+    if (strcmp(name, "RV_MANY_CHAIN_WIDE_LARGE") == 0) { m->chain_wide_large = value != 0; return 0; }
+    if (strcmp(name, "RV_MANY_CHAIN_WIDE_LARGE_MIN") == 0) { if (value < 0) { rv_set_error("RV_MANY_CHAIN_WIDE_LARGE_MIN: negative"); return -1; } m->chain_wide_large_min = value; return 0; }
     if (strcmp(name, "RV_MANY_CHAIN_LARGE_MIN") == 0) { if (value < 0) { rv_set_error("RV_MANY_CHAIN_LARGE_MIN: negative"); return -1; } m->chain_large_min = value; return 0; }
     if (strcmp(name, "RV_MANY_CHAIN_FLAG") == 0) { if (value < 0) { rv_set_error("RV_MANY_CHAIN_FLAG: negative"); return -1; } m->chain_flag = value; return 0; }
     if (strcmp(name, "RV_MANY_WIDE_LARGE_MIN") == 0) { if (value < 0) { rv_set_error("RV_MANY_WIDE_LARGE_MIN: negative"); return -1; } m->wide_large_min = value; return 0; }
@@ -1246,6 +1283,12 @@ int64_t rv_many_text(rv_many *m, int64_t job, char *out, int64_t cap) {
     if (cap < jb.ranks) { rv_set_error("buffer too small"); return -1; }
     memcpy(out, m->out_text.data() + jb.text_off, (size_t)jb.ranks);
     return jb.ranks;
+}
+
+int rv_many_flagged(const rv_many *m, int64_t *out) {
+    if (!m || !out) { rv_set_error("rv_many_flagged: null argument"); return -1; }
+    for (int k = 0; k < 8; k++) out[k] = m->flagged[k];
+    return 0;
 }
 
 int rv_many_info(const rv_many *m, int64_t *out) {

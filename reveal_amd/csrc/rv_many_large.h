@@ -11,6 +11,10 @@
 // count measured at which the shared rounds win (profiles/many_chain_large_multi.txt: one job loses, 5.6 against 3.6 ms; four win, 11.2 against 17.4 ms).  Not
 // RV_MANY_LARGE_MULTI_MIN's 16: the ordinary path costs 4 - 5 ms a job under a picker, 0.8 ms without
 #define RV_MANY_CHAIN_LARGE_MULTI_MIN_DEFAULT 4
+// default of RV_MANY_CHAIN_WIDE_LARGE_MIN (fewer admitted jobs of 17 .. 64 sequences above RV_LEAF_N ranks in a call under a picker stay ordinary): the smallest
+// count measured at which the shared rounds win (profiles/many_chain_wide_large.txt, jobs of 32 sequences: one job ties, 3.0 against 3.0 ms; two win, 3.4
+// against 5.8 ms, far outside both spreads of 0.1 ms).  Lower than RV_MANY_CHAIN_LARGE_MULTI_MIN's 4: a round of a job or two costs 3 ms here, 5 - 8 ms there
+#define RV_MANY_CHAIN_WIDE_LARGE_MIN_DEFAULT 2
 #define RV_MANY_CHAIN_LARGE_MIN_DEFAULT 4      // RV_MANY_CHAIN_LARGE_MIN: fewer admitted pair jobs above RV_LEAF_N ranks in a call under a picker stay ordinary
 // default of RV_MANY_WIDE_LARGE_MIN (fewer jobs of 17 .. 64 sequences above RV_LEAF_N ranks than this in a call stay ordinary): the smallest
 // count measured at which the shared rounds are not slower at k = 17, 32 and 64 (profiles/many_wide.txt: 4 jobs of 32 sequences tie, 8 win)

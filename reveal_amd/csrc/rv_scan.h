@@ -78,13 +78,18 @@ int rv_scan_multi_launch(Workspace &ws, const sa_t *SA, const lcp_t *LCP, int64_
 // kernel cannot decide sets bits in the flag word of its JOB and gets no pick: 1 the reference's own trim_overlap raises, 2 broken chain or a match
 // outside the intervals, 8 twin offsets, 32 more than `cap` candidates, 64 an interval of 2^17 positions or more.  job_begin[q * njobs + j]: where
 // sequence q of job j begins in the text, every row ascending (a job without a q-th sequence: the begin of the next one that has it).  cap: at most
-// RV_PICK_MCHAIN_CAP_MAX (RV_PICK_MCHAIN_CAP lowers it: test hook).
+// RV_PICK_MCHAIN_CAP_MAX (RV_PICK_WCHAIN_CAP_MAX with more than RV_PICK_MCHAIN_KMAX samples; RV_PICK_MCHAIN_CAP lowers either: test hook).
 #define RV_PICK_MCHAIN_CAP_MAX 512
 #define RV_PICK_MCHAIN_WMAX 512        // (rv_pick_multi_chain.hip derives it: 2^17 ranks x 120 pairs do not keep the scores in 32 bits at RV_LEAF_MCHAIN_WMAX)
 #define RV_PICK_MCHAIN_KMAX 16
+// ... and of the kernel's 64-sample form (rv_many's RV_MANY_CHAIN_WIDE_LARGE rounds: more than RV_PICK_MCHAIN_KMAX samples): the cap that keeps 64 coordinates a
+// candidate in LDS, and the weight bound rv_pick_multi_chain.hip derives for 2^17 ranks x 2016 pairs
+#define RV_PICK_WCHAIN_CAP_MAX 256
+#define RV_PICK_WCHAIN_WMAX 128
+#define RV_PICK_WCHAIN_KMAX 64
 struct RvPickMultiChainArgs {
     const sa_t *nodes; int W;
-    int32_t wscore, wpen;                                    // 0 .. RV_PICK_MCHAIN_WMAX
+    int32_t wscore, wpen;                                    // 0 .. RV_PICK_MCHAIN_WMAX (W > RV_PICK_MCHAIN_KMAX: RV_PICK_WCHAIN_WMAX)
     int gcmodel;                                             // 0 sumofpairs, 1 star-avg, 2 star-med
     u32 cap;
     u32 *job_flags; const int64_t *job_begin; int njobs;

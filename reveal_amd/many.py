@@ -9,7 +9,7 @@ inside the same call.  The built-in picker (as `index.align_builtin`) unless `pi
 (schemes.graphmumpicker: trim the overlaps, chain, split on the largest match of the chain) -- what `reveal refine` gets from
 `rem.align` for a bubble, and what `index.set_picker(args)` + `align_builtin` give a stand-alone index of the job.  The shared
 classes below all finish with built-in-picker kernels, so with a picker set none of them takes a job, whatever its switch says:
-without one of the three chain switches the jobs run the ordinary way with the picker in host C++ (`info["ordinary"]`).  With the switch RV_MANY_CHAIN on
+without one of the chain switches the jobs run the ordinary way with the picker in host C++ (`info["ordinary"]`).  With the switch RV_MANY_CHAIN on
 (`align_many(.., chain=True)`, `Batch.option("RV_MANY_CHAIN", 1)` or the environment variable; off by default, and it means
 something with a picker only) the pair jobs of at most 2048 ranks share their launches all the same, finished by the leaf kernel
 with the picker's decision for two samples as its pick stage (csrc/rv_leaf_chain.hip), when the options leave the picker nothing a
@@ -31,7 +31,7 @@ default, independent of every other switch, and it means something with a picker
 their launches under the picker too, in rounds of their own: layout and index build of the small RV_MANY_WIDE rounds and one launch of the 64-sample
 form of the same kernel (a wavefront holds one predecessor of a chain step, a lane per path; the gap costs over up to 64 paths by reductions over the
 wavefront), under the same conditions (`takes_shared_launch(.., picker=args, chain_wide=True)`); flagged jobs as above.  Under a picker the jobs of
-17 .. 64 sequences above 2048 ranks and the jobs of more than 64 sequences always run the ordinary way.  The results do not depend on the switch.
+more than 64 sequences always run the ordinary way.  The results do not depend on the switch.
 
 With the switch RV_MANY_CHAIN_LARGE on (`align_many(.., chain_large=True)`, `Batch.option("RV_MANY_CHAIN_LARGE", 1)` or the environment variable; off by
 default, independent of every other switch, and it means something with a picker only) the pair jobs of 2049 .. min(RV_MANY_LARGE_MAX, 2^17) ranks share
@@ -51,7 +51,17 @@ decision for up to 16 samples (csrc/rv_pick_multi_chain.hip: a wavefront per sub
 child) in place of the longest-match kernels -- when trim is on, minlength > 0, the weights are 0 .. 512, no match can reach seedsize and maxmums is at
 least the job's ranks (`takes_shared_launch(.., picker=args, chain_large_multi=True)`): `rem.align`'s default maxmums of 10 000 admits jobs of up to
 10 000 ranks only.  A call with fewer than RV_MANY_CHAIN_LARGE_MULTI_MIN such jobs (default 4) leaves them on the ordinary path; a flagged job runs the
-ordinary way inside the same call.  Jobs of 17 .. 64 sequences above 2048 ranks stay ordinary under a picker.  The results do not depend on the switch.
+ordinary way inside the same call.  The results do not depend on the switch.
+
+With the switch RV_MANY_CHAIN_WIDE_LARGE on (`align_many(.., chain_wide_large=True)`, `Batch.option("RV_MANY_CHAIN_WIDE_LARGE", 1)` or the environment
+variable; off by default, independent of every other switch, and it means something with a picker only) the jobs of 17 .. 64 sequences and 2049 ..
+min(RV_MANY_LARGE_MAX, 2^17) ranks -- the bubbles of a graph of 25 or 100 genomes with alleles above about 60 bases -- share their launches under the
+picker too, in rounds of their own: the rounds of RV_MANY_CHAIN_LARGE_MULTI with up to 64 samples, the pick of every sub-index made by the 64-sample form
+of the same kernel (a lane per sample, one predecessor a chain step, 64-bit sample sets, up to 256 candidates a sub-index) -- when trim is on,
+minlength > 0, the weights are 0 .. 128, no match can reach seedsize and maxmums is at least the job's ranks
+(`takes_shared_launch(.., picker=args, chain_wide_large=True)`).  A call with fewer than RV_MANY_CHAIN_WIDE_LARGE_MIN such jobs (default 2) leaves them on
+the ordinary path; a flagged job (more than 256 candidates in one sub-index, or where the reference's trim_overlap raises) runs the ordinary way inside
+the same call.  The results do not depend on the switch.
 
 Jobs of three and more sequences -- a bubble of a graph of N genomes carries up to N -- run the ordinary way unless the switch
 RV_MANY_MULTI is on (`align_many(.., multi=True)`, `Batch.option("RV_MANY_MULTI", 1)` or the environment variable; off by default).
@@ -103,6 +113,8 @@ LARGE_MAX = 1 << 17        # default of RV_MANY_LARGE_MAX: ranks of the largest 
 CHAIN_LARGE_RANKS = 1 << 17  # RV_PICK_CHAIN_RANKS: ranks of the largest pair job RV_MANY_CHAIN_LARGE takes, whatever RV_MANY_LARGE_MAX says (17-bit positions)
 CHAIN_LARGE_MULTI_WMAX = 512  # RV_PICK_MCHAIN_WMAX: weights up to this keep the chain's scores in 32 bits over up to 16 paths of a job of 2^17 ranks (csrc/rv_pick_multi_chain.hip)
 CHAIN_LARGE_MULTI_MIN = 4  # default of RV_MANY_CHAIN_LARGE_MULTI_MIN: fewer admitted jobs of 3 .. 16 sequences above 2048 ranks in a call under a picker stay ordinary
+CHAIN_WIDE_LARGE_WMAX = 128  # RV_PICK_WCHAIN_WMAX: the same over up to 64 paths (2016 pairs) of a job of 2^17 ranks: 256 does not hold (csrc/rv_pick_multi_chain.hip)
+CHAIN_WIDE_LARGE_MIN = 2   # default of RV_MANY_CHAIN_WIDE_LARGE_MIN: fewer admitted jobs of 17 .. 64 sequences above 2048 ranks in a call under a picker stay ordinary
 CHAIN_LARGE_MIN = 4        # default of RV_MANY_CHAIN_LARGE_MIN: fewer admitted pair jobs above 2048 ranks in a call under a picker stay ordinary
 
 
@@ -146,7 +158,7 @@ def picker_struct(args):
 
 
 def takes_shared_launch(seqs, multi=False, large=False, large_max=LARGE_MAX, large_multi=False, wide=False, picker=None, chain=False, minlength=20,
-                        chain_multi=False, chain_wide=False, chain_large=False, chain_large_multi=False):
+                        chain_multi=False, chain_wide=False, chain_large=False, chain_large_multi=False, chain_wide_large=False):
     """whether the library builds and finishes this job in the shared launches; multi: with RV_MANY_MULTI on; large: with RV_MANY_LARGE
     on and RV_MANY_LARGE_MAX = large_max (in a call with at least RV_MANY_LARGE_MIN such jobs, and with rounds that hold the job);
     large_multi: with RV_MANY_LARGE_MULTI on (in a call with at least RV_MANY_LARGE_MULTI_MIN such jobs, and with rounds that hold the job);
@@ -157,17 +169,22 @@ def takes_shared_launch(seqs, multi=False, large=False, large_max=LARGE_MAX, lar
     (csrc/rv_many.hip many_chain_wide_admits); chain_large: with RV_MANY_CHAIN_LARGE on -- under a picker, the pair jobs of 2049 .. min(large_max, 2^17)
     ranks (csrc/rv_many.hip many_chain_large_admits), in a call with at least RV_MANY_CHAIN_LARGE_MIN such jobs and with rounds that hold the job;
     chain_large_multi: with RV_MANY_CHAIN_LARGE_MULTI on -- under a picker, the jobs of 3 .. 16 sequences and 2049 .. min(large_max, 2^17) ranks
-    (csrc/rv_many.hip many_chain_large_multi_admits), in a call with at least RV_MANY_CHAIN_LARGE_MULTI_MIN such jobs and with rounds that hold the job"""
+    (csrc/rv_many.hip many_chain_large_multi_admits), in a call with at least RV_MANY_CHAIN_LARGE_MULTI_MIN such jobs and with rounds that hold the job;
+    chain_wide_large: with RV_MANY_CHAIN_WIDE_LARGE on -- under a picker, the jobs of 17 .. 64 sequences and 2049 .. min(large_max, 2^17) ranks
+    (csrc/rv_many.hip many_chain_wide_large_admits: the same rule with a weight bound of 128), in a call with at least RV_MANY_CHAIN_WIDE_LARGE_MIN such jobs
+    and with rounds that hold the job"""
     k = len(seqs)
     ranks = sum(len(s) for s in seqs) + k
     if any(b"\0" in s for s in seqs):
         return False
     if picker is not None:
         A = picker_struct(picker)
-        if ranks > LEAF_RANKS and 3 <= k <= MULTI_KMAX:
-            if not chain_large_multi or ranks > min(int(large_max), CHAIN_LARGE_RANKS):
+        if ranks > LEAF_RANKS and 3 <= k <= WIDE_KMAX:
+            # (csrc/rv_many.hip many_chain_large_k_admits: one rule, the switch and the weight bound by the number of sequences)
+            on, wmax = (chain_large_multi, CHAIN_LARGE_MULTI_WMAX) if k <= MULTI_KMAX else (chain_wide_large, CHAIN_WIDE_LARGE_WMAX)
+            if not on or ranks > min(int(large_max), CHAIN_LARGE_RANKS):
                 return False
-            return bool(A.trim and int(minlength) > 0 and 0 <= A.wscore <= CHAIN_LARGE_MULTI_WMAX and 0 <= A.wpen <= CHAIN_LARGE_MULTI_WMAX
+            return bool(A.trim and int(minlength) > 0 and 0 <= A.wscore <= wmax and 0 <= A.wpen <= wmax
                         and (A.seedsize <= 0 or A.seedsize > max(len(s) for s in seqs)) and (A.maxmums <= 0 or A.maxmums >= ranks))
         if ranks > LEAF_RANKS:
             if not chain_large or k != 2 or ranks > min(int(large_max), CHAIN_LARGE_RANKS):
@@ -266,7 +283,8 @@ class Batch:
                 self.option(name, iv)
         for name in ("RV_MANY_KEEP", "RV_MANY_ROUND", "RV_MANY_WAVE_MAX", "RV_MANY_MULTI", "RV_MANY_LARGE", "RV_MANY_LARGE_MAX", "RV_MANY_LARGE_MIN",
                      "RV_MANY_LARGE_MULTI", "RV_MANY_LARGE_MULTI_MIN", "RV_MANY_WIDE", "RV_MANY_WIDE_LARGE_MIN", "RV_MANY_CHAIN", "RV_MANY_CHAIN_MULTI", "RV_MANY_CHAIN_WIDE",
-                     "RV_MANY_CHAIN_LARGE", "RV_MANY_CHAIN_LARGE_MIN", "RV_MANY_CHAIN_LARGE_MULTI", "RV_MANY_CHAIN_LARGE_MULTI_MIN"):
+                     "RV_MANY_CHAIN_LARGE", "RV_MANY_CHAIN_LARGE_MIN", "RV_MANY_CHAIN_LARGE_MULTI", "RV_MANY_CHAIN_LARGE_MULTI_MIN",
+                     "RV_MANY_CHAIN_WIDE_LARGE", "RV_MANY_CHAIN_WIDE_LARGE_MIN"):
             v = os.environ.get(name)
             if v is not None and v.strip():
                 self.option(name, int(v))
@@ -314,6 +332,14 @@ class Batch:
         self._dll.rv_many_info(self._m, o)
         return dict(jobs=int(o[0]), shared=int(o[1]), ordinary=int(o[2]), rounds=int(o[3]), launches=int(o[4]))
 
+    def flagged(self):
+        """-> {bit: jobs}: the jobs of the last run a round under a picker gave back to the ordinary path, by the bits of their flag words (1 trim_overlap
+        raises in the reference, 2 a broken chain, 8 twin offsets, 16 the RV_MANY_CHAIN_FLAG hook, 32 more candidates than a kernel's cap, 64 an interval
+        of 2^17 positions, 128 the host's picker gave up); bits no job set are left out"""
+        o = (ctypes.c_int64 * 8)()
+        self._dll.rv_many_flagged(self._m, o)
+        return {1 << b: int(o[b]) for b in range(8) if o[b]}
+
     def run(self, minlength=20, minn=2):
         st = _lib.RvAlignStats()
         if self._dll.rv_many_run(self._m, int(minlength), int(minn), ctypes.byref(st)) != 0:
@@ -349,7 +375,7 @@ class Batch:
 
 
 def align_many(jobs, minlength=20, minn=2, sa64=False, toupper=True, batch=None, multi=None, large=None, large_multi=None, wide=None, picker=None, chain=None,
-               chain_multi=None, chain_wide=None, chain_large=None, chain_large_multi=None):
+               chain_multi=None, chain_wide=None, chain_large=None, chain_large_multi=None, chain_wide_large=None):
     """jobs: a list of jobs, each a list of (name, seq) or of plain sequences (two or more, none empty; every sequence is a sample
     of its own, like the inputs of `reveal rem`).  -> (results, info): results[j] = dict(anchors=[(l, (pos, ..)), ..], T=final text
     `s0$s1$..` lower-cased where aligned), positions in the coordinates of the job's own text -- what index.align_builtin gives a
@@ -366,7 +392,8 @@ def align_many(jobs, minlength=20, minn=2, sa64=False, toupper=True, batch=None,
     same for RV_MANY_CHAIN_MULTI (with a picker: the jobs of 3 .. 16 sequences and at most 2048 ranks through the shared launches), `chain_wide`: the
     same for RV_MANY_CHAIN_WIDE (with a picker: the jobs of 17 .. 64 sequences and at most 2048 ranks through the shared launches), `chain_large`: the
     same for RV_MANY_CHAIN_LARGE (with a picker: the pair jobs of 2049 .. 2^17 ranks through the shared launches), `chain_large_multi`: the same for
-    RV_MANY_CHAIN_LARGE_MULTI (with a picker: the jobs of 3 .. 16 sequences and 2049 .. 2^17 ranks through the shared launches)."""
+    RV_MANY_CHAIN_LARGE_MULTI (with a picker: the jobs of 3 .. 16 sequences and 2049 .. 2^17 ranks through the shared launches), `chain_wide_large`: the
+    same for RV_MANY_CHAIN_WIDE_LARGE (with a picker: the jobs of 17 .. 64 sequences and 2049 .. 2^17 ranks through the shared launches)."""
     if isinstance(jobs, (str, bytes, bytearray)) or not hasattr(jobs, "__iter__"):
         raise error("jobs is a list of jobs")
     if int(minlength) < 0 or int(minn) < 2:
@@ -386,6 +413,8 @@ def align_many(jobs, minlength=20, minn=2, sa64=False, toupper=True, batch=None,
         b.option("RV_MANY_CHAIN_LARGE", 1 if chain_large else 0)
     if chain_large_multi is not None:
         b.option("RV_MANY_CHAIN_LARGE_MULTI", 1 if chain_large_multi else 0)
+    if chain_wide_large is not None:
+        b.option("RV_MANY_CHAIN_WIDE_LARGE", 1 if chain_wide_large else 0)
     if multi is not None:
         b.option("RV_MANY_MULTI", 1 if multi else 0)
     if large is not None:

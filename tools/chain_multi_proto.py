@@ -14,8 +14,16 @@ the kernel.  That form holds ONE predecessor of a chain step per wavefront where
 ascending sort order, the step of activation is the match at which a predecessor first ends in front, and the choice is the maximum of the one key,
 whatever the order the candidates are looked at in.  What it does differently is the gap cost over up to 64 paths, and `gapcost_lanes` restates that
 arithmetic lane by lane -- a lane per sample, the set's paths taken in turn, two sums per lane, wave sums with the lanes outside the set contributing
-zero -- and is what the picker uses under `--cases wide` (tests/test_cpu_many_chain_wide.py also holds it against `gapcost` on random gaps with ties)."""
+zero -- and is what the picker uses under `--cases wide` (tests/test_cpu_many_chain_wide.py also holds it against `gapcost` on random gaps with ties).
+
+`--cases wide_large`: the same over tests/many_chain_wide_large_cases.py and tests/golden/many_chain_wide_large.json -- jobs of 17 .. 64 sequences above
+2048 ranks, the 64-sample form of k_pick_multi_chain (csrc/rv_pick_multi_chain.hip).  Its chain step is the 64-lane one (`gapcost_lanes`); what it adds
+is restated here as well: the sample of a member by binary search over the ascending begins of the sub-index' live intervals, a coordinate as position
+(17 bits) | sample << 17 (six bits) whose order is the order of the text, sample sets as 64-bit words, and the cap of 256 candidates -- the matches in
+every sample, all of the list where there is none -- above which the kernel flags the job (give-up 32).  The job whose positions need 17 bits runs too,
+under its own set."""
 import argparse
+import bisect
 import os
 import sys
 
@@ -62,7 +70,10 @@ def gapcost_lanes(d_by_sample, model, lanes=64):
     return sum(acc)
 
 
-def make_picker(seqs, args, stat, orig, wide=False):
+POS_BITS, WIDE_CAP = 17, 256      # MultiPickStage<64>: bits of a position inside its interval; RV_PICK_WCHAIN_CAP_MAX
+
+
+def make_picker(seqs, args, stat, orig, wide=False, large=False):
     ends, at = [], 0
     for s in seqs:
         at += len(s) + 1
@@ -84,6 +95,29 @@ def make_picker(seqs, args, stat, orig, wide=False):
         iv = {sample_of(b): (b, e) for b, e in (tuple(x) for x in idx.nodes)}
         ns = idx.nsamples
         cand = [[m[0], [p for _, p in m[2]], 0] for m in mums]               # l, members in the order handed out, shift
+        if large:
+            # the 64-sample form of k_pick_multi_chain: what counts against the cap, the sample of a member by binary search over the live begins, the
+            # packed coordinate and the 64-bit sample set
+            full = sum(1 for c in cand if len(c[1]) == ns)
+            if (full if full else len(cand)) > WIDE_CAP:
+                return give_up(self, 32, mums, idx, minlength)
+            lsmp = sorted(iv, key=lambda s: iv[s][0])
+            lbeg = [iv[s][0] for s in lsmp]
+            assert lsmp == sorted(lsmp), "the live intervals ascend with their samples: the text is sample-major"
+
+            def packed(p, l):
+                s = lsmp[bisect.bisect_right(lbeg, p) - 1]
+                assert s == sample_of(p) and iv[s][0] <= p and p + l <= iv[s][1] and s < 64 and p - iv[s][0] < 1 << POS_BITS
+                return (s << POS_BITS) | (p - iv[s][0])
+            for l, mem, _ in cand:
+                crd = [packed(p, l) for p in mem]
+                assert [c >> POS_BITS for c in crd] == [sample_of(p) for p in mem]
+                assert sorted(range(len(mem)), key=lambda q: crd[q]) == sorted(range(len(mem)), key=lambda q: mem[q])      # the order of the text
+                word = 0
+                for c in crd:
+                    assert not (word >> (c >> POS_BITS)) & 1
+                    word |= 1 << (c >> POS_BITS)
+                assert word < 1 << 64
         masks = [frozenset(sample_of(p) for p in c[1]) for c in cand]
         if any(len(c[1]) == ns for c in cand):
             want = frozenset(iv)
@@ -186,10 +220,49 @@ def make_picker(seqs, args, stat, orig, wide=False):
     return picker
 
 
+def run_wide_large(refmod, sets=None, which=None, big=True, out=None):
+    """the prototype over tests/many_chain_wide_large_cases.py: sets (names, default: all), which (job indices, default: all), big (the job whose
+    positions need 17 bits, under its own set) -> (jobs that differ from the golden file, give-ups by bit)"""
+    import many_chain_wide_large_cases as cw
+    from reveal_amd import schemes
+    jobs, golden = cw.jobs(), cw.load_golden()
+    orig = schemes.GraphPicker.graphmumpicker
+    todo = [(name, kw, j, jobs[j][1], golden[name][j]) for name, kw in cw.SETS if sets is None or name in sets
+            for j in (range(len(jobs)) if which is None else which)]
+    if big:
+        todo.append((cw.BIG_SET[0], cw.BIG_SET[1], -1, cw.big_job(), golden["big"][0]))
+    bad, gave_up = [], {}
+    for name, kw, j, seqs, want in todo:
+        stat = {}
+        schemes.GraphPicker.graphmumpicker = make_picker([s.upper() for s in seqs], cw.picker_args(kw), stat, orig, wide=True, large=True)
+        try:
+            an, T = cw.rem_align_job(seqs, indexmod=refmod, **kw)
+        finally:
+            schemes.GraphPicker.graphmumpicker = orig
+        if (an, cw.sha(T)) != want:
+            bad.append((name, j))
+        for k, v in stat.items():
+            if k not in ("calls", "shared"):
+                gave_up[k] = gave_up.get(k, 0) + v
+        if out:
+            print("%-9s job %3d: %s, picker calls %d, gave up: %s" % (name, j, "differs" if (name, j) in bad else "equal", stat.get("calls", 0),
+                  {k: v for k, v in stat.items() if k not in ("calls", "shared")} or "never"), file=out)
+    return bad, gave_up
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("--cases", choices=("multi", "wide"), default="multi", help="multi: jobs of 3 .. 16 sequences (many_chain_multi_cases); wide: 17 .. 64 (many_chain_wide_cases)")
+    ap.add_argument("--cases", choices=("multi", "wide", "wide_large"), default="multi",
+                    help="multi: jobs of 3 .. 16 sequences (many_chain_multi_cases); wide: 17 .. 64 (many_chain_wide_cases); wide_large: 17 .. 64 above 2048 ranks (many_chain_wide_large_cases)")
     opt = ap.parse_args()
+    if opt.cases == "wide_large":
+        import pin_oracle
+        refmod = pin_oracle.load_refmod(False)
+        if refmod is None:
+            sys.exit("oracle/_ref/reveallib.so is not built: make -C oracle && make -C oracle refmod")
+        bad, gave_up = run_wide_large(refmod, out=sys.stdout)
+        print("%d results differ from the golden file; gave up: %s" % (len(bad), gave_up or "never"))
+        sys.exit(1 if bad else 0)
     if opt.cases == "wide":
         import many_chain_wide_cases as cm
         matches = lambda rec, an, T: cm.same(rec, an, cm.sha(T))

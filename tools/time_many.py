@@ -4,7 +4,7 @@
     python tools/time_many.py [--jobs 10000] [--lmin 50] [--lmax 1000] [--reps 5] [--minlength 20] [--wave-max N] [--only loop|many] [--check]
                               [--seqs K] [--multi 0|1|ab] [--large 0|1|ab] [--large-multi 0|1|ab] [--large-max R] [--large-min J]
                               [--wide 0|1|ab] [--wide-large-min J] [--no-cut] [--sites] [--picker [--rem-jobs N]]
-                              [--chain-wide [--save-digests FILE] [--compare-digests FILE]]
+                              [--chain-wide [--save-digests FILE] [--compare-digests FILE]] [--chain-wide-large [--chain-wide-large-min J]]
 
 Workload: J jobs of 2 x L bases, L uniform in lmin .. lmax, 1 % substitutions.  The two sides run alternately, `reps` times each:
   loop   rv_reset, rv_add_sample / rv_add_sequence x 2, rv_construct, rv_align_builtin, rv_fetch_anchors, the text -- per job, straight at
@@ -41,6 +41,10 @@ ordinary side alone is timed, on the same jobs: the yardstick.
 ranks / sequences so that all are admitted): the same for jobs of K sequences above 2048 ranks -- RV_MANY_CHAIN_LARGE_MULTI on (the multi-sample level pipeline
 with the picker's decision made by k_pick_multi_chain), off (the ordinary path), and the built-in picker with RV_MANY_LARGE_MULTI on (the same rounds with the
 longest-match kernels).  --chain-large-multi-min J sets RV_MANY_CHAIN_LARGE_MULTI_MIN.
+--chain-wide-large (with --seqs K, K = 17 .. 64; implies --picker and --no-cut; use --sites, --lmin / --lmax so that the jobs lie above 2048 ranks, and --maxmums /
+--seedsize above their ranks / sequences): the same for jobs of K sequences above 2048 ranks -- RV_MANY_CHAIN_WIDE_LARGE on (the 64-sample form of
+k_pick_multi_chain), off (the ordinary path), and the built-in picker with RV_MANY_WIDE on (the same rounds with the longest-match kernels).
+--chain-wide-large-min J sets RV_MANY_CHAIN_WIDE_LARGE_MIN.  The chain side also prints the jobs it gave back by the bits of their flag words (Batch.flagged).
 The chain side's info["ordinary"] is the number of jobs the kernel flagged.  --save-digests FILE writes a digest per job of the picker side's anchors (the chain side, or
 the ordinary side where the build has none); --compare-digests FILE counts the jobs whose digest differs from that file's: two builds run in a process
 each, and this is how their results are compared."""
@@ -202,6 +206,8 @@ def main_picker(a, jobs, bases):
         switch = "RV_MANY_CHAIN_LARGE"
     if a.chain_large_multi:
         switch = "RV_MANY_CHAIN_LARGE_MULTI"
+    if a.chain_wide_large:
+        switch = "RV_MANY_CHAIN_WIDE_LARGE"
     for name, pk, chain in (("chain", args, 1), ("ordinary", args, 0), ("builtin", None, 0)):
         b = many.Batch(False)
         b.set_picker(pk)
@@ -218,6 +224,10 @@ def main_picker(a, jobs, bases):
             b.option("RV_MANY_LARGE_MULTI_MIN", 1)
         if a.chain_large_multi and chain and a.chain_large_multi_min is not None:
             b.option("RV_MANY_CHAIN_LARGE_MULTI_MIN", a.chain_large_multi_min)
+        if a.chain_wide_large and pk is None:
+            b.option("RV_MANY_WIDE_LARGE_MIN", 1)
+        if a.chain_wide_large and chain and a.chain_wide_large_min is not None:
+            b.option("RV_MANY_CHAIN_WIDE_LARGE_MIN", a.chain_wide_large_min)
         if a.chain_large and pk is None:
             b.option("RV_MANY_LARGE", 1)
         if a.chain_large and chain and a.chain_large_min is not None:
@@ -258,6 +268,9 @@ def main_picker(a, jobs, bases):
         print(json.dumps(out))
         return 1 if out.get("digest_bad_jobs") else 0
     out["flagged"] = out["chain_info"]["ordinary"]
+    if hasattr(sides["chain"]["batch"], "flagged"):
+        out["flagged_by_bit"] = sides["chain"]["batch"].flagged()
+        print("flagged: %d jobs of the chain side went back to the ordinary path; by bit of their flag words: %r" % (out["flagged"], out["flagged_by_bit"] or "none"))
     out["chain_vs_rem"] = out["rem_per_job_s"] / (out["chain_median_s"] / a.jobs)
     out["ordinary_vs_chain"] = out["ordinary_median_s"] / out["chain_median_s"]
     out["chain_vs_builtin"] = out["chain_median_s"] / out["builtin_median_s"]
@@ -310,12 +323,19 @@ def main():
     ap.add_argument("--chain-large-min", type=int, default=None, help="RV_MANY_CHAIN_LARGE_MIN")
     ap.add_argument("--chain-large-multi", action="store_true", help="--picker for jobs of --seqs K = 3 .. 16 sequences above 2048 ranks: RV_MANY_CHAIN_LARGE_MULTI on / off, the built-in picker with RV_MANY_LARGE_MULTI")
     ap.add_argument("--chain-large-multi-min", type=int, default=None, help="RV_MANY_CHAIN_LARGE_MULTI_MIN")
+    ap.add_argument("--chain-wide-large", action="store_true", help="--picker for jobs of --seqs K = 17 .. 64 sequences above 2048 ranks: RV_MANY_CHAIN_WIDE_LARGE on / off, the built-in picker with RV_MANY_WIDE")
+    ap.add_argument("--chain-wide-large-min", type=int, default=None, help="RV_MANY_CHAIN_WIDE_LARGE_MIN")
     ap.add_argument("--maxmums", type=int, default=10000, help="--picker: the picker's maxmums (rem.align's default)")
     ap.add_argument("--seedsize", type=int, default=10000, help="--picker: the picker's seedsize (rem.align's default)")
     ap.add_argument("--save-digests", default=None, help="--picker: write a digest per job of the picker side's anchors to this file")
     ap.add_argument("--compare-digests", default=None, help="--picker: count the jobs whose digest differs from this file's")
     a = ap.parse_args()
-    if a.chain_wide:
+    if a.chain_wide_large:
+        if not 17 <= a.seqs <= 64:
+            ap.error("--chain-wide-large times jobs of 17 .. 64 sequences: --seqs K")
+        a.picker = True
+        a.no_cut = True
+    elif a.chain_wide:
         if not 17 <= a.seqs <= 64:
             ap.error("--chain-wide wants jobs of 17 .. 64 sequences: --seqs K")
         a.picker = True
