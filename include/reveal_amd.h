@@ -568,7 +568,26 @@ void rv_batch_free(rv_batch *b);
  *                   same for the jobs of 17 .. 64 sequences above 2048 ranks named above), RV_MANY_CHAIN_WIDE_LARGE_MIN (fewer such jobs than this in a call stay
  *                   ordinary, default 2), RV_MANY_CHAIN_FLAG (test hook: every n-th job of such a round is treated as flagged by the kernel --
  *                   dropped from the round and run the ordinary way; 0: off); any other name: rv_set_option on the internal handles
- *   rv_many_arrays  test hook: which = RV_SA / RV_LCP of a shared-launch job in job-local positions, native element width; -2: not kept */
+ *   rv_many_arrays  test hook: which = RV_SA / RV_LCP of a shared-launch job in job-local positions, native element width; -2: not kept
+ * Match lists instead of a finished recursion (what `reveal chain --recurse` asks of a fresh index per gap, reveal/chain.py:102-112, 214-224): rv_many_scan
+ * gives every job of rv_many_add the list rv_getmums / rv_getmultimums give a stand-alone index of its sequences, in that index' coordinates and emission
+ * order.  Text and jobs are untouched, so a scan and a run may follow each other on the same jobs; the LIVE result is the last call's: rv_many_scan
+ * invalidates anchors and texts, rv_many_run invalidates matches, and rv_many_anchor_count / rv_many_fetch / rv_many_text on the one side,
+ * rv_many_match_count / rv_many_fetch_matches on the other return -1 with an error text when the other kind is live.  rv_many_info reports the last call
+ * of either kind.  Shared launches take every job of 2 .. 64 sequences, at most 2048 ranks and no NUL byte, with no switch: every such job contiguous in
+ * the round's text (pair jobs too), the index build of rv_many_run's small rounds, then a count pass, an exclusive sum and a write pass flat over the ranks
+ * of the round (rv_many_scan.hip) -- out[4] counts the two or one launches of the build, the count pass, the 1 / 3 / 5 of the sum (by the round's ranks:
+ * up to 2048, up to 2^22, above), one for the jobs' firsts, and the write pass when there is a match.  Every other job -- more than 2048 ranks, more than
+ * 64 sequences, a NUL byte -- runs the ordinary way inside the call (rv_reset, construct, rv_getmums / rv_getmultimums on the internal handle); the
+ * results do not depend on the path.  Jobs above 2048 ranks on the segmented build of the large rounds are a follow-up: the kernels take segments plus a
+ * table of sequence begins, which those rounds have.  RV_MANY_ROUND (a round of a scan holds 2^26 ranks at most), RV_MANY_WAVE_MAX and RV_MANY_KEEP act
+ * as in rv_many_run.
+ *   rv_many_scan    kind 0: getmums(minl) -- sample 0 against the rest for a job of more than two sequences, minn unused; kind 1: getmultimums(minl,
+ *                   minn) -- on a job of two sequences (where rv_getmultimums refuses the index) the same intervals, i.e. getmums' records with their
+ *                   members in SA order; kind 2: getmums for the jobs of two sequences, getmultimums for the rest.  minl 0 is minl 1 (a match has l > 0)
+ *   rv_many_match_count -> matches of all jobs; first[0 .. jobs] (may be NULL): job j owns the matches first[j] .. first[j+1]; *members: all positions
+ *   rv_many_fetch_matches  l[k], n[k], off[k .. k+1] -> so[], pos[]: the layout of rv_fetch_multi; a getmums record has n = 2, members (0, a), (sample of b, b)
+ *   RV_MANY_SCAN_ORDINARY (rv_many_option, test hook and A/B leg): 1 sends every job of a scan the ordinary way */
 typedef struct rv_many rv_many;
 rv_many *rv_many_new(int device);       /* NULL on failure */
 void rv_many_free(rv_many *m);
@@ -577,6 +596,9 @@ int rv_many_set_picker(rv_many *m, int kind, const rv_picker_args *args);
 int64_t rv_many_add(rv_many *m, const char *const *seqs, const int64_t *lens, int k);
 int rv_many_clear(rv_many *m);
 int rv_many_run(rv_many *m, int minl, int minn, rv_align_stats *total);
+int rv_many_scan(rv_many *m, int minl, int minn, int kind);
+int64_t rv_many_match_count(rv_many *m, int64_t *first, int64_t *members);
+int rv_many_fetch_matches(rv_many *m, uint32_t *l, int32_t *n, int64_t *off, uint16_t *so, int64_t *pos);
 int64_t rv_many_anchor_count(rv_many *m, int64_t *first, int64_t *members);
 int rv_many_fetch(rv_many *m, uint32_t *l, int64_t *off, int64_t *pos);
 int64_t rv_many_text(rv_many *m, int64_t job, char *out, int64_t cap);

@@ -178,6 +178,9 @@ SYMBOLS = {
     "rv_many_add": (_L, [V, V, V, _I]),
     "rv_many_clear": (_I, [V]),
     "rv_many_run": (_I, [V, _I, _I, ctypes.POINTER(RvAlignStats)]),
+    "rv_many_scan": (_I, [V, _I, _I, _I]),
+    "rv_many_match_count": (_L, [V, V, c_i64p]),
+    "rv_many_fetch_matches": (_I, [V, V, V, V, V, V]),
     "rv_many_anchor_count": (_L, [V, V, c_i64p]),
     "rv_many_fetch": (_I, [V, V, V, V]),
     "rv_many_text": (_L, [V, _L, V, _L]),

@@ -84,6 +84,11 @@
 // their own, from RV_MANY_CHAIN_WIDE_LARGE_MIN such jobs in a call on: the rounds of RV_MANY_CHAIN_LARGE_MULTI with kmax = RV_MANY_WIDE_KMAX
 // (many_round_large_multi with `redo`), every sub-index picked by the 64-sample form of k_pick_multi_chain.  That form holds 256 candidates a sub-index, not
 // 512, and its weight bound is 128: a sub-index with more flags its job (32), which finishes on the ordinary path.  Jobs of more than 64 sequences stay ordinary.
+// rv_many_scan: the MUM / multi-MUM lists of every job instead of a finished recursion (many_scan below; the kernels are rv_many_scan.hip's).  Every clean job
+// of 2 .. RV_MANY_WIDE_KMAX sequences and at most RV_LEAF_N ranks goes through rounds of its own kind (many_round_scan): the job-contiguous layout of
+// many_round_multi for every k, k_many_build as it is, then a count pass, an exclusive sum and a write pass flat over the ranks of the round.  No switch, no
+// threshold.  The other jobs run rv_getmums / rv_getmultimums on the internal handle.  A scan does not touch the jobs or their text; `ran` and `scanned` say
+// which result is live.
 // Size classes (DESIGN.md "Many small alignments" has the measurements): up to `wave_max` ranks (default 512) a wavefront per job,
 // four jobs per workgroup, no workgroup barrier; above, a workgroup of 256 threads per job.  Both hold 22.6 KB of LDS per workgroup:
 // seven workgroups per CU.
@@ -91,6 +96,7 @@
 #include "rv_leaf.h"
 #include "rv_leaf_multi.h"
 #include "rv_many_large.h"
+#include "rv_many_scan.h"
 #include <algorithm>
 #include <limits.h>
 #include <new>
@@ -262,6 +268,7 @@ struct ManyJob {
     int64_t arr_off = -1;                  // RV_MANY_KEEP: SA / LCP in keep_sa / keep_lcp
 };
 struct ManyRec { int job; u32 l; int np; int64_t p0; };
+struct ManyScanSlice { int64_t rec0 = 0, nrec = 0, mem0 = 0, nmem = 0; };      // a job's matches in the scratch of a scan
 
 }  // namespace
 
@@ -299,6 +306,15 @@ struct rv_many {
     RvManyLargeBufs large_bufs;                      // rounds of large pair jobs: the scratch of their index build
     // scratch of a run
     std::vector<ManyRec> recs; std::vector<int64_t> rpos;
+    // rv_many_scan: at most one of `ran` and `scanned` is set -- the live result is the last call's
+    int64_t scan_ordinary = 0;                  // RV_MANY_SCAN_ORDINARY
+    bool scanned = false;
+    std::vector<int64_t> mt_first, mt_off, mt_pos;
+    std::vector<u32> mt_l; std::vector<int32_t> mt_n; std::vector<uint16_t> mt_so;
+    DBuf dScanTab, dScanCnt, dScanFirst, dScanOut;
+    // scratch of a scan: the lists as the rounds and the ordinary path deliver them, and every job's slice of them
+    std::vector<ManyScanSlice> sc_job;
+    std::vector<u32> sc_l; std::vector<int32_t> sc_n; std::vector<uint16_t> sc_so; std::vector<int64_t> sc_pos;
 };
 
 namespace {
@@ -993,7 +1009,8 @@ int many_ordinary(rv_many *m, int job, int minl, int minn, rv_align_stats *total
 
 int many_run(rv_many *m, int minl, int minn, rv_align_stats *total) {
     RV_HIP(hipSetDevice(m->device));
-    m->ran = false;
+    m->ran = false; m->scanned = false;
+    m->mt_first.clear(); m->mt_l.clear(); m->mt_n.clear(); m->mt_off.clear(); m->mt_so.clear(); m->mt_pos.clear();
     m->recs.clear(); m->rpos.clear(); m->out_text.clear(); m->keep_sa.clear(); m->keep_lcp.clear();
     for (int k = 0; k < 5; k++) m->info[k] = 0;
     for (int k = 0; k < 8; k++) m->flagged[k] = 0;
@@ -1154,6 +1171,257 @@ int many_run(rv_many *m, int minl, int minn, rv_align_stats *total) {
     return 0;
 }
 
+// ---- rv_many_scan: the match lists of every job instead of a finished recursion ----
+// The jobs the shared launches take: 2 .. RV_MANY_WIDE_KMAX sequences, at most RV_LEAF_N ranks, no NUL byte (many.takes_shared_scan mirrors it).  No
+// switch and no threshold: the entry is new, nothing that exists is pinned to a count.
+bool many_scan_admits(const rv_many *m, const ManyJob &jb) {
+    return !m->scan_ordinary && jb.k >= 2 && jb.k <= RV_MANY_WIDE_KMAX && jb.clean && jb.ranks <= RV_LEAF_N;
+}
+bool many_scan_pair_kind(int kind, int k) { return kind == 0 || (kind == 2 && k == 2); }
+
+// one round of the scan: the jobs order[lo .. hi) (ascending size), every one contiguous in the round's text as in many_round_multi -- pair jobs too: to
+// k_many_build a job is its first sequence and "the rest", so the side bit of its BWT bytes says "behind the job's first '$'" for every k.  Then the count
+// pass, the sums and the write pass of rv_many_scan.hip over the built segments.  Two copies come back: the sums at the jobs' first ranks with the error
+// words behind them, and the records with the write pass' error word behind them.
+int many_round_scan(rv_many *m, const std::vector<int> &order, size_t lo, size_t hi, int minl, int minn, int kind) {
+    RV_TRY(many_handle(m, &m->hs));
+    rv_index *h = m->hs;
+    const size_t J = hi - lo;
+    int64_t n = 0;
+    size_t nseq = 0, nsmall = 0;
+    for (size_t s = 0; s < J; s++) {
+        const ManyJob &jb = m->jobs[(size_t)order[lo + s]];
+        if (jb.k < 2 || jb.k > RV_MANY_WIDE_KMAX || jb.ranks > CAP_L) { rv_set_error("rv_many_scan: a job of %d sequences and %lld ranks in a shared round", jb.k, (long long)jb.ranks); return -1; }
+        n += jb.ranks; nseq += (size_t)jb.k;
+    }
+    if (n > RV_MANY_SCAN_RANKS) { rv_set_error("rv_many_scan: a round of %lld ranks", (long long)n); return -1; }
+    // the tables of the round in one upload: off[J + 1], beg[nseq] (64 bits) | sfirst[J + 1], loc[nseq] (32 bits)
+    const size_t n64 = J + 1 + nseq, n32 = J + 1 + nseq;
+    std::vector<int64_t> tab(n64 + (n32 + 1) / 2, 0);
+    int64_t *t_off = tab.data(), *t_beg = t_off + J + 1;
+    int32_t *t_sf = (int32_t *)(tab.data() + n64), *t_loc = t_sf + J + 1;
+    std::vector<ManyDevJob> dj(J);
+    std::vector<char> txt((size_t)n);
+    int64_t at = 0;
+    size_t sq = 0;
+    for (size_t s = 0; s < J; s++) {
+        const ManyJob &jb = m->jobs[(size_t)order[lo + s]];
+        const int64_t la = m->lens[jb.seq0];
+        dj[s].abeg = at; dj[s].bbeg = at + la + 1; dj[s].off = at; dj[s].la = (int32_t)la; dj[s].lb = (int32_t)(jb.ranks - la - 2);
+        t_off[s] = at; t_sf[s] = (int32_t)sq;
+        if (jb.ranks <= m->wave_max && jb.ranks <= CAP_S) nsmall = s + 1;      // (ascending sizes: the small class is a prefix)
+        const int64_t job0 = at;
+        for (int q = 0; q < jb.k; q++) {
+            const int64_t len = m->lens[jb.seq0 + (size_t)q];
+            t_beg[sq] = at; t_loc[sq] = (int32_t)(at - job0); sq++;
+            memcpy(txt.data() + at, m->in.data() + m->starts[jb.seq0 + (size_t)q], (size_t)len);
+            txt[(size_t)(at + len)] = '$';
+            at += len + 1;
+        }
+    }
+    t_off[J] = at; t_sf[J] = (int32_t)sq;
+    if (at != n || sq != nseq) { rv_set_error("rv_many_scan: the jobs' ranks do not add up to the text"); return -1; }
+    hipStream_t q = h->ws.stream;
+    const size_t first_bytes = (J + 1) * sizeof(u64), words_bytes = 16;      // words: [0] max LCP, [1] error bits of the build, [2] of the count pass
+    RV_TRY(m->dJobs.reserve(J * sizeof(ManyDevJob)));
+    RV_TRY(m->dScanTab.reserve(tab.size() * sizeof(int64_t)));
+    RV_TRY(m->dTxt.reserve((size_t)n + 64));
+    RV_TRY(m->dSA.reserve((size_t)(n + 64) * sizeof(sa_t)));
+    RV_TRY(m->dLCP.reserve((size_t)(n + 64) * sizeof(lcp_t)));
+    RV_TRY(m->dBWT.reserve((size_t)n + 64));
+    RV_TRY(m->dScanCnt.reserve((size_t)(n + 1) * sizeof(u64)));
+    RV_TRY(m->dScanFirst.reserve(first_bytes + words_bytes));
+    RV_HIP(hipMemcpyAsync(m->dJobs.p, dj.data(), J * sizeof(ManyDevJob), hipMemcpyHostToDevice, q));
+    RV_HIP(hipMemcpyAsync(m->dScanTab.p, tab.data(), tab.size() * sizeof(int64_t), hipMemcpyHostToDevice, q));
+    RV_HIP(hipMemcpyAsync(m->dTxt.p, txt.data(), (size_t)n, hipMemcpyHostToDevice, q));
+    u32 *d_words = (u32 *)((char *)m->dScanFirst.p + first_bytes);
+    RV_HIP(hipMemsetAsync(d_words, 0, words_bytes, q));
+    RV_TRY(many_build(m, q, m->dJobs.as<ManyDevJob>(), J, nsmall, m->dTxt.as<uint8_t>(), d_words, d_words + 1));
+    RvManyScanRound R;
+    R.SA = m->dSA.as<sa_t>(); R.LCP = m->dLCP.as<lcp_t>(); R.BWT = m->dBWT.as<uint8_t>(); R.m = n;
+    R.off = m->dScanTab.as<int64_t>(); R.beg = R.off + J + 1;
+    R.sfirst = (const int32_t *)(m->dScanTab.as<int64_t>() + n64); R.loc = R.sfirst + J + 1;
+    R.njobs = (int)J; R.nbeg = (int)nseq; R.minl = minl; R.minn = minn; R.kind = kind; R.err = d_words + 2;
+    RV_TRY(rv_many_scan_count(h->ws, R, m->dScanCnt.as<u64>(), m->dScanFirst.as<u64>(), &m->info[4]));
+    std::vector<u64> first(J + 3, 0);
+    RV_TRY(rv_read_back(h->ws, first.data(), m->dScanFirst.p, first_bytes + words_bytes));
+    u32 words[4];
+    memcpy(words, first.data() + J + 1, sizeof words);
+    if (words[1]) { rv_set_error("rv_many_scan: the index build refused a job (error bits %u)", words[1]); return -1; }
+    if (words[2]) { rv_set_error("rv_many_scan: the count pass met a descriptor outside the round (error bits %u: 1 job, 2 position)", words[2]); return -1; }
+    const u64 mmask = ((u64)1 << RV_MANY_SCAN_MBITS) - 1;
+    const u64 nrec = first[J] >> RV_MANY_SCAN_MBITS, nmem = first[J] & mmask;
+    if (nrec > (u64)n || nmem > (u64)n * 64) { rv_set_error("rv_many_scan: more records than the round has room for"); return -1; }
+    // records | pos | so | the write pass' error word
+    const size_t o_pos = (size_t)nrec * sizeof(RvManyScanRec), o_so = o_pos + (size_t)nmem * sizeof(u32), o_err = (o_so + (size_t)nmem * sizeof(uint16_t) + 3) & ~(size_t)3;
+    std::vector<u64> out((o_err + 4 + 7) / 8, 0);      // (64-bit words: the records are read in place)
+    std::vector<sa_t> sa; std::vector<lcp_t> lc;
+    if (nrec) {
+        RV_TRY(m->dScanOut.reserve(o_err + 4));
+        char *d_out = (char *)m->dScanOut.p;
+        RV_HIP(hipMemsetAsync(d_out + o_err, 0, 4, q));
+        R.err = (u32 *)(d_out + o_err);
+        RV_TRY(rv_many_scan_write(h->ws, R, m->dScanCnt.as<u64>(), (RvManyScanRec *)d_out, nrec, (uint16_t *)(d_out + o_so), (u32 *)(d_out + o_pos), nmem, &m->info[4]));
+        RV_HIP(hipMemcpyAsync(out.data(), d_out, o_err + 4, hipMemcpyDeviceToHost, q));
+    }
+    if (m->keep) {
+        sa.resize((size_t)n); lc.resize((size_t)n);
+        RV_HIP(hipMemcpyAsync(sa.data(), m->dSA.p, (size_t)n * sizeof(sa_t), hipMemcpyDeviceToHost, q));
+        RV_HIP(hipMemcpyAsync(lc.data(), m->dLCP.p, (size_t)n * sizeof(lcp_t), hipMemcpyDeviceToHost, q));
+    }
+    RV_HIP(hipStreamSynchronize(q));
+    const char *hout = (const char *)out.data();
+    u32 werr = 0;
+    memcpy(&werr, hout + o_err, 4);
+    if (werr) { rv_set_error("rv_many_scan: the write pass did not find what the count pass counted (error bits %u: 1 job, 2 position, 4 room)", werr); return -1; }
+    const RvManyScanRec *rec = (const RvManyScanRec *)hout;
+    const u32 *hpos = (const u32 *)(hout + o_pos);
+    const uint16_t *hso = (const uint16_t *)(hout + o_so);
+    const size_t kbase = m->keep_sa.size();
+    if (m->keep) { m->keep_sa.resize(kbase + (size_t)n); m->keep_lcp.resize(kbase + (size_t)n); }
+    for (size_t s = 0; s < J; s++) {
+        ManyJob &jb = m->jobs[(size_t)order[lo + s]];
+        const u64 r0 = first[s] >> RV_MANY_SCAN_MBITS, r1 = first[s + 1] >> RV_MANY_SCAN_MBITS, m0 = first[s] & mmask, m1 = first[s + 1] & mmask;
+        if (r0 > r1 || r1 > nrec || m0 > m1 || m1 > nmem) { rv_set_error("rv_many_scan: the sums of the round do not increase"); return -1; }
+        ManyScanSlice &sl = m->sc_job[(size_t)order[lo + s]];
+        sl.rec0 = (int64_t)m->sc_l.size(); sl.nrec = (int64_t)(r1 - r0); sl.mem0 = (int64_t)m->sc_pos.size(); sl.nmem = (int64_t)(m1 - m0);
+        u64 mo = m0;
+        for (u64 r = r0; r < r1; r++) {
+            if (rec[r].moff != mo || rec[r].n < 2 || rec[r].n > (u32)jb.k || mo + rec[r].n > m1) { rv_set_error("rv_many_scan: a malformed record"); return -1; }
+            m->sc_l.push_back(rec[r].l); m->sc_n.push_back((int32_t)rec[r].n);
+            for (u32 x = 0; x < rec[r].n; x++) {
+                if (hso[mo + x] >= (uint16_t)jb.k || (int64_t)hpos[mo + x] + rec[r].l > jb.ranks) { rv_set_error("rv_many_scan: a match outside its job"); return -1; }
+                m->sc_so.push_back(hso[mo + x]); m->sc_pos.push_back((int64_t)hpos[mo + x]);
+            }
+            mo += rec[r].n;
+        }
+        if (mo != m1) { rv_set_error("rv_many_scan: a malformed record"); return -1; }
+        jb.shared = true;
+        if (m->keep) {
+            // test hook: SA / LCP of every job in job-local positions
+            jb.arr_off = (int64_t)kbase + t_off[s];
+            for (int64_t r = t_off[s]; r < t_off[s + 1]; r++) { m->keep_sa[kbase + (size_t)r] = (sa_t)(sa[(size_t)r] - (sa_t)t_off[s]); m->keep_lcp[kbase + (size_t)r] = lc[(size_t)r]; }
+        }
+    }
+    m->info[1] += (int64_t)J; m->info[3]++;
+    return 0;
+}
+
+// a job the shared launches do not take: construct() + rv_getmums / rv_getmultimums on the reused handle, every sequence a sample
+int many_scan_ordinary(rv_many *m, int job, int minl, int minn, int kind) {
+    RV_TRY(many_handle(m, &m->ho));
+    rv_index *h = m->ho;
+    ManyJob &jb = m->jobs[(size_t)job];
+    RV_TRY(rv_reset(h));
+    for (int s = 0; s < jb.k; s++) {
+        RV_TRY(rv_add_sample(h));
+        RV_TRY(rv_add_sequence(h, m->in.data() + m->starts[jb.seq0 + (size_t)s], m->lens[jb.seq0 + (size_t)s], nullptr, nullptr));
+    }
+    RV_TRY(rv_construct(h, 0, nullptr, nullptr, 0));
+    ManyScanSlice &sl = m->sc_job[(size_t)job];
+    sl.rec0 = (int64_t)m->sc_l.size(); sl.mem0 = (int64_t)m->sc_pos.size();
+    // (rv_getmultimums refuses an index of two samples, as the reference's has no SO then; on such an index its records are getmums' -- one interval
+    // of two ranks per MUM, the same side test and left-maximality -- with the members in SA order)
+    const bool by_rank = !many_scan_pair_kind(kind, jb.k) && jb.k == 2;
+    if (by_rank && minn > 2) {
+        // (an interval of a pair index has two members)
+    } else if (many_scan_pair_kind(kind, jb.k) || by_rank) {
+        const int64_t nm = rv_getmums(h, minl);
+        if (nm < 0) return -1;
+        std::vector<u32> l((size_t)std::max<int64_t>(nm, 1));
+        std::vector<int64_t> a((size_t)std::max<int64_t>(nm, 1)), b((size_t)std::max<int64_t>(nm, 1));
+        RV_TRY(rv_fetch_mums(h, l.data(), a.data(), b.data(), nm));
+        std::vector<int64_t> sbeg((size_t)jb.k);      // where the job's sequences begin in its text s0$s1$..
+        int64_t at = 0;
+        for (int s = 0; s < jb.k; s++) { sbeg[(size_t)s] = at; at += m->lens[jb.seq0 + (size_t)s] + 1; }
+        std::vector<int64_t> inv;
+        if (by_rank && nm > 0) {
+            std::vector<sa_t> sa((size_t)jb.ranks);
+            if (rv_get_array(h, RV_SA, sa.data(), jb.ranks) != jb.ranks) return -1;
+            inv.assign((size_t)jb.ranks, 0);
+            for (int64_t r = 0; r < jb.ranks; r++) {
+                if ((int64_t)sa[(size_t)r] < 0 || (int64_t)sa[(size_t)r] >= jb.ranks) { rv_set_error("rv_many_scan: a suffix array entry outside its job"); return -1; }
+                inv[(size_t)sa[(size_t)r]] = r;
+            }
+        }
+        for (int64_t x = 0; x < nm; x++) {
+            int64_t pa = std::min(a[(size_t)x], b[(size_t)x]), pb = std::max(a[(size_t)x], b[(size_t)x]);
+            if (pa < 0 || pb >= jb.ranks) { rv_set_error("rv_many_scan: a match outside its job"); return -1; }
+            if (by_rank && inv[(size_t)pa] > inv[(size_t)pb]) std::swap(pa, pb);
+            m->sc_l.push_back(l[(size_t)x]); m->sc_n.push_back(2);
+            m->sc_so.push_back((uint16_t)((std::upper_bound(sbeg.begin(), sbeg.end(), pa) - sbeg.begin()) - 1)); m->sc_pos.push_back(pa);
+            m->sc_so.push_back((uint16_t)((std::upper_bound(sbeg.begin(), sbeg.end(), pb) - sbeg.begin()) - 1)); m->sc_pos.push_back(pb);
+        }
+    } else {
+        int64_t members = 0;
+        const int64_t nm = rv_getmultimums(h, minl, minn, 0, &members);
+        if (nm < 0) return -1;
+        std::vector<u32> l((size_t)std::max<int64_t>(nm, 1));
+        std::vector<int32_t> cn((size_t)std::max<int64_t>(nm, 1));
+        std::vector<int64_t> off((size_t)nm + 1, 0), pos((size_t)std::max<int64_t>(members, 1));
+        std::vector<uint16_t> so((size_t)std::max<int64_t>(members, 1));
+        RV_TRY(rv_fetch_multi(h, l.data(), cn.data(), off.data(), so.data(), pos.data()));
+        for (int64_t x = 0; x < nm; x++) {
+            if (off[(size_t)x + 1] - off[(size_t)x] != cn[(size_t)x]) { rv_set_error("rv_many_scan: a match of %d members with %lld positions", cn[(size_t)x], (long long)(off[(size_t)x + 1] - off[(size_t)x])); return -1; }
+            m->sc_l.push_back(l[(size_t)x]); m->sc_n.push_back(cn[(size_t)x]);
+        }
+        m->sc_so.insert(m->sc_so.end(), so.begin(), so.begin() + (ptrdiff_t)members);
+        m->sc_pos.insert(m->sc_pos.end(), pos.begin(), pos.begin() + (ptrdiff_t)members);
+    }
+    sl.nrec = (int64_t)m->sc_l.size() - sl.rec0; sl.nmem = (int64_t)m->sc_pos.size() - sl.mem0;
+    jb.shared = false;
+    m->info[2]++;
+    return 0;
+}
+
+int many_scan(rv_many *m, int minl, int minn, int kind) {
+    RV_HIP(hipSetDevice(m->device));
+    m->ran = false; m->scanned = false;
+    m->an_first.clear(); m->an_l.clear(); m->an_off.clear(); m->an_pos.clear(); m->out_text.clear(); m->keep_sa.clear(); m->keep_lcp.clear();
+    m->sc_l.clear(); m->sc_n.clear(); m->sc_so.clear(); m->sc_pos.clear();
+    for (int k = 0; k < 5; k++) m->info[k] = 0;
+    for (int k = 0; k < 8; k++) m->flagged[k] = 0;
+    const int nj = (int)m->jobs.size();
+    m->info[0] = nj;
+    m->sc_job.assign((size_t)nj, ManyScanSlice());
+    // rounds: RV_MANY_ROUND positions at most, and few enough for the packed sums of the scan (RV_MANY_SCAN_RANKS)
+    const int64_t lim = std::max<int64_t>(std::min<int64_t>(m->round_max, RV_MANY_SCAN_RANKS), 1);
+    std::vector<int> order, rest;
+    for (int j = 0; j < nj; j++) {
+        m->jobs[(size_t)j].arr_off = -1;
+        (many_scan_admits(m, m->jobs[(size_t)j]) ? order : rest).push_back(j);
+    }
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return m->jobs[(size_t)a].ranks < m->jobs[(size_t)b].ranks; });
+    for (size_t lo = 0; lo < order.size();) {
+        size_t hi = lo; int64_t sum = 0;
+        while (hi < order.size() && (hi == lo || sum + m->jobs[(size_t)order[hi]].ranks <= lim)) sum += m->jobs[(size_t)order[hi++]].ranks;
+        RV_TRY(many_round_scan(m, order, lo, hi, minl, minn, kind));
+        lo = hi;
+    }
+    for (int j : rest) RV_TRY(many_scan_ordinary(m, j, minl, minn, kind));
+    // the lists job by job
+    m->mt_first.assign((size_t)nj + 1, 0);
+    size_t nmem = 0;
+    for (int j = 0; j < nj; j++) { m->mt_first[(size_t)j + 1] = m->mt_first[(size_t)j] + m->sc_job[(size_t)j].nrec; nmem += (size_t)m->sc_job[(size_t)j].nmem; }
+    const size_t nrec = (size_t)m->mt_first[(size_t)nj];
+    m->mt_l.clear(); m->mt_n.clear(); m->mt_so.clear(); m->mt_pos.clear();
+    m->mt_l.reserve(nrec); m->mt_n.reserve(nrec); m->mt_so.reserve(nmem); m->mt_pos.reserve(nmem);
+    m->mt_off.assign(nrec + 1, 0);
+    for (int j = 0; j < nj; j++) {
+        const ManyScanSlice &sl = m->sc_job[(size_t)j];
+        m->mt_l.insert(m->mt_l.end(), m->sc_l.begin() + (ptrdiff_t)sl.rec0, m->sc_l.begin() + (ptrdiff_t)(sl.rec0 + sl.nrec));
+        m->mt_n.insert(m->mt_n.end(), m->sc_n.begin() + (ptrdiff_t)sl.rec0, m->sc_n.begin() + (ptrdiff_t)(sl.rec0 + sl.nrec));
+        m->mt_so.insert(m->mt_so.end(), m->sc_so.begin() + (ptrdiff_t)sl.mem0, m->sc_so.begin() + (ptrdiff_t)(sl.mem0 + sl.nmem));
+        m->mt_pos.insert(m->mt_pos.end(), m->sc_pos.begin() + (ptrdiff_t)sl.mem0, m->sc_pos.begin() + (ptrdiff_t)(sl.mem0 + sl.nmem));
+    }
+    // (a match's members are as many as the positions between its offsets: getmultimums' count field, 2 for getmums)
+    for (size_t k = 0; k < nrec; k++) m->mt_off[k + 1] = m->mt_off[k] + m->mt_n[k];
+    if ((size_t)m->mt_off[nrec] != nmem) { rv_set_error("rv_many_scan: the members of the lists do not add up"); return -1; }
+    m->sc_job.clear(); m->sc_l.clear(); m->sc_n.clear(); m->sc_so.clear(); m->sc_pos.clear();
+    m->scanned = true;
+    return 0;
+}
+
 }  // namespace
 
 #define MANY_GUARD(body, fail)                                                                                   \
@@ -1176,6 +1444,7 @@ void rv_many_free(rv_many *m) {
     if (m->hs) rv_free(m->hs);
     if (m->ho) rv_free(m->ho);
     m->dJobs.release(); m->dKJobs.release(); m->dSA.release(); m->dLCP.release(); m->dBWT.release(); m->dCnt.release();
+    m->dScanTab.release(); m->dScanCnt.release(); m->dScanFirst.release(); m->dScanOut.release();
     m->dTxt.release(); m->dMJobs.release(); m->dAn.release(); m->dAnPos.release(); m->dFlag.release(); m->dBeg.release();
     m->large_bufs.release();
     delete m;
@@ -1184,6 +1453,7 @@ void rv_many_free(rv_many *m) {
 int rv_many_option(rv_many *m, const char *name, int64_t value) {
     if (!m || !name) { rv_set_error("rv_many_option: null argument"); return -1; }
     if (strcmp(name, "RV_MANY_KEEP") == 0) { m->keep = value; return 0; }
+    if (strcmp(name, "RV_MANY_SCAN_ORDINARY") == 0) { m->scan_ordinary = value != 0; return 0; }
     if (strcmp(name, "RV_MANY_ROUND") == 0) { if (value < 1) { rv_set_error("RV_MANY_ROUND: at least 1"); return -1; } m->round_max = value; return 0; }
     if (strcmp(name, "RV_MANY_MULTI") == 0) { m->multi = value != 0; return 0; }
     if (strcmp(name, "RV_MANY_LARGE") == 0) { m->large = value != 0; return 0; }
@@ -1245,7 +1515,7 @@ int64_t rv_many_add(rv_many *m, const char *const *seqs, const int64_t *lens, in
             m->in.insert(m->in.end(), seqs[s], seqs[s] + lens[s]);
         }
         m->jobs.push_back(jb);
-        m->ran = false;
+        m->ran = false; m->scanned = false;
         return (int64_t)m->jobs.size() - 1;, -1)
 }
 
@@ -1253,7 +1523,8 @@ int rv_many_clear(rv_many *m) {
     if (!m) { rv_set_error("rv_many_clear: null handle"); return -1; }
     m->in.clear(); m->lens.clear(); m->starts.clear(); m->jobs.clear();
     m->an_first.clear(); m->an_l.clear(); m->an_off.clear(); m->an_pos.clear(); m->out_text.clear(); m->keep_sa.clear(); m->keep_lcp.clear();
-    m->ran = false;
+    m->mt_first.clear(); m->mt_l.clear(); m->mt_n.clear(); m->mt_off.clear(); m->mt_so.clear(); m->mt_pos.clear();
+    m->ran = false; m->scanned = false;
     return 0;
 }
 
@@ -1262,7 +1533,32 @@ int rv_many_run(rv_many *m, int minl, int minn, rv_align_stats *total) {
     MANY_GUARD(return many_run(m, minl, minn, total);, -1)
 }
 
+int rv_many_scan(rv_many *m, int minl, int minn, int kind) {
+    if (!m) { rv_set_error("rv_many_scan: null handle"); return -1; }
+    if (kind < 0 || kind > 2) { rv_set_error("rv_many_scan: kind 0 (getmums), 1 (getmultimums) or 2 (getmums for the jobs of two sequences, getmultimums for the rest), not %d", kind); return -1; }
+    if (minl < 0) { rv_set_error("rv_many_scan: a negative minimal length"); return -1; }
+    MANY_GUARD(return many_scan(m, minl, minn, kind);, -1)
+}
+
+int64_t rv_many_match_count(rv_many *m, int64_t *first, int64_t *members) {
+    if (m && m->ran) { rv_set_error("rv_many_match_count: the live result is a run's (rv_many_run): it has anchors, no match lists"); return -1; }
+    if (!m || !m->scanned) { rv_set_error("rv_many_match_count: no finished scan"); return -1; }
+    if (first) for (size_t k = 0; k < m->mt_first.size(); k++) first[k] = m->mt_first[k];
+    if (members) *members = (int64_t)m->mt_pos.size();
+    return (int64_t)m->mt_l.size();
+}
+
+int rv_many_fetch_matches(rv_many *m, uint32_t *l, int32_t *n, int64_t *off, uint16_t *so, int64_t *pos) {
+    if (m && m->ran) { rv_set_error("rv_many_fetch_matches: the live result is a run's (rv_many_run): it has anchors, no match lists"); return -1; }
+    if (!m || !m->scanned || !l || !n || !off || !so || !pos) { rv_set_error("rv_many_fetch_matches: no finished scan, or null argument"); return -1; }
+    if (!m->mt_l.empty()) { memcpy(l, m->mt_l.data(), m->mt_l.size() * sizeof(u32)); memcpy(n, m->mt_n.data(), m->mt_n.size() * sizeof(int32_t)); }
+    memcpy(off, m->mt_off.data(), m->mt_off.size() * sizeof(int64_t));
+    if (!m->mt_pos.empty()) { memcpy(so, m->mt_so.data(), m->mt_so.size() * sizeof(uint16_t)); memcpy(pos, m->mt_pos.data(), m->mt_pos.size() * sizeof(int64_t)); }
+    return 0;
+}
+
 int64_t rv_many_anchor_count(rv_many *m, int64_t *first, int64_t *members) {
+    if (m && m->scanned) { rv_set_error("rv_many_anchor_count: the live result is a scan's (rv_many_scan): it has matches, no anchors"); return -1; }
     if (!m || !m->ran) { rv_set_error("rv_many_anchor_count: no finished run"); return -1; }
     if (first) for (size_t k = 0; k < m->an_first.size(); k++) first[k] = m->an_first[k];
     if (members) *members = (int64_t)m->an_pos.size();
@@ -1270,6 +1566,7 @@ int64_t rv_many_anchor_count(rv_many *m, int64_t *first, int64_t *members) {
 }
 
 int rv_many_fetch(rv_many *m, uint32_t *l, int64_t *off, int64_t *pos) {
+    if (m && m->scanned) { rv_set_error("rv_many_fetch: the live result is a scan's (rv_many_scan): it has matches, no anchors"); return -1; }
     if (!m || !m->ran || !l || !off || !pos) { rv_set_error("rv_many_fetch: no finished run, or null argument"); return -1; }
     if (!m->an_l.empty()) memcpy(l, m->an_l.data(), m->an_l.size() * sizeof(u32));
     memcpy(off, m->an_off.data(), m->an_off.size() * sizeof(int64_t));
@@ -1278,6 +1575,7 @@ int rv_many_fetch(rv_many *m, uint32_t *l, int64_t *off, int64_t *pos) {
 }
 
 int64_t rv_many_text(rv_many *m, int64_t job, char *out, int64_t cap) {
+    if (m && m->scanned) { rv_set_error("rv_many_text: the live result is a scan's (rv_many_scan), which leaves the jobs' text as it was given"); return -1; }
     if (!m || !m->ran || job < 0 || job >= (int64_t)m->jobs.size() || !out) { rv_set_error("rv_many_text: no finished run, or no such job"); return -1; }
     const ManyJob &jb = m->jobs[(size_t)job];
     if (cap < jb.ranks) { rv_set_error("buffer too small"); return -1; }
@@ -1298,7 +1596,7 @@ int rv_many_info(const rv_many *m, int64_t *out) {
 }
 
 int64_t rv_many_arrays(rv_many *m, int64_t job, int which, void *out, int64_t cap) {
-    if (!m || !m->ran || job < 0 || job >= (int64_t)m->jobs.size() || !out) { rv_set_error("rv_many_arrays: no finished run, or no such job"); return -1; }
+    if (!m || !(m->ran || m->scanned) || job < 0 || job >= (int64_t)m->jobs.size() || !out) { rv_set_error("rv_many_arrays: no finished run or scan, or no such job"); return -1; }
     const ManyJob &jb = m->jobs[(size_t)job];
     if (jb.arr_off < 0) { rv_set_error("rv_many_arrays: job %lld did not go through the shared launches with RV_MANY_KEEP set", (long long)job); return -2; }
     if (cap < jb.ranks) { rv_set_error("buffer too small"); return -1; }

@@ -95,6 +95,14 @@ RV_MANY_LARGE_MAX ranks the sample-major rounds of RV_MANY_LARGE_MULTI with up t
 RV_MANY_WIDE_LARGE_MIN such jobs (default 8, counted on their own).  64 is the limit because a lane of a wavefront owns a sample in the
 leaf kernel, the sample id has six bits of its per-position byte, and the level pipeline's scan keeps a one-word census up to 64 samples.
 Jobs of more than 64 sequences always run the ordinary way.  The results do not depend on this switch either.
+
+`mums_many(jobs, minlength, minn, kind)` (`Batch.scan` + `Batch.matches`) gives the MUM / multi-MUM LISTS of the jobs instead of a finished recursion:
+what `index.getmums` / `index.getmultimums` give a stand-alone index of each job, in its coordinates and in the reference's emission order -- for a
+caller who brings a picker of their own, or for `reveal chain --recurse`, which builds an index per gap for exactly these two calls.  Every job of
+2 .. 64 sequences, at most 2048 ranks and no NUL byte shares its launches, with no switch (`takes_shared_scan`): the index build above, then a count
+pass, an exclusive sum and a write pass flat over the ranks of the round (csrc/rv_many_scan.hip) into CSR arrays.  Every other job runs the ordinary way
+inside the call; jobs above 2048 ranks on the segmented build are a follow-up.  A scan leaves jobs and text untouched, so `scan` and `run` may follow
+each other on one Batch; the live result is the last call's (`text` / `anchors` after a scan and `matches` after a run raise `error`).
 """
 import ctypes
 import os
@@ -116,6 +124,7 @@ CHAIN_LARGE_MULTI_MIN = 4  # default of RV_MANY_CHAIN_LARGE_MULTI_MIN: fewer adm
 CHAIN_WIDE_LARGE_WMAX = 128  # RV_PICK_WCHAIN_WMAX: the same over up to 64 paths (2016 pairs) of a job of 2^17 ranks: 256 does not hold (csrc/rv_pick_multi_chain.hip)
 CHAIN_WIDE_LARGE_MIN = 2   # default of RV_MANY_CHAIN_WIDE_LARGE_MIN: fewer admitted jobs of 17 .. 64 sequences above 2048 ranks in a call under a picker stay ordinary
 CHAIN_LARGE_MIN = 4        # default of RV_MANY_CHAIN_LARGE_MIN: fewer admitted pair jobs above 2048 ranks in a call under a picker stay ordinary
+SCAN_KINDS = {"mums": 0, "multimums": 1, "auto": 2}      # rv_many_scan's kind: getmums, getmultimums, getmums for pair jobs and getmultimums for the rest
 
 
 class error(Exception):
@@ -209,6 +218,13 @@ def takes_shared_launch(seqs, multi=False, large=False, large_max=LARGE_MAX, lar
     return ranks <= large_max and bool(large if k == 2 else large_multi)
 
 
+def takes_shared_scan(seqs):
+    """whether `mums_many` / `Batch.scan` build and scan this job in the shared launches (csrc/rv_many.hip many_scan_admits): 2 .. 64 sequences,
+    at most 2048 ranks, no NUL byte.  No switch; every other job runs the ordinary way inside the call."""
+    k = len(seqs)
+    return 2 <= k <= WIDE_KMAX and sum(len(s) for s in seqs) + k <= LEAF_RANKS and not any(b"\0" in s for s in seqs)
+
+
 def shared_layout(pairs):
     """the shared text of pair jobs [(a, b), ..] in the given order: every first sequence, then every second one, a '$' behind
     each -> (text, a_begin[], b_begin[])"""
@@ -284,7 +300,7 @@ class Batch:
         for name in ("RV_MANY_KEEP", "RV_MANY_ROUND", "RV_MANY_WAVE_MAX", "RV_MANY_MULTI", "RV_MANY_LARGE", "RV_MANY_LARGE_MAX", "RV_MANY_LARGE_MIN",
                      "RV_MANY_LARGE_MULTI", "RV_MANY_LARGE_MULTI_MIN", "RV_MANY_WIDE", "RV_MANY_WIDE_LARGE_MIN", "RV_MANY_CHAIN", "RV_MANY_CHAIN_MULTI", "RV_MANY_CHAIN_WIDE",
                      "RV_MANY_CHAIN_LARGE", "RV_MANY_CHAIN_LARGE_MIN", "RV_MANY_CHAIN_LARGE_MULTI", "RV_MANY_CHAIN_LARGE_MULTI_MIN",
-                     "RV_MANY_CHAIN_WIDE_LARGE", "RV_MANY_CHAIN_WIDE_LARGE_MIN"):
+                     "RV_MANY_CHAIN_WIDE_LARGE", "RV_MANY_CHAIN_WIDE_LARGE_MIN", "RV_MANY_SCAN_ORDINARY"):
             v = os.environ.get(name)
             if v is not None and v.strip():
                 self.option(name, int(v))
@@ -359,9 +375,31 @@ class Batch:
             self._fail()
         return first, l[:na], off, pos[:mem.value]
 
+    def scan(self, minlength=20, minn=2, kind="auto"):
+        """rv_many_scan: the match lists of every job instead of a finished recursion.  kind "mums" (0): getmums; "multimums" (1): getmultimums;
+        "auto" (2): getmums for the jobs of two sequences, getmultimums for the rest.  The jobs stay; the result of an earlier run() does not."""
+        if self._dll.rv_many_scan(self._m, int(minlength), int(minn), SCAN_KINDS[kind] if kind in SCAN_KINDS else int(kind)) != 0:
+            self._fail()
+
+    def matches(self):
+        """-> (first[jobs + 1], l, n, off, so, pos): job j owns the matches first[j] .. first[j+1], match k the members off[k] .. off[k+1] of so / pos
+        (sample and position in the coordinates of the job's own text), in the reference's emission order"""
+        nj = len(self._lens)
+        first = np.zeros(nj + 1, np.int64)
+        mem = ctypes.c_int64(0)
+        nm = self._dll.rv_many_match_count(self._m, first.ctypes.data, ctypes.byref(mem))
+        if nm < 0:
+            self._fail()
+        l = np.zeros(max(nm, 1), np.uint32); n = np.zeros(max(nm, 1), np.int32); off = np.zeros(nm + 1, np.int64)
+        so = np.zeros(max(mem.value, 1), np.uint16); pos = np.zeros(max(mem.value, 1), np.int64)
+        if self._dll.rv_many_fetch_matches(self._m, l.ctypes.data, n.ctypes.data, off.ctypes.data, so.ctypes.data, pos.ctypes.data) != 0:
+            self._fail()
+        return first, l[:nm], n[:nm], off, so[:mem.value], pos[:mem.value]
+
     def text(self, j):
-        buf = ctypes.create_string_buffer(self._lens[j])
-        if self._dll.rv_many_text(self._m, j, buf, self._lens[j]) != self._lens[j]:
+        n = self._lens[j] if 0 <= j < len(self._lens) else 0      # (no such job: the library says so)
+        buf = ctypes.create_string_buffer(max(n, 1))
+        if self._dll.rv_many_text(self._m, j, buf, n) != n or n == 0:
             self._fail()
         return buf.raw
 
@@ -436,3 +474,52 @@ def align_many(jobs, minlength=20, minn=2, sa64=False, toupper=True, batch=None,
     info = b.info()
     info["stats"] = stats
     return results, info
+
+
+class Matches:
+    """the match lists of `mums_many`: `arrays` = the CSR (first, l, n, off, so, pos) as numpy arrays; matches[j] = job j's list in the reference's
+    shapes, built when asked for: [(l, (a, b), 0), ..] where the job was scanned with getmums, [(l, n, ((sample, pos), ..)), ..] with getmultimums"""
+
+    def __init__(self, arrays, pair_shape):
+        self.arrays = arrays
+        self._pair = pair_shape      # per job: the list has getmums' shape
+
+    def __len__(self):
+        return len(self._pair)
+
+    def __getitem__(self, j):
+        if not -len(self._pair) <= j < len(self._pair):
+            raise IndexError("job %d of %d" % (j, len(self._pair)))
+        j %= len(self._pair)
+        first, l, n, off, so, pos = self.arrays
+        lo, hi = int(first[j]), int(first[j + 1])
+        if self._pair[j]:
+            return [(int(l[k]), (int(pos[off[k]]), int(pos[off[k] + 1])), 0) for k in range(lo, hi)]
+        return [(int(l[k]), int(n[k]), tuple((int(so[q]), int(pos[q])) for q in range(int(off[k]), int(off[k + 1])))) for k in range(lo, hi)]
+
+    def __iter__(self):
+        return (self[j] for j in range(len(self._pair)))
+
+
+def mums_many(jobs, minlength=20, minn=2, kind="auto", sa64=False, toupper=True, batch=None):
+    """jobs: as for `align_many`.  -> (matches, info): the MUM / multi-MUM list of every job -- what `index.getmums(minlength)` (kind "mums"; for a
+    job of more than two sequences: sample 0 against the rest) or `index.getmultimums(minlength, minn)` (kind "multimums") give a stand-alone index
+    of the job, in its coordinates and emission order; kind "auto": getmums for the jobs of two sequences, getmultimums for the rest, as
+    `reveal chain --recurse` asks per gap.  The jobs `takes_shared_scan` names share their launches (index build with the text in LDS, a count
+    pass, a sum and a write pass over every job of a round at once); every other job runs the ordinary way inside the call.  matches: a `Matches`
+    (`.arrays` = first, l, n, off, so, pos; matches[j] = the job's list in the reference's shapes); info = dict(jobs, shared, ordinary, rounds,
+    launches).  `batch`: a Batch to reuse."""
+    if isinstance(jobs, (str, bytes, bytearray)) or not hasattr(jobs, "__iter__"):
+        raise error("jobs is a list of jobs")
+    if kind not in SCAN_KINDS:
+        raise error("kind is one of %s" % ", ".join(sorted(SCAN_KINDS)))
+    if int(minlength) < 0:
+        raise error("minlength >= 0")
+    prepared = [job_sequences(j, toupper) for j in jobs]      # (argument errors before the library is asked for a device)
+    b = batch if batch is not None else Batch(sa64)
+    b.clear()
+    for seqs in prepared:
+        b.add(seqs)
+    b.scan(minlength, minn, kind)
+    code = SCAN_KINDS[kind]
+    return Matches(b.matches(), [code == 0 or (code == 2 and len(s) == 2) for s in prepared]), b.info()

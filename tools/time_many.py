@@ -5,6 +5,7 @@
                               [--seqs K] [--multi 0|1|ab] [--large 0|1|ab] [--large-multi 0|1|ab] [--large-max R] [--large-min J]
                               [--wide 0|1|ab] [--wide-large-min J] [--no-cut] [--sites] [--picker [--rem-jobs N]]
                               [--chain-wide [--save-digests FILE] [--compare-digests FILE]] [--chain-wide-large [--chain-wide-large-min J]]
+                              [--mums [--only many]]
 
 Workload: J jobs of 2 x L bases, L uniform in lmin .. lmax, 1 % substitutions.  The two sides run alternately, `reps` times each:
   loop   rv_reset, rv_add_sample / rv_add_sequence x 2, rv_construct, rv_align_builtin, rv_fetch_anchors, the text -- per job, straight at
@@ -47,7 +48,11 @@ k_pick_multi_chain), off (the ordinary path), and the built-in picker with RV_MA
 --chain-wide-large-min J sets RV_MANY_CHAIN_WIDE_LARGE_MIN.  The chain side also prints the jobs it gave back by the bits of their flag words (Batch.flagged).
 The chain side's info["ordinary"] is the number of jobs the kernel flagged.  --save-digests FILE writes a digest per job of the picker side's anchors (the chain side, or
 the ordinary side where the build has none); --compare-digests FILE counts the jobs whose digest differs from that file's: two builds run in a process
-each, and this is how their results are compared."""
+each, and this is how their results are compared.
+--mums (with --seqs K, 2 .. 64): the match lists instead of alignments -- Batch.add x J, scan (kind auto), matches -- on three legs run alternately in one
+process: the shared path, the same call with RV_MANY_SCAN_ORDINARY, and the loop through one reused handle (rv_reset, add, rv_construct, rv_getmums /
+rv_getmultimums, fetch: calls the commit before mums_many has too).  Medians, spreads, jobs per second, the gate (the shared median below the loop's by
+more than both spreads), then both sides at 1, 4, 16, 64 and 256 jobs.  --check compares the legs job by job.  Exit status 1 when the gate is missed."""
 import argparse
 import ctypes
 import hashlib
@@ -196,6 +201,114 @@ def main_ab(a, jobs, bases, switch="RV_MANY_MULTI"):
     return 1 if out.get("check_bad_jobs") else 0
 
 
+def run_scan_loop(idx, jobs, minl, minn=2):
+    """leg (c) of --mums: the jobs one after the other through one handle, straight at the C ABI -- rv_reset, add, rv_construct, rv_getmums (two
+    sequences) or rv_getmultimums (more), and the fetch; -> per job (l, n, so, pos) with getmums' records as (0, a), (sample of b, b)"""
+    dll, h = idx._dll, idx._h
+    mem = ctypes.c_int64(0)
+    res = []
+    for job in jobs:
+        ok = dll.rv_reset(h) == 0
+        for s in job:
+            ok = ok and dll.rv_add_sample(h) == 0 and dll.rv_add_sequence(h, s, len(s), None, None) == 0
+        ok = ok and dll.rv_construct(h, 0, None, None, 0) == 0
+        if not ok:
+            raise RuntimeError(idx._lib.err())
+        if len(job) == 2:
+            nm = dll.rv_getmums(h, minl)
+            if nm < 0:
+                raise RuntimeError(idx._lib.err())
+            l = np.empty(max(nm, 1), np.uint32); x = np.empty(max(nm, 1), np.int64); y = np.empty(max(nm, 1), np.int64)
+            if dll.rv_fetch_mums(h, l.ctypes.data, x.ctypes.data, y.ctypes.data, nm) != 0:
+                raise RuntimeError(idx._lib.err())
+            pos = np.stack([x[:nm], y[:nm]], 1).reshape(-1)
+            so = np.tile(np.array([0, 1], np.uint16), nm)
+            res.append((l[:nm], np.full(nm, 2, np.int32), so, pos))
+        else:
+            nm = dll.rv_getmultimums(h, minl, minn, 0, ctypes.byref(mem))
+            if nm < 0:
+                raise RuntimeError(idx._lib.err())
+            l = np.empty(max(nm, 1), np.uint32); n = np.empty(max(nm, 1), np.int32); off = np.empty(nm + 1, np.int64)
+            so = np.empty(max(mem.value, 1), np.uint16); pos = np.empty(max(mem.value, 1), np.int64)
+            if dll.rv_fetch_multi(h, l.ctypes.data, n.ctypes.data, off.ctypes.data, so.ctypes.data, pos.ctypes.data) != 0:
+                raise RuntimeError(idx._lib.err())
+            res.append((l[:nm], n[:nm], so[:mem.value], pos[:mem.value]))
+    return res
+
+
+def run_scan_c(batch, jobs, minl, minn=2):
+    batch.clear()
+    for j in jobs:
+        batch.add(j)
+    batch.scan(minl, minn, "auto")
+    return batch.matches()
+
+
+def main_mums(a, jobs, bases):
+    """--mums: the match lists of every job (many.mums_many's C part: Batch.add x J, scan, matches) -- the shared path, the same call with
+    RV_MANY_SCAN_ORDINARY, and the loop through one reused handle -- alternately in one process; then the smallest job count at which the
+    shared path beats the loop, out of 1, 4, 16, 64, 256.  Every leg ends with its results on the host."""
+    from reveal_amd import many
+    idx = reveallib.index()
+    shared, ordinary = many.Batch(False), many.Batch(False)
+    ordinary.option("RV_MANY_SCAN_ORDINARY", 1)
+    if a.wave_max is not None:
+        shared.option("RV_MANY_WAVE_MAX", a.wave_max)
+    legs = (("shared", lambda js: run_scan_c(shared, js, a.minlength)), ("ordinary", lambda js: run_scan_c(ordinary, js, a.minlength)),
+            ("loop", lambda js: run_scan_loop(idx, js, a.minlength)))
+    if a.only == "many":      # the shared leg alone (under a profiler: the kernels of the scan and nothing else)
+        ts = []
+        for rep in range(a.reps + 1):
+            t0 = time.perf_counter(); run_scan_c(shared, jobs, a.minlength); ts.append(time.perf_counter() - t0)
+        print("shared  : runs %s s (the first one cold); %r" % (" ".join("%.4f" % x for x in ts), shared.info()))
+        return 0
+    for _, f in legs:
+        f(jobs[:64])      # (first use: allocations, code objects)
+    t = {name: [] for name, _ in legs}
+    res = {}
+    for rep in range(a.reps):
+        for name, f in legs:
+            t0 = time.perf_counter(); res[name] = f(jobs); t[name].append(time.perf_counter() - t0)
+    out = dict(mode="mums", jobs=a.jobs, seqs=a.seqs, lmin=a.lmin, lmax=a.lmax, bases=bases, minlength=a.minlength, reps=a.reps, lib_dir=os.environ.get("RV_LIB_DIR", ""))
+    for name, _ in legs:
+        out[name + "_s"] = t[name]; out[name + "_median_s"] = statistics.median(t[name]); out[name + "_spread_s"] = max(t[name]) - min(t[name])
+        print("%-8s: runs %s s; median %.4f s, spread (max - min) %.4f s, %.0f jobs/s"
+              % (name, " ".join("%.4f" % x for x in t[name]), out[name + "_median_s"], out[name + "_spread_s"], a.jobs / out[name + "_median_s"]))
+    out["shared_info"] = shared.info(); out["ordinary_info"] = ordinary.info()
+    out["matches"] = int(len(res["shared"][1])); out["members"] = int(len(res["shared"][5]))
+    out["ratio_loop"] = out["loop_median_s"] / out["shared_median_s"]; out["ratio_ordinary"] = out["ordinary_median_s"] / out["shared_median_s"]
+    out["gate"] = bool(out["loop_median_s"] - out["shared_median_s"] > out["loop_spread_s"] + out["shared_spread_s"])
+    print("shared against the loop: %.1f x (gain %.4f s against spreads of %.4f + %.4f s: gate %s); against the ordinary leg: %.1f x; %d matches, %d members; %r"
+          % (out["ratio_loop"], out["loop_median_s"] - out["shared_median_s"], out["loop_spread_s"], out["shared_spread_s"], "met" if out["gate"] else "MISSED",
+             out["ratio_ordinary"], out["matches"], out["members"], out["shared_info"]))
+    if a.check:
+        first, l, n, off, so, pos = res["shared"]
+        same = all(np.array_equal(x, y) for x, y in zip(res["shared"], res["ordinary"]))
+        bad = 0
+        for j, (ll, ln, lso, lpos) in enumerate(res["loop"]):
+            lo, hi = int(first[j]), int(first[j + 1])
+            bad += not (np.array_equal(l[lo:hi], ll) and np.array_equal(n[lo:hi], ln) and np.array_equal(so[off[lo]:off[hi]], lso) and np.array_equal(pos[off[lo]:off[hi]], lpos))
+        out["check_ordinary_same"] = bool(same); out["check_bad_jobs"] = int(bad) + (0 if same else 1)
+        print("check : shared and ordinary arrays %s; %d of %d jobs differ between the shared leg and the loop" % ("identical" if same else "DIFFER", bad, a.jobs))
+    small = {}
+    for J in (1, 4, 16, 64, 256):
+        if J > len(jobs):
+            break
+        ts, tl = [], []
+        for rep in range(max(a.reps, 5)):
+            t0 = time.perf_counter(); run_scan_c(shared, jobs[:J], a.minlength); ts.append(time.perf_counter() - t0)
+            t0 = time.perf_counter(); run_scan_loop(idx, jobs[:J], a.minlength); tl.append(time.perf_counter() - t0)
+        small[J] = dict(shared_median_s=statistics.median(ts), shared_spread_s=max(ts) - min(ts), loop_median_s=statistics.median(tl), loop_spread_s=max(tl) - min(tl))
+        print("%4d jobs: shared median %.6f s (spread %.6f), loop median %.6f s (spread %.6f)" % (J, small[J]["shared_median_s"], small[J]["shared_spread_s"],
+                                                                                                small[J]["loop_median_s"], small[J]["loop_spread_s"]))
+    out["small"] = small
+    wins = [J for J, v in small.items() if v["shared_median_s"] < v["loop_median_s"]]
+    out["smallest_winning_jobs"] = min(wins) if wins else None
+    print("smallest job count at which the shared path beats the loop: %s" % out["smallest_winning_jobs"])
+    print(json.dumps(out))
+    return 1 if out.get("check_bad_jobs") or not out["gate"] else 0
+
+
 def main_picker(a, jobs, bases):
     """the reference's default picker: RV_MANY_CHAIN on / off, the built-in picker beside them, rem.align per job"""
     from reveal_amd import many, rem, schemes
@@ -329,7 +442,10 @@ def main():
     ap.add_argument("--seedsize", type=int, default=10000, help="--picker: the picker's seedsize (rem.align's default)")
     ap.add_argument("--save-digests", default=None, help="--picker: write a digest per job of the picker side's anchors to this file")
     ap.add_argument("--compare-digests", default=None, help="--picker: count the jobs whose digest differs from this file's")
+    ap.add_argument("--mums", action="store_true", help="the match lists (Batch.scan): the shared path, RV_MANY_SCAN_ORDINARY, and the loop through one handle")
     a = ap.parse_args()
+    if a.mums and (a.picker or a.chain_wide or a.chain_large or a.chain_large_multi or a.chain_wide_large or "ab" in (a.multi, a.large, a.large_multi, a.wide)):
+        ap.error("--mums is a mode of its own")
     if a.chain_wide_large:
         if not 17 <= a.seqs <= 64:
             ap.error("--chain-wide-large times jobs of 17 .. 64 sequences: --seqs K")
@@ -358,6 +474,8 @@ def main():
         ap.error("--large-multi wants jobs of three and more sequences: --seqs K")
     jobs = workload(a.jobs, a.lmin, a.lmax, seqs=a.seqs, cut=a.large_multi is None and not a.no_cut, sites=a.sites)
     bases = sum(len(s) for j in jobs for s in j)
+    if a.mums:
+        return main_mums(a, jobs, bases)
     if a.picker:
         return main_picker(a, jobs, bases)
     if a.multi == "ab":
