@@ -579,15 +579,21 @@ void rv_batch_free(rv_batch *b);
  * of the round (rv_many_scan.hip) -- out[4] counts the two or one launches of the build, the count pass, the 1 / 3 / 5 of the sum (by the round's ranks:
  * up to 2048, up to 2^22, above), one for the jobs' firsts, and the write pass when there is a match.  Every other job -- more than 2048 ranks, more than
  * 64 sequences, a NUL byte -- runs the ordinary way inside the call (rv_reset, construct, rv_getmums / rv_getmultimums on the internal handle); the
- * results do not depend on the path.  Jobs above 2048 ranks on the segmented build of the large rounds are a follow-up: the kernels take segments plus a
- * table of sequence begins, which those rounds have.  RV_MANY_ROUND (a round of a scan holds 2^26 ranks at most), RV_MANY_WAVE_MAX and RV_MANY_KEEP act
+ * results do not depend on the path.  With RV_MANY_SCAN_LARGE on (rv_many_option; off by default) the jobs of 2 .. 64 sequences, no NUL byte and 2049 ..
+ * RV_MANY_LARGE_MAX ranks (default 2^17) that fit a round share their launches too, from RV_MANY_SCAN_LARGE_MIN such jobs in a call on (default 4: measured,
+ * profiles/many_mums_large.txt; fewer stay ordinary): rounds of their own after the small ones, of one kind for every k -- the same job-contiguous text and
+ * tables, the index of every job of the round built at once by the segmented prefix doubling of rv_many_run's large rounds on that text in place
+ * (rv_many_large.hip rv_many_large_build_c: no gather, 16 bytes of descriptor a job), then the same passes.  out[4] counts the build's launches (radix
+ * passes times doubling rounds, some hundreds: by the round's ranks and its longest repeat, never by the number of jobs).  1000 pairs of 2 x (1100 .. 9999)
+ * bases: 17.6 ms against 365 ms with the switch off; 1000 jobs of 3 / 8 / 32 sequences at 2100 .. 30 000 ranks: 14.3 x / 13.6 x / 6.3 x.  RV_MANY_ROUND (a round of a scan holds 2^26 ranks at most), RV_MANY_WAVE_MAX and RV_MANY_KEEP act
  * as in rv_many_run.
  *   rv_many_scan    kind 0: getmums(minl) -- sample 0 against the rest for a job of more than two sequences, minn unused; kind 1: getmultimums(minl,
  *                   minn) -- on a job of two sequences (where rv_getmultimums refuses the index) the same intervals, i.e. getmums' records with their
  *                   members in SA order; kind 2: getmums for the jobs of two sequences, getmultimums for the rest.  minl 0 is minl 1 (a match has l > 0)
  *   rv_many_match_count -> matches of all jobs; first[0 .. jobs] (may be NULL): job j owns the matches first[j] .. first[j+1]; *members: all positions
  *   rv_many_fetch_matches  l[k], n[k], off[k .. k+1] -> so[], pos[]: the layout of rv_fetch_multi; a getmums record has n = 2, members (0, a), (sample of b, b)
- *   RV_MANY_SCAN_ORDINARY (rv_many_option, test hook and A/B leg): 1 sends every job of a scan the ordinary way */
+ *   RV_MANY_SCAN_ORDINARY (rv_many_option, test hook and A/B leg): 1 sends every job of a scan the ordinary way
+ *   RV_MANY_SCAN_LARGE (0 / 1), RV_MANY_SCAN_LARGE_MIN (>= 0; negative: refused): the jobs above 2048 ranks of a scan, as described above */
 typedef struct rv_many rv_many;
 rv_many *rv_many_new(int device);       /* NULL on failure */
 void rv_many_free(rv_many *m);

@@ -87,7 +87,10 @@
 // rv_many_scan: the MUM / multi-MUM lists of every job instead of a finished recursion (many_scan below; the kernels are rv_many_scan.hip's).  Every clean job
 // of 2 .. RV_MANY_WIDE_KMAX sequences and at most RV_LEAF_N ranks goes through rounds of its own kind (many_round_scan): the job-contiguous layout of
 // many_round_multi for every k, k_many_build as it is, then a count pass, an exclusive sum and a write pass flat over the ranks of the round.  No switch, no
-// threshold.  The other jobs run rv_getmums / rv_getmultimums on the internal handle.  A scan does not touch the jobs or their text; `ran` and `scanned` say
+// threshold.  With RV_MANY_SCAN_LARGE on, the clean jobs of 2 .. RV_MANY_WIDE_KMAX sequences and RV_LEAF_N + 1 .. RV_MANY_LARGE_MAX ranks go through rounds of the
+// same layout as well, from RV_MANY_SCAN_LARGE_MIN such jobs in a call on: the index build is rv_many_large_build_c -- the segmented prefix doubling on the
+// round's text in place --, everything behind it is the small rounds' (many_round_scan with `large`).  One class for every k.
+// The other jobs run rv_getmums / rv_getmultimums on the internal handle.  A scan does not touch the jobs or their text; `ran` and `scanned` say
 // which result is live.
 // Size classes (DESIGN.md "Many small alignments" has the measurements): up to `wave_max` ranks (default 512) a wavefront per job,
 // four jobs per workgroup, no workgroup barrier; above, a workgroup of 256 threads per job.  Both hold 22.6 KB of LDS per workgroup:
@@ -308,6 +311,7 @@ struct rv_many {
     std::vector<ManyRec> recs; std::vector<int64_t> rpos;
     // rv_many_scan: at most one of `ran` and `scanned` is set -- the live result is the last call's
     int64_t scan_ordinary = 0;                  // RV_MANY_SCAN_ORDINARY
+    int64_t scan_large = 0, scan_large_min = RV_MANY_SCAN_LARGE_MIN_DEFAULT;      // RV_MANY_SCAN_LARGE, RV_MANY_SCAN_LARGE_MIN
     bool scanned = false;
     std::vector<int64_t> mt_first, mt_off, mt_pos;
     std::vector<u32> mt_l; std::vector<int32_t> mt_n; std::vector<uint16_t> mt_so;
@@ -1173,9 +1177,14 @@ int many_run(rv_many *m, int minl, int minn, rv_align_stats *total) {
 
 // ---- rv_many_scan: the match lists of every job instead of a finished recursion ----
 // The jobs the shared launches take: 2 .. RV_MANY_WIDE_KMAX sequences, at most RV_LEAF_N ranks, no NUL byte (many.takes_shared_scan mirrors it).  No
-// switch and no threshold: the entry is new, nothing that exists is pinned to a count.
+// switch and no threshold for these.
 bool many_scan_admits(const rv_many *m, const ManyJob &jb) {
     return !m->scan_ordinary && jb.k >= 2 && jb.k <= RV_MANY_WIDE_KMAX && jb.clean && jb.ranks <= RV_LEAF_N;
+}
+// ... and with RV_MANY_SCAN_LARGE on (many.takes_shared_scan(.., large=True)): the same above RV_LEAF_N ranks up to RV_MANY_LARGE_MAX, where the job fits
+// a round (lim: many_scan's round limit) -- in a call with at least RV_MANY_SCAN_LARGE_MIN of them.  One class for every k: see many_round_scan
+bool many_scan_large_admits(const rv_many *m, const ManyJob &jb, int64_t lim) {
+    return !m->scan_ordinary && m->scan_large && jb.k >= 2 && jb.k <= RV_MANY_WIDE_KMAX && jb.clean && jb.ranks > RV_LEAF_N && jb.ranks <= m->large_max && jb.ranks <= lim;
 }
 bool many_scan_pair_kind(int kind, int k) { return kind == 0 || (kind == 2 && k == 2); }
 
@@ -1183,7 +1192,11 @@ bool many_scan_pair_kind(int kind, int k) { return kind == 0 || (kind == 2 && k 
 // k_many_build a job is its first sequence and "the rest", so the side bit of its BWT bytes says "behind the job's first '$'" for every k.  Then the count
 // pass, the sums and the write pass of rv_many_scan.hip over the built segments.  Two copies come back: the sums at the jobs' first ranks with the error
 // words behind them, and the records with the write pass' error word behind them.
-int many_round_scan(rv_many *m, const std::vector<int> &order, size_t lo, size_t hi, int minl, int minn, int kind) {
+// large: a round of jobs above RV_LEAF_N ranks (RV_MANY_SCAN_LARGE).  The same layout, the same tables and the same passes; only the index build differs:
+// rv_many_large_build_c, the segmented prefix doubling on the round's text in place (segment j is [off_j, off_j + n_j) in elements and in ranks alike,
+// so its descriptor is the offset, the size and the first sequence's length).  One round class for every k of 2 .. 64: a build is a long chain of
+// launches -- radix passes times doubling rounds --, and a class per k range would pay it once per class in a mixed call.
+int many_round_scan(rv_many *m, const std::vector<int> &order, size_t lo, size_t hi, int minl, int minn, int kind, bool large) {
     RV_TRY(many_handle(m, &m->hs));
     rv_index *h = m->hs;
     const size_t J = hi - lo;
@@ -1191,7 +1204,7 @@ int many_round_scan(rv_many *m, const std::vector<int> &order, size_t lo, size_t
     size_t nseq = 0, nsmall = 0;
     for (size_t s = 0; s < J; s++) {
         const ManyJob &jb = m->jobs[(size_t)order[lo + s]];
-        if (jb.k < 2 || jb.k > RV_MANY_WIDE_KMAX || jb.ranks > CAP_L) { rv_set_error("rv_many_scan: a job of %d sequences and %lld ranks in a shared round", jb.k, (long long)jb.ranks); return -1; }
+        if (jb.k < 2 || jb.k > RV_MANY_WIDE_KMAX || (large ? jb.ranks <= CAP_L || jb.ranks > INT32_MAX : jb.ranks > CAP_L)) { rv_set_error("rv_many_scan: a job of %d sequences and %lld ranks in a shared round", jb.k, (long long)jb.ranks); return -1; }
         n += jb.ranks; nseq += (size_t)jb.k;
     }
     if (n > RV_MANY_SCAN_RANKS) { rv_set_error("rv_many_scan: a round of %lld ranks", (long long)n); return -1; }
@@ -1200,14 +1213,16 @@ int many_round_scan(rv_many *m, const std::vector<int> &order, size_t lo, size_t
     std::vector<int64_t> tab(n64 + (n32 + 1) / 2, 0);
     int64_t *t_off = tab.data(), *t_beg = t_off + J + 1;
     int32_t *t_sf = (int32_t *)(tab.data() + n64), *t_loc = t_sf + J + 1;
-    std::vector<ManyDevJob> dj(J);
+    std::vector<ManyDevJob> dj(large ? 0 : J);
+    std::vector<ManyDevJobC> djc(large ? J : 0);
     std::vector<char> txt((size_t)n);
-    int64_t at = 0;
+    int64_t at = 0, maxn = 0;
     size_t sq = 0;
     for (size_t s = 0; s < J; s++) {
         const ManyJob &jb = m->jobs[(size_t)order[lo + s]];
         const int64_t la = m->lens[jb.seq0];
-        dj[s].abeg = at; dj[s].bbeg = at + la + 1; dj[s].off = at; dj[s].la = (int32_t)la; dj[s].lb = (int32_t)(jb.ranks - la - 2);
+        if (large) { djc[s].off = at; djc[s].n = (int32_t)jb.ranks; djc[s].la = (int32_t)la; maxn = std::max(maxn, jb.ranks); }
+        else { dj[s].abeg = at; dj[s].bbeg = at + la + 1; dj[s].off = at; dj[s].la = (int32_t)la; dj[s].lb = (int32_t)(jb.ranks - la - 2); }
         t_off[s] = at; t_sf[s] = (int32_t)sq;
         if (jb.ranks <= m->wave_max && jb.ranks <= CAP_S) nsmall = s + 1;      // (ascending sizes: the small class is a prefix)
         const int64_t job0 = at;
@@ -1223,7 +1238,8 @@ int many_round_scan(rv_many *m, const std::vector<int> &order, size_t lo, size_t
     if (at != n || sq != nseq) { rv_set_error("rv_many_scan: the jobs' ranks do not add up to the text"); return -1; }
     hipStream_t q = h->ws.stream;
     const size_t first_bytes = (J + 1) * sizeof(u64), words_bytes = 16;      // words: [0] max LCP, [1] error bits of the build, [2] of the count pass
-    RV_TRY(m->dJobs.reserve(J * sizeof(ManyDevJob)));
+    const size_t jobs_bytes = large ? J * sizeof(ManyDevJobC) : J * sizeof(ManyDevJob);
+    RV_TRY(m->dJobs.reserve(jobs_bytes));
     RV_TRY(m->dScanTab.reserve(tab.size() * sizeof(int64_t)));
     RV_TRY(m->dTxt.reserve((size_t)n + 64));
     RV_TRY(m->dSA.reserve((size_t)(n + 64) * sizeof(sa_t)));
@@ -1231,12 +1247,16 @@ int many_round_scan(rv_many *m, const std::vector<int> &order, size_t lo, size_t
     RV_TRY(m->dBWT.reserve((size_t)n + 64));
     RV_TRY(m->dScanCnt.reserve((size_t)(n + 1) * sizeof(u64)));
     RV_TRY(m->dScanFirst.reserve(first_bytes + words_bytes));
-    RV_HIP(hipMemcpyAsync(m->dJobs.p, dj.data(), J * sizeof(ManyDevJob), hipMemcpyHostToDevice, q));
+    RV_HIP(hipMemcpyAsync(m->dJobs.p, large ? (const void *)djc.data() : (const void *)dj.data(), jobs_bytes, hipMemcpyHostToDevice, q));
     RV_HIP(hipMemcpyAsync(m->dScanTab.p, tab.data(), tab.size() * sizeof(int64_t), hipMemcpyHostToDevice, q));
     RV_HIP(hipMemcpyAsync(m->dTxt.p, txt.data(), (size_t)n, hipMemcpyHostToDevice, q));
     u32 *d_words = (u32 *)((char *)m->dScanFirst.p + first_bytes);
     RV_HIP(hipMemsetAsync(d_words, 0, words_bytes, q));
-    RV_TRY(many_build(m, q, m->dJobs.as<ManyDevJob>(), J, nsmall, m->dTxt.as<uint8_t>(), d_words, d_words + 1));
+    if (large) {
+        RV_HIP(hipMemsetAsync(m->dTxt.as<uint8_t>() + n, 0, 64, q));      // (the build reads eight bytes at a time, on the text in place)
+        RV_TRY(rv_many_large_build_c(h->ws, m->large_bufs, m->dJobs.as<ManyDevJobC>(), (int64_t)J, n, maxn, m->dTxt.as<uint8_t>(), m->dSA.as<sa_t>(), m->dLCP.as<lcp_t>(),
+                                     m->dBWT.as<uint8_t>(), d_words, &m->info[4]));
+    } else RV_TRY(many_build(m, q, m->dJobs.as<ManyDevJob>(), J, nsmall, m->dTxt.as<uint8_t>(), d_words, d_words + 1));
     RvManyScanRound R;
     R.SA = m->dSA.as<sa_t>(); R.LCP = m->dLCP.as<lcp_t>(); R.BWT = m->dBWT.as<uint8_t>(); R.m = n;
     R.off = m->dScanTab.as<int64_t>(); R.beg = R.off + J + 1;
@@ -1384,19 +1404,28 @@ int many_scan(rv_many *m, int minl, int minn, int kind) {
     const int nj = (int)m->jobs.size();
     m->info[0] = nj;
     m->sc_job.assign((size_t)nj, ManyScanSlice());
-    // rounds: RV_MANY_ROUND positions at most, and few enough for the packed sums of the scan (RV_MANY_SCAN_RANKS)
+    // rounds: RV_MANY_ROUND positions at most, and few enough for the packed sums of the scan (RV_MANY_SCAN_RANKS: below the segmented build's 2^31 elements)
     const int64_t lim = std::max<int64_t>(std::min<int64_t>(m->round_max, RV_MANY_SCAN_RANKS), 1);
-    std::vector<int> order, rest;
+    // (a large job has to fit a round: one that does not goes the ordinary way)
+    int64_t nlarge = 0;
+    for (const ManyJob &jb : m->jobs) nlarge += many_scan_large_admits(m, jb, lim) ? 1 : 0;
+    const bool take_large = nlarge > 0 && nlarge >= m->scan_large_min;
+    std::vector<int> order, lorder, rest;
     for (int j = 0; j < nj; j++) {
+        const ManyJob &jb = m->jobs[(size_t)j];
         m->jobs[(size_t)j].arr_off = -1;
-        (many_scan_admits(m, m->jobs[(size_t)j]) ? order : rest).push_back(j);
+        (many_scan_admits(m, jb) ? order : take_large && many_scan_large_admits(m, jb, lim) ? lorder : rest).push_back(j);
     }
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return m->jobs[(size_t)a].ranks < m->jobs[(size_t)b].ranks; });
-    for (size_t lo = 0; lo < order.size();) {
-        size_t hi = lo; int64_t sum = 0;
-        while (hi < order.size() && (hi == lo || sum + m->jobs[(size_t)order[hi]].ranks <= lim)) sum += m->jobs[(size_t)order[hi++]].ranks;
-        RV_TRY(many_round_scan(m, order, lo, hi, minl, minn, kind));
-        lo = hi;
+    // the small rounds, then the large ones (a job above RV_LEAF_N ranks holds more than 2^11 of a round's at most 2^26 ranks: fewer than the build's 2^20 jobs)
+    for (int large = 0; large < 2; large++) {
+        std::vector<int> &ord = large ? lorder : order;
+        std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return m->jobs[(size_t)a].ranks < m->jobs[(size_t)b].ranks; });
+        for (size_t lo = 0; lo < ord.size();) {
+            size_t hi = lo; int64_t sum = 0;
+            while (hi < ord.size() && (hi == lo || sum + m->jobs[(size_t)ord[hi]].ranks <= lim)) sum += m->jobs[(size_t)ord[hi++]].ranks;
+            RV_TRY(many_round_scan(m, ord, lo, hi, minl, minn, kind, large != 0));
+            lo = hi;
+        }
     }
     for (int j : rest) RV_TRY(many_scan_ordinary(m, j, minl, minn, kind));
     // the lists job by job
@@ -1454,6 +1483,8 @@ int rv_many_option(rv_many *m, const char *name, int64_t value) {
     if (!m || !name) { rv_set_error("rv_many_option: null argument"); return -1; }
     if (strcmp(name, "RV_MANY_KEEP") == 0) { m->keep = value; return 0; }
     if (strcmp(name, "RV_MANY_SCAN_ORDINARY") == 0) { m->scan_ordinary = value != 0; return 0; }
+    if (strcmp(name, "RV_MANY_SCAN_LARGE") == 0) { m->scan_large = value != 0; return 0; }
+    if (strcmp(name, "RV_MANY_SCAN_LARGE_MIN") == 0) { if (value < 0) { rv_set_error("RV_MANY_SCAN_LARGE_MIN: negative"); return -1; } m->scan_large_min = value; return 0; }
     if (strcmp(name, "RV_MANY_ROUND") == 0) { if (value < 1) { rv_set_error("RV_MANY_ROUND: at least 1"); return -1; } m->round_max = value; return 0; }
     if (strcmp(name, "RV_MANY_MULTI") == 0) { m->multi = value != 0; return 0; }
     if (strcmp(name, "RV_MANY_LARGE") == 0) { m->large = value != 0; return 0; }

@@ -19,6 +19,10 @@
 // default of RV_MANY_WIDE_LARGE_MIN (fewer jobs of 17 .. 64 sequences above RV_LEAF_N ranks than this in a call stay ordinary): the smallest
 // count measured at which the shared rounds are not slower at k = 17, 32 and 64 (profiles/many_wide.txt: 4 jobs of 32 sequences tie, 8 win)
 #define RV_MANY_WIDE_LARGE_MIN_DEFAULT 8
+// default of RV_MANY_SCAN_LARGE_MIN (fewer admitted jobs above RV_LEAF_N ranks than this in a call of rv_many_scan stay ordinary): the smallest count measured at
+// which the shared rounds are not slower for pair jobs and for jobs of 8 sequences (profiles/many_mums_large.txt: a round costs 1.1 - 1.3 ms whatever it holds; one job
+// loses, 1.09 against 0.38 ms and 1.24 against 0.65 ms; two lose or tie, 1.14 against 0.75 and 1.29 against 1.25 ms; four win, 1.38 against 1.48 and 1.57 against 2.51 ms)
+#define RV_MANY_SCAN_LARGE_MIN_DEFAULT 4
 
 // a pair job of a round: where its two sequences begin in the round's shared text, the first rank of its segment
 struct ManyDevJob { int64_t abeg, bbeg, off; int32_t la, lb; };
@@ -28,6 +32,11 @@ struct ManyDevJob { int64_t abeg, bbeg, off; int32_t la, lb; };
 // text; pend[q]: the end of sequence q's local prefix, lengths + 1 accumulated -- sequence q and its '$' are the local positions
 // [pend[q - 1], pend[q]) of the stand-alone text s0$s1$..s(k-1)$, and pend[k - 1] = n
 struct ManyDevJobK { int64_t off; int64_t beg[RV_MANY_WIDE_KMAX]; int32_t pend[RV_MANY_WIDE_KMAX]; int32_t k, n; };
+
+// a job of k = 2 .. RV_MANY_WIDE_KMAX sequences of a job-contiguous round (the scan rounds of rv_many_scan above RV_LEAF_N ranks): the job lies in the
+// round's text as its stand-alone text s0$s1$..s(k-1)$ at [off, off + n), which is its segment of ranks as well.  la: the length of its first sequence
+// (the side bit of a BWT byte says "behind the job's first '$'", for every k).  The build needs nothing else: 16 bytes a job, against 784 of ManyDevJobK
+struct ManyDevJobC { int64_t off; int32_t n, la; };
 
 // scratch of the build, kept by rv_many between calls: 37 B per position (+ the radix sort's digit byte and histograms in the workspace)
 struct RvManyLargeBufs {
@@ -43,4 +52,10 @@ int rv_many_large_build(Workspace &ws, RvManyLargeBufs &B, const ManyDevJob *djo
 // the same for jobs of 3 .. RV_MANY_WIDE_KMAX sequences in the sample-major layout: segment [off, off + n) of a job = construct() of its stand-alone text
 // s0$s1$..s(k-1)$, SA in shared-text positions.  nT: bytes of T (a descriptor that points outside it is refused through d_cnt[1], not read).
 int rv_many_large_build_k(Workspace &ws, RvManyLargeBufs &B, const ManyDevJobK *djobs, int64_t njobs, int64_t n, int64_t maxn, const uint8_t *T, int64_t nT,
+                          sa_t *SA, lcp_t *LCP, uint8_t *BWT, u32 *d_cnt, int64_t *launches);
+// the same for jobs of 2 .. RV_MANY_WIDE_KMAX sequences in the job-contiguous layout: T holds the n bytes of the round, job j's stand-alone text at
+// [off, off + n_j), and the build works on T in place (nothing is gathered: B.txt stays unused).  The keys and the LCP loop read eight bytes at a time,
+// so the caller keeps 64 zero bytes behind T[n - 1].  SA in positions of T (job-local: SA - off).  A descriptor that is not back to back with its
+// neighbours, has n < 4 or la outside 1 .. n - 3, or whose text has no '$' at la and at n - 1 is refused through d_cnt[1]; nothing outside T is read.
+int rv_many_large_build_c(Workspace &ws, RvManyLargeBufs &B, const ManyDevJobC *djobs, int64_t njobs, int64_t n, int64_t maxn, const uint8_t *T,
                           sa_t *SA, lcp_t *LCP, uint8_t *BWT, u32 *d_cnt, int64_t *launches);

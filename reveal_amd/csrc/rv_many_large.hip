@@ -17,6 +17,9 @@
 //   finish    text order with Kasai's carry, a thread per 16 consecutive elements (the carry starts afresh at a job's first position): LCP with
 //             the reference's stops at '$' and 'N' (interface.c:97-114), eight bytes per step; SA in shared-text positions; the BWT byte
 // Every kernel is a streaming pass of a few bytes per element, plus the gather rank[e + h] inside a job's segment.
+// Three forms share the passes in between (ml_build's JobT): the pair rounds (ManyDevJob), the sample-major rounds of 3 .. 64 sequences (ManyDevJobK), and
+// the job-contiguous rounds of rv_many_scan (ManyDevJobC, 2 .. 64 sequences): there a job's stand-alone text IS [off_j, off_j + n_j) of the round's text, so
+// nothing is gathered -- the build reads the round's text in place -- and an element is its own text position.
 #include "rv_many_large.h"
 #include "rv_index.h"
 #include <type_traits>
@@ -37,6 +40,9 @@ __device__ inline u64 ml_zero_bytes(u64 v) { return (v - 0x0101010101010101ull) 
 template <class JobT>
 __device__ inline int64_t ml_end(const JobT *jobs, u32 j, int64_t n) {
     if constexpr (std::is_same_v<JobT, ManyDevJobK>) {      // never behind the round's last element, whatever a descriptor the gather has refused says
+        const int64_t end = jobs[j].off + jobs[j].n;
+        return end < n ? end : n;
+    } else if constexpr (std::is_same_v<JobT, ManyDevJobC>) {      // the same: k_mlc_jobs may have refused it
         const int64_t end = jobs[j].off + jobs[j].n;
         return end < n ? end : n;
     } else return jobs[j].off + jobs[j].la + jobs[j].lb + 2;
@@ -206,6 +212,66 @@ __global__ __launch_bounds__(LT) void k_mlk_finish(const ManyDevJobK *__restrict
     if ((threadIdx.x & 63) == 0 && lmax > __atomic_load_n(d_maxlcp, __ATOMIC_RELAXED)) atomicMax(d_maxlcp, lmax);
 }
 
+// The first kernel of a job-contiguous round (ManyDevJobC): the job of every element, by the search in the offsets.  Nothing is gathered -- the round's
+// text is the build's text in place.  The thread of a job's first element checks the whole descriptor: its segment back to back with its neighbours'
+// inside [0, n), at least s$t$ (n >= 4, 1 <= la <= n - 3), a '$' behind the first sequence and at the job's end (the finish relies on the last one: its
+// comparisons stop there).  A malformed descriptor sets the error word; T is read inside [0, n) only, and only where the descriptor has passed.
+__global__ __launch_bounds__(LT) void k_mlc_jobs(const ManyDevJobC *__restrict__ jobs, int njobs, int64_t n, const uint8_t *__restrict__ T,
+                                                  u32 *__restrict__ job, u32 *__restrict__ d_err) {
+    const int64_t e = (int64_t)blockIdx.x * LT + threadIdx.x;
+    if (e >= n) return;
+    int lo = 0, hi = njobs;                // the last job whose segment begins at or in front of e
+    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (jobs[mid].off <= e) lo = mid; else hi = mid; }
+    const ManyDevJobC J = jobs[lo];
+    const int64_t p = e - J.off, nj = J.n, la = J.la;
+    job[e] = (u32)lo;
+    bool bad = p < 0 || p >= nj;
+    if (!bad && p == 0) {                  // (off == e: inside [0, n))
+        const int64_t end = J.off + nj;
+        if (end > n || end != (lo + 1 < njobs ? jobs[lo + 1].off : n)) bad = true;
+        if (nj < 4 || la < 1 || la > nj - 3) bad = true;
+        if (!bad && (T[J.off + la] != (uint8_t)'$' || T[end - 1] != (uint8_t)'$')) bad = true;
+    }
+    if (bad) atomicOr(d_err, 1u);
+}
+
+// The finish of a job-contiguous round: k_ml_finish where an element IS its position of the shared text (SA[k] = e), the side bit of the BWT byte is
+// "behind the first sequence's '$'" (p > la).  Kasai's carry starts afresh at a job's first position; the LCP stops at '$' and 'N'.  Where k_mlc_jobs
+// has refused a descriptor the kernel does nothing (a text it did not check need not end in '$'): the host reports the error word.
+__global__ __launch_bounds__(LT) void k_mlc_finish(const ManyDevJobC *__restrict__ jobs, int64_t n, const uint8_t *__restrict__ txt, const u32 *__restrict__ job,
+                                                    const u32 *__restrict__ rank, const u32 *__restrict__ order, sa_t *__restrict__ SA, lcp_t *__restrict__ LCP,
+                                                    uint8_t *__restrict__ BWT, u32 *__restrict__ d_maxlcp, const u32 *__restrict__ d_err) {
+    if (__atomic_load_n(d_err, __ATOMIC_RELAXED)) return;
+    const int64_t e0 = ((int64_t)blockIdx.x * LT + threadIdx.x) * FIN_CHUNK;
+    u32 lmax = 0, jcur = ~0u;
+    int64_t off = 0, la = 0, hh = 0;
+    for (int64_t e = e0; e < e0 + FIN_CHUNK && e < n; e++) {
+        const u32 j = job[e];
+        if (j != jcur) { const ManyDevJobC J = jobs[j]; off = J.off; la = J.la; jcur = j; hh = 0; }      // (a job's first position: no carry)
+        const int64_t p = e - off, k = (int64_t)rank[e] - 1;
+        if (k > off) {
+            const int64_t o = order[k - 1];
+            for (;;) {
+                u64 a, b;
+                __builtin_memcpy(&a, txt + e + hh, 8);
+                __builtin_memcpy(&b, txt + o + hh, 8);
+                const u64 x = a ^ b, z = ml_zero_bytes(a ^ 0x2424242424242424ull) | ml_zero_bytes(a ^ 0x4E4E4E4E4E4E4E4Eull);      // '$', 'N'
+                const int m = x ? (int)(__builtin_ctzll(x) >> 3) : 8, s = z ? (int)(__builtin_ctzll(z) >> 3) : 8;
+                const int step = m < s ? m : s;
+                hh += step;
+                if (step < 8) break;       // (a job's text ends with '$': no comparison runs past it)
+            }
+            LCP[k] = (lcp_t)hh;
+            if ((u32)hh > lmax) lmax = (u32)hh;
+        } else { LCP[k] = 0; hh = 0; }     // the job's first rank
+        SA[k] = (sa_t)e;
+        BWT[k] = (uint8_t)((p > 0 ? txt[e - 1] : (uint8_t)'$') | (p > la ? RV_BWT_SIDE : 0u));
+        if (hh > 0) hh--;
+    }
+    lmax = (u32)rv_wave_max_u64((u64)lmax);
+    if ((threadIdx.x & 63) == 0 && lmax > __atomic_load_n(d_maxlcp, __ATOMIC_RELAXED)) atomicMax(d_maxlcp, lmax);
+}
+
 int ml_bits(int64_t v) { int b = 1; while (b < 63 && ((int64_t)1 << b) <= v) b++; return b; }      // bits that hold 0 .. v
 
 // kernels of the primitives (rv_prims.hip), for the launch count
@@ -215,20 +281,23 @@ int ml_sort_launches(const Workspace &ws, int64_t n, int bits) {
     return rv_radix_passes(ws, bits) * (2 + ml_scan_launches(((int64_t)1 << width) * ceil_div(n, 4096)));
 }
 
-// JobT: ManyDevJob (pair rounds) or ManyDevJobK (sample-major rounds: their own gather and finish; nT, the bytes of T, is theirs alone); the kernels
-// in between only need a segment's end
+// JobT: ManyDevJob (pair rounds), ManyDevJobK (sample-major rounds: their own gather and finish; nT, the bytes of T, is theirs alone) or ManyDevJobC
+// (job-contiguous rounds: no gather -- the build's text is T in place, padded by the caller --, their own first kernel and finish); the kernels in
+// between only need a segment's end
 template <class JobT>
 int ml_build(Workspace &ws, RvManyLargeBufs &B, const JobT *djobs, int64_t njobs, int64_t n, int64_t maxn, const uint8_t *T, int64_t nT,
              sa_t *SA, lcp_t *LCP, uint8_t *BWT, u32 *d_cnt, int64_t *launches) {
     if (njobs < 1 || njobs >= ((int64_t)1 << JOB_BITS) || n < 1 || n >= ((int64_t)1 << RANK_BITS) || maxn < 1 || maxn > n) { rv_set_error("rv_many_run: a round of large jobs of bad sizes"); return -1; }
     const int b2 = ml_bits(maxn);          // a job-local rank is 0 .. maxn
     hipStream_t q = ws.stream;
-    RV_TRY(B.txt.reserve((size_t)n + 64));
+    constexpr bool in_place = std::is_same_v<JobT, ManyDevJobC>;
+    if (!in_place) RV_TRY(B.txt.reserve((size_t)n + 64));
     RV_TRY(B.job.reserve((size_t)n * sizeof(u32)));
     RV_TRY(B.rank.reserve((size_t)n * sizeof(u32)));
     RV_TRY(B.head.reserve((size_t)n * sizeof(u32)));
     for (int k = 0; k < 2; k++) { RV_TRY(B.key[k].reserve((size_t)n * sizeof(u64))); RV_TRY(B.val[k].reserve((size_t)n * sizeof(u32))); }
-    uint8_t *txt = B.txt.as<uint8_t>();
+    uint8_t *gtxt = in_place ? nullptr : B.txt.as<uint8_t>();      // what a gather writes
+    const uint8_t *txt = in_place ? T : gtxt;
     u32 *job = B.job.as<u32>(), *rank = B.rank.as<u32>(), *head = B.head.as<u32>();
     u64 *key[2] = {B.key[0].as<u64>(), B.key[1].as<u64>()};
     u32 *val[2] = {B.val[0].as<u32>(), B.val[1].as<u32>()};
@@ -236,9 +305,10 @@ int ml_build(Workspace &ws, RvManyLargeBufs &B, const JobT *djobs, int64_t njobs
     u32 *d_max = d_cnt, *d_err = d_cnt + 1, *d_tied = B.flag.as<u32>();
     std::vector<u32> slots(TIE_SLOTS);
     const dim3 grid((unsigned)ceil_div(n, LT)), block(LT);
-    RV_HIP(hipMemsetAsync(txt + n, 0, 64, q));
-    if constexpr (std::is_same_v<JobT, ManyDevJobK>) hipLaunchKernelGGL(k_mlk_gather, grid, block, 0, q, djobs, (int)njobs, n, T, nT, txt, job, d_err);
-    else hipLaunchKernelGGL(k_ml_gather, grid, block, 0, q, djobs, (int)njobs, n, T, txt, job, d_err);
+    if (!in_place) RV_HIP(hipMemsetAsync(gtxt + n, 0, 64, q));
+    if constexpr (in_place) hipLaunchKernelGGL(k_mlc_jobs, grid, block, 0, q, djobs, (int)njobs, n, T, job, d_err);
+    else if constexpr (std::is_same_v<JobT, ManyDevJobK>) hipLaunchKernelGGL(k_mlk_gather, grid, block, 0, q, djobs, (int)njobs, n, T, nT, gtxt, job, d_err);
+    else hipLaunchKernelGGL(k_ml_gather, grid, block, 0, q, djobs, (int)njobs, n, T, gtxt, job, d_err);
     RV_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_ml_first_keys<JobT>, grid, block, 0, q, djobs, n, (const uint8_t *)txt, (const u32 *)job, key[0], val[0]);
     RV_LAUNCH_CHECK();
@@ -267,7 +337,9 @@ int ml_build(Workspace &ws, RvManyLargeBufs &B, const JobT *djobs, int64_t njobs
         h <<= 1;
     }
     const dim3 fgrid((unsigned)ceil_div(ceil_div(n, FIN_CHUNK), LT));
-    if constexpr (std::is_same_v<JobT, ManyDevJobK>)
+    if constexpr (in_place)
+        hipLaunchKernelGGL(k_mlc_finish, fgrid, block, 0, q, djobs, n, (const uint8_t *)txt, (const u32 *)job, (const u32 *)rank, (const u32 *)val[cur], SA, LCP, BWT, d_max, (const u32 *)d_err);
+    else if constexpr (std::is_same_v<JobT, ManyDevJobK>)
         hipLaunchKernelGGL(k_mlk_finish, fgrid, block, 0, q, djobs, n, (const uint8_t *)txt, (const u32 *)job, (const u32 *)rank, (const u32 *)val[cur], SA, LCP, BWT, d_max, (const u32 *)d_err);
     else
         hipLaunchKernelGGL(k_ml_finish, fgrid, block, 0, q, djobs, n, (const uint8_t *)txt, (const u32 *)job, (const u32 *)rank, (const u32 *)val[cur], SA, LCP, BWT, d_max);
@@ -286,4 +358,9 @@ int rv_many_large_build(Workspace &ws, RvManyLargeBufs &B, const ManyDevJob *djo
 int rv_many_large_build_k(Workspace &ws, RvManyLargeBufs &B, const ManyDevJobK *djobs, int64_t njobs, int64_t n, int64_t maxn, const uint8_t *T, int64_t nT,
                           sa_t *SA, lcp_t *LCP, uint8_t *BWT, u32 *d_cnt, int64_t *launches) {
     return ml_build(ws, B, djobs, njobs, n, maxn, T, nT, SA, LCP, BWT, d_cnt, launches);
+}
+
+int rv_many_large_build_c(Workspace &ws, RvManyLargeBufs &B, const ManyDevJobC *djobs, int64_t njobs, int64_t n, int64_t maxn, const uint8_t *T,
+                          sa_t *SA, lcp_t *LCP, uint8_t *BWT, u32 *d_cnt, int64_t *launches) {
+    return ml_build(ws, B, djobs, njobs, n, maxn, T, n, SA, LCP, BWT, d_cnt, launches);
 }

@@ -101,7 +101,14 @@ what `index.getmums` / `index.getmultimums` give a stand-alone index of each job
 caller who brings a picker of their own, or for `reveal chain --recurse`, which builds an index per gap for exactly these two calls.  Every job of
 2 .. 64 sequences, at most 2048 ranks and no NUL byte shares its launches, with no switch (`takes_shared_scan`): the index build above, then a count
 pass, an exclusive sum and a write pass flat over the ranks of the round (csrc/rv_many_scan.hip) into CSR arrays.  Every other job runs the ordinary way
-inside the call; jobs above 2048 ranks on the segmented build are a follow-up.  A scan leaves jobs and text untouched, so `scan` and `run` may follow
+inside the call -- jobs above 2048 ranks too, unless the switch RV_MANY_SCAN_LARGE is on (`mums_many(.., large=True)`, `Batch.option("RV_MANY_SCAN_LARGE", 1)`
+or the environment variable; off by default).  With it the jobs of 2 .. 64 sequences, 2049 .. RV_MANY_LARGE_MAX ranks (default 2^17) and no NUL byte share
+their launches too (`takes_shared_scan(.., large=True)`), in rounds of their own but of one kind for every k: each job contiguous in the round's text as
+for the small ones, the index of every job of the round built at once by the segmented prefix doubling on that text in place
+(csrc/rv_many_large.hip rv_many_large_build_c), then the same count pass, sum and write pass.  A call with fewer than RV_MANY_SCAN_LARGE_MIN such jobs
+(default 4: measured, one or two such jobs lose or tie against the ordinary path, four win) leaves them on the ordinary path, and so does a job larger than a round (RV_MANY_ROUND, 2^26 ranks at most).  The lists
+do not depend on the switch.  1000 pairs of 2 x (1100 .. 9999) bases: 17.6 ms against 365 ms with the switch off (20.8 x); 1000 jobs of 3 / 8 / 32 sequences at
+2100 .. 30 000 ranks: 14.3 x / 13.6 x / 6.3 x (profiles/many_mums_large.txt).  A scan leaves jobs and text untouched, so `scan` and `run` may follow
 each other on one Batch; the live result is the last call's (`text` / `anchors` after a scan and `matches` after a run raise `error`).
 """
 import ctypes
@@ -123,6 +130,8 @@ CHAIN_LARGE_MULTI_WMAX = 512  # RV_PICK_MCHAIN_WMAX: weights up to this keep the
 CHAIN_LARGE_MULTI_MIN = 4  # default of RV_MANY_CHAIN_LARGE_MULTI_MIN: fewer admitted jobs of 3 .. 16 sequences above 2048 ranks in a call under a picker stay ordinary
 CHAIN_WIDE_LARGE_WMAX = 128  # RV_PICK_WCHAIN_WMAX: the same over up to 64 paths (2016 pairs) of a job of 2^17 ranks: 256 does not hold (csrc/rv_pick_multi_chain.hip)
 CHAIN_WIDE_LARGE_MIN = 2   # default of RV_MANY_CHAIN_WIDE_LARGE_MIN: fewer admitted jobs of 17 .. 64 sequences above 2048 ranks in a call under a picker stay ordinary
+SCAN_LARGE_MIN = 4         # default of RV_MANY_SCAN_LARGE_MIN: fewer admitted jobs above 2048 ranks in a call of mums_many with RV_MANY_SCAN_LARGE stay ordinary
+SCAN_ROUND_RANKS = 1 << 26  # RV_MANY_SCAN_RANKS: ranks of the largest round of a scan, whatever RV_MANY_ROUND says
 CHAIN_LARGE_MIN = 4        # default of RV_MANY_CHAIN_LARGE_MIN: fewer admitted pair jobs above 2048 ranks in a call under a picker stay ordinary
 SCAN_KINDS = {"mums": 0, "multimums": 1, "auto": 2}      # rv_many_scan's kind: getmums, getmultimums, getmums for pair jobs and getmultimums for the rest
 
@@ -218,11 +227,16 @@ def takes_shared_launch(seqs, multi=False, large=False, large_max=LARGE_MAX, lar
     return ranks <= large_max and bool(large if k == 2 else large_multi)
 
 
-def takes_shared_scan(seqs):
+def takes_shared_scan(seqs, large=False, large_max=LARGE_MAX):
     """whether `mums_many` / `Batch.scan` build and scan this job in the shared launches (csrc/rv_many.hip many_scan_admits): 2 .. 64 sequences,
-    at most 2048 ranks, no NUL byte.  No switch; every other job runs the ordinary way inside the call."""
+    at most 2048 ranks, no NUL byte, with no switch.  large: with RV_MANY_SCAN_LARGE on and RV_MANY_LARGE_MAX = large_max, the same jobs of 2049 ..
+    large_max ranks as well (many_scan_large_admits) -- in a call with at least RV_MANY_SCAN_LARGE_MIN such jobs, and with rounds that hold the job
+    (RV_MANY_ROUND, at most 2^26 ranks).  Every other job runs the ordinary way inside the call."""
     k = len(seqs)
-    return 2 <= k <= WIDE_KMAX and sum(len(s) for s in seqs) + k <= LEAF_RANKS and not any(b"\0" in s for s in seqs)
+    ranks = sum(len(s) for s in seqs) + k
+    if not 2 <= k <= WIDE_KMAX or any(b"\0" in s for s in seqs):
+        return False
+    return ranks <= LEAF_RANKS or (bool(large) and ranks <= min(int(large_max), SCAN_ROUND_RANKS))
 
 
 def shared_layout(pairs):
@@ -300,7 +314,7 @@ class Batch:
         for name in ("RV_MANY_KEEP", "RV_MANY_ROUND", "RV_MANY_WAVE_MAX", "RV_MANY_MULTI", "RV_MANY_LARGE", "RV_MANY_LARGE_MAX", "RV_MANY_LARGE_MIN",
                      "RV_MANY_LARGE_MULTI", "RV_MANY_LARGE_MULTI_MIN", "RV_MANY_WIDE", "RV_MANY_WIDE_LARGE_MIN", "RV_MANY_CHAIN", "RV_MANY_CHAIN_MULTI", "RV_MANY_CHAIN_WIDE",
                      "RV_MANY_CHAIN_LARGE", "RV_MANY_CHAIN_LARGE_MIN", "RV_MANY_CHAIN_LARGE_MULTI", "RV_MANY_CHAIN_LARGE_MULTI_MIN",
-                     "RV_MANY_CHAIN_WIDE_LARGE", "RV_MANY_CHAIN_WIDE_LARGE_MIN", "RV_MANY_SCAN_ORDINARY"):
+                     "RV_MANY_CHAIN_WIDE_LARGE", "RV_MANY_CHAIN_WIDE_LARGE_MIN", "RV_MANY_SCAN_ORDINARY", "RV_MANY_SCAN_LARGE", "RV_MANY_SCAN_LARGE_MIN"):
             v = os.environ.get(name)
             if v is not None and v.strip():
                 self.option(name, int(v))
@@ -501,14 +515,16 @@ class Matches:
         return (self[j] for j in range(len(self._pair)))
 
 
-def mums_many(jobs, minlength=20, minn=2, kind="auto", sa64=False, toupper=True, batch=None):
+def mums_many(jobs, minlength=20, minn=2, kind="auto", sa64=False, toupper=True, batch=None, large=None):
     """jobs: as for `align_many`.  -> (matches, info): the MUM / multi-MUM list of every job -- what `index.getmums(minlength)` (kind "mums"; for a
     job of more than two sequences: sample 0 against the rest) or `index.getmultimums(minlength, minn)` (kind "multimums") give a stand-alone index
     of the job, in its coordinates and emission order; kind "auto": getmums for the jobs of two sequences, getmultimums for the rest, as
     `reveal chain --recurse` asks per gap.  The jobs `takes_shared_scan` names share their launches (index build with the text in LDS, a count
     pass, a sum and a write pass over every job of a round at once); every other job runs the ordinary way inside the call.  matches: a `Matches`
     (`.arrays` = first, l, n, off, so, pos; matches[j] = the job's list in the reference's shapes); info = dict(jobs, shared, ordinary, rounds,
-    launches).  `batch`: a Batch to reuse."""
+    launches).  `batch`: a Batch to reuse.  `large`: True / False sets RV_MANY_SCAN_LARGE (the jobs of 2049 .. RV_MANY_LARGE_MAX ranks through shared
+    launches as well, their indices built by the segmented prefix doubling; `takes_shared_scan(.., large=True)`) for this and later scans of the
+    batch; None leaves it as the batch has it (off, unless the environment variable is set)."""
     if isinstance(jobs, (str, bytes, bytearray)) or not hasattr(jobs, "__iter__"):
         raise error("jobs is a list of jobs")
     if kind not in SCAN_KINDS:
@@ -517,6 +533,8 @@ def mums_many(jobs, minlength=20, minn=2, kind="auto", sa64=False, toupper=True,
         raise error("minlength >= 0")
     prepared = [job_sequences(j, toupper) for j in jobs]      # (argument errors before the library is asked for a device)
     b = batch if batch is not None else Batch(sa64)
+    if large is not None:
+        b.option("RV_MANY_SCAN_LARGE", 1 if large else 0)
     b.clear()
     for seqs in prepared:
         b.add(seqs)

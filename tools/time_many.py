@@ -5,7 +5,7 @@
                               [--seqs K] [--multi 0|1|ab] [--large 0|1|ab] [--large-multi 0|1|ab] [--large-max R] [--large-min J]
                               [--wide 0|1|ab] [--wide-large-min J] [--no-cut] [--sites] [--picker [--rem-jobs N]]
                               [--chain-wide [--save-digests FILE] [--compare-digests FILE]] [--chain-wide-large [--chain-wide-large-min J]]
-                              [--mums [--only many]]
+                              [--mums [--only many]] [--mums-large [--sweep]]
 
 Workload: J jobs of 2 x L bases, L uniform in lmin .. lmax, 1 % substitutions.  The two sides run alternately, `reps` times each:
   loop   rv_reset, rv_add_sample / rv_add_sequence x 2, rv_construct, rv_align_builtin, rv_fetch_anchors, the text -- per job, straight at
@@ -52,7 +52,11 @@ each, and this is how their results are compared.
 --mums (with --seqs K, 2 .. 64): the match lists instead of alignments -- Batch.add x J, scan (kind auto), matches -- on three legs run alternately in one
 process: the shared path, the same call with RV_MANY_SCAN_ORDINARY, and the loop through one reused handle (rv_reset, add, rv_construct, rv_getmums /
 rv_getmultimums, fetch: calls the commit before mums_many has too).  Medians, spreads, jobs per second, the gate (the shared median below the loop's by
-more than both spreads), then both sides at 1, 4, 16, 64 and 256 jobs.  --check compares the legs job by job.  Exit status 1 when the gate is missed."""
+more than both spreads), then both sides at 1, 4, 16, 64 and 256 jobs.  --check compares the legs job by job.  Exit status 1 when the gate is missed.
+--mums-large (with --seqs K, 2 .. 64; implies --no-cut; choose --lmin / --lmax so that K x (L + 1) lies above 2048): the same for jobs above 2048 ranks -- the shared
+path with RV_MANY_SCAN_LARGE on (RV_MANY_SCAN_LARGE_MIN 1), the same call with the switch off (every such job the ordinary way inside the call), and the loop through one
+reused handle, alternately in one process, every leg ending with its results on the host.  The gate: the shared median below the switch-off leg's by more than the larger
+of the two spreads.  --sweep: then shared against switch-off at 1, 2, 4, 8 and 16 jobs a call (the evidence for the default of RV_MANY_SCAN_LARGE_MIN)."""
 import argparse
 import ctypes
 import hashlib
@@ -309,6 +313,67 @@ def main_mums(a, jobs, bases):
     return 1 if out.get("check_bad_jobs") or not out["gate"] else 0
 
 
+def main_mums_large(a, jobs, bases):
+    """--mums-large: the match lists of jobs above 2048 ranks -- RV_MANY_SCAN_LARGE on, off, and the loop through one reused handle -- alternately in one
+    process; --sweep: on against off at 1 .. 16 jobs a call.  Every leg ends with its results on the host."""
+    from reveal_amd import many
+    idx = reveallib.index()
+    shared, off = many.Batch(False), many.Batch(False)
+    shared.option("RV_MANY_SCAN_LARGE", 1)
+    shared.option("RV_MANY_SCAN_LARGE_MIN", 1)
+    off.option("RV_MANY_SCAN_LARGE", 0)
+    legs = (("shared", lambda js: run_scan_c(shared, js, a.minlength)), ("off", lambda js: run_scan_c(off, js, a.minlength)),
+            ("loop", lambda js: run_scan_loop(idx, js, a.minlength)))
+    for _, f in legs:
+        f(jobs[:16])      # (first use: allocations, code objects)
+    t = {name: [] for name, _ in legs}
+    res = {}
+    for rep in range(a.reps):
+        for name, f in legs:
+            t0 = time.perf_counter(); res[name] = f(jobs); t[name].append(time.perf_counter() - t0)
+    ranks = [sum(len(s) for s in j) + len(j) for j in jobs]
+    out = dict(mode="mums-large", jobs=a.jobs, seqs=a.seqs, lmin=a.lmin, lmax=a.lmax, bases=bases, ranks_min=min(ranks), ranks_max=max(ranks), minlength=a.minlength, reps=a.reps)
+    for name, _ in legs:
+        out[name + "_s"] = t[name]; out[name + "_median_s"] = statistics.median(t[name]); out[name + "_spread_s"] = max(t[name]) - min(t[name])
+        print("%-8s: runs %s s; median %.4f s, spread (max - min) %.4f s, %.0f jobs/s"
+              % (name, " ".join("%.4f" % x for x in t[name]), out[name + "_median_s"], out[name + "_spread_s"], a.jobs / out[name + "_median_s"]))
+    out["shared_info"] = shared.info(); out["off_info"] = off.info()
+    out["matches"] = int(len(res["shared"][1])); out["members"] = int(len(res["shared"][5]))
+    out["ratio_off"] = out["off_median_s"] / out["shared_median_s"]; out["ratio_loop"] = out["loop_median_s"] / out["shared_median_s"]
+    out["gate"] = bool(out["off_median_s"] - out["shared_median_s"] > max(out["off_spread_s"], out["shared_spread_s"]))
+    print("shared against the switch-off leg: %.1f x (gain %.4f s against spreads of %.4f and %.4f s: gate %s); against the loop: %.1f x; %d .. %d ranks a job; %d matches, %d members; shared %r; off %r"
+          % (out["ratio_off"], out["off_median_s"] - out["shared_median_s"], out["off_spread_s"], out["shared_spread_s"], "met" if out["gate"] else "MISSED",
+             out["ratio_loop"], out["ranks_min"], out["ranks_max"], out["matches"], out["members"], out["shared_info"], out["off_info"]))
+    if a.check:
+        first, l, n, off_, so, pos = res["shared"]
+        same = all(np.array_equal(x, y) for x, y in zip(res["shared"], res["off"]))
+        bad = 0
+        for j, (ll, ln, lso, lpos) in enumerate(res["loop"]):
+            lo, hi = int(first[j]), int(first[j + 1])
+            bad += not (np.array_equal(l[lo:hi], ll) and np.array_equal(n[lo:hi], ln) and np.array_equal(so[off_[lo]:off_[hi]], lso) and np.array_equal(pos[off_[lo]:off_[hi]], lpos))
+        out["check_off_same"] = bool(same); out["check_bad_jobs"] = int(bad) + (0 if same else 1)
+        print("check : shared and switch-off arrays %s; %d of %d jobs differ between the shared leg and the loop" % ("identical" if same else "DIFFER", bad, a.jobs))
+    if a.sweep:
+        small = {}
+        for J in (1, 2, 4, 8, 16):
+            if J > len(jobs):
+                break
+            ts, to = [], []
+            for rep in range(max(a.reps, 9)):
+                js = jobs[rep * J:(rep + 1) * J] if (rep + 1) * J <= len(jobs) else jobs[:J]      # (other jobs every time: sizes vary 1 : 14)
+                t0 = time.perf_counter(); run_scan_c(shared, js, a.minlength); ts.append(time.perf_counter() - t0)
+                t0 = time.perf_counter(); run_scan_c(off, js, a.minlength); to.append(time.perf_counter() - t0)
+            small[J] = dict(shared_median_s=statistics.median(ts), shared_spread_s=max(ts) - min(ts), off_median_s=statistics.median(to), off_spread_s=max(to) - min(to))
+            print("%4d jobs: shared median %.6f s (spread %.6f), switch off median %.6f s (spread %.6f)" % (J, small[J]["shared_median_s"], small[J]["shared_spread_s"],
+                                                                                                          small[J]["off_median_s"], small[J]["off_spread_s"]))
+        out["sweep"] = small
+        ok = [J for J in small if all(small[K]["shared_median_s"] <= small[K]["off_median_s"] for K in small if K >= J)]
+        out["smallest_not_slower_jobs"] = min(ok) if ok else None
+        print("smallest job count from which the shared path is not slower: %s" % out["smallest_not_slower_jobs"])
+    print(json.dumps(out))
+    return 1 if out.get("check_bad_jobs") or not out["gate"] else 0
+
+
 def main_picker(a, jobs, bases):
     """the reference's default picker: RV_MANY_CHAIN on / off, the built-in picker beside them, rem.align per job"""
     from reveal_amd import many, rem, schemes
@@ -443,7 +508,12 @@ def main():
     ap.add_argument("--save-digests", default=None, help="--picker: write a digest per job of the picker side's anchors to this file")
     ap.add_argument("--compare-digests", default=None, help="--picker: count the jobs whose digest differs from this file's")
     ap.add_argument("--mums", action="store_true", help="the match lists (Batch.scan): the shared path, RV_MANY_SCAN_ORDINARY, and the loop through one handle")
+    ap.add_argument("--mums-large", action="store_true", help="the match lists of jobs above 2048 ranks: RV_MANY_SCAN_LARGE on, off, and the loop through one handle")
+    ap.add_argument("--sweep", action="store_true", help="--mums-large: then on against off at 1, 2, 4, 8 and 16 jobs a call")
     a = ap.parse_args()
+    if a.mums_large:
+        a.mums = True
+        a.no_cut = True
     if a.mums and (a.picker or a.chain_wide or a.chain_large or a.chain_large_multi or a.chain_wide_large or "ab" in (a.multi, a.large, a.large_multi, a.wide)):
         ap.error("--mums is a mode of its own")
     if a.chain_wide_large:
@@ -474,6 +544,8 @@ def main():
         ap.error("--large-multi wants jobs of three and more sequences: --seqs K")
     jobs = workload(a.jobs, a.lmin, a.lmax, seqs=a.seqs, cut=a.large_multi is None and not a.no_cut, sites=a.sites)
     bases = sum(len(s) for j in jobs for s in j)
+    if a.mums_large:
+        return main_mums_large(a, jobs, bases)
     if a.mums:
         return main_mums(a, jobs, bases)
     if a.picker:
