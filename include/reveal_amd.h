@@ -605,6 +605,24 @@ int rv_many_run(rv_many *m, int minl, int minn, rv_align_stats *total);
 int rv_many_scan(rv_many *m, int minl, int minn, int kind);
 int64_t rv_many_match_count(rv_many *m, int64_t *first, int64_t *members);
 int rv_many_fetch_matches(rv_many *m, uint32_t *l, int32_t *n, int64_t *off, uint16_t *so, int64_t *pos);
+/* The collinear chain of `reveal chain` (reveal/chain.py:214-314 chain()) for every job: rv_many_kchain scans as rv_many_scan does with kind 1 and minn =
+ * the job's number of sequences, and chains each list: the matches in all k sequences, capped at maxmums (0: no cap; the last maxmums of a stable sort by
+ * length over emission order), the k-dimensional chaining programme with gap cost model gcmodel (0 sumofpairs, 1 star-avg, 2 star-med) and weights wpen /
+ * wscore (0 .. 2^20; 64-bit scores), equal scores decided as the reference's kd-tree range search decides them.  A job of two sequences is chained from the
+ * multi-MUM shape (l, 2, ((0, a), (1, b))): the reference's getmums hands chain() a shape its filter drops entirely (the one deliberate departure).  The jobs
+ * of the scan's shared rounds are chained on the device (rv_kchain.hip k_many_kchain, one workgroup per job) when they hold at most 2048 members and
+ * RV_KCHAIN_CAP (at most 1024) records; any other job by rv_kchain on the host inside the call -- one the kernel gives back counts in rv_many_flagged under
+ * bit 4.  RV_MANY_KCHAIN_HOST (rv_many_option) sends every job through rv_kchain.  The live result is the last call's, as for rv_many_scan / rv_many_run.
+ *   rv_many_kchain_count -> nodes of all paths; first[0 .. jobs] (may be NULL): job j owns the nodes first[j] .. first[j+1]; *members: all positions
+ *   rv_many_kchain_fetch  l[node], score[node], pos[k per node, sequence order, relative to each sequence's begin], end_score[job]: the end sentinel's score
+ *                         (a job without a full match: -wpen gapcost(p1, p2))
+ *   rv_kchain   the host restatement for one job: records (l, n, off -> so / pos in the coordinates of the job's text s0$s1$..) and the k sequence lengths
+ *               in; the path without its sentinels out (room for nrec nodes); returns the nodes, < 0 on error */
+int rv_many_kchain(rv_many *m, int minl, int64_t maxmums, int64_t wpen, int64_t wscore, int gcmodel);
+int64_t rv_many_kchain_count(rv_many *m, int64_t *first, int64_t *members);
+int rv_many_kchain_fetch(rv_many *m, uint32_t *l, int64_t *score, int64_t *pos, int64_t *end_score);
+int64_t rv_kchain(int k, int64_t nrec, const uint32_t *l, const int32_t *n, const int64_t *off, const uint16_t *so, const int64_t *pos, const int64_t *lens,
+                  int64_t maxmums, int64_t wpen, int64_t wscore, int gcmodel, uint32_t *out_l, int64_t *out_pos, int64_t *out_score, int64_t *end_score);
 int64_t rv_many_anchor_count(rv_many *m, int64_t *first, int64_t *members);
 int rv_many_fetch(rv_many *m, uint32_t *l, int64_t *off, int64_t *pos);
 int64_t rv_many_text(rv_many *m, int64_t job, char *out, int64_t cap);

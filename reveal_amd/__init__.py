@@ -6,4 +6,4 @@ behind the reference's own `reveallib.index` API.
     from reveal_amd import reveallib          # 32-bit suffix arrays
     from reveal_amd import reveallib64        # 64-bit suffix arrays (`--64`)
 """
-__all__ = ["reveallib", "reveallib64", "rem"]
+__all__ = ["reveallib", "reveallib64", "rem", "kchain"]

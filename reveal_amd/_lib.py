@@ -180,6 +180,10 @@ SYMBOLS = {
     "rv_many_run": (_I, [V, _I, _I, ctypes.POINTER(RvAlignStats)]),
     "rv_many_scan": (_I, [V, _I, _I, _I]),
     "rv_many_match_count": (_L, [V, V, c_i64p]),
+    "rv_many_kchain": (_I, [V, _I, _L, _L, _L, _I]),
+    "rv_many_kchain_count": (_L, [V, V, c_i64p]),
+    "rv_many_kchain_fetch": (_I, [V, V, V, V, V]),
+    "rv_kchain": (_L, [_I, _L, V, V, V, V, V, V, _L, _L, _L, _I, V, V, V, V]),
     "rv_many_fetch_matches": (_I, [V, V, V, V, V, V]),
     "rv_many_anchor_count": (_L, [V, V, c_i64p]),
     "rv_many_fetch": (_I, [V, V, V, V]),

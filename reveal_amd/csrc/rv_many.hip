@@ -100,6 +100,7 @@
 #include "rv_leaf_multi.h"
 #include "rv_many_large.h"
 #include "rv_many_scan.h"
+#include "rv_kchain.h"
 #include <algorithm>
 #include <limits.h>
 #include <new>
@@ -272,6 +273,7 @@ struct ManyJob {
 };
 struct ManyRec { int job; u32 l; int np; int64_t p0; };
 struct ManyScanSlice { int64_t rec0 = 0, nrec = 0, mem0 = 0, nmem = 0; };      // a job's matches in the scratch of a scan
+struct ManyKchainSlice { bool done = false; int64_t node0 = 0, nnodes = 0, pos0 = 0, end = 0; };      // a job's chain in the scratch of rv_many_kchain
 
 }  // namespace
 
@@ -319,6 +321,15 @@ struct rv_many {
     // scratch of a scan: the lists as the rounds and the ordinary path deliver them, and every job's slice of them
     std::vector<ManyScanSlice> sc_job;
     std::vector<u32> sc_l; std::vector<int32_t> sc_n; std::vector<uint16_t> sc_so; std::vector<int64_t> sc_pos;
+    // rv_many_kchain: a scan (kind 1, minn = k per job) whose lists are chained where they lie; `chained` is live alone, as `ran` and `scanned` are
+    const RvKchainArgs *kc = nullptr;           // set while rv_many_kchain runs
+    bool kc_host = false;                       // RV_MANY_KCHAIN_HOST of that call
+    bool chained = false;
+    std::vector<int64_t> kch_first, kch_score, kch_pos, kch_end;
+    std::vector<u32> kch_l;
+    DBuf dKcStage, dKcJob, dKcOut;
+    std::vector<ManyKchainSlice> kc_job;        // scratch of the call
+    std::vector<u32> kc_l; std::vector<int64_t> kc_score, kc_pos;
 };
 
 namespace {
@@ -1013,7 +1024,7 @@ int many_ordinary(rv_many *m, int job, int minl, int minn, rv_align_stats *total
 
 int many_run(rv_many *m, int minl, int minn, rv_align_stats *total) {
     RV_HIP(hipSetDevice(m->device));
-    m->ran = false; m->scanned = false;
+    m->ran = false; m->scanned = false; m->chained = false;
     m->mt_first.clear(); m->mt_l.clear(); m->mt_n.clear(); m->mt_off.clear(); m->mt_so.clear(); m->mt_pos.clear();
     m->recs.clear(); m->rpos.clear(); m->out_text.clear(); m->keep_sa.clear(); m->keep_lcp.clear();
     for (int k = 0; k < 5; k++) m->info[k] = 0;
@@ -1261,7 +1272,7 @@ int many_round_scan(rv_many *m, const std::vector<int> &order, size_t lo, size_t
     R.SA = m->dSA.as<sa_t>(); R.LCP = m->dLCP.as<lcp_t>(); R.BWT = m->dBWT.as<uint8_t>(); R.m = n;
     R.off = m->dScanTab.as<int64_t>(); R.beg = R.off + J + 1;
     R.sfirst = (const int32_t *)(m->dScanTab.as<int64_t>() + n64); R.loc = R.sfirst + J + 1;
-    R.njobs = (int)J; R.nbeg = (int)nseq; R.minl = minl; R.minn = minn; R.kind = kind; R.err = d_words + 2;
+    R.njobs = (int)J; R.nbeg = (int)nseq; R.minl = minl; R.minn = minn; R.minn_k = m->kc ? 1 : 0; R.kind = kind; R.err = d_words + 2;
     RV_TRY(rv_many_scan_count(h->ws, R, m->dScanCnt.as<u64>(), m->dScanFirst.as<u64>(), &m->info[4]));
     std::vector<u64> first(J + 3, 0);
     RV_TRY(rv_read_back(h->ws, first.data(), m->dScanFirst.p, first_bytes + words_bytes));
@@ -1274,7 +1285,7 @@ int many_round_scan(rv_many *m, const std::vector<int> &order, size_t lo, size_t
     if (nrec > (u64)n || nmem > (u64)n * 64) { rv_set_error("rv_many_scan: more records than the round has room for"); return -1; }
     // records | pos | so | the write pass' error word
     const size_t o_pos = (size_t)nrec * sizeof(RvManyScanRec), o_so = o_pos + (size_t)nmem * sizeof(u32), o_err = (o_so + (size_t)nmem * sizeof(uint16_t) + 3) & ~(size_t)3;
-    std::vector<u64> out((o_err + 4 + 7) / 8, 0);      // (64-bit words: the records are read in place)
+    std::vector<u64> out;      // (64-bit words: the records are read in place)
     std::vector<sa_t> sa; std::vector<lcp_t> lc;
     if (nrec) {
         RV_TRY(m->dScanOut.reserve(o_err + 4));
@@ -1282,8 +1293,56 @@ int many_round_scan(rv_many *m, const std::vector<int> &order, size_t lo, size_t
         RV_HIP(hipMemsetAsync(d_out + o_err, 0, 4, q));
         R.err = (u32 *)(d_out + o_err);
         RV_TRY(rv_many_scan_write(h->ws, R, m->dScanCnt.as<u64>(), (RvManyScanRec *)d_out, nrec, (uint16_t *)(d_out + o_so), (u32 *)(d_out + o_pos), nmem, &m->info[4]));
-        RV_HIP(hipMemcpyAsync(out.data(), d_out, o_err + 4, hipMemcpyDeviceToHost, q));
     }
+    // rv_many_kchain: the chains on the device, from the records where the write pass has left them.  What comes back is the paths and a word per job;
+    // the records themselves only where a job is flagged for the host
+    const bool dev_chain = m->kc && !m->kc_host;
+    std::vector<u64> kjob;      // cfirst[J + 1] | end[J] | flag[J] (32 bits) | error word
+    std::vector<u64> kout;      // score[nodes] | l[nodes] | pos[nodes x k]
+    u64 knodes = 0, kmem = 0;
+    bool any_flag = false;
+    const size_t kj_end = (J + 1) * sizeof(u64), kj_flag = kj_end + J * sizeof(int64_t), kj_err = kj_flag + ((J + 1) / 2) * 8, kj_bytes = kj_err + 8;
+    if (dev_chain) {
+        char *d_out = (char *)m->dScanOut.p;
+        RV_TRY(m->dKcStage.reserve((size_t)std::max<u64>(nrec, 1) * (sizeof(int64_t) + sizeof(u32))));
+        RV_TRY(m->dKcJob.reserve(kj_bytes));
+        char *d_job = (char *)m->dKcJob.p;
+        RvKchainRound K;
+        K.rec = nrec ? (const RvManyScanRec *)d_out : nullptr; K.so = nrec ? (const uint16_t *)(d_out + o_so) : nullptr; K.pos = nrec ? (const u32 *)(d_out + o_pos) : nullptr;
+        K.nrec = nrec; K.nmem = nmem; K.first = m->dScanFirst.as<u64>();
+        K.stage_score = m->dKcStage.as<int64_t>(); K.stage_rec = (u32 *)(K.stage_score + std::max<u64>(nrec, 1));
+        K.nodes = m->dScanCnt.as<u64>();      // (the write pass has read its sums: the room is free, and a word per rank is what the chain's sum wants)
+        K.end = (int64_t *)(d_job + kj_end); K.flag = (u32 *)(d_job + kj_flag); K.err = (u32 *)(d_job + kj_err);
+        RV_HIP(hipMemsetAsync(K.nodes, 0, (size_t)(n + 1) * sizeof(u64), q));
+        RV_HIP(hipMemsetAsync(K.err, 0, 8, q));
+        RV_TRY(rv_many_kchain_run(h->ws, R, K, *m->kc, &m->info[4]));
+        RV_TRY(rv_exclusive_sum_u64(h->ws, K.nodes, K.nodes, n + 1));
+        m->info[4] += n + 1 <= 2048 ? 1 : n + 1 <= (int64_t)2048 * 2048 ? 3 : 5;
+        RV_TRY(rv_many_kchain_first(h->ws, R, K, (u64 *)d_job, &m->info[4]));
+        kjob.assign(kj_bytes / 8, 0);
+        RV_TRY(rv_read_back(h->ws, kjob.data(), d_job, kj_bytes));
+        u32 kerr = 0;
+        memcpy(&kerr, (const char *)kjob.data() + kj_err, 4);
+        if (kerr) { rv_set_error("rv_many_kchain: the chain kernel met a job outside its room (error bits %u: 1 descriptor, 2 member, 4 path)", kerr); return -1; }
+        knodes = kjob[J] >> RV_MANY_SCAN_MBITS; kmem = kjob[J] & mmask;
+        if (knodes > nrec || kmem > nmem) { rv_set_error("rv_many_kchain: more nodes than the round has records"); return -1; }
+        const u32 *kflag = (const u32 *)((const char *)kjob.data() + kj_flag);
+        for (size_t s = 0; s < J; s++) any_flag = any_flag || kflag[s] != 0;
+        if (knodes) {
+            const size_t ko_l = (size_t)knodes * sizeof(int64_t), ko_pos = ko_l + (size_t)knodes * sizeof(u32), ko_bytes = ko_pos + (size_t)kmem * sizeof(u32);
+            RV_TRY(m->dKcOut.reserve(ko_bytes));
+            char *d_ko = (char *)m->dKcOut.p;
+            RV_TRY(rv_many_kchain_write(h->ws, R, K, (const u64 *)d_job, (u32 *)(d_ko + ko_l), (int64_t *)d_ko, (u32 *)(d_ko + ko_pos), knodes, kmem, &m->info[4]));
+            kout.assign((ko_bytes + 7) / 8, 0);
+            RV_HIP(hipMemcpyAsync(kout.data(), d_ko, ko_bytes, hipMemcpyDeviceToHost, q));
+            RV_HIP(hipMemcpyAsync(kjob.data() + kj_err / 8, K.err, 8, hipMemcpyDeviceToHost, q));
+        }
+    }
+    const bool fetch = nrec && (!dev_chain || any_flag);
+    out.assign(((fetch ? o_err : 0) + 4 + 7) / 8, 0);
+    const size_t h_err = fetch ? o_err : 0;      // where the write pass' error word lands
+    if (fetch) RV_HIP(hipMemcpyAsync(out.data(), (char *)m->dScanOut.p, o_err + 4, hipMemcpyDeviceToHost, q));
+    else if (nrec) RV_HIP(hipMemcpyAsync(out.data(), (char *)m->dScanOut.p + o_err, 4, hipMemcpyDeviceToHost, q));
     if (m->keep) {
         sa.resize((size_t)n); lc.resize((size_t)n);
         RV_HIP(hipMemcpyAsync(sa.data(), m->dSA.p, (size_t)n * sizeof(sa_t), hipMemcpyDeviceToHost, q));
@@ -1292,15 +1351,50 @@ int many_round_scan(rv_many *m, const std::vector<int> &order, size_t lo, size_t
     RV_HIP(hipStreamSynchronize(q));
     const char *hout = (const char *)out.data();
     u32 werr = 0;
-    memcpy(&werr, hout + o_err, 4);
+    memcpy(&werr, hout + h_err, 4);
     if (werr) { rv_set_error("rv_many_scan: the write pass did not find what the count pass counted (error bits %u: 1 job, 2 position, 4 room)", werr); return -1; }
     const RvManyScanRec *rec = (const RvManyScanRec *)hout;
     const u32 *hpos = (const u32 *)(hout + o_pos);
     const uint16_t *hso = (const uint16_t *)(hout + o_so);
     const size_t kbase = m->keep_sa.size();
     if (m->keep) { m->keep_sa.resize(kbase + (size_t)n); m->keep_lcp.resize(kbase + (size_t)n); }
+    const u32 *kflag = dev_chain ? (const u32 *)((const char *)kjob.data() + kj_flag) : nullptr;
+    if (dev_chain) {
+        u32 kerr = 0;
+        memcpy(&kerr, (const char *)kjob.data() + kj_err, 4);
+        if (kerr) { rv_set_error("rv_many_kchain: the write kernel met a node outside its room (error bits %u: 1 descriptor, 2 member, 4 path)", kerr); return -1; }
+    }
     for (size_t s = 0; s < J; s++) {
         ManyJob &jb = m->jobs[(size_t)order[lo + s]];
+        if (dev_chain) {
+            // the job's path: nodes kjob[s] .. kjob[s + 1] of the round's CSR, or a flag word
+            if (kflag[s]) many_count_flags(m, kflag[s]);
+            else {
+                const u64 n0 = kjob[s] >> RV_MANY_SCAN_MBITS, n1 = kjob[s + 1] >> RV_MANY_SCAN_MBITS, p0 = kjob[s] & mmask, p1 = kjob[s + 1] & mmask;
+                if (n0 > n1 || n1 > knodes || p1 - p0 != (n1 - n0) * (u64)jb.k || p1 > kmem) { rv_set_error("rv_many_kchain: the sums of the chains do not add up"); return -1; }
+                ManyKchainSlice &ks = m->kc_job[(size_t)order[lo + s]];
+                ks.done = true; ks.node0 = (int64_t)m->kc_l.size(); ks.pos0 = (int64_t)m->kc_pos.size(); ks.nnodes = (int64_t)(n1 - n0);
+                ks.end = ((const int64_t *)((const char *)kjob.data() + kj_end))[s];
+                const int64_t *ksc = (const int64_t *)kout.data();
+                const u32 *kl = (const u32 *)(ksc + knodes), *kp = kl + knodes;
+                for (u64 x = n0; x < n1; x++) {
+                    m->kc_l.push_back(kl[x]); m->kc_score.push_back(ksc[x]);
+                    for (int d = 0; d < jb.k; d++) {
+                        const int64_t p = (int64_t)kp[p0 + (x - n0) * (u64)jb.k + (u64)d];
+                        if (p + kl[x] > m->lens[jb.seq0 + (size_t)d]) { rv_set_error("rv_many_kchain: a node outside its sequence"); return -1; }
+                        m->kc_pos.push_back(p);
+                    }
+                }
+            }
+        }
+        if (dev_chain && !kflag[s]) {      // (its records stay on the device)
+            jb.shared = true;
+            if (m->keep) {
+                jb.arr_off = (int64_t)kbase + t_off[s];
+                for (int64_t r = t_off[s]; r < t_off[s + 1]; r++) { m->keep_sa[kbase + (size_t)r] = (sa_t)(sa[(size_t)r] - (sa_t)t_off[s]); m->keep_lcp[kbase + (size_t)r] = lc[(size_t)r]; }
+            }
+            continue;
+        }
         const u64 r0 = first[s] >> RV_MANY_SCAN_MBITS, r1 = first[s + 1] >> RV_MANY_SCAN_MBITS, m0 = first[s] & mmask, m1 = first[s + 1] & mmask;
         if (r0 > r1 || r1 > nrec || m0 > m1 || m1 > nmem) { rv_set_error("rv_many_scan: the sums of the round do not increase"); return -1; }
         ManyScanSlice &sl = m->sc_job[(size_t)order[lo + s]];
@@ -1342,6 +1436,7 @@ int many_scan_ordinary(rv_many *m, int job, int minl, int minn, int kind) {
     sl.rec0 = (int64_t)m->sc_l.size(); sl.mem0 = (int64_t)m->sc_pos.size();
     // (rv_getmultimums refuses an index of two samples, as the reference's has no SO then; on such an index its records are getmums' -- one interval
     // of two ranks per MUM, the same side test and left-maximality -- with the members in SA order)
+    if (m->kc) minn = jb.k;
     const bool by_rank = !many_scan_pair_kind(kind, jb.k) && jb.k == 2;
     if (by_rank && minn > 2) {
         // (an interval of a pair index has two members)
@@ -1394,9 +1489,40 @@ int many_scan_ordinary(rv_many *m, int job, int minl, int minn, int kind) {
     return 0;
 }
 
-int many_scan(rv_many *m, int minl, int minn, int kind) {
+// a switch of RV_OPTION_LIST as rv_many_option has taken it for the internal handles: the last value given, or the default
+int64_t many_fwd_option(const rv_many *m, const char *name, int64_t def) {
+    for (const auto &o : m->fwd) if (o.first == name) def = o.second;
+    return def;
+}
+
+// a job rv_many_kchain chains on the host: rv_kchain on its list as the scan has delivered it
+int many_kchain_host(rv_many *m, int job) {
+    const ManyJob &jb = m->jobs[(size_t)job];
+    const ManyScanSlice &sl = m->sc_job[(size_t)job];
+    std::vector<int64_t> off((size_t)sl.nrec + 1, 0), opos((size_t)std::max<int64_t>(sl.nrec, 1) * jb.k), osc((size_t)std::max<int64_t>(sl.nrec, 1));
+    std::vector<u32> ol((size_t)std::max<int64_t>(sl.nrec, 1));
+    for (int64_t r = 0; r < sl.nrec; r++) off[(size_t)r + 1] = off[(size_t)r] + m->sc_n[(size_t)(sl.rec0 + r)];
+    if (off[(size_t)sl.nrec] != sl.nmem) { rv_set_error("rv_many_kchain: the members of a list do not add up"); return -1; }
+    int64_t end = 0;
+    const int64_t nn = rv_kchain(jb.k, sl.nrec, m->sc_l.data() + sl.rec0, m->sc_n.data() + sl.rec0, off.data(), m->sc_so.data() + sl.mem0, m->sc_pos.data() + sl.mem0,
+                                 m->lens.data() + jb.seq0, m->kc->maxmums, m->kc->wpen, m->kc->wscore, m->kc->gcmodel, ol.data(), opos.data(), osc.data(), &end);
+    if (nn < 0) return -1;
+    ManyKchainSlice &ks = m->kc_job[(size_t)job];
+    ks.done = true; ks.node0 = (int64_t)m->kc_l.size(); ks.pos0 = (int64_t)m->kc_pos.size(); ks.nnodes = nn; ks.end = end;
+    m->kc_l.insert(m->kc_l.end(), ol.begin(), ol.begin() + (ptrdiff_t)nn);
+    m->kc_score.insert(m->kc_score.end(), osc.begin(), osc.begin() + (ptrdiff_t)nn);
+    m->kc_pos.insert(m->kc_pos.end(), opos.begin(), opos.begin() + (ptrdiff_t)(nn * jb.k));
+    return 0;
+}
+
+// kc: rv_many_kchain -- the scan of kind 1 with minn = k per job, every list chained (on the device where it lies, or by rv_kchain) instead of handed out
+int many_scan(rv_many *m, int minl, int minn, int kind, const RvKchainArgs *kc = nullptr) {
     RV_HIP(hipSetDevice(m->device));
-    m->ran = false; m->scanned = false;
+    m->ran = false; m->scanned = false; m->chained = false;
+    m->kc = kc; m->kc_host = kc && many_fwd_option(m, "RV_MANY_KCHAIN_HOST", 0) != 0;
+    struct KcReset { rv_many *m; ~KcReset() { m->kc = nullptr; } } kc_reset{m};
+    m->kc_job.assign(kc ? m->jobs.size() : 0, ManyKchainSlice());
+    m->kc_l.clear(); m->kc_score.clear(); m->kc_pos.clear();
     m->an_first.clear(); m->an_l.clear(); m->an_off.clear(); m->an_pos.clear(); m->out_text.clear(); m->keep_sa.clear(); m->keep_lcp.clear();
     m->sc_l.clear(); m->sc_n.clear(); m->sc_so.clear(); m->sc_pos.clear();
     for (int k = 0; k < 5; k++) m->info[k] = 0;
@@ -1428,6 +1554,26 @@ int many_scan(rv_many *m, int minl, int minn, int kind) {
         }
     }
     for (int j : rest) RV_TRY(many_scan_ordinary(m, j, minl, minn, kind));
+    if (kc) {
+        // the chains job by job; what no round has chained is the host's
+        m->kch_first.assign((size_t)nj + 1, 0); m->kch_end.assign((size_t)nj, 0);
+        m->kch_l.clear(); m->kch_score.clear(); m->kch_pos.clear();
+        for (int j = 0; j < nj; j++) {
+            if (!m->kc_job[(size_t)j].done) RV_TRY(many_kchain_host(m, j));
+            const ManyKchainSlice &ks = m->kc_job[(size_t)j];
+            m->kch_first[(size_t)j + 1] = m->kch_first[(size_t)j] + ks.nnodes; m->kch_end[(size_t)j] = ks.end;
+            m->kch_l.insert(m->kch_l.end(), m->kc_l.begin() + (ptrdiff_t)ks.node0, m->kc_l.begin() + (ptrdiff_t)(ks.node0 + ks.nnodes));
+            m->kch_score.insert(m->kch_score.end(), m->kc_score.begin() + (ptrdiff_t)ks.node0, m->kc_score.begin() + (ptrdiff_t)(ks.node0 + ks.nnodes));
+        }
+        for (int j = 0; j < nj; j++) {
+            const ManyKchainSlice &ks = m->kc_job[(size_t)j];
+            m->kch_pos.insert(m->kch_pos.end(), m->kc_pos.begin() + (ptrdiff_t)ks.pos0, m->kc_pos.begin() + (ptrdiff_t)(ks.pos0 + ks.nnodes * m->jobs[(size_t)j].k));
+        }
+        m->sc_job.clear(); m->sc_l.clear(); m->sc_n.clear(); m->sc_so.clear(); m->sc_pos.clear();
+        m->kc_job.clear(); m->kc_l.clear(); m->kc_score.clear(); m->kc_pos.clear();
+        m->chained = true;
+        return 0;
+    }
     // the lists job by job
     m->mt_first.assign((size_t)nj + 1, 0);
     size_t nmem = 0;
@@ -1474,6 +1620,7 @@ void rv_many_free(rv_many *m) {
     if (m->ho) rv_free(m->ho);
     m->dJobs.release(); m->dKJobs.release(); m->dSA.release(); m->dLCP.release(); m->dBWT.release(); m->dCnt.release();
     m->dScanTab.release(); m->dScanCnt.release(); m->dScanFirst.release(); m->dScanOut.release();
+    m->dKcStage.release(); m->dKcJob.release(); m->dKcOut.release();
     m->dTxt.release(); m->dMJobs.release(); m->dAn.release(); m->dAnPos.release(); m->dFlag.release(); m->dBeg.release();
     m->large_bufs.release();
     delete m;
@@ -1546,7 +1693,7 @@ int64_t rv_many_add(rv_many *m, const char *const *seqs, const int64_t *lens, in
             m->in.insert(m->in.end(), seqs[s], seqs[s] + lens[s]);
         }
         m->jobs.push_back(jb);
-        m->ran = false; m->scanned = false;
+        m->ran = false; m->scanned = false; m->chained = false;
         return (int64_t)m->jobs.size() - 1;, -1)
 }
 
@@ -1555,7 +1702,8 @@ int rv_many_clear(rv_many *m) {
     m->in.clear(); m->lens.clear(); m->starts.clear(); m->jobs.clear();
     m->an_first.clear(); m->an_l.clear(); m->an_off.clear(); m->an_pos.clear(); m->out_text.clear(); m->keep_sa.clear(); m->keep_lcp.clear();
     m->mt_first.clear(); m->mt_l.clear(); m->mt_n.clear(); m->mt_off.clear(); m->mt_so.clear(); m->mt_pos.clear();
-    m->ran = false; m->scanned = false;
+    m->kch_first.clear(); m->kch_l.clear(); m->kch_score.clear(); m->kch_pos.clear(); m->kch_end.clear();
+    m->ran = false; m->scanned = false; m->chained = false;
     return 0;
 }
 
@@ -1569,6 +1717,33 @@ int rv_many_scan(rv_many *m, int minl, int minn, int kind) {
     if (kind < 0 || kind > 2) { rv_set_error("rv_many_scan: kind 0 (getmums), 1 (getmultimums) or 2 (getmums for the jobs of two sequences, getmultimums for the rest), not %d", kind); return -1; }
     if (minl < 0) { rv_set_error("rv_many_scan: a negative minimal length"); return -1; }
     MANY_GUARD(return many_scan(m, minl, minn, kind);, -1)
+}
+
+int rv_many_kchain(rv_many *m, int minl, int64_t maxmums, int64_t wpen, int64_t wscore, int gcmodel) {
+    if (!m) { rv_set_error("rv_many_kchain: null handle"); return -1; }
+    if (minl < 0 || maxmums < 0) { rv_set_error("rv_many_kchain: a negative minimal length or maxmums"); return -1; }
+    if (gcmodel < 0 || gcmodel > 2) { rv_set_error("rv_many_kchain: gap cost model 0 (sumofpairs), 1 (star-avg) or 2 (star-med)"); return -1; }
+    if (wpen < 0 || wpen > RV_KCHAIN_WMAX || wscore < 0 || wscore > RV_KCHAIN_WMAX) { rv_set_error("rv_many_kchain: weights of 0 .. 2^20 (64-bit scores)"); return -1; }
+    MANY_GUARD(
+        RvKchainArgs A;
+        A.maxmums = maxmums; A.wpen = wpen; A.wscore = wscore; A.gcmodel = gcmodel;
+        A.cap = (int)std::min<int64_t>(std::max<int64_t>(many_fwd_option(m, "RV_KCHAIN_CAP", RV_KCHAIN_CAP), 0), RV_KCHAIN_CAP);
+        return many_scan(m, minl, 2, 1, &A);, -1)
+}
+
+int64_t rv_many_kchain_count(rv_many *m, int64_t *first, int64_t *members) {
+    if (!m || !m->chained) { rv_set_error("rv_many_kchain_count: no finished rv_many_kchain (the live result is the last call's)"); return -1; }
+    if (first) for (size_t k = 0; k < m->kch_first.size(); k++) first[k] = m->kch_first[k];
+    if (members) *members = (int64_t)m->kch_pos.size();
+    return (int64_t)m->kch_l.size();
+}
+
+int rv_many_kchain_fetch(rv_many *m, uint32_t *l, int64_t *score, int64_t *pos, int64_t *end_score) {
+    if (!m || !m->chained || !l || !score || !pos || !end_score) { rv_set_error("rv_many_kchain_fetch: no finished rv_many_kchain, or null argument"); return -1; }
+    if (!m->kch_l.empty()) { memcpy(l, m->kch_l.data(), m->kch_l.size() * sizeof(u32)); memcpy(score, m->kch_score.data(), m->kch_score.size() * sizeof(int64_t)); }
+    if (!m->kch_pos.empty()) memcpy(pos, m->kch_pos.data(), m->kch_pos.size() * sizeof(int64_t));
+    if (!m->kch_end.empty()) memcpy(end_score, m->kch_end.data(), m->kch_end.size() * sizeof(int64_t));
+    return 0;
 }
 
 int64_t rv_many_match_count(rv_many *m, int64_t *first, int64_t *members) {
@@ -1627,7 +1802,7 @@ int rv_many_info(const rv_many *m, int64_t *out) {
 }
 
 int64_t rv_many_arrays(rv_many *m, int64_t job, int which, void *out, int64_t cap) {
-    if (!m || !(m->ran || m->scanned) || job < 0 || job >= (int64_t)m->jobs.size() || !out) { rv_set_error("rv_many_arrays: no finished run or scan, or no such job"); return -1; }
+    if (!m || !(m->ran || m->scanned || m->chained) || job < 0 || job >= (int64_t)m->jobs.size() || !out) { rv_set_error("rv_many_arrays: no finished run or scan, or no such job"); return -1; }
     const ManyJob &jb = m->jobs[(size_t)job];
     if (jb.arr_off < 0) { rv_set_error("rv_many_arrays: job %lld did not go through the shared launches with RV_MANY_KEEP set", (long long)job); return -2; }
     if (cap < jb.ranks) { rv_set_error("buffer too small"); return -1; }

@@ -12,6 +12,7 @@ struct RvManyScanRound {
     const int64_t *off; const int32_t *sfirst; const int64_t *beg; const int32_t *loc;
     int njobs, nbeg;
     int minl, minn, kind;      // kind 0: getmums, 1: getmultimums, 2: getmums for the jobs of two sequences, getmultimums for the rest
+    int minn_k;                // 1: every job's minn is its number of sequences (rv_many_kchain), whatever minn says
     u32 *err;                  // error bits: 1 a job descriptor outside the round, 2 a position outside its job's sequences, 4 a record outside the counted room
 };
 // a record of the lists: value, members, first member in so[] / pos[] (counted over the round)

@@ -85,7 +85,7 @@ __global__ __launch_bounds__(TB) void k_many_scan(RvManyScanRound R, u64 *__rest
                 while (lb > j0 && (u32)R.LCP[lb] >= cur) { lb--; if (u - lb + 1 > k) break; }
                 const int64_t n = u - lb + 1;
                 if (n > k || (u32)R.LCP[lb] >= cur) break;      // every further interval is larger still (or the segment does not begin with 0)
-                bool take = n >= R.minn;
+                bool take = n >= (R.minn_k ? (int64_t)k : (int64_t)R.minn);
                 if (take) {
                     if (k == 2) take = ((R.BWT[lb] ^ R.BWT[u]) & RV_BWT_SIDE) != 0;
                     else {

@@ -364,7 +364,7 @@ class Batch:
 
     def flagged(self):
         """-> {bit: jobs}: the jobs of the last run a round under a picker gave back to the ordinary path, by the bits of their flag words (1 trim_overlap
-        raises in the reference, 2 a broken chain, 8 twin offsets, 16 the RV_MANY_CHAIN_FLAG hook, 32 more candidates than a kernel's cap, 64 an interval
+        raises in the reference, 2 a broken chain, 4 a job `kchain_many`'s kernel gave back to the host's rv_kchain, 8 twin offsets, 16 the RV_MANY_CHAIN_FLAG hook, 32 more candidates than a kernel's cap, 64 an interval
         of 2^17 positions, 128 the host's picker gave up); bits no job set are left out"""
         o = (ctypes.c_int64 * 8)()
         self._dll.rv_many_flagged(self._m, o)

@@ -5,7 +5,7 @@
                               [--seqs K] [--multi 0|1|ab] [--large 0|1|ab] [--large-multi 0|1|ab] [--large-max R] [--large-min J]
                               [--wide 0|1|ab] [--wide-large-min J] [--no-cut] [--sites] [--picker [--rem-jobs N]]
                               [--chain-wide [--save-digests FILE] [--compare-digests FILE]] [--chain-wide-large [--chain-wide-large-min J]]
-                              [--mums [--only many]] [--mums-large [--sweep]]
+                              [--mums [--only many]] [--mums-large [--sweep]] [--kchain [--large-scan] [--python-jobs N]]
 
 Workload: J jobs of 2 x L bases, L uniform in lmin .. lmax, 1 % substitutions.  The two sides run alternately, `reps` times each:
   loop   rv_reset, rv_add_sample / rv_add_sequence x 2, rv_construct, rv_align_builtin, rv_fetch_anchors, the text -- per job, straight at
@@ -374,6 +374,79 @@ def main_mums_large(a, jobs, bases):
     return 1 if out.get("check_bad_jobs") or not out["gate"] else 0
 
 
+def run_kchain_c(batch, jobs, minl):
+    batch.clear()
+    for j in jobs:
+        batch.add(j)
+    batch.kchain(minl)
+    return batch.chains()
+
+
+def main_kchain(a, jobs, bases):
+    """--kchain: the collinear chain of every job (kchain.kchain_many's C part: Batch.add x J, kchain, chains) -- chained on the device, the same call with
+    RV_MANY_KCHAIN_HOST, and the means of a build without it: the scan of every job (kind multimums) with the lists taken apart on the host, then
+    kchain.kchain_python per job -- alternately in one process.  Every leg ends with its paths on the host.  --python-jobs N: kchain_python on the first N
+    jobs only (the scan still on all of them), its share scaled to all jobs and said so.  The D2H bytes are computed from the sizes of what each call
+    copies back (records 16 bytes, members 6; nodes 12, their positions 4, 20 bytes a job), not measured."""
+    from reveal_amd import kchain, many
+    dev, host, scan = many.Batch(False), many.Batch(False), many.Batch(False)
+    host.option("RV_MANY_KCHAIN_HOST", 1)
+    for b in (dev, host, scan):
+        if a.large_scan:
+            b.option("RV_MANY_SCAN_LARGE", 1)
+    npy = min(a.python_jobs if a.python_jobs is not None else len(jobs), len(jobs))
+
+    def run_python(js, count):
+        scan.clear()
+        for j in js:
+            scan.add(j)
+        scan.scan(a.minlength, 2, "multimums")
+        t1 = time.perf_counter()
+        m = many.Matches(scan.matches(), [False] * len(js))
+        paths = [kchain.kchain_python(m[j], [len(s) for s in js[j]]) for j in range(min(count, len(js)))]
+        return paths, time.perf_counter() - t1
+    legs = (("device", lambda js: run_kchain_c(dev, js, a.minlength)), ("host", lambda js: run_kchain_c(host, js, a.minlength)))
+    for _, f in legs:
+        f(jobs)      # (first use at full size: allocations, code objects)
+    run_python(jobs, 8)
+    t = {"device": [], "host": [], "python": []}
+    res = {}
+    for rep in range(a.reps):
+        for name, f in legs:
+            t0 = time.perf_counter(); res[name] = f(jobs); t[name].append(time.perf_counter() - t0)
+        t0 = time.perf_counter(); res["python"], tpy = run_python(jobs, npy); whole = time.perf_counter() - t0
+        t["python"].append(whole - tpy + tpy * len(jobs) / max(npy, 1))
+    out = dict(mode="kchain", jobs=a.jobs, seqs=a.seqs, lmin=a.lmin, lmax=a.lmax, bases=bases, minlength=a.minlength, reps=a.reps, large=bool(a.large_scan), python_jobs=npy)
+    for name in t:
+        out[name + "_s"] = t[name]; out[name + "_median_s"] = statistics.median(t[name]); out[name + "_spread_s"] = max(t[name]) - min(t[name])
+        print("%-8s: runs %s s; median %.4f s, spread (max - min) %.4f s, %.0f jobs/s%s"
+              % (name, " ".join("%.4f" % x for x in t[name]), out[name + "_median_s"], out[name + "_spread_s"], a.jobs / out[name + "_median_s"],
+                 "" if name != "python" or npy == len(jobs) else " (kchain_python on %d jobs, scaled)" % npy))
+    first, l, score, pos, end = res["device"]
+    out["device_info"] = dev.info(); out["host_info"] = host.info(); out["flagged"] = dev.flagged().get(kchain.KCHAIN_FLAG, 0)
+    out["nodes"] = int(len(l)); out["positions"] = int(len(pos))
+    mfirst, ml, mn, moff, mso, mpos = scan.matches()
+    out["records"] = int(len(ml)); out["members"] = int(len(mpos))
+    out["d2h_scan_bytes"] = out["records"] * 16 + out["members"] * 6 + (len(jobs) + 1) * 8
+    out["d2h_kchain_bytes"] = out["nodes"] * 12 + out["positions"] * 4 + len(jobs) * 20 + 2 * (len(jobs) + 1) * 8
+    gain = out["host_median_s"] - out["device_median_s"]
+    out["gate"] = bool(gain > max(out["host_spread_s"], out["device_spread_s"]))
+    same = all(np.array_equal(x, y) for x, y in zip(res["device"], res["host"]))
+    bad = 0
+    k_of = [len(j) for j in jobs]
+    ch = kchain.Chains(res["device"], k_of)
+    for j, (path, e) in enumerate(res["python"]):
+        bad += not (ch[j] == path and int(end[j]) == e)
+    out["check_host_same"] = bool(same); out["check_bad_jobs"] = int(bad) + (0 if same else 1)
+    print("device against RV_MANY_KCHAIN_HOST: %.2f x (gain %.4f s against spreads of %.4f and %.4f s: gate %s); against scan + kchain_python: %.1f x; %d nodes of %d records;"
+          " D2H %d bytes against the scan's %d; %d jobs flagged; device %r" % (out["host_median_s"] / out["device_median_s"], gain, out["host_spread_s"], out["device_spread_s"],
+                                                                             "met" if out["gate"] else "MISSED", out["python_median_s"] / out["device_median_s"], out["nodes"], out["records"],
+                                                                             out["d2h_kchain_bytes"], out["d2h_scan_bytes"], out["flagged"], out["device_info"]))
+    print("check : device and host arrays %s; %d of %d jobs differ between the device leg and kchain_python" % ("identical" if same else "DIFFER", bad, npy))
+    print(json.dumps(out))
+    return 1 if out["check_bad_jobs"] or not out["gate"] else 0
+
+
 def main_picker(a, jobs, bases):
     """the reference's default picker: RV_MANY_CHAIN on / off, the built-in picker beside them, rem.align per job"""
     from reveal_amd import many, rem, schemes
@@ -509,10 +582,15 @@ def main():
     ap.add_argument("--compare-digests", default=None, help="--picker: count the jobs whose digest differs from this file's")
     ap.add_argument("--mums", action="store_true", help="the match lists (Batch.scan): the shared path, RV_MANY_SCAN_ORDINARY, and the loop through one handle")
     ap.add_argument("--mums-large", action="store_true", help="the match lists of jobs above 2048 ranks: RV_MANY_SCAN_LARGE on, off, and the loop through one handle")
+    ap.add_argument("--kchain", action="store_true", help="the collinear chains (Batch.kchain): on the device, RV_MANY_KCHAIN_HOST, and scan + kchain_python per job")
+    ap.add_argument("--large-scan", action="store_true", help="--kchain: RV_MANY_SCAN_LARGE on in every leg (jobs above 2048 ranks)")
+    ap.add_argument("--python-jobs", type=int, default=None, help="--kchain: kchain_python on the first N jobs only, scaled")
     ap.add_argument("--sweep", action="store_true", help="--mums-large: then on against off at 1, 2, 4, 8 and 16 jobs a call")
     a = ap.parse_args()
     if a.mums_large:
         a.mums = True
+        a.no_cut = True
+    if a.kchain and a.large_scan:
         a.no_cut = True
     if a.mums and (a.picker or a.chain_wide or a.chain_large or a.chain_large_multi or a.chain_wide_large or "ab" in (a.multi, a.large, a.large_multi, a.wide)):
         ap.error("--mums is a mode of its own")
@@ -544,6 +622,8 @@ def main():
         ap.error("--large-multi wants jobs of three and more sequences: --seqs K")
     jobs = workload(a.jobs, a.lmin, a.lmax, seqs=a.seqs, cut=a.large_multi is None and not a.no_cut, sites=a.sites)
     bases = sum(len(s) for j in jobs for s in j)
+    if a.kchain:
+        return main_kchain(a, jobs, bases)
     if a.mums_large:
         return main_mums_large(a, jobs, bases)
     if a.mums:
