@@ -617,12 +617,29 @@ int rv_many_fetch_matches(rv_many *m, uint32_t *l, int32_t *n, int64_t *off, uin
  *   rv_many_kchain_fetch  l[node], score[node], pos[k per node, sequence order, relative to each sequence's begin], end_score[job]: the end sentinel's score
  *                         (a job without a full match: -wpen gapcost(p1, p2))
  *   rv_kchain   the host restatement for one job: records (l, n, off -> so / pos in the coordinates of the job's text s0$s1$..) and the k sequence lengths
- *               in; the path without its sentinels out (room for nrec nodes); returns the nodes, < 0 on error */
+ *               in; the path without its sentinels out (room for nrec nodes); returns the nodes, < 0 on error
+ * A list no round has chained (a flagged job, a job the scan runs the ordinary way) goes through one host preparation (the cap, the points, the order of the
+ * targets, the kd order).  With at least RV_KCHAIN_BIG_MIN kept points (default 512, 1 .. 1025) the programme then runs in device memory, tile by tile
+ * (rv_kchain_big.hip), all such lists of the call in the same launches -- unless the preparation refuses the list: a record of length 0, a coordinate shared
+ * by two points, a length or position beyond 31 bits or a point outside its sequence, more than 2^20 kept points or 2^24 members, more than 64 sequences,
+ * scores that might leave 64 bits.  Every other list runs the programme on the host.  RV_MANY_KCHAIN_BIG = 0 (rv_many_option) sends them all through
+ * rv_kchain, as does RV_MANY_KCHAIN_HOST.  The results do not depend on the path.
+ *   rv_many_kchain_big    out[0]: the lists of the last call the device programme chained; out[1]: its step launches (the tiles of the longest list)
+ *   rv_many_kchain_lists  chains lists the caller brings, with no scan: list x has k[x] sequences (lengths: the next k[x] entries of lens) and the next
+ *                         nrec[x] records of l / n / off, which index so / pos as rv_kchain's do (off: all records + 1 entries); results through
+ *                         rv_many_kchain_count / rv_many_kchain_fetch, first[0 .. nlists]
+ *   rv_kchain_admit       host only: why the preparation would refuse the list (bits: 1 length 0, 2 shared coordinate, 4 beyond 31 bits or outside its
+ *                         sequence, 8 too many points, 16 more than 64 sequences, 32 the score bound), 0: admitted, < 0 on error */
 int rv_many_kchain(rv_many *m, int minl, int64_t maxmums, int64_t wpen, int64_t wscore, int gcmodel);
 int64_t rv_many_kchain_count(rv_many *m, int64_t *first, int64_t *members);
 int rv_many_kchain_fetch(rv_many *m, uint32_t *l, int64_t *score, int64_t *pos, int64_t *end_score);
 int64_t rv_kchain(int k, int64_t nrec, const uint32_t *l, const int32_t *n, const int64_t *off, const uint16_t *so, const int64_t *pos, const int64_t *lens,
                   int64_t maxmums, int64_t wpen, int64_t wscore, int gcmodel, uint32_t *out_l, int64_t *out_pos, int64_t *out_score, int64_t *end_score);
+int rv_many_kchain_big(const rv_many *m, int64_t *out);
+int rv_many_kchain_lists(rv_many *m, int64_t nlists, const int32_t *k, const int64_t *nrec, const uint32_t *l, const int32_t *n, const int64_t *off, const uint16_t *so,
+                         const int64_t *pos, const int64_t *lens, int64_t maxmums, int64_t wpen, int64_t wscore, int gcmodel);
+int rv_kchain_admit(int k, int64_t nrec, const uint32_t *l, const int32_t *n, const int64_t *off, const int64_t *pos, const int64_t *lens, int64_t maxmums,
+                    int64_t wpen, int64_t wscore);
 int64_t rv_many_anchor_count(rv_many *m, int64_t *first, int64_t *members);
 int rv_many_fetch(rv_many *m, uint32_t *l, int64_t *off, int64_t *pos);
 int64_t rv_many_text(rv_many *m, int64_t job, char *out, int64_t cap);

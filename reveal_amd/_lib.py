@@ -184,6 +184,9 @@ SYMBOLS = {
     "rv_many_kchain_count": (_L, [V, V, c_i64p]),
     "rv_many_kchain_fetch": (_I, [V, V, V, V, V]),
     "rv_kchain": (_L, [_I, _L, V, V, V, V, V, V, _L, _L, _L, _I, V, V, V, V]),
+    "rv_many_kchain_big": (_I, [V, V]),
+    "rv_many_kchain_lists": (_I, [V, _L, V, V, V, V, V, V, V, V, _L, _L, _L, _I]),
+    "rv_kchain_admit": (_I, [_I, _L, V, V, V, V, V, _L, _L, _L]),
     "rv_many_fetch_matches": (_I, [V, V, V, V, V, V]),
     "rv_many_anchor_count": (_L, [V, V, c_i64p]),
     "rv_many_fetch": (_I, [V, V, V, V]),

@@ -115,7 +115,9 @@ void rv_set_error(const char *fmt, ...);
     X(decide_max_subs, "RV_DECIDE_MAX_SUBS", 65536) \
     X(pick_mchain_cap, "RV_PICK_MCHAIN_CAP", 512) \
     X(many_kchain_host, "RV_MANY_KCHAIN_HOST", 0) \
-    X(kchain_cap, "RV_KCHAIN_CAP", 1024)
+    X(kchain_cap, "RV_KCHAIN_CAP", 1024) \
+    X(many_kchain_big, "RV_MANY_KCHAIN_BIG", 1) \
+    X(kchain_big_min, "RV_KCHAIN_BIG_MIN", 512)
 struct RvOptions {
 #define RV_X_(f, name, def) int64_t f = def;
     RV_OPTION_LIST(RV_X_)

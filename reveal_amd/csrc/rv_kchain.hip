@@ -14,10 +14,13 @@
 //   stage 3  the targets one after another, the threads over the candidates, a reduction over (score, kd order); scores are 64-bit throughout
 //   stage 4  backtrack into a reversed path, staged as (record, score) in the room of the job's records
 // then the sum of the node counts over the RANKS of the round and k_kchain_write place the paths in CSR arrays.  A job of more than RV_KCHAIN_MEMBERS
-// members or RV_KCHAIN_CAP records, or with a coordinate shared by two points, is flagged (RV_KCHAIN_FLAG) and chained by rv_kchain on the host.
+// members or RV_KCHAIN_CAP records, or with a coordinate shared by two points, is flagged (RV_KCHAIN_FLAG) and chained from its fetched records: by the
+// programme in device memory (rv_kchain_big.hip) or on the host.  rv_kchain is three parts for that: kc_prepare (filter, cap, points, orders -- and why the
+// device programme would not take the list), kc_programme_host, kc_backtrack; the device leg shares the first and the last.
 #include "../../include/reveal_amd.h"
-#include "rv_kchain.h"
+#include "rv_kchain_big.h"
 #include <algorithm>
+#include <climits>
 #include <vector>
 
 namespace {
@@ -62,6 +65,117 @@ int kc_kd_order(const std::vector<int64_t> &P, int k, std::vector<int> pts, int 
 
 }  // namespace
 
+int kc_prepare(int k, int64_t nrec, const uint32_t *l, const int32_t *n, const int64_t *off, const int64_t *pos, const int64_t *lens, int64_t maxmums,
+               int64_t wpen, int64_t wscore, KcPrep &out) {
+    out = KcPrep();
+    out.k = k;
+    std::vector<int64_t> begin((size_t)k);
+    int64_t at = 0;
+    for (int d = 0; d < k; d++) { if (lens[d] < 0) { rv_set_error("rv_kchain: a negative length"); return -1; } begin[(size_t)d] = at; at += lens[d] + 1; }
+    // chain.py:236: the matches in all k sequences, in emission order
+    std::vector<int64_t> &kept = out.kept;
+    for (int64_t r = 0; r < nrec; r++) if (n[r] == k) {
+        if (off[r + 1] - off[r] != k) { rv_set_error("rv_kchain: a match of %d sequences with %lld members", k, (long long)(off[r + 1] - off[r])); return -1; }
+        kept.push_back(r);
+    }
+    // :238-245: stably sorted by length; the cap keeps the last maxmums of that
+    std::stable_sort(kept.begin(), kept.end(), [&](int64_t a, int64_t b) { return l[a] < l[b]; });
+    if ((int64_t)kept.size() > maxmums && maxmums != 0) kept.erase(kept.begin(), kept.end() - (ptrdiff_t)std::max<int64_t>(maxmums, 0));
+    if (kept.size() >= (size_t)INT_MAX / 2) { rv_set_error("rv_kchain: too many records"); return -1; }
+    const int m = out.m = (int)kept.size();
+    std::vector<int64_t> &P = out.P;
+    P.assign((size_t)(m + 1) * k, 0);
+    out.L.assign((size_t)m + 1, 0);
+    for (int d = 0; d < k; d++) P[(size_t)m * k + d] = lens[d];      // p2
+    if (m == 0) return 0;
+    // :249-257: a point = the sorted positions, each relative to its sequence's begin
+    std::vector<int64_t> tmp((size_t)k);
+    for (int i = 0; i < m; i++) {
+        for (int q = 0; q < k; q++) tmp[(size_t)q] = pos[off[kept[(size_t)i]] + q];
+        std::sort(tmp.begin(), tmp.end());
+        for (int d = 0; d < k; d++) P[(size_t)i * k + d] = tmp[(size_t)d] - begin[(size_t)d];
+        out.L[(size_t)i] = (int64_t)l[kept[(size_t)i]];
+    }
+    // :262-266: p2 appended, the list stably sorted by dimension 0, the tree over that list
+    std::vector<int> &order = out.order;
+    order.resize((size_t)m + 1);
+    for (int i = 0; i <= m; i++) order[(size_t)i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return P[(size_t)a * k] < P[(size_t)b * k]; });
+    RV_TRY(kc_kd_order(P, k, order, 0, out.kd));
+    // what the device programme does not take
+    int why = 0;
+    if (k > 64) why |= RV_KCHAIN_REFUSE_K;
+    if ((int64_t)m > RV_KCHAIN_BIG_CAP || ((int64_t)m + 1) * k > RV_KCHAIN_BIG_MEMBERS) why |= RV_KCHAIN_REFUSE_CAP;
+    const int64_t lim = (int64_t)1 << 31;
+    int64_t minlen = lens[0];
+    __int128 sumlen = 0;
+    for (int d = 0; d < k; d++) { if (lens[d] >= lim) why |= RV_KCHAIN_REFUSE_BITS; minlen = std::min(minlen, lens[d]); sumlen += (__int128)lens[d] + 1; }
+    for (int i = 0; i < m; i++) {
+        const int64_t li = out.L[(size_t)i];
+        if (li == 0) why |= RV_KCHAIN_REFUSE_L0;
+        if (li >= lim) why |= RV_KCHAIN_REFUSE_BITS;
+        for (int d = 0; d < k; d++) { const int64_t p = P[(size_t)i * k + d]; if (p < 0 || p >= lim || p + li > lens[d]) why |= RV_KCHAIN_REFUSE_BITS; }
+    }
+    std::vector<int64_t> col((size_t)m + 1);
+    for (int d = 0; d < k && !(why & RV_KCHAIN_REFUSE_SHARED); d++) {
+        for (int i = 0; i <= m; i++) col[(size_t)i] = P[(size_t)i * k + d];
+        std::sort(col.begin(), col.end());
+        if (std::adjacent_find(col.begin(), col.end()) != col.end()) why |= RV_KCHAIN_REFUSE_SHARED;
+    }
+    const __int128 pairs = (__int128)k * (k - 1) / 2;
+    const __int128 bound = (__int128)(wscore < 0 ? 0 : wscore) * pairs * minlen + (__int128)(wpen < 0 ? 0 : wpen) * pairs * sumlen;      // (rv_kchain.h derives it)
+    if (2 * bound >= (__int128)RV_KCHAIN_BIG_SCORE) why |= RV_KCHAIN_REFUSE_SCORE;
+    out.refuse = why;
+    return 0;
+}
+
+int64_t kc_empty_end(const KcPrep &pp, int64_t wpen, int gcmodel) {
+    std::vector<int64_t> p1((size_t)pp.k, -1), D;
+    return -wpen * kc_gapcost_host(p1.data(), pp.P.data() + (size_t)pp.m * pp.k, pp.k, gcmodel, D);
+}
+
+int kc_programme_host(const KcPrep &pp, int64_t wpen, int64_t wscore, int gcmodel, std::vector<int64_t> &score, std::vector<int> &back) {
+    const int k = pp.k, m = pp.m;
+    const std::vector<int64_t> &P = pp.P, &L = pp.L;
+    std::vector<int64_t> p1((size_t)k, -1), D;
+    score.assign((size_t)m + 1, 0);
+    back.assign((size_t)m + 1, -1);
+    std::vector<char> done((size_t)m + 1, 0);
+    const int64_t gain = (int64_t)k * (k - 1) / 2;
+    for (int t : pp.order) {      // :269-289
+        int best = -1;
+        int64_t bs = -wpen * kc_gapcost_host(p1.data(), &P[(size_t)t * k], k, gcmodel, D);
+        for (int v : pp.kd) {
+            if (v == t) continue;
+            bool adm = true;
+            for (int d = 0; d < k && adm; d++) adm = P[(size_t)v * k + d] <= P[(size_t)t * k + d] && P[(size_t)v * k + d] + L[(size_t)v] <= P[(size_t)t * k + d];
+            if (!adm) continue;
+            if (!done[(size_t)v] && v != m) { rv_set_error("rv_kchain: a candidate without a score (the reference raises KeyError here)"); return -1; }
+            const int64_t sc = score[(size_t)v] + wscore * (L[(size_t)v] * gain) - wpen * kc_gapcost_host(&P[(size_t)v * k], &P[(size_t)t * k], k, gcmodel, D);
+            if (sc > bs) { bs = sc; best = v; }
+        }
+        score[(size_t)t] = bs; back[(size_t)t] = best; done[(size_t)t] = 1;
+    }
+    return 0;
+}
+
+int64_t kc_backtrack(const KcPrep &pp, const std::vector<int64_t> &score, const std::vector<int> &back, uint32_t *out_l, int64_t *out_pos, int64_t *out_score,
+                     int64_t *end_score) {
+    const int k = pp.k, m = pp.m;
+    std::vector<int> path;
+    for (int v = back[(size_t)m]; v >= 0; v = back[(size_t)v]) {
+        if ((int)path.size() > m || v >= m) { rv_set_error("rv_kchain: broken back-pointer chain"); return -1; }
+        path.push_back(v);
+    }
+    std::reverse(path.begin(), path.end());
+    for (size_t x = 0; x < path.size(); x++) {
+        out_l[x] = (uint32_t)pp.L[(size_t)path[x]]; out_score[x] = score[(size_t)path[x]];
+        for (int d = 0; d < k; d++) out_pos[x * (size_t)k + d] = pp.P[(size_t)path[x] * k + d];
+    }
+    *end_score = score[(size_t)m];
+    return (int64_t)path.size();
+}
+
 extern "C" int64_t rv_kchain(int k, int64_t nrec, const uint32_t *l, const int32_t *n, const int64_t *off, const uint16_t *so, const int64_t *pos,
                              const int64_t *lens, int64_t maxmums, int64_t wpen, int64_t wscore, int gcmodel, uint32_t *out_l, int64_t *out_pos,
                              int64_t *out_score, int64_t *end_score) {
@@ -70,67 +184,25 @@ extern "C" int64_t rv_kchain(int k, int64_t nrec, const uint32_t *l, const int32
         return -1;
     }
     try {
-        std::vector<int64_t> begin((size_t)k), D;
-        int64_t at = 0;
-        for (int d = 0; d < k; d++) { if (lens[d] < 0) { rv_set_error("rv_kchain: a negative length"); return -1; } begin[(size_t)d] = at; at += lens[d] + 1; }
-        // chain.py:236: the matches in all k sequences, in emission order
-        std::vector<int64_t> kept;
-        for (int64_t r = 0; r < nrec; r++) if (n[r] == k) {
-            if (off[r + 1] - off[r] != k) { rv_set_error("rv_kchain: a match of %d sequences with %lld members", k, (long long)(off[r + 1] - off[r])); return -1; }
-            kept.push_back(r);
-        }
-        // :238-245: stably sorted by length; the cap keeps the last maxmums of that
-        std::stable_sort(kept.begin(), kept.end(), [&](int64_t a, int64_t b) { return l[a] < l[b]; });
-        if ((int64_t)kept.size() > maxmums && maxmums != 0) kept.erase(kept.begin(), kept.end() - (ptrdiff_t)std::max<int64_t>(maxmums, 0));
-        const int m = (int)kept.size();
-        std::vector<int64_t> p1((size_t)k, -1), P((size_t)(m + 1) * k);
-        for (int d = 0; d < k; d++) P[(size_t)m * k + d] = lens[d];      // p2
-        if (m == 0) { *end_score = -wpen * kc_gapcost_host(p1.data(), P.data(), k, gcmodel, D); return 0; }      // (chain() returns [p1, p2] and scores nothing)
-        // :249-257: a point = the sorted positions, each relative to its sequence's begin
-        std::vector<int64_t> tmp((size_t)k);
-        for (int i = 0; i < m; i++) {
-            for (int q = 0; q < k; q++) tmp[(size_t)q] = pos[off[kept[(size_t)i]] + q];
-            std::sort(tmp.begin(), tmp.end());
-            for (int d = 0; d < k; d++) P[(size_t)i * k + d] = tmp[(size_t)d] - begin[(size_t)d];
-        }
-        auto L = [&](int i) -> int64_t { return i < m ? (int64_t)l[kept[(size_t)i]] : 0; };
-        // :262-266: p2 appended, the list stably sorted by dimension 0, the tree over that list
-        std::vector<int> order((size_t)m + 1);
-        for (int i = 0; i <= m; i++) order[(size_t)i] = i;
-        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return P[(size_t)a * k] < P[(size_t)b * k]; });
-        std::vector<int> kd;
-        RV_TRY(kc_kd_order(P, k, order, 0, kd));
-        std::vector<int64_t> score((size_t)m + 1, 0);
-        std::vector<int> back((size_t)m + 1, -1);
-        std::vector<char> done((size_t)m + 1, 0);
-        const int64_t gain = (int64_t)k * (k - 1) / 2;
-        for (int t : order) {      // :269-289
-            int best = -1;
-            int64_t bs = -wpen * kc_gapcost_host(p1.data(), &P[(size_t)t * k], k, gcmodel, D);
-            for (int v : kd) {
-                if (v == t) continue;
-                bool adm = true;
-                for (int d = 0; d < k && adm; d++) adm = P[(size_t)v * k + d] <= P[(size_t)t * k + d] && P[(size_t)v * k + d] + L(v) <= P[(size_t)t * k + d];
-                if (!adm) continue;
-                if (!done[(size_t)v] && v != m) { rv_set_error("rv_kchain: a candidate without a score (the reference raises KeyError here)"); return -1; }
-                const int64_t sc = score[(size_t)v] + wscore * (L(v) * gain) - wpen * kc_gapcost_host(&P[(size_t)v * k], &P[(size_t)t * k], k, gcmodel, D);
-                if (sc > bs) { bs = sc; best = v; }
-            }
-            score[(size_t)t] = bs; back[(size_t)t] = best; done[(size_t)t] = 1;
-        }
-        std::vector<int> path;
-        for (int v = back[(size_t)m]; v >= 0; v = back[(size_t)v]) {
-            if ((int)path.size() > m || v == m) { rv_set_error("rv_kchain: broken back-pointer chain"); return -1; }
-            path.push_back(v);
-        }
-        std::reverse(path.begin(), path.end());
-        for (size_t x = 0; x < path.size(); x++) {
-            out_l[x] = (uint32_t)L(path[x]); out_score[x] = score[(size_t)path[x]];
-            for (int d = 0; d < k; d++) out_pos[x * (size_t)k + d] = P[(size_t)path[x] * k + d];
-        }
-        *end_score = score[(size_t)m];
-        return (int64_t)path.size();
+        KcPrep pp;
+        RV_TRY(kc_prepare(k, nrec, l, n, off, pos, lens, maxmums, wpen, wscore, pp));
+        if (pp.m == 0) { *end_score = kc_empty_end(pp, wpen, gcmodel); return 0; }      // (chain() returns [p1, p2] and scores nothing)
+        std::vector<int64_t> score;
+        std::vector<int> back;
+        RV_TRY(kc_programme_host(pp, wpen, wscore, gcmodel, score, back));
+        return kc_backtrack(pp, score, back, out_l, out_pos, out_score, end_score);
     } catch (const std::exception &e) { rv_set_error("rv_kchain: %s", e.what()); return -1; }
+}
+
+// why the device programme would leave this list to the host (RV_KCHAIN_REFUSE_* of rv_kchain.h; 0: it takes it); host only, no device is asked for
+extern "C" int rv_kchain_admit(int k, int64_t nrec, const uint32_t *l, const int32_t *n, const int64_t *off, const int64_t *pos, const int64_t *lens,
+                               int64_t maxmums, int64_t wpen, int64_t wscore) {
+    if (k < 2 || nrec < 0 || !lens || (nrec > 0 && (!l || !n || !off || !pos))) { rv_set_error("rv_kchain_admit: bad arguments"); return -1; }
+    try {
+        KcPrep pp;
+        RV_TRY(kc_prepare(k, nrec, l, n, off, pos, lens, maxmums, wpen, wscore, pp));
+        return pp.refuse;
+    } catch (const std::exception &e) { rv_set_error("rv_kchain_admit: %s", e.what()); return -1; }
 }
 
 // ---- device ----
@@ -152,32 +224,6 @@ struct KcShared {
     u32 rk[KTB / 64];
     int cnt;
 };
-
-// utils.gapcost; a == nullptr: p1 = (-1, ..)
-__device__ inline int64_t kc_gap(const u32 *a, const u32 *b, int k, int model) {
-#define KC_D(i) ((a ? (int64_t)a[i] : (int64_t)-1) - (int64_t)b[i])
-    if (model == 1) {
-        int64_t s = 0;
-        for (int i = 0; i < k; i++) s += KC_D(i);
-        return (s < 0 ? -s : s) / k;
-    }
-    if (model == 2) {      // sorted(D)[k / 2]: the value with k / 2 values in front of it, equal ones counted by index
-        for (int i = 0; i < k; i++) {
-            int64_t di = KC_D(i); di = di < 0 ? -di : di;
-            int before = 0;
-            for (int j = 0; j < k; j++) { int64_t dj = KC_D(j); dj = dj < 0 ? -dj : dj; before += (dj < di || (dj == di && j < i)) ? 1 : 0; }
-            if (before == k / 2) return di;
-        }
-        return 0;
-    }
-    int64_t p = 0;
-    for (int i = 0; i < k; i++) {
-        int64_t di = KC_D(i); di = di < 0 ? -di : di;
-        for (int j = i + 1; j < k; j++) { int64_t dj = KC_D(j); dj = dj < 0 ? -dj : dj; const int64_t d = di - dj; p += d < 0 ? -d : d; }
-    }
-    return p;
-#undef KC_D
-}
 
 __global__ __launch_bounds__(KTB) void k_many_kchain(RvManyScanRound R, RvKchainRound K, RvKchainArgs A) {
     __shared__ KcShared S;
@@ -290,7 +336,7 @@ __global__ __launch_bounds__(KTB) void k_many_kchain(RvManyScanRound R, RvKchain
             bool adm = true;
             for (int d = 0; d < k; d++) if (pv[d] + lv > pt[d]) { adm = false; break; }
             if (!adm) continue;      // (admissible: in front of t in dimension 0, so it has its score)
-            const int64_t sc = S.u.s3.score[v] + A.wscore * ((int64_t)lv * gain) - A.wpen * kc_gap(pv, pt, k, A.gcmodel);
+            const int64_t sc = S.u.s3.score[v] + A.wscore * ((int64_t)lv * gain) - A.wpen * kc_gap(KcStrided{pv, 1}, KcStrided{pt, 1}, k, A.gcmodel);
             const u32 key = (u32)S.kdr[v] << 16 | (u32)v;
             if (sc > bs || (sc == bs && key < bk)) { bs = sc; bk = key; }
         }
@@ -303,7 +349,7 @@ __global__ __launch_bounds__(KTB) void k_many_kchain(RvManyScanRound R, RvKchain
         __syncthreads();
         if (tid == 0) {
             for (int w = 1; w < KTB / 64; w++) if (S.rs[w] > bs || (S.rs[w] == bs && S.rk[w] < bk)) { bs = S.rs[w]; bk = S.rk[w]; }
-            const int64_t ps = -A.wpen * kc_gap(nullptr, pt, k, A.gcmodel);
+            const int64_t ps = -A.wpen * kc_gap(KcP1(), KcStrided{pt, 1}, k, A.gcmodel);
             const bool take = bk != 0xFFFFFFFFu && bs > ps;      // strict: p1 stays where nothing beats it
             S.u.s3.score[t] = take ? bs : ps;
             S.u.s3.back[t] = (uint16_t)(take ? (bk & 0xFFFFu) : KNONE);

@@ -100,7 +100,7 @@
 #include "rv_leaf_multi.h"
 #include "rv_many_large.h"
 #include "rv_many_scan.h"
-#include "rv_kchain.h"
+#include "rv_kchain_big.h"
 #include <algorithm>
 #include <limits.h>
 #include <new>
@@ -328,6 +328,8 @@ struct rv_many {
     std::vector<int64_t> kch_first, kch_score, kch_pos, kch_end;
     std::vector<u32> kch_l;
     DBuf dKcStage, dKcJob, dKcOut;
+    RvKchainBigBufs kc_big_bufs;                // the device programme for the lists no round has chained (rv_kchain_big.hip)
+    int64_t kc_big[2] = {0, 0};                 // rv_many_kchain_big: the lists of the last call it chained, its step launches
     std::vector<ManyKchainSlice> kc_job;        // scratch of the call
     std::vector<u32> kc_l; std::vector<int64_t> kc_score, kc_pos;
 };
@@ -1495,27 +1497,97 @@ int64_t many_fwd_option(const rv_many *m, const char *name, int64_t def) {
     return def;
 }
 
-// a job rv_many_kchain chains on the host: rv_kchain on its list as the scan has delivered it
-int many_kchain_host(rv_many *m, int job) {
-    const ManyJob &jb = m->jobs[(size_t)job];
-    const ManyScanSlice &sl = m->sc_job[(size_t)job];
-    std::vector<int64_t> off((size_t)sl.nrec + 1, 0), opos((size_t)std::max<int64_t>(sl.nrec, 1) * jb.k), osc((size_t)std::max<int64_t>(sl.nrec, 1));
-    std::vector<u32> ol((size_t)std::max<int64_t>(sl.nrec, 1));
-    for (int64_t r = 0; r < sl.nrec; r++) off[(size_t)r + 1] = off[(size_t)r] + m->sc_n[(size_t)(sl.rec0 + r)];
-    if (off[(size_t)sl.nrec] != sl.nmem) { rv_set_error("rv_many_kchain: the members of a list do not add up"); return -1; }
-    int64_t end = 0;
-    const int64_t nn = rv_kchain(jb.k, sl.nrec, m->sc_l.data() + sl.rec0, m->sc_n.data() + sl.rec0, off.data(), m->sc_so.data() + sl.mem0, m->sc_pos.data() + sl.mem0,
-                                 m->lens.data() + jb.seq0, m->kc->maxmums, m->kc->wpen, m->kc->wscore, m->kc->gcmodel, ol.data(), opos.data(), osc.data(), &end);
-    if (nn < 0) return -1;
-    ManyKchainSlice &ks = m->kc_job[(size_t)job];
+// a list rv_many_kchain has to chain outside the rounds: rv_kchain's arguments and where the path goes
+struct ManyKchainSrc {
+    int k; int64_t nrec; const u32 *l; const int32_t *n; const int64_t *off; const uint16_t *so; const int64_t *pos; const int64_t *lens;
+    ManyKchainSlice *out;
+};
+
+void many_kchain_store(rv_many *m, const ManyKchainSrc &s, int64_t nn, const u32 *ol, const int64_t *osc, const int64_t *opos, int64_t end) {
+    ManyKchainSlice &ks = *s.out;
     ks.done = true; ks.node0 = (int64_t)m->kc_l.size(); ks.pos0 = (int64_t)m->kc_pos.size(); ks.nnodes = nn; ks.end = end;
-    m->kc_l.insert(m->kc_l.end(), ol.begin(), ol.begin() + (ptrdiff_t)nn);
-    m->kc_score.insert(m->kc_score.end(), osc.begin(), osc.begin() + (ptrdiff_t)nn);
-    m->kc_pos.insert(m->kc_pos.end(), opos.begin(), opos.begin() + (ptrdiff_t)(nn * jb.k));
+    m->kc_l.insert(m->kc_l.end(), ol, ol + nn);
+    m->kc_score.insert(m->kc_score.end(), osc, osc + nn);
+    m->kc_pos.insert(m->kc_pos.end(), opos, opos + nn * s.k);
+}
+
+// The lists no round has chained.  With RV_MANY_KCHAIN_HOST, or RV_MANY_KCHAIN_BIG at 0, rv_kchain on each.  Otherwise one preparation per list
+// (kc_prepare); the lists it admits with at least RV_KCHAIN_BIG_MIN kept points are chained together by the device programme (rv_kchain_big.hip), the
+// rest by the host programme; one backtrack for both.
+int many_kchain_rest(rv_many *m, const std::vector<ManyKchainSrc> &src, const RvKchainArgs &A) {
+    const bool big = !m->kc_host && many_fwd_option(m, "RV_MANY_KCHAIN_BIG", 1) != 0;
+    const int64_t big_min = std::min<int64_t>(std::max<int64_t>(many_fwd_option(m, "RV_KCHAIN_BIG_MIN", RV_KCHAIN_BIG_MIN_DEFAULT), 1), RV_KCHAIN_CAP + 1);
+    std::vector<u32> ol;
+    std::vector<int64_t> opos, osc;
+    auto room = [&](const ManyKchainSrc &s) {
+        const size_t nr = (size_t)std::max<int64_t>(s.nrec, 1);
+        if (ol.size() < nr) { ol.resize(nr); osc.resize(nr); }
+        if (opos.size() < nr * (size_t)s.k) opos.resize(nr * (size_t)s.k);
+    };
+    if (!big) {
+        for (const ManyKchainSrc &s : src) {
+            room(s);
+            int64_t end = 0;
+            const int64_t nn = rv_kchain(s.k, s.nrec, s.l, s.n, s.off, s.so, s.pos, s.lens, A.maxmums, A.wpen, A.wscore, A.gcmodel, ol.data(), opos.data(), osc.data(), &end);
+            if (nn < 0) return -1;
+            many_kchain_store(m, s, nn, ol.data(), osc.data(), opos.data(), end);
+        }
+        return 0;
+    }
+    std::vector<KcPrep> prep(src.size());
+    std::vector<const KcPrep *> dev;
+    std::vector<size_t> dev_src;
+    std::vector<int64_t> score;
+    std::vector<int> back;
+    for (size_t x = 0; x < src.size(); x++) {
+        const ManyKchainSrc &s = src[x];
+        room(s);
+        KcPrep &pp = prep[x];
+        RV_TRY(kc_prepare(s.k, s.nrec, s.l, s.n, s.off, s.pos, s.lens, A.maxmums, A.wpen, A.wscore, pp));
+        if (pp.m == 0) { many_kchain_store(m, s, 0, ol.data(), osc.data(), opos.data(), kc_empty_end(pp, A.wpen, A.gcmodel)); continue; }
+        if (!pp.refuse && pp.m >= big_min) { dev.push_back(&pp); dev_src.push_back(x); continue; }
+        RV_TRY(kc_programme_host(pp, A.wpen, A.wscore, A.gcmodel, score, back));
+        int64_t end = 0;
+        const int64_t nn = kc_backtrack(pp, score, back, ol.data(), opos.data(), osc.data(), &end);
+        if (nn < 0) return -1;
+        many_kchain_store(m, s, nn, ol.data(), osc.data(), opos.data(), end);
+        pp = KcPrep();
+    }
+    if (dev.empty()) return 0;
+    RV_TRY(many_handle(m, &m->hs));
+    std::vector<std::vector<int64_t>> dscore;
+    std::vector<std::vector<int>> dback;
+    RV_TRY(rv_kchain_big_run(m->hs->ws, m->kc_big_bufs, dev, A.wpen, A.wscore, A.gcmodel, dscore, dback, &m->kc_big[1]));
+    for (size_t y = 0; y < dev.size(); y++) {
+        const ManyKchainSrc &s = src[dev_src[y]];
+        int64_t end = 0;
+        const int64_t nn = kc_backtrack(*dev[y], dscore[y], dback[y], ol.data(), opos.data(), osc.data(), &end);
+        if (nn < 0) return -1;
+        many_kchain_store(m, s, nn, ol.data(), osc.data(), opos.data(), end);
+    }
+    m->kc_big[0] += (int64_t)dev.size();
+    m->info[4] += m->kc_big[1];
     return 0;
 }
 
-// kc: rv_many_kchain -- the scan of kind 1 with minn = k per job, every list chained (on the device where it lies, or by rv_kchain) instead of handed out
+// the results of rv_many_kchain / rv_many_kchain_lists from the slices, list by list (k: sequences of each)
+void many_kchain_collect(rv_many *m, const std::vector<ManyKchainSlice> &slices, const std::vector<int> &ks) {
+    const size_t nj = slices.size();
+    m->kch_first.assign(nj + 1, 0); m->kch_end.assign(nj, 0);
+    m->kch_l.clear(); m->kch_score.clear(); m->kch_pos.clear();
+    for (size_t j = 0; j < nj; j++) {
+        const ManyKchainSlice &ks_ = slices[j];
+        m->kch_first[j + 1] = m->kch_first[j] + ks_.nnodes; m->kch_end[j] = ks_.end;
+        m->kch_l.insert(m->kch_l.end(), m->kc_l.begin() + (ptrdiff_t)ks_.node0, m->kc_l.begin() + (ptrdiff_t)(ks_.node0 + ks_.nnodes));
+        m->kch_score.insert(m->kch_score.end(), m->kc_score.begin() + (ptrdiff_t)ks_.node0, m->kc_score.begin() + (ptrdiff_t)(ks_.node0 + ks_.nnodes));
+    }
+    for (size_t j = 0; j < nj; j++) {
+        const ManyKchainSlice &ks_ = slices[j];
+        m->kch_pos.insert(m->kch_pos.end(), m->kc_pos.begin() + (ptrdiff_t)ks_.pos0, m->kc_pos.begin() + (ptrdiff_t)(ks_.pos0 + ks_.nnodes * ks[j]));
+    }
+}
+
+// kc: rv_many_kchain -- the scan of kind 1 with minn = k per job, every list chained (on the device where it lies, or by many_kchain_rest) instead of handed out
 int many_scan(rv_many *m, int minl, int minn, int kind, const RvKchainArgs *kc = nullptr) {
     RV_HIP(hipSetDevice(m->device));
     m->ran = false; m->scanned = false; m->chained = false;
@@ -1527,6 +1599,7 @@ int many_scan(rv_many *m, int minl, int minn, int kind, const RvKchainArgs *kc =
     m->sc_l.clear(); m->sc_n.clear(); m->sc_so.clear(); m->sc_pos.clear();
     for (int k = 0; k < 5; k++) m->info[k] = 0;
     for (int k = 0; k < 8; k++) m->flagged[k] = 0;
+    m->kc_big[0] = m->kc_big[1] = 0;
     const int nj = (int)m->jobs.size();
     m->info[0] = nj;
     m->sc_job.assign((size_t)nj, ManyScanSlice());
@@ -1555,20 +1628,24 @@ int many_scan(rv_many *m, int minl, int minn, int kind, const RvKchainArgs *kc =
     }
     for (int j : rest) RV_TRY(many_scan_ordinary(m, j, minl, minn, kind));
     if (kc) {
-        // the chains job by job; what no round has chained is the host's
-        m->kch_first.assign((size_t)nj + 1, 0); m->kch_end.assign((size_t)nj, 0);
-        m->kch_l.clear(); m->kch_score.clear(); m->kch_pos.clear();
-        for (int j = 0; j < nj; j++) {
-            if (!m->kc_job[(size_t)j].done) RV_TRY(many_kchain_host(m, j));
-            const ManyKchainSlice &ks = m->kc_job[(size_t)j];
-            m->kch_first[(size_t)j + 1] = m->kch_first[(size_t)j] + ks.nnodes; m->kch_end[(size_t)j] = ks.end;
-            m->kch_l.insert(m->kch_l.end(), m->kc_l.begin() + (ptrdiff_t)ks.node0, m->kc_l.begin() + (ptrdiff_t)(ks.node0 + ks.nnodes));
-            m->kch_score.insert(m->kch_score.end(), m->kc_score.begin() + (ptrdiff_t)ks.node0, m->kc_score.begin() + (ptrdiff_t)(ks.node0 + ks.nnodes));
+        // the chains job by job; what no round has chained goes to the device programme or to the host
+        std::vector<ManyKchainSrc> src;
+        std::vector<std::vector<int64_t>> offs;
+        for (int j = 0; j < nj; j++) if (!m->kc_job[(size_t)j].done) {
+            const ManyJob &jb = m->jobs[(size_t)j];
+            const ManyScanSlice &sl = m->sc_job[(size_t)j];
+            offs.emplace_back((size_t)sl.nrec + 1, 0);
+            std::vector<int64_t> &off = offs.back();
+            for (int64_t r = 0; r < sl.nrec; r++) off[(size_t)r + 1] = off[(size_t)r] + m->sc_n[(size_t)(sl.rec0 + r)];
+            if (off[(size_t)sl.nrec] != sl.nmem) { rv_set_error("rv_many_kchain: the members of a list do not add up"); return -1; }
+            src.push_back({jb.k, sl.nrec, m->sc_l.data() + sl.rec0, m->sc_n.data() + sl.rec0, nullptr, m->sc_so.data() + sl.mem0, m->sc_pos.data() + sl.mem0,
+                           m->lens.data() + jb.seq0, &m->kc_job[(size_t)j]});
         }
-        for (int j = 0; j < nj; j++) {
-            const ManyKchainSlice &ks = m->kc_job[(size_t)j];
-            m->kch_pos.insert(m->kch_pos.end(), m->kc_pos.begin() + (ptrdiff_t)ks.pos0, m->kc_pos.begin() + (ptrdiff_t)(ks.pos0 + ks.nnodes * m->jobs[(size_t)j].k));
-        }
+        for (size_t x = 0; x < src.size(); x++) src[x].off = offs[x].data();
+        RV_TRY(many_kchain_rest(m, src, *kc));
+        std::vector<int> ks((size_t)nj);
+        for (int j = 0; j < nj; j++) ks[(size_t)j] = m->jobs[(size_t)j].k;
+        many_kchain_collect(m, m->kc_job, ks);
         m->sc_job.clear(); m->sc_l.clear(); m->sc_n.clear(); m->sc_so.clear(); m->sc_pos.clear();
         m->kc_job.clear(); m->kc_l.clear(); m->kc_score.clear(); m->kc_pos.clear();
         m->chained = true;
@@ -1620,7 +1697,7 @@ void rv_many_free(rv_many *m) {
     if (m->ho) rv_free(m->ho);
     m->dJobs.release(); m->dKJobs.release(); m->dSA.release(); m->dLCP.release(); m->dBWT.release(); m->dCnt.release();
     m->dScanTab.release(); m->dScanCnt.release(); m->dScanFirst.release(); m->dScanOut.release();
-    m->dKcStage.release(); m->dKcJob.release(); m->dKcOut.release();
+    m->dKcStage.release(); m->dKcJob.release(); m->dKcOut.release(); m->kc_big_bufs.release();
     m->dTxt.release(); m->dMJobs.release(); m->dAn.release(); m->dAnPos.release(); m->dFlag.release(); m->dBeg.release();
     m->large_bufs.release();
     delete m;
@@ -1729,6 +1806,49 @@ int rv_many_kchain(rv_many *m, int minl, int64_t maxmums, int64_t wpen, int64_t 
         A.maxmums = maxmums; A.wpen = wpen; A.wscore = wscore; A.gcmodel = gcmodel;
         A.cap = (int)std::min<int64_t>(std::max<int64_t>(many_fwd_option(m, "RV_KCHAIN_CAP", RV_KCHAIN_CAP), 0), RV_KCHAIN_CAP);
         return many_scan(m, minl, 2, 1, &A);, -1)
+}
+
+int rv_many_kchain_big(const rv_many *m, int64_t *out) {
+    if (!m || !out) { rv_set_error("rv_many_kchain_big: null argument"); return -1; }
+    out[0] = m->kc_big[0]; out[1] = m->kc_big[1];
+    return 0;
+}
+
+int rv_many_kchain_lists(rv_many *m, int64_t nlists, const int32_t *k, const int64_t *nrec, const uint32_t *l, const int32_t *n, const int64_t *off, const uint16_t *so,
+                         const int64_t *pos, const int64_t *lens, int64_t maxmums, int64_t wpen, int64_t wscore, int gcmodel) {
+    if (!m || nlists < 0 || (nlists > 0 && (!k || !nrec || !lens || !off))) { rv_set_error("rv_many_kchain_lists: null handle or argument"); return -1; }
+    if (maxmums < 0) { rv_set_error("rv_many_kchain_lists: a negative maxmums"); return -1; }
+    if (gcmodel < 0 || gcmodel > 2) { rv_set_error("rv_many_kchain_lists: gap cost model 0 (sumofpairs), 1 (star-avg) or 2 (star-med)"); return -1; }
+    if (wpen < 0 || wpen > RV_KCHAIN_WMAX || wscore < 0 || wscore > RV_KCHAIN_WMAX) { rv_set_error("rv_many_kchain_lists: weights of 0 .. 2^20 (64-bit scores)"); return -1; }
+    MANY_GUARD(
+        RV_HIP(hipSetDevice(m->device));
+        m->ran = false; m->scanned = false; m->chained = false;
+        for (int x = 0; x < 5; x++) m->info[x] = 0;
+        for (int x = 0; x < 8; x++) m->flagged[x] = 0;
+        m->kc_big[0] = m->kc_big[1] = 0;
+        m->info[0] = nlists;
+        m->kc_host = many_fwd_option(m, "RV_MANY_KCHAIN_HOST", 0) != 0;
+        m->kc_l.clear(); m->kc_score.clear(); m->kc_pos.clear();
+        RvKchainArgs A;
+        A.maxmums = maxmums; A.wpen = wpen; A.wscore = wscore; A.gcmodel = gcmodel; A.cap = 0;
+        std::vector<ManyKchainSlice> slices((size_t)nlists);
+        std::vector<ManyKchainSrc> src;
+        std::vector<int> ks((size_t)nlists);
+        int64_t r0 = 0; int64_t s0 = 0;
+        for (int64_t x = 0; x < nlists; x++) {
+            if (k[x] < 2 || nrec[x] < 0) { rv_set_error("rv_many_kchain_lists: list %lld has %d sequences and %lld records", (long long)x, k[x], (long long)nrec[x]); return -1; }
+            if (nrec[x] > 0 && (!l || !n || !so || !pos)) { rv_set_error("rv_many_kchain_lists: records without their arrays"); return -1; }
+            for (int64_t r = r0; r < r0 + nrec[x]; r++) if (off[r] < 0 || off[r] > off[r + 1]) { rv_set_error("rv_many_kchain_lists: offsets that do not ascend"); return -1; }
+            // (rv_kchain's offsets index pos / so as given: each list keeps the whole arrays and its own stretch of the records)
+            src.push_back({k[x], nrec[x], l ? l + r0 : nullptr, n ? n + r0 : nullptr, off + r0, so, pos, lens + s0, &slices[(size_t)x]});
+            ks[(size_t)x] = k[x];
+            r0 += nrec[x]; s0 += k[x];
+        }
+        RV_TRY(many_kchain_rest(m, src, A));
+        many_kchain_collect(m, slices, ks);
+        m->kc_l.clear(); m->kc_score.clear(); m->kc_pos.clear();
+        m->chained = true;
+        return 0;, -1)
 }
 
 int64_t rv_many_kchain_count(rv_many *m, int64_t *first, int64_t *members) {

@@ -4,7 +4,10 @@
 (chain.py:214-314): the matches in all k sequences, capped at maxmums, a k-dimensional collinear-chaining programme with `gapcost`, the best path; its
 gaps are the next level's jobs.  `kchain_many` does that for every job of a call: the scan of `mums_many`, then each list chained on the device where
 the write pass has left it; only the paths come back.  A job the kernel does not take (more than 2048 members or RV_KCHAIN_CAP records, a job the scan
-runs the ordinary way) is chained by the host restatement `rv_kchain` inside the call; the results do not depend on the path.  Ties between
+runs the ordinary way) is prepared on the host inside the call (the cap, the points, the order of the targets, the kd order); with at least
+RV_KCHAIN_BIG_MIN kept points its programme then runs in device memory, tile by tile, together with every other such list of the call
+(csrc/rv_kchain_big.hip: up to 2^20 points), otherwise -- or where the preparation refuses the list, see include/reveal_amd.h -- on the host
+(`rv_kchain`).  The results do not depend on the path.  `kchain_device` chains lists the caller brings the same way, with no scan.  Ties between
 predecessors of equal score are decided as the reference decides them: by the order in which `range_search` hands out the leaves of `kdtree` (`kd_order`).
 
 The one deliberate departure: a job of TWO sequences.  The reference's `getmums` returns `(l, (a, b), rc)`, `chain()`'s filter `m[1] == k` drops every
@@ -12,7 +15,7 @@ such record, and a two-genome `reveal chain` anchors nothing.  The function plai
 (reveal.c:167; `mums_many(kind="multimums")` gives it): pairs are chained from that shape.
 
 Positions of a path are relative to each sequence's begin (the reference's coordinates with `offsets` all zero).  Scores are 64-bit, weights 0 .. 2^20.
-`kchain_python` and `rv_kchain` are O(m^2 k^2) per job with no tree.
+`kchain_python`, `rv_kchain` and the programme in device memory are O(m^2 k^2) per job with no tree; the last spreads it over the device.
 """
 import ctypes
 
@@ -26,6 +29,11 @@ KCHAIN_MEMBERS = 2048      # RV_KCHAIN_MEMBERS: members (records x k) of the lar
 KCHAIN_CAP = 1024          # RV_KCHAIN_CAP: ... and its records (the switch of that name lowers it)
 KCHAIN_WMAX = 1 << 20      # RV_KCHAIN_WMAX
 KCHAIN_FLAG = 4            # bit of `Batch.flagged()` of a job the kernel gave back to the host
+KCHAIN_BIG_TILE = 64       # RV_KCHAIN_BIG_TILE: targets of a tile of the programme in device memory
+KCHAIN_BIG_CAP = 1 << 20   # RV_KCHAIN_BIG_CAP: kept points of the longest list it takes
+KCHAIN_BIG_MIN = 512        # default of the switch RV_KCHAIN_BIG_MIN: kept points from which a list the kernel above did not chain goes there (1 .. 1025)
+# rv_kchain_admit: why the preparation leaves a list to the host programme
+KCHAIN_REFUSE = {"l0": 1, "shared": 2, "bits": 4, "cap": 8, "k": 16, "score": 32}
 
 
 # ---- plain Python restatement ----
@@ -133,7 +141,68 @@ def kchain_native(records, lens, maxmums=0, wpen=1, wscore=1, gcmodel="sumofpair
     return [(int(ol[x]), tuple(int(p) for p in op[x * k:(x + 1) * k]), int(osc[x])) for x in range(nn)], int(end.value)
 
 
+def _pack_lists(lists):
+    """[(records, lens), ..] -> the arrays of rv_many_kchain_lists (records of all lists back to back)"""
+    ks = np.array([len(lens) for _, lens in lists] or [0], np.int32)
+    nrec = np.array([len(recs) for recs, _ in lists] or [0], np.int64)
+    allrec = [r for recs, _ in lists for r in recs]
+    l = np.array([r[0] for r in allrec] or [0], np.uint32)
+    n = np.array([r[1] for r in allrec] or [0], np.int32)
+    off = np.zeros(len(allrec) + 1, np.int64)
+    np.cumsum([len(r[2]) for r in allrec], out=off[1:])
+    so = np.array([s for r in allrec for s, _ in r[2]] or [0], np.uint16)
+    pos = np.array([p for r in allrec for _, p in r[2]] or [0], np.int64)
+    ln = np.array([x for _, lens in lists for x in lens] or [0], np.int64)
+    return ks, nrec, l, n, off, so, pos, ln
+
+
+def kchain_admit(records, lens, maxmums=0, wpen=1, wscore=1, sa64=False):
+    """rv_kchain_admit (host C++; no device is asked for): the KCHAIN_REFUSE bits for which the preparation leaves this list to the host programme; 0: the
+    device programme takes it"""
+    lib = _lib.get(sa64)
+    ks, nrec, l, n, off, so, pos, ln = _pack_lists([(records, lens)])
+    r = lib.dll.rv_kchain_admit(len(lens), len(records), l.ctypes.data, n.ctypes.data, off.ctypes.data, pos.ctypes.data, ln.ctypes.data, int(maxmums), int(wpen), int(wscore))
+    if r < 0:
+        raise error(lib.err())
+    return r
+
+
+def kchain_device(lists, maxmums=0, wpen=1, wscore=1, gcmodel="sumofpairs", sa64=False, batch=None, big_min=None):
+    """rv_many_kchain_lists: chain() for lists the caller brings, with no scan.  lists: [(records, lens), ..] as for `kchain_python`.  -> ([(path,
+    end_score), ..], info): info = dict(lists, big, host, big_launches): `big` lists ran the programme in device memory (all of them in the same
+    `big_launches` launches: the tiles of the longest), `host` on the host.  `big_min`: sets the switch RV_KCHAIN_BIG_MIN of the batch (kept points from
+    which a list goes to the device; default KCHAIN_BIG_MIN)."""
+    if gcmodel not in GCMODELS:
+        raise error("unknown gap cost model %r (%s)" % (gcmodel, ", ".join(sorted(GCMODELS))))
+    if int(maxmums) < 0:
+        raise error("maxmums >= 0")
+    if not (0 <= int(wpen) <= KCHAIN_WMAX and 0 <= int(wscore) <= KCHAIN_WMAX):
+        raise error("weights of 0 .. 2^20")
+    lists = [(list(recs), [int(x) for x in lens]) for recs, lens in lists]
+    if any(len(lens) < 2 for _, lens in lists):
+        raise error("a list needs at least two sequences")
+    b = batch if batch is not None else Batch(sa64)
+    if big_min is not None:
+        b.option("RV_KCHAIN_BIG_MIN", int(big_min))
+    ks, nrec, l, n, off, so, pos, ln = _pack_lists(lists)
+    if b._dll.rv_many_kchain_lists(b._m, len(lists), ks.ctypes.data, nrec.ctypes.data, l.ctypes.data, n.ctypes.data, off.ctypes.data, so.ctypes.data, pos.ctypes.data,
+                                   ln.ctypes.data, int(maxmums), int(wpen), int(wscore), GCMODELS[gcmodel]) != 0:
+        b._fail()
+    chains = Chains(b.chains(len(lists)), [len(lens) for _, lens in lists])
+    big = b.kchain_big()
+    info = dict(lists=len(lists), big=big[0], host=len(lists) - big[0], big_launches=big[1])
+    return [(chains[j], int(chains.end_score[j])) for j in range(len(lists))], info
+
+
 # ---- the batch ----
+def _batch_kchain_big(self):
+    """rv_many_kchain_big -> (lists of the last kchain call the programme in device memory chained, its step launches)"""
+    o = (ctypes.c_int64 * 2)()
+    if self._dll.rv_many_kchain_big(self._m, o) != 0:
+        self._fail()
+    return int(o[0]), int(o[1])
+
+
 def _batch_kchain(self, minlength=20, maxmums=0, wpen=1, wscore=1, gcmodel="sumofpairs"):
     """rv_many_kchain: the chain of every job instead of its match list.  The jobs stay; the result of an earlier run() or scan() does not."""
     if gcmodel not in GCMODELS:
@@ -142,10 +211,11 @@ def _batch_kchain(self, minlength=20, maxmums=0, wpen=1, wscore=1, gcmodel="sumo
         self._fail()
 
 
-def _batch_chains(self):
+def _batch_chains(self, nlists=None):
     """-> (first[jobs + 1], l, score, pos, end_score): job j owns the nodes first[j] .. first[j+1] of l / score; the positions of ALL nodes lie back
-    to back in pos, k of job j for each of its nodes, in sequence order and relative to each sequence's begin"""
-    nj = len(self._lens)
+    to back in pos, k of job j for each of its nodes, in sequence order and relative to each sequence's begin.  nlists: after rv_many_kchain_lists,
+    whose lists are not the batch's jobs"""
+    nj = len(self._lens) if nlists is None else int(nlists)
     first = np.zeros(nj + 1, np.int64)
     mem = ctypes.c_int64(0)
     nn = self._dll.rv_many_kchain_count(self._m, first.ctypes.data, ctypes.byref(mem))
@@ -158,6 +228,7 @@ def _batch_chains(self):
 
 
 Batch.kchain = _batch_kchain
+Batch.kchain_big = _batch_kchain_big
 Batch.chains = _batch_chains
 
 
@@ -191,9 +262,12 @@ class Chains:
 
 def kchain_many(jobs, minlength=20, maxmums=0, wpen=1, wscore=1, gcmodel="sumofpairs", sa64=False, toupper=True, batch=None, large=None):
     """jobs: as for `align_many`.  -> (chains, info): what the reference's `chain()` returns for a fresh index of every job (`offsets` all zero).
-    chains: a `Chains`; info = dict(jobs, shared, ordinary, rounds, launches, flagged): `shared` jobs went through the scan's shared launches, `flagged` of
-    them were given back to `rv_kchain` by the kernel.  `batch`: a Batch to reuse; `large`: sets RV_MANY_SCAN_LARGE as for `mums_many`.  The switch
-    RV_MANY_KCHAIN_HOST (`Batch.option` or the environment) chains every job on the host; RV_KCHAIN_CAP lowers the records a job may hold on the device."""
+    chains: a `Chains`; info = dict(jobs, shared, ordinary, rounds, launches, flagged, big, big_launches): `shared` jobs went through the scan's shared
+    launches, `flagged` of them were given back by the kernel; `big` jobs (flagged or ordinary ones) ran the programme in device memory, in
+    `big_launches` launches (counted in `launches` too).  `batch`: a Batch to reuse; `large`: sets RV_MANY_SCAN_LARGE as for `mums_many`.  The switches
+    (`Batch.option` or the environment): RV_MANY_KCHAIN_HOST chains every job on the host; RV_KCHAIN_CAP lowers the records a job may hold in the
+    kernel of the rounds; RV_MANY_KCHAIN_BIG = 0 keeps every list no round has chained on the host; RV_KCHAIN_BIG_MIN: the kept points from which
+    such a list goes to the device."""
     if isinstance(jobs, (str, bytes, bytearray)) or not hasattr(jobs, "__iter__"):
         raise error("jobs is a list of jobs")
     if gcmodel not in GCMODELS:
@@ -212,6 +286,7 @@ def kchain_many(jobs, minlength=20, maxmums=0, wpen=1, wscore=1, gcmodel="sumofp
     b.kchain(minlength, maxmums, wpen, wscore, gcmodel)
     info = b.info()
     info["flagged"] = b.flagged().get(KCHAIN_FLAG, 0)
+    info["big"], info["big_launches"] = b.kchain_big()
     return Chains(b.chains(), [len(s) for s in prepared]), info
 
 
@@ -235,8 +310,8 @@ def chain_recurse(seqs, minlength=20, minn=2, maxmums=0, wpen=1, wscore=1, gcmod
     """the loop of `reveal chain --recurse` (chain.py:57-124), level by level instead of by a stack: ONE `kchain_many` call per level over all gaps of
     that level (`level_jobs`); a job whose chain is empty ends there.  seqs: the k input sequences, each a sample.  -> (anchors, infos): anchors =
     [(l, ((sequence, position in the top-level text `s0$s1$..`), ..), depth), ..] of all levels, sorted; infos = the `info` of every level's call.  The
-    sub-jobs are independent, so the set equals the stack order's.  Not here: the variant nodes, the graph and the GFA of chain_cmd; a top level whose
-    full-match list exceeds the kernel's caps goes to the O(m^2 k^2) restatement on the host, which is not meant for the lists of whole genomes."""
+    sub-jobs are independent, so the set equals the stack order's.  A top level whose full-match list exceeds the caps of the rounds' kernel runs its
+    programme in device memory (`info["big"]`), up to 2^20 full matches.  Not here: the variant nodes, the graph and the GFA of chain_cmd."""
     top = many.job_sequences(seqs, toupper)
     if int(minn) < 2:
         raise error("minn >= 2")

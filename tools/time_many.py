@@ -56,7 +56,13 @@ more than both spreads), then both sides at 1, 4, 16, 64 and 256 jobs.  --check 
 --mums-large (with --seqs K, 2 .. 64; implies --no-cut; choose --lmin / --lmax so that K x (L + 1) lies above 2048): the same for jobs above 2048 ranks -- the shared
 path with RV_MANY_SCAN_LARGE on (RV_MANY_SCAN_LARGE_MIN 1), the same call with the switch off (every such job the ordinary way inside the call), and the loop through one
 reused handle, alternately in one process, every leg ending with its results on the host.  The gate: the shared median below the switch-off leg's by more than the larger
-of the two spreads.  --sweep: then shared against switch-off at 1, 2, 4, 8 and 16 jobs a call (the evidence for the default of RV_MANY_SCAN_LARGE_MIN)."""
+of the two spreads.  --sweep: then shared against switch-off at 1, 2, 4, 8 and 16 jobs a call (the evidence for the default of RV_MANY_SCAN_LARGE_MIN).
+--kchain-big [--kb-ks 2,3,8] [--kb-logm 8,17] [--kb-host-once S] [--kb-host-skip S] [--kb-budget S] [--kb-recurse L] [--kb-only lists|many|recurse]: the chaining
+programme in device memory (rv_kchain_big.hip) against RV_MANY_KCHAIN_BIG = 0 (every list on the host: the parent commit's behaviour), alternately in one process, five
+repetitions after a full-size warm-up per leg, medians and spreads: abstract lists of m = 2^8 .. 2^17 points through rv_many_kchain_lists with RV_KCHAIN_BIG_MIN = 1 (a
+host leg expected above --kb-host-once seconds runs once, without a warm-up; one expected above --kb-host-skip seconds is left out; both are said), 16 lists of 4096
+points in one call, and chain_recurse on two synthetic genomes of --kb-recurse bases (1 % variants, a fifth of them indels) at the defaults.  The gate per workload: the
+big leg's median below the host leg's by more than both spreads."""
 import argparse
 import ctypes
 import hashlib
@@ -447,6 +453,104 @@ def main_kchain(a, jobs, bases):
     return 1 if out["check_bad_jobs"] or not out["gate"] else 0
 
 
+def kb_lists(k, m, nlists, seed):
+    """nlists abstract lists of m points in k sequences as the arrays of rv_many_kchain_lists: distinct coordinates in every dimension, a tenth of the
+    points off the backbone in each dimension behind the first, lengths 1 .. 40, records in random order"""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    span = 40 * m + 200
+    ls, ns, sos, poss, lens = [], [], [], [], []
+    for _ in range(nlists):
+        ln = [span + 40 + int(rng.integers(0, 31)) for _ in range(k)]
+        begin = np.concatenate([[0], np.cumsum(np.array(ln[:-1], np.int64) + 1)])
+        cols = np.stack([np.sort(rng.choice(span, size=m, replace=False)) for _ in range(k)], axis=1).astype(np.int64)
+        for d in range(1, k):
+            a_, b_ = rng.integers(0, m, size=m // 10), rng.integers(0, m, size=m // 10)
+            for x, y in zip(a_, b_):
+                cols[x, d], cols[y, d] = cols[y, d], cols[x, d]
+        cols = cols[rng.permutation(m)]
+        ls.append(rng.integers(1, 41, size=m).astype(np.uint32)); ns.append(np.full(m, k, np.int32))
+        sos.append(np.tile(np.arange(k, dtype=np.uint16), m)); poss.append((cols + begin[None, :]).reshape(-1)); lens += ln
+    tot = m * nlists
+    return (np.full(nlists, k, np.int32), np.full(nlists, m, np.int64), np.concatenate(ls), np.concatenate(ns), np.arange(tot + 1, dtype=np.int64) * k,
+            np.concatenate(sos), np.concatenate(poss), np.array(lens, np.int64))
+
+
+def kb_call(b, arrs, nlists):
+    ks, nrec, l, n, off, so, pos, ln = arrs
+    if b._dll.rv_many_kchain_lists(b._m, nlists, ks.ctypes.data, nrec.ctypes.data, l.ctypes.data, n.ctypes.data, off.ctypes.data, so.ctypes.data, pos.ctypes.data,
+                                   ln.ctypes.data, 0, 1, 1, 0) != 0:
+        b._fail()
+    return b.chains(nlists)
+
+
+def kb_legs(name, big_f, host_f, reps, host_mode, out):
+    """the two legs alternately; host_mode: "reps", "once" (no warm-up, one run) or "skip" """
+    t = {"big": [], "host": []}
+    res = {}
+    big_f()
+    if host_mode == "reps":
+        host_f()
+    for rep in range(reps):
+        t0 = time.perf_counter(); res["big"] = big_f(); t["big"].append(time.perf_counter() - t0)
+        if host_mode == "reps" or (host_mode == "once" and rep == 0):
+            t0 = time.perf_counter(); res["host"] = host_f(); t["host"].append(time.perf_counter() - t0)
+    r = dict(workload=name, host_mode=host_mode, big_s=t["big"], host_s=t["host"], big_median_s=statistics.median(t["big"]), big_spread_s=max(t["big"]) - min(t["big"]))
+    line = "%-34s big: median %.5f s, spread %.5f s" % (name, r["big_median_s"], r["big_spread_s"])
+    if t["host"]:
+        r["host_median_s"] = statistics.median(t["host"]); r["host_spread_s"] = max(t["host"]) - min(t["host"])
+        r["same"] = bool(all(np.array_equal(x, y) for x, y in zip(res["big"], res["host"])))
+        r["gate"] = bool(r["host_median_s"] - r["big_median_s"] > max(r["host_spread_s"], r["big_spread_s"])) if host_mode == "reps" else None
+        line += "; host: median %.5f s, spread %.5f s%s; %.2f x; gate %s; results %s" % (
+            r["host_median_s"], r["host_spread_s"], " (ONE run, no warm-up)" if host_mode == "once" else "", r["host_median_s"] / r["big_median_s"],
+            "not judged" if r["gate"] is None else "met" if r["gate"] else "MISSED", "identical" if r["same"] else "DIFFER")
+    else:
+        line += "; host leg left out (expected above the limit)"
+    print(line, flush=True)
+    out.append(r)
+    return r
+
+
+def main_kchain_big(a):
+    from reveal_amd import kchain, many, synth
+    t_start = time.perf_counter()
+    big, host = many.Batch(False), many.Batch(False)
+    big.option("RV_KCHAIN_BIG_MIN", 1)
+    host.option("RV_MANY_KCHAIN_BIG", 0)
+    out = []
+    lo, hi = (int(x) for x in a.kb_logm.split(","))
+    if a.kb_only in (None, "lists"):
+        for k in (int(x) for x in a.kb_ks.split(",")):
+            expect = 0.0
+            for lg in range(lo, hi + 1):
+                if time.perf_counter() - t_start > a.kb_budget:
+                    print("k = %d: stopped in front of m = 2^%d (the time budget of this run)" % (k, lg), flush=True)
+                    break
+                m = 1 << lg
+                arrs = kb_lists(k, m, 1, 100 * k + lg)
+                mode = "skip" if expect > a.kb_host_skip else "once" if expect > a.kb_host_once else "reps"
+                r = kb_legs("lists k=%d m=2^%d" % (k, lg), lambda: kb_call(big, arrs, 1), lambda: kb_call(host, arrs, 1), a.reps, mode, out)
+                r["launches"] = big.kchain_big()[1]; r["big_lists"] = big.kchain_big()[0]
+                expect = 4 * r.get("host_median_s", expect)
+    if a.kb_only in (None, "many"):
+        arrs = kb_lists(2, 4096, 16, 7)
+        r = kb_legs("16 lists k=2 m=4096, one call", lambda: kb_call(big, arrs, 16), lambda: kb_call(host, arrs, 16), a.reps, "reps", out)
+        r["launches"] = big.kchain_big()[1]; r["big_lists"] = big.kchain_big()[0]
+    if a.kb_only in (None, "recurse") and a.kb_recurse > 0:
+        seqs = [g.decode() for g in synth.genomes(a.kb_recurse, 2, snp=0.01, indelfrac=0.2)]
+        dflt, off = many.Batch(False), many.Batch(False)
+        off.option("RV_MANY_KCHAIN_BIG", 0)
+        infos = {}
+
+        def rec(b, key):
+            an, infos[key] = kchain.chain_recurse(seqs, batch=b, toupper=False)
+            return (np.array([x[0] for x in an]), np.array([p for x in an for _, p in x[1]]), np.array([x[2] for x in an]))
+        r = kb_legs("chain_recurse 2 x %d bases" % a.kb_recurse, lambda: rec(dflt, "big"), lambda: rec(off, "host"), a.reps, "reps", out)
+        r["levels"] = len(infos["big"]); r["top_big"] = infos["big"][0]["big"]; r["top_launches"] = infos["big"][0]["big_launches"]; r["top_info"] = infos["big"][0]
+        print("chain_recurse: %d levels; top level %r" % (r["levels"], infos["big"][0]), flush=True)
+    print(json.dumps(dict(mode="kchain-big", reps=a.reps, lib_dir=os.environ.get("RV_LIB_DIR"), results=out)))
+    return 0
+
+
 def main_picker(a, jobs, bases):
     """the reference's default picker: RV_MANY_CHAIN on / off, the built-in picker beside them, rem.align per job"""
     from reveal_amd import many, rem, schemes
@@ -585,8 +689,18 @@ def main():
     ap.add_argument("--kchain", action="store_true", help="the collinear chains (Batch.kchain): on the device, RV_MANY_KCHAIN_HOST, and scan + kchain_python per job")
     ap.add_argument("--large-scan", action="store_true", help="--kchain: RV_MANY_SCAN_LARGE on in every leg (jobs above 2048 ranks)")
     ap.add_argument("--python-jobs", type=int, default=None, help="--kchain: kchain_python on the first N jobs only, scaled")
+    ap.add_argument("--kchain-big", action="store_true", help="the chaining programme in device memory against RV_MANY_KCHAIN_BIG = 0: abstract lists, 16 lists a call, chain_recurse")
+    ap.add_argument("--kb-ks", default="2,3,8", help="--kchain-big: the k of the abstract lists")
+    ap.add_argument("--kb-logm", default="8,17", help="--kchain-big: m = 2^lo .. 2^hi")
+    ap.add_argument("--kb-host-once", type=float, default=2.0, help="--kchain-big: a host leg expected above this many seconds runs once")
+    ap.add_argument("--kb-host-skip", type=float, default=30.0, help="--kchain-big: a host leg expected above this many seconds is left out")
+    ap.add_argument("--kb-budget", type=float, default=300.0, help="--kchain-big: seconds after which the sweep over m stops")
+    ap.add_argument("--kb-recurse", type=int, default=1000000, help="--kchain-big: bases of the two genomes of the chain_recurse workload (0: none)")
+    ap.add_argument("--kb-only", choices=("lists", "many", "recurse"), default=None, help="--kchain-big: one workload")
     ap.add_argument("--sweep", action="store_true", help="--mums-large: then on against off at 1, 2, 4, 8 and 16 jobs a call")
     a = ap.parse_args()
+    if a.kchain_big:
+        return main_kchain_big(a)
     if a.mums_large:
         a.mums = True
         a.no_cut = True
