@@ -117,6 +117,32 @@ int rv_fetch_mums(rv_index *h, uint32_t *l, int64_t *a, int64_t *b, int64_t cap)
 int64_t rv_getmultimums(rv_index *h, int minlength, int minn, int mems, int64_t *members);
 int rv_fetch_multi(rv_index *h, uint32_t *l, int32_t *n, int64_t *off, uint16_t *so, int64_t *pos);
 
+/* getblocks: the first stage of `reveal transform` (transform.py:252-293) on an index of two samples -- the MUMs of rv_getmums(minlength),
+ * tagged with the sequences they lie in (addctginfo) and, with cluster != 0, merged along their diagonal (clustermumsbydiagonal).  o = the rc of
+ * the last rv_construct; end[i] = the '$' of the i-th sequence added, over all samples.
+ *   refid = #{i: end[i] < a}, ctgid = #{i: end[i] < b}.
+ *   cluster == 0: one block (a, a+l, b, b+l) of score l per MUM, ascending b; maxdist and minclustsize are not read.
+ *   cluster != 0: MUMs ordered by (a - b, a) for o = 0 and by (a + b + l, a) for o = 1 (the reference's (a-b, a+b) / (a+b+l, a-(b+l)): the same
+ *     total order); a MUM continues its predecessor's cluster iff first key component, refid and ctgid agree and a - (a' + l') < maxdist.  A
+ *     cluster with first member F and last member L is (a_F, a_L+l_L, b_F, b_L+l_L) for o = 0, (a_F, a_L+l_L, b_L, b_F+l_F) for o = 1, its score the
+ *     sum of l.  Blocks with score >= minclustsize stay, in sorted order.  A negative distance inside a cluster candidate is an error
+ *     ("overlapping matches on a diagonal"), never a merge.
+ *   No MUMs: no blocks (the reference's forward leg raises IndexError there).
+ * rv_getblocks returns the number of blocks, -2 where rv_getmums does, <0 otherwise; counts = {MUMs scanned, clusters before the filter}.  The
+ * records stay in device memory between the scan and the block kernels (rv_blocks.hip); switch RV_BLOCKS_HOST = 1: they are fetched as for
+ * rv_getmums and rv_blocks_host's rule runs (the A/B leg).  A list of fewer than RV_BLOCKS_HOST_BELOW records (switch, default 4096; 0: never) takes
+ * that rule as well -- it arrives with the copy of the scan's header, and the kernels' launches cost more than they save there.  rv_fetch_blocks copies the blocks of the handle's last rv_getblocks / rv_blocks_records.
+ * rv_blocks_records: the same kernels on the caller's list (b in forward coordinates, as rv_fetch_mums gives it; any non-negative coordinates below
+ * 2^61); the handle lends stream and workspace and need not be constructed.  rv_blocks_host: the rule in host C++, no device is asked for; the
+ * arrays take `cap` blocks (n always suffices). */
+int64_t rv_getblocks(rv_index *h, int minlength, int cluster, int64_t maxdist, int64_t minclustsize, int64_t counts[2]);
+int rv_fetch_blocks(rv_index *h, int64_t *s1, int64_t *e1, int64_t *s2, int64_t *e2, int64_t *score, int32_t *refid, int32_t *ctgid, int64_t cap);
+int64_t rv_blocks_records(rv_index *h, int64_t n, const uint32_t *l, const int64_t *a, const int64_t *b, int o, int64_t nseq, const int64_t *end,
+                          int cluster, int64_t maxdist, int64_t minclustsize);
+int64_t rv_blocks_host(int64_t n, const uint32_t *l, const int64_t *a, const int64_t *b, int o, int64_t nseq, const int64_t *end, int cluster, int64_t maxdist,
+                       int64_t minclustsize, int64_t counts[2], int64_t *s1, int64_t *e1, int64_t *s2, int64_t *e2, int64_t *score, int32_t *refid, int32_t *ctgid,
+                       int64_t cap);
+
 /* ---- the recursion: align() / aligner() (interface.c:293-415, reveal.c:731-1338)
  *
  * The reference pops one sub-index at a time (LIFO) and calls back into

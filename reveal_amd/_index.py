@@ -354,6 +354,38 @@ def make_index_type(sa64, error):
             rc = 1 if getattr(self, "_rc", 0) else 0
             return [(int(l[k]), (int(a[k]), int(b[k])), rc) for k in range(cnt)]
 
+        def getblocks_arrays(self, minlength=20, cluster=True, maxdist=30, minclustsize=50):
+            """Not in the reference's index: the first stage of `reveal transform` (transform.py:252-293) on this index of two samples --
+            getmums(minlength), addctginfo over every sequence added, and with `cluster` clustermumsbydiagonal -- with the MUMs kept in device
+            memory (rv_getblocks; the rule is stated in include/reveal_amd.h).  -> dict of numpy arrays s1, e1, s2, e2, score (int64), refid,
+            ctgid (int32), o (the rc of the last construct) and info = dict(mums, clusters): MUMs scanned, clusters before the minclustsize filter.
+            No MUMs give no blocks (the reference's forward leg raises IndexError there).  Switches: RV_BLOCKS_HOST = 1 fetches the MUMs and runs
+            the rule in host C++ (the A/B leg); a list of fewer than RV_BLOCKS_HOST_BELOW MUMs (default 4096, 0: never) does so by itself."""
+            if self._sx or self._slot is not None:
+                raise error("getblocks is for a main index")
+            counts = np.zeros(2, dtype=np.int64)
+            cnt = self._dll.rv_getblocks(self._h, int(minlength), 1 if cluster else 0, int(maxdist), int(minclustsize), counts.ctypes.data)
+            if cnt < 0:
+                self._fail(TypeError if cnt == -2 else error)
+            out = self._fetch_blocks(cnt)
+            out["o"] = 1 if getattr(self, "_rc", 0) else 0
+            out["info"] = dict(mums=int(counts[0]), clusters=int(counts[1]))
+            return out
+
+        def _fetch_blocks(self, cnt):
+            out = {k: np.zeros(max(cnt, 1), dtype=np.int64) for k in ("s1", "e1", "s2", "e2", "score")}
+            out.update({k: np.zeros(max(cnt, 1), dtype=np.int32) for k in ("refid", "ctgid")})
+            if self._dll.rv_fetch_blocks(self._h, *[out[k].ctypes.data for k in ("s1", "e1", "s2", "e2", "score", "refid", "ctgid")], max(cnt, 1)) != 0:
+                self._fail()
+            return {k: v[:cnt] for k, v in out.items()}
+
+        def getblocks(self, minlength=20, cluster=True, maxdist=30, minclustsize=50):
+            """getblocks_arrays as the list `reveal transform` goes on with: [(s1, e1, s2, e2, o, score, refid, ctgid)]; the defaults are its own"""
+            r = self.getblocks_arrays(minlength, cluster, maxdist, minclustsize)
+            o = r["o"]
+            cols = [r[k].tolist() for k in ("s1", "e1", "s2", "e2", "score", "refid", "ctgid")]
+            return [(s1, e1, s2, e2, o, sc, rf, cg) for s1, e1, s2, e2, sc, rf, cg in zip(*cols)]
+
         def _multi(self, minlength, minn, mems):
             if self._sx:
                 if mems or self._dll.rv_nsamples(self._h) <= 2:

@@ -74,6 +74,10 @@ SYMBOLS = {
     "rv_fetch_mums": (_I, [V, V, V, V, _L]),
     "rv_getmultimums": (_L, [V, _I, _I, _I, c_i64p]),
     "rv_fetch_multi": (_I, [V, V, V, V, V, V]),
+    "rv_getblocks": (_L, [V, _I, _I, _L, _L, V]),
+    "rv_fetch_blocks": (_I, [V, V, V, V, V, V, V, V, _L]),
+    "rv_blocks_records": (_L, [V, _L, V, V, V, _I, _L, V, _I, _L, _L]),
+    "rv_blocks_host": (_L, [_L, V, V, V, _I, _L, V, _I, _L, _L, V, V, V, V, V, V, V, V, _L]),
     "rv_align_begin": (_I, [V, _I, _I]),
     "rv_frontier_size": (_I, [V]),
     "rv_frontier_scan": (_I, [V]),

@@ -325,6 +325,7 @@ int rv_reset(rv_index *h) {
     h->maxlcp = 0;
     h->m_l.clear(); h->m_a.clear(); h->m_b.clear();
     h->mm_l.clear(); h->mm_n.clear(); h->mm_off.clear(); h->mm_pos.clear(); h->mm_so.clear();
+    h->blk.clear();
     memset(h->ws.cap_events, 0, sizeof h->ws.cap_events);
     return 0;
 }
@@ -704,6 +705,79 @@ static int pair_topk(rv_index *h, const RvPairRec *recs, u32 total, const int64_
     return 0;
 }
 
+// The buffers of a pair scan and the launch of one attempt: shared by the picker's loop and by pair_scan_dense below.
+namespace {
+struct PairScanBufs {
+    DBuf *bcnt, *btab, *bslot, *bovf, *bout;
+    u32 *tilecnt, *tileovf, *tileoff;
+    int64_t ntile;
+    size_t ocap, vcap;      // of the attempt pair_scan_launch started last
+};
+}  // namespace
+static int pair_scan_bufs(rv_index *h, int64_t m, PairScanBufs &pb) {
+    hipStream_t q = h->ws.stream;
+    const int64_t ntile = ceil_div(m, RV_PAIR_TILE);
+    DBuf &bcnt = h->ws.misc[14], &btab = h->ws.misc[2], &bslot = h->ws.misc[3], &bovf = h->ws.misc[4], &bout = h->ws.misc[5];   // misc[14]: the pair scan's own counter (self-resetting)
+    if (bcnt.cap == 0) { RV_TRY(bcnt.reserve(64)); RV_HIP(hipMemsetAsync(bcnt.p, 0, 64, q)); }      // counters return to zero by themselves afterwards
+    RV_TRY(btab.reserve((size_t)(ntile + 1) * 3 * sizeof(u32)));
+    RV_TRY(bslot.reserve((size_t)ntile * RV_PAIR_SLOTS * sizeof(RvPairRec)));
+    if (bovf.cap < 4096 * sizeof(RvPairRec)) RV_TRY(bovf.reserve(4096 * sizeof(RvPairRec)));
+    if (bout.cap < 4096 * sizeof(RvPairRec)) RV_TRY(bout.reserve(sizeof(RvPairRec) * (size_t)std::max<int64_t>(4096, m / 64)));
+    pb.bcnt = &bcnt; pb.btab = &btab; pb.bslot = &bslot; pb.bovf = &bovf; pb.bout = &bout;
+    pb.tilecnt = btab.as<u32>(); pb.tileovf = pb.tilecnt + (ntile + 1); pb.tileoff = pb.tileovf + (ntile + 1);
+    pb.ntile = ntile; pb.ocap = pb.vcap = 0;
+    return 0;
+}
+// picks != NULL: with the tables of the device-side picker (nsubs sub-indices)
+static int pair_scan_launch(rv_index *h, PairScanBufs &pb, const sa_t *SA, const lcp_t *LCP, const uint8_t *BWT, int64_t m, int minl, RvPairRec *picks, int nsubs) {
+    pb.ocap = pb.bout->cap / sizeof(RvPairRec) - RV_PAIR_HDR; pb.vcap = pb.bovf->cap / sizeof(RvPairRec);
+    h->ws.pair_ovf_cap = (u32)std::min<size_t>(pb.vcap, 0xffffffffu);      // (what k_decide compares the header's overflow count with)
+    hipEvent_t ev_a, ev_b;      /* 8 B/rank (12 B in the 64-bit build); the BWT byte is not counted */
+    (void)h->prof.attach(RV_K_SCAN_PAIR, (double)m * 8.0, &ev_a, &ev_b);      // 8 B per rank (a 4-byte suffix + a 4-byte LCP value), also for the 64-bit library -- the kernel reads suffixes only where a match may start
+    return rv_scan_pair_launch(h->ws, SA, LCP, m, BWT, (sa_t)h->nsep[0], minl, pb.bslot->as<RvPairRec>(), pb.bovf->as<RvPairRec>(),
+                               (u32)std::min<size_t>(pb.vcap, 0xffffffffu), pb.bcnt->as<u32>(), pb.tilecnt, pb.tileovf,
+                               h->ws.misc[12].as<unsigned long long>(), picks, picks ? nsubs : 0, ev_a, ev_b);
+}
+
+// Scan, scan of the tile counts, compaction and the capacity retries (pair_ovf, pair_out), up to the point where the records lie dense and in rank
+// order in device memory.  One copy brings the header and the first `want` records (as many as fit the list) to h->hscan: want = 0 brings the
+// header alone (rv_getblocks: the records stay where they are).
+namespace {
+struct RvPairDense {
+    const RvPairRec *recs = nullptr;      // device
+    u32 total = 0, err = 0;
+    size_t have = 0;                      // records behind the header in h->hscan
+};
+}  // namespace
+static int pair_scan_dense(rv_index *h, const sa_t *SA, const lcp_t *LCP, const uint8_t *BWT, int64_t m, int minl, const u32 *d_err, size_t want, RvPairDense &res) {
+    hipStream_t q = h->ws.stream;
+    PairScanBufs pb;
+    RV_TRY(pair_scan_bufs(h, m, pb));
+    DBuf &bovf = *pb.bovf, &bout = *pb.bout;
+    for (int attempt = 0; attempt < 3; attempt++) {
+        RV_TRY(pair_scan_launch(h, pb, SA, LCP, BWT, m, minl, nullptr, 0));
+        const size_t ocap = pb.ocap, vcap = pb.vcap;
+        RV_TRY(rv_exclusive_sum_u32(h->ws, pb.tilecnt, pb.tileoff, pb.ntile + 1));
+        RV_TRY(rv_pair_compact_launch(h->ws, pb.bslot->as<RvPairRec>(), bovf.as<RvPairRec>(), pb.tilecnt, pb.tileovf, pb.tileoff, pb.ntile, bout.as<RvPairRec>(),
+                                      (u32)std::min<size_t>(ocap, 0xffffffffu), pb.bcnt->as<u32>(), d_err, (u32)std::min<size_t>(vcap, 0xffffffffu)));
+        const size_t guess = std::min<size_t>(ocap, want);
+        RV_TRY(h->hscan.reserve((guess + RV_PAIR_HDR) * sizeof(RvPairRec)));
+        RV_HIP(hipMemcpyAsync(h->hscan.p, bout.p, (guess + RV_PAIR_HDR) * sizeof(RvPairRec), hipMemcpyDeviceToHost, q));
+        RV_HIP(hipStreamSynchronize(q));
+        const u32 *hdr = h->hscan.as<u32>();
+        const u32 total = hdr[0], novf = hdr[1];
+        res.err = hdr[2];
+        if (total <= ocap && novf <= vcap) {
+            res.recs = bout.as<RvPairRec>() + RV_PAIR_HDR; res.total = total; res.have = std::min<size_t>(total, guess);
+            return 0;
+        }
+        if (novf > vcap) { h->ws.cap_events[RV_CE_PAIR_OVF]++; RV_TRY(bovf.reserve((size_t)novf * sizeof(RvPairRec))); }
+        if (total > ocap) { h->ws.cap_events[RV_CE_PAIR_OUT]++; RV_TRY(bout.reserve(((size_t)total + RV_PAIR_HDR) * sizeof(RvPairRec))); }
+    }
+    rv_set_error("pair scan: output buffer sizing failed");
+    return -1;
+}
+
 int rv_run_pair_scan(rv_index *h, const sa_t *SA, const lcp_t *LCP, const uint8_t *BWT, int64_t m, int minl, std::vector<RvPairRec> &out,
                      const u32 *d_err, u32 *err_out, const int64_t *d_sub_start, int nsubs, int (*after_pick)(rv_index *), bool use_hook,
                      const int *d_tile_sub, const int64_t *d_presel_start, int presel_subs, int64_t presel, const RvPickChainArgs *chain) {
@@ -715,32 +789,49 @@ int rv_run_pair_scan(rv_index *h, const sa_t *SA, const lcp_t *LCP, const uint8_
     }
     if (h->nsep.empty()) { rv_set_error("pairwise scan needs at least two samples"); return -1; }
     hipStream_t q = h->ws.stream;
-    const int64_t ntile = ceil_div(m, RV_PAIR_TILE);
-    DBuf &bcnt = h->ws.misc[14], &btab = h->ws.misc[2], &bslot = h->ws.misc[3], &bovf = h->ws.misc[4], &bout = h->ws.misc[5];   // misc[14]: the pair scan's own counter (self-resetting)
-    if (bcnt.cap == 0) { RV_TRY(bcnt.reserve(64)); RV_HIP(hipMemsetAsync(bcnt.p, 0, 64, q)); }      // counters return to zero by themselves afterwards
-    RV_TRY(btab.reserve((size_t)(ntile + 1) * 3 * sizeof(u32)));
-    RV_TRY(bslot.reserve((size_t)ntile * RV_PAIR_SLOTS * sizeof(RvPairRec)));
-    if (bovf.cap < 4096 * sizeof(RvPairRec)) RV_TRY(bovf.reserve(4096 * sizeof(RvPairRec)));
-    if (bout.cap < 4096 * sizeof(RvPairRec)) RV_TRY(bout.reserve(sizeof(RvPairRec) * (size_t)std::max<int64_t>(4096, m / 64)));
-    u32 *tilecnt = btab.as<u32>(), *tileovf = tilecnt + (ntile + 1), *tileoff = tileovf + (ntile + 1);
+    if (!d_sub_start) {
+        // one copy: header + as many records as the previous scan produced (record counts shrink level by level).  With a pre-selection cap
+        // the copy brings RV_PRESEL_DEV_MIN records at most: a level with more is capped on the device (pair_topk) and its records never cross
+        // into host memory -- the header that decides this arrives with the same copy (it used to be a round trip of its own per level)
+        const bool presel_on = d_presel_start && presel > 0 && presel_subs > 0;
+        size_t want = h->scan_guess;
+        if (presel_on) want = std::min<size_t>(want, (size_t)std::max<int64_t>(h->ws.opt.presel_dev_min, 1));
+        RvPairDense dn;
+        const int rd = pair_scan_dense(h, SA, LCP, BWT, m, minl, d_err, want, dn);
+        if (err_out) *err_out = dn.err;
+        if (rd != 0) return rd;
+        const u32 total = dn.total;
+        if (presel_on && (int64_t)total >= h->ws.opt.presel_dev_min && (int64_t)total > presel) {
+            RV_TRY(pair_topk(h, dn.recs, total, d_presel_start, presel_subs, presel, out));
+            h->scan_guess = (size_t)total + total / 16 + 64;
+            return 0;
+        }
+        out.resize(total);
+        const RvPairRec *src = h->hscan.as<RvPairRec>() + RV_PAIR_HDR;
+        const size_t have = dn.have;
+        if (have) memcpy(out.data(), src, have * sizeof(RvPairRec));
+        if (total > have) {
+            h->ws.cap_events[RV_CE_PAIR_SECOND_COPY]++;
+            RV_HIP(hipMemcpy(out.data() + have, dn.recs + have, (total - have) * sizeof(RvPairRec), hipMemcpyDeviceToHost));
+        }
+        h->scan_guess = (size_t)total + total / 16 + 64;
+        return 0;
+    }
+    PairScanBufs pb;
+    RV_TRY(pair_scan_bufs(h, m, pb));
+    DBuf &bcnt = *pb.bcnt, &bslot = *pb.bslot, &bovf = *pb.bovf;
+    u32 *tilecnt = pb.tilecnt, *tileovf = pb.tileovf;
+    const int64_t ntile = pb.ntile;
     for (int attempt = 0; attempt < 3; attempt++) {
-        const size_t ocap = bout.cap / sizeof(RvPairRec) - RV_PAIR_HDR, vcap = bovf.cap / sizeof(RvPairRec);
-        h->ws.pair_ovf_cap = (u32)std::min<size_t>(vcap, 0xffffffffu);      // (what k_decide compares the header's overflow count with)
         // picker tables; the picks go straight to pinned host memory (the kernels write them over PCIe: a few KB), so the level's
         // round trip needs no copy command, only the wait for the stream
         DBuf &bbest = h->ws.misc[12];
-        RvPairRec *picks = nullptr;
-        if (d_sub_start) {
-            RV_TRY(bbest.reserve((size_t)nsubs * 8));
-            RV_TRY(h->hscan.reserve((size_t)(nsubs + RV_PAIR_HDR) * sizeof(RvPairRec)));
-            picks = h->hscan.as<RvPairRec>();
-        }
-        hipEvent_t ev_a, ev_b;      /* 8 B/rank (12 B in the 64-bit build); the BWT byte is not counted */
-        (void)h->prof.attach(RV_K_SCAN_PAIR, (double)m * 8.0, &ev_a, &ev_b);      // 8 B per rank (a 4-byte suffix + a 4-byte LCP value), also for the 64-bit library -- the kernel reads suffixes only where a match may start
-        RV_TRY(rv_scan_pair_launch(h->ws, SA, LCP, m, BWT, (sa_t)h->nsep[0], minl, bslot.as<RvPairRec>(), bovf.as<RvPairRec>(),
-                                   (u32)std::min<size_t>(vcap, 0xffffffffu), bcnt.as<u32>(), tilecnt, tileovf,
-                                   bbest.as<unsigned long long>(), picks, d_sub_start ? nsubs : 0, ev_a, ev_b));
-        if (d_sub_start) {
+        RV_TRY(bbest.reserve((size_t)nsubs * 8));
+        RV_TRY(h->hscan.reserve((size_t)(nsubs + RV_PAIR_HDR) * sizeof(RvPairRec)));
+        RvPairRec *picks = h->hscan.as<RvPairRec>();
+        RV_TRY(pair_scan_launch(h, pb, SA, LCP, BWT, m, minl, picks, nsubs));
+        const size_t vcap = pb.vcap;
+        {
             // the built-in picker only wants the best record of each sub-index: pick on the device straight from the slots
             // (the chain route of rv_many's handle: the reference's default picker's choice instead, one wavefront per sub-index -- rv_pick_chain.hip)
             if (chain) RV_TRY(rv_pick_chain_launch(h->ws, bslot.as<RvPairRec>(), bovf.as<RvPairRec>(), (u32)std::min<size_t>(vcap, 0xffffffffu), tilecnt, tileovf, ntile,
@@ -767,42 +858,7 @@ int rv_run_pair_scan(rv_index *h, const sa_t *SA, const lcp_t *LCP, const uint8_
             }
             h->ws.cap_events[RV_CE_PAIR_PICK_OVF]++;
             RV_TRY(bovf.reserve((size_t)novf * sizeof(RvPairRec)));
-            continue;
         }
-        RV_TRY(rv_exclusive_sum_u32(h->ws, tilecnt, tileoff, ntile + 1));
-        RV_TRY(rv_pair_compact_launch(h->ws, bslot.as<RvPairRec>(), bovf.as<RvPairRec>(), tilecnt, tileovf, tileoff, ntile, bout.as<RvPairRec>(),
-                                      (u32)std::min<size_t>(ocap, 0xffffffffu), bcnt.as<u32>(), d_err, (u32)std::min<size_t>(vcap, 0xffffffffu)));
-        // one copy: header + as many records as the previous scan produced (record counts shrink level by level).  With a pre-selection cap
-        // the copy brings RV_PRESEL_DEV_MIN records at most: a level with more is capped on the device (pair_topk) and its records never cross
-        // into host memory -- the header that decides this arrives with the same copy (it used to be a round trip of its own per level)
-        const bool presel_on = d_presel_start && presel > 0 && presel_subs > 0;
-        size_t guess = std::min<size_t>(ocap, h->scan_guess);
-        if (presel_on) guess = std::min<size_t>(guess, (size_t)std::max<int64_t>(h->ws.opt.presel_dev_min, 1));
-        RV_TRY(h->hscan.reserve((guess + RV_PAIR_HDR) * sizeof(RvPairRec)));
-        RV_HIP(hipMemcpyAsync(h->hscan.p, bout.p, (guess + RV_PAIR_HDR) * sizeof(RvPairRec), hipMemcpyDeviceToHost, q));
-        RV_HIP(hipStreamSynchronize(q));
-        const u32 *hdr = h->hscan.as<u32>();
-        const u32 total = hdr[0], novf = hdr[1];
-        if (err_out) *err_out = hdr[2];
-        if (presel_on && total <= ocap && novf <= vcap && (int64_t)total >= h->ws.opt.presel_dev_min && (int64_t)total > presel) {
-            RV_TRY(pair_topk(h, bout.as<RvPairRec>() + RV_PAIR_HDR, total, d_presel_start, presel_subs, presel, out));
-            h->scan_guess = (size_t)total + total / 16 + 64;
-            return 0;
-        }
-        if (total <= ocap && novf <= vcap) {
-            out.resize(total);
-            const RvPairRec *src = h->hscan.as<RvPairRec>() + RV_PAIR_HDR;
-            const size_t have = std::min<size_t>(total, guess);
-            if (have) memcpy(out.data(), src, have * sizeof(RvPairRec));
-            if (total > have) {
-                h->ws.cap_events[RV_CE_PAIR_SECOND_COPY]++;
-                RV_HIP(hipMemcpy(out.data() + have, bout.as<RvPairRec>() + RV_PAIR_HDR + have, (total - have) * sizeof(RvPairRec), hipMemcpyDeviceToHost));
-            }
-            h->scan_guess = (size_t)total + total / 16 + 64;
-            return 0;
-        }
-        if (novf > vcap) { h->ws.cap_events[RV_CE_PAIR_OVF]++; RV_TRY(bovf.reserve((size_t)novf * sizeof(RvPairRec))); }
-        if (total > ocap) { h->ws.cap_events[RV_CE_PAIR_OUT]++; RV_TRY(bout.reserve(((size_t)total + RV_PAIR_HDR) * sizeof(RvPairRec))); }
     }
     rv_set_error("pair scan: output buffer sizing failed");
     return -1;
@@ -1051,6 +1107,104 @@ int rv_fetch_mums(rv_index *h, uint32_t *l, int64_t *a, int64_t *b, int64_t cap)
     if (cap < (int64_t)h->m_l.size()) { rv_set_error("buffer too small"); return -1; }
     for (size_t k = 0; k < h->m_l.size(); k++) { l[k] = h->m_l[k]; a[k] = h->m_a[k]; b[k] = h->m_b[k]; }
     return 0;
+}
+
+}  // extern "C"
+// the host rule on scan records in host memory (b mapped back to forward coordinates as rv_getmums does) -> h->blk
+static int blocks_of_host_records(rv_index *h, const RvPairRec *recs, size_t n, const std::vector<int64_t> &end, const RvBlkArgs &args) {
+    try {
+        std::vector<uint32_t> l(n); std::vector<int64_t> a(n), b(n);
+        for (size_t k = 0; k < n; k++) {
+            int64_t bb = recs[k].b;
+            if (h->rc == 1) bb = h->nsep[0] + (h->nT - bb - (int64_t)recs[k].l);     /* reveal.c:98-100 */
+            l[k] = recs[k].l; a[k] = recs[k].a; b[k] = bb;
+        }
+        return rv_blocks_rule_host((int64_t)n, l.data(), a.data(), b.data(), end.data(), (int64_t)end.size(), args, h->blk);
+    } catch (...) { rv_set_error("getblocks: out of host memory"); return -1; }
+}
+extern "C" {
+
+/* transform.py:252-293: the MUMs of the two-sample scan, tagged with their sequences (addctginfo) and clustered by diagonal
+ * (clustermumsbydiagonal) -- rv_blocks.hip.  The records go from the scan's compaction straight into the block kernels; the header, the
+ * counts and the kept blocks are all that is copied back.  RV_BLOCKS_HOST: the records cross as for rv_getmums and the host rule runs; a list
+ * of fewer than RV_BLOCKS_HOST_BELOW records takes the host rule too (it arrives with the header's copy). */
+int64_t rv_getblocks(rv_index *h, int minlength, int cluster, int64_t maxdist, int64_t minclustsize, int64_t counts[2]) {
+    if (!h) { rv_set_error("rv_getblocks: null handle"); return -1; }
+    if (!h->constructed || h->main_arrays_freed) { rv_set_error("Index not yet constructed."); return -2; }
+    if (h->nsep.empty()) { rv_set_error("getblocks needs at least two samples"); return -1; }
+    (void)hipSetDevice(h->device);
+    RvBlkArgs args; args.o = h->rc == 1 ? 1 : 0; args.cluster = cluster ? 1 : 0; args.maxdist = maxdist; args.minclustsize = minclustsize;
+    std::vector<int64_t> end;
+    try { end.reserve(h->nodes.size()); for (const RvIntv &v : h->nodes) end.push_back(v.end); }
+    catch (...) { rv_set_error("getblocks: out of host memory"); return -1; }
+    h->blk.clear();
+    if (h->ws.opt.blocks_host) {
+        std::vector<RvPairRec> recs;
+        if (rv_run_pair_scan(h, h->dSA.as<sa_t>(), h->dLCP.as<lcp_t>(), h->dBWT.as<uint8_t>(), h->n, minlength, recs, nullptr, nullptr, nullptr, 0, nullptr, false) != 0) return -1;
+        if (blocks_of_host_records(h, recs.data(), recs.size(), end, args) != 0) return -1;
+    } else if (h->n > 1) {
+        // The one copy behind the compaction brings the header and up to RV_BLOCKS_HOST_BELOW records: a list shorter than that is already on the
+        // host and takes the host rule (the kernels' fifteen launches cost more than they save there); a longer one stays on the device.
+        const int64_t below = std::max<int64_t>(h->ws.opt.blocks_host_below, 0);
+        RvPairDense dn;
+        if (pair_scan_dense(h, h->dSA.as<sa_t>(), h->dLCP.as<lcp_t>(), h->dBWT.as<uint8_t>(), h->n, minlength, nullptr, (size_t)below, dn) != 0) return -1;
+        if ((int64_t)dn.total < below && dn.have == dn.total) {
+            if (blocks_of_host_records(h, h->hscan.as<RvPairRec>() + RV_PAIR_HDR, dn.total, end, args) != 0) return -1;
+            if (counts) { counts[0] = h->blk.nmums; counts[1] = h->blk.nclusters; }
+            return (int64_t)h->blk.s1.size();
+        }
+        RvBlkIn in;
+        in.recs = dn.recs; in.n = dn.total; in.rc_map = h->rc == 1; in.nsep0 = h->nsep[0]; in.nT = h->nT;
+        in.max_a = h->nsep[0]; in.max_b = h->nT; in.max_l = h->nT;
+        if (rv_blocks_device(h->ws, in, end.data(), (int64_t)end.size(), args, h->blk) != 0) return -1;
+    }
+    if (counts) { counts[0] = h->blk.nmums; counts[1] = h->blk.nclusters; }
+    return (int64_t)h->blk.s1.size();
+}
+
+int rv_fetch_blocks(rv_index *h, int64_t *s1, int64_t *e1, int64_t *s2, int64_t *e2, int64_t *score, int32_t *refid, int32_t *ctgid, int64_t cap) {
+    if (!h) { rv_set_error("rv_fetch_blocks: null handle"); return -1; }
+    const size_t k = h->blk.s1.size();
+    if (cap < (int64_t)k) { rv_set_error("buffer too small"); return -1; }
+    if (!k) return 0;
+    memcpy(s1, h->blk.s1.data(), k * 8); memcpy(e1, h->blk.e1.data(), k * 8); memcpy(s2, h->blk.s2.data(), k * 8); memcpy(e2, h->blk.e2.data(), k * 8);
+    memcpy(score, h->blk.score.data(), k * 8); memcpy(refid, h->blk.refid.data(), k * 4); memcpy(ctgid, h->blk.ctgid.data(), k * 4);
+    return 0;
+}
+
+/* the same kernels on a list the caller brings (b in forward coordinates, as rv_fetch_mums gives it): the handle lends its stream and its
+ * workspace and need not be constructed.  The blocks wait for rv_fetch_blocks. */
+int64_t rv_blocks_records(rv_index *h, int64_t n, const uint32_t *l, const int64_t *a, const int64_t *b, int o, int64_t nseq, const int64_t *end,
+                          int cluster, int64_t maxdist, int64_t minclustsize) {
+    if (!h || n < 0 || (n && (!l || !a || !b))) { rv_set_error("rv_blocks_records: bad arguments"); return -1; }
+    (void)hipSetDevice(h->device);
+    h->blk.clear();
+    RvBlkArgs args; args.o = o ? 1 : 0; args.cluster = cluster ? 1 : 0; args.maxdist = maxdist; args.minclustsize = minclustsize;
+    RvBlkIn in;
+    in.l = l; in.a = a; in.b = b; in.n = n;
+    for (int64_t k = 0; k < n; k++) {
+        if (a[k] < 0 || b[k] < 0) { rv_set_error("blocks: coordinates outside 0 .. 2^61"); return -1; }
+        in.max_a = std::max(in.max_a, a[k]); in.max_b = std::max(in.max_b, b[k]); in.max_l = std::max<int64_t>(in.max_l, l[k]);
+    }
+    if (rv_blocks_device(h->ws, in, end, nseq, args, h->blk) != 0) return -1;
+    return (int64_t)h->blk.s1.size();
+}
+
+/* the rule in host C++ from the same arrays: no device is asked for.  cap >= the number of blocks (n always suffices); counts = {records, clusters
+ * before the minclustsize filter}. */
+int64_t rv_blocks_host(int64_t n, const uint32_t *l, const int64_t *a, const int64_t *b, int o, int64_t nseq, const int64_t *end, int cluster, int64_t maxdist,
+                       int64_t minclustsize, int64_t counts[2], int64_t *s1, int64_t *e1, int64_t *s2, int64_t *e2, int64_t *score, int32_t *refid, int32_t *ctgid, int64_t cap) {
+    RvBlkArgs args; args.o = o ? 1 : 0; args.cluster = cluster ? 1 : 0; args.maxdist = maxdist; args.minclustsize = minclustsize;
+    RvBlkOut out;
+    if (rv_blocks_rule_host(n, l, a, b, end, nseq, args, out) != 0) return -1;
+    const size_t k = out.s1.size();
+    if (cap < (int64_t)k) { rv_set_error("buffer too small"); return -1; }
+    if (k) {
+        memcpy(s1, out.s1.data(), k * 8); memcpy(e1, out.e1.data(), k * 8); memcpy(s2, out.s2.data(), k * 8); memcpy(e2, out.e2.data(), k * 8);
+        memcpy(score, out.score.data(), k * 8); memcpy(refid, out.refid.data(), k * 4); memcpy(ctgid, out.ctgid.data(), k * 4);
+    }
+    if (counts) { counts[0] = out.nmums; counts[1] = out.nclusters; }
+    return (int64_t)k;
 }
 
 int rv_prof_enable(rv_index *h, int on) {      /* 0 off; 1 every class; otherwise bit k+1 selects class k */

@@ -117,7 +117,9 @@ void rv_set_error(const char *fmt, ...);
     X(many_kchain_host, "RV_MANY_KCHAIN_HOST", 0) \
     X(kchain_cap, "RV_KCHAIN_CAP", 1024) \
     X(many_kchain_big, "RV_MANY_KCHAIN_BIG", 1) \
-    X(kchain_big_min, "RV_KCHAIN_BIG_MIN", 512)
+    X(kchain_big_min, "RV_KCHAIN_BIG_MIN", 512) \
+    X(blocks_host, "RV_BLOCKS_HOST", 0) \
+    X(blocks_host_below, "RV_BLOCKS_HOST_BELOW", 4096)
 struct RvOptions {
 #define RV_X_(f, name, def) int64_t f = def;
     RV_OPTION_LIST(RV_X_)
@@ -384,6 +386,7 @@ struct Workspace {
     DBuf rs_hist;          // radix sort: per-block digit histograms
     DBuf rs_digits;        // radix sort: the next pass' digit of every key, a byte each
     DBuf misc[20];
+    DBuf blk[15];          // getblocks (rv_blocks.hip): records, ids, keys, sums and the block arrays
     DBuf sa[32];           // SA-build scratch, kept between construct() calls
     HBuf hpin;             // pinned landing zone of rv_read_back
     hipEvent_t ev_rb = nullptr;
@@ -405,6 +408,7 @@ struct Workspace {
         for (auto &b : scan_tmp) b.release();
         rs_hist.release(); rs_digits.release();
         for (auto &b : misc) b.release();
+        for (auto &b : blk) b.release();
         for (auto &b : sa) b.release();
     }
 };

@@ -2,6 +2,7 @@
 #pragma once
 #include "rv_common.h"
 #include "rv_scan.h"
+#include "rv_blocks.h"
 #include "../../include/reveal_amd.h"
 #include <utility>
 
@@ -148,6 +149,7 @@ struct rv_index {
     // ---- scan results of the main index (getmums / getmultimums)
     std::vector<u32> m_l; std::vector<int64_t> m_a, m_b;
     std::vector<u32> mm_l; std::vector<int32_t> mm_n; std::vector<int64_t> mm_off, mm_pos; std::vector<uint16_t> mm_so;
+    RvBlkOut blk;                      // rv_getblocks / rv_blocks_records -> rv_fetch_blocks
     // ---- recursion state (rv_align.hip)
     struct Align *al = nullptr;
     struct RvBatchGroup *batch = nullptr;      // rv_batch_run: the group this handle's job meets in the middle of its anchor cascade (rv_cascade_multi.hip)
