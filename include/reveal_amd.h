@@ -143,6 +143,60 @@ int64_t rv_blocks_host(int64_t n, const uint32_t *l, const int64_t *a, const int
                        int64_t minclustsize, int64_t counts[2], int64_t *s1, int64_t *e1, int64_t *s2, int64_t *e2, int64_t *score, int32_t *refid, int32_t *ctgid,
                        int64_t cap);
 
+/* glocalchain: the second stage of `reveal transform` (transform.py:301-360; glocalchain :947-1180 with useheap=False, gapcost :1182-1244) on a block
+ * list (s1, e1, s2, e2, o, score, refid, ctgid), n blocks.  rs[i] / re[i] = begin and '$' of the i-th sequence (ctg2range); the sequences that begin in
+ * front of `sep` are the reference's, the others the contigs.  params = {rearrangecost, inversioncost, lambda, eps, alfa, gapopen, lastn, lastbp}.
+ * ONE PASS on axis 0 (the reference) or 1 (the query); c1 = the axis' own coordinates [a, ae] of a block, c2 = the other axis' [b, be]:
+ *   dummies   one per sequence of the axis at (its '$', its '$'), appended behind the list in sequence order; `end` = the last one; `start` = (begin, begin)
+ *             of the axis' first sequence, in front of everything.  A dummy has score 0 and no ids.
+ *   sort      list + dummies stably by (a, -score): ties stay in input order.  H[0] = start, H[k] = the k-th sorted entry; predecessors of H[k] are
+ *             H[k-1], H[k-2], ... in that order.
+ *   filters   between two real blocks p, b: p is skipped where p.a == b.a or p.ae >= b.ae, or where p lies inside b on c2 (p.b >= b.b and p.be <= b.be).
+ *   window    deepest = the first sorted entry whose ae >= b.a.  The walk back counts the predecessors not skipped (l) and ends behind the first of
+ *             them with b.a - p.a > lastbp and l >= lastn and p.a < H[deepest].a; start is the last predecessor in any case.
+ *   cost c(p, b), by case:
+ *             both dummies: gapopen + |b.a - p.ae| * eps.
+ *             one dummy: it takes the other's ids and orientation and, on c2, the point where that block is left or entered (p real, o = 0: p.be,
+ *               o = 1: p.b; b real, o = 0: b.b, o = 1: b.be); then as the next case.
+ *             same reference sequence and same contig: gapcost.  d1 = b.a - p.ae.  Equal orientations: where b lies on the wrong side of p on c2
+ *               (o = 0: b.b < p.b; o = 1: b.b > p.b) gapopen + rearrangecost + eps * max(d1, 0); else d2 = b.b - p.be (o = 0) or p.b - b.be (o = 1) and
+ *               gapopen + min(rearrangecost, lambda * |d1 - d2|) + eps * max(min(d1, d2), 0).  Unequal orientations: d1 = max(d1, 0), d2 = max(0, b.b > p.b ?
+ *               b.b - p.be : p.b - b.be), the same sum plus inversioncost.
+ *             same sequence on the axis (reference sequence on axis 0, contig on axis 1), another one on c2: with (S, E) the c2 sequence of each block,
+ *               cp = p.o == 0 ? |E - p.be| : |p.b - S|;  cb = (b.o == 0) == (axis == 0) ? |E - b.be| : |b.b - S|;  gapopen + min(rearrangecost, (cp + cb) * eps).
+ *             the rest: rearrangecost + gapopen + |b.a - p.ae| * eps.
+ *   recurrence  score[0] = 0;  score[k] = max over the window's unskipped p of (score[p] - c(p, H[k])) + alfa * H[k].score;  among equal values the nearest
+ *             predecessor (the largest p) wins; back[k] = that p.
+ *   chain     from back[end] along back[] to start, the dummies dropped, reversed: the real blocks of the best path in sorted order.
+ * THE FILTER (transform.py:307-356): passes on axis 0, each on the chain of the one before in the order that pass left it, until a pass drops nothing; then
+ * the same on axis 1.  useheap=True is a different algorithm (it ends the walk at the first predecessor that cannot win) and is not provided.
+ * Arithmetic is 64-bit integer: weights are non-negative integers (a negative one is an error, the reference's assert(c>=0)), and rv_glocal_admit -> 1 where
+ * the largest possible |score| on n blocks with coordinates <= maxcoord and scores <= maxscore stays inside 62 bits, 0 where it might not (such a call is
+ * refused; reveal_amd.transform.glocalchain_python has Python's arithmetic).  The list is validated: 0 <= s <= e < 2^61, o in {0, 1}, 0 <= score,
+ * refid names a sequence in front of sep, ctgid one behind it, ranges ascending.  Departures from the reference: every list entry is a block of its own
+ * (its dictionary merges equal tuples; getblocks cannot produce them), and an empty list gives an empty chain.
+ * A chain is returned as the indices of its blocks in the caller's list.  axes: bit 0 = axis 0, bit 1 = axis 1.  info (ninfo >= 12 words, or NULL):
+ * [0] route (0 kernels, 1 host rule), [1] / [2] passes on axis 0 / 1, [3] tiles over all passes, [4] most tiles in one pass, [5] nanoseconds in the recurrence
+ * kernel (events round its launches), [6] entries it went through, [7] / [8] bytes copied to / from the device, [9] edges, [10] sort keys (1: one 64-bit key,
+ * 2: two stable sorts), [11] passes made, [12 ..] the blocks left by each pass.
+ * rv_glocal_host: the rule in host C++, no device is asked for (fixed = 0: one pass per axis named, 1: the filter).  rv_glocal_blocks: one pass through the
+ * kernels (rv_glocal.hip); rv_glocal_filter: the whole filter in one call, the list staying in device memory between the passes -- a count comes back per
+ * pass, the chain once, through rv_fetch_glocal.  The handle lends stream and workspace and need not be constructed.  Switches: RV_GLOCAL_HOST = 1 runs the
+ * host rule inside these two (the A/B leg), a list of fewer than RV_GLOCAL_HOST_BELOW blocks takes it by itself -- as shipped 2^31, above every list: the kernels lose to
+ * the host rule at every length measured and run where the switch is lowered (0: always); RV_GLOCAL_EDGE_BUDGET = the most edges
+ * (8 bytes each) whose costs are held at a time: a pass works through its blocks in tiles of that many. */
+int rv_glocal_admit(int64_t n, int64_t nseq, int64_t maxcoord, int64_t maxscore, const int64_t *params);
+int64_t rv_glocal_host(int64_t n, const int64_t *s1, const int64_t *e1, const int64_t *s2, const int64_t *e2, const int32_t *o, const int64_t *score, const int32_t *refid,
+                       const int32_t *ctgid, int64_t nseq, const int64_t *rs, const int64_t *re, int64_t sep, const int64_t *params, int axes, int fixed, int64_t *info,
+                       int ninfo, int32_t *idx, int64_t cap);
+int64_t rv_glocal_blocks(rv_index *h, int64_t n, const int64_t *s1, const int64_t *e1, const int64_t *s2, const int64_t *e2, const int32_t *o, const int64_t *score,
+                         const int32_t *refid, const int32_t *ctgid, int64_t nseq, const int64_t *rs, const int64_t *re, int64_t sep, const int64_t *params, int axis,
+                         int64_t *info, int ninfo);
+int64_t rv_glocal_filter(rv_index *h, int64_t n, const int64_t *s1, const int64_t *e1, const int64_t *s2, const int64_t *e2, const int32_t *o, const int64_t *score,
+                         const int32_t *refid, const int32_t *ctgid, int64_t nseq, const int64_t *rs, const int64_t *re, int64_t sep, const int64_t *params, int axes,
+                         int64_t *info, int ninfo);
+int rv_fetch_glocal(rv_index *h, int32_t *idx, int64_t cap);
+
 /* ---- the recursion: align() / aligner() (interface.c:293-415, reveal.c:731-1338)
  *
  * The reference pops one sub-index at a time (LIFO) and calls back into

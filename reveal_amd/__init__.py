@@ -5,6 +5,6 @@ behind the reference's own `reveallib.index` API.
 
     from reveal_amd import reveallib          # 32-bit suffix arrays
     from reveal_amd import reveallib64        # 64-bit suffix arrays (`--64`)
-    from reveal_amd import transform          # the blocks of `reveal transform`: index.getblocks, transform.synteny_blocks
+    from reveal_amd import transform          # `reveal transform`: index.getblocks, transform.synteny_blocks, transform.glocal_filter, transform.synteny_chain
 """
 __all__ = ["reveallib", "reveallib64", "rem", "kchain", "transform"]

@@ -78,6 +78,11 @@ SYMBOLS = {
     "rv_fetch_blocks": (_I, [V, V, V, V, V, V, V, V, _L]),
     "rv_blocks_records": (_L, [V, _L, V, V, V, _I, _L, V, _I, _L, _L]),
     "rv_blocks_host": (_L, [_L, V, V, V, _I, _L, V, _I, _L, _L, V, V, V, V, V, V, V, V, _L]),
+    "rv_glocal_admit": (_I, [_L, _L, _L, _L, V]),
+    "rv_glocal_host": (_L, [_L, V, V, V, V, V, V, V, V, _L, V, V, _L, V, _I, _I, V, _I, V, _L]),
+    "rv_glocal_blocks": (_L, [V, _L, V, V, V, V, V, V, V, V, _L, V, V, _L, V, _I, V, _I]),
+    "rv_glocal_filter": (_L, [V, _L, V, V, V, V, V, V, V, V, _L, V, V, _L, V, _I, V, _I]),
+    "rv_fetch_glocal": (_I, [V, V, _L]),
     "rv_align_begin": (_I, [V, _I, _I]),
     "rv_frontier_size": (_I, [V]),
     "rv_frontier_scan": (_I, [V]),

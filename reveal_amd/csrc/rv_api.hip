@@ -325,7 +325,7 @@ int rv_reset(rv_index *h) {
     h->maxlcp = 0;
     h->m_l.clear(); h->m_a.clear(); h->m_b.clear();
     h->mm_l.clear(); h->mm_n.clear(); h->mm_off.clear(); h->mm_pos.clear(); h->mm_so.clear();
-    h->blk.clear();
+    h->blk.clear(); h->glc.clear();
     memset(h->ws.cap_events, 0, sizeof h->ws.cap_events);
     return 0;
 }
@@ -1205,6 +1205,71 @@ int64_t rv_blocks_host(int64_t n, const uint32_t *l, const int64_t *a, const int
     }
     if (counts) { counts[0] = out.nmums; counts[1] = out.nclusters; }
     return (int64_t)k;
+}
+
+/* ---- the glocal chain of `reveal transform` (transform.py:301-360, 947-1180) on a block list the caller brings: rv_glocal.hip.  The rule is stated in
+ * include/reveal_amd.h.  params = {rearrangecost, inversioncost, lambda, eps, alfa, gapopen, lastn, lastbp}. */
+static void glc_args(RvGlcIn &in, RvGlcParams &w, int64_t n, const int64_t *s1, const int64_t *e1, const int64_t *s2, const int64_t *e2, const int32_t *o, const int64_t *score,
+                     const int32_t *refid, const int32_t *ctgid, int64_t nseq, const int64_t *rs, const int64_t *re, int64_t sep, const int64_t *p) {
+    in.n = n; in.s1 = s1; in.e1 = e1; in.s2 = s2; in.e2 = e2; in.o = o; in.score = score; in.refid = refid; in.ctgid = ctgid;
+    in.nseq = nseq; in.rs = rs; in.re = re; in.sep = sep;
+    w.rearr = p[0]; w.inv = p[1]; w.lambda = p[2]; w.eps = p[3]; w.alfa = p[4]; w.gapopen = p[5]; w.lastn = p[6]; w.lastbp = p[7];
+}
+/* the kernels, or -- by RV_GLOCAL_HOST, and for a list of fewer than RV_GLOCAL_HOST_BELOW blocks -- the host rule: -> h->glc.  As shipped the threshold lies above
+ * every list the library takes: one wavefront's recurrence (480 ns a block measured) loses to the host loop at every length tried, so the kernels run
+ * where RV_GLOCAL_HOST_BELOW is lowered. */
+static int64_t glc_run(rv_index *h, const RvGlcIn &in, const RvGlcParams &w, int axes, int fixed, int64_t *info, int ninfo) {
+    (void)hipSetDevice(h->device);
+    h->glc.clear();
+    const bool host = h->ws.opt.glocal_host != 0 || in.n < std::max<int64_t>(h->ws.opt.glocal_host_below, 0);
+    const int r = host ? rv_glocal_rule_host(in, w, axes, fixed, info, ninfo, h->glc) : rv_glocal_device(h->ws, in, w, axes, fixed, info, ninfo, h->glc);
+    if (r != 0) { h->glc.clear(); return -1; }
+    return (int64_t)h->glc.idx.size();
+}
+
+int rv_glocal_admit(int64_t n, int64_t nseq, int64_t maxcoord, int64_t maxscore, const int64_t *params) {
+    if (!params) { rv_set_error("rv_glocal_admit: null params"); return -1; }
+    RvGlcIn in; RvGlcParams w;
+    glc_args(in, w, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, params);
+    return rv_glocal_admit_rule(n, nseq, maxcoord, maxscore, w);
+}
+
+int64_t rv_glocal_host(int64_t n, const int64_t *s1, const int64_t *e1, const int64_t *s2, const int64_t *e2, const int32_t *o, const int64_t *score, const int32_t *refid,
+                       const int32_t *ctgid, int64_t nseq, const int64_t *rs, const int64_t *re, int64_t sep, const int64_t *params, int axes, int fixed, int64_t *info,
+                       int ninfo, int32_t *idx, int64_t cap) {
+    if (!params) { rv_set_error("rv_glocal_host: null params"); return -1; }
+    RvGlcIn in; RvGlcParams w; RvGlcOut out;
+    glc_args(in, w, n, s1, e1, s2, e2, o, score, refid, ctgid, nseq, rs, re, sep, params);
+    if (rv_glocal_rule_host(in, w, axes, fixed, info, ninfo, out) != 0) return -1;
+    if (cap < (int64_t)out.idx.size() || (!idx && !out.idx.empty())) { rv_set_error("buffer too small"); return -1; }
+    if (!out.idx.empty()) memcpy(idx, out.idx.data(), out.idx.size() * 4);
+    return (int64_t)out.idx.size();
+}
+
+int64_t rv_glocal_blocks(rv_index *h, int64_t n, const int64_t *s1, const int64_t *e1, const int64_t *s2, const int64_t *e2, const int32_t *o, const int64_t *score,
+                         const int32_t *refid, const int32_t *ctgid, int64_t nseq, const int64_t *rs, const int64_t *re, int64_t sep, const int64_t *params, int axis,
+                         int64_t *info, int ninfo) {
+    if (!h || !params || (axis != 0 && axis != 1)) { rv_set_error("rv_glocal_blocks: bad arguments"); return -1; }
+    RvGlcIn in; RvGlcParams w;
+    glc_args(in, w, n, s1, e1, s2, e2, o, score, refid, ctgid, nseq, rs, re, sep, params);
+    return glc_run(h, in, w, 1 << axis, 0, info, ninfo);
+}
+
+int64_t rv_glocal_filter(rv_index *h, int64_t n, const int64_t *s1, const int64_t *e1, const int64_t *s2, const int64_t *e2, const int32_t *o, const int64_t *score,
+                         const int32_t *refid, const int32_t *ctgid, int64_t nseq, const int64_t *rs, const int64_t *re, int64_t sep, const int64_t *params, int axes,
+                         int64_t *info, int ninfo) {
+    if (!h || !params) { rv_set_error("rv_glocal_filter: bad arguments"); return -1; }
+    RvGlcIn in; RvGlcParams w;
+    glc_args(in, w, n, s1, e1, s2, e2, o, score, refid, ctgid, nseq, rs, re, sep, params);
+    return glc_run(h, in, w, axes, 1, info, ninfo);
+}
+
+int rv_fetch_glocal(rv_index *h, int32_t *idx, int64_t cap) {
+    if (!h) { rv_set_error("rv_fetch_glocal: null handle"); return -1; }
+    const size_t k = h->glc.idx.size();
+    if (cap < (int64_t)k || (k && !idx)) { rv_set_error("buffer too small"); return -1; }
+    if (k) memcpy(idx, h->glc.idx.data(), k * 4);
+    return 0;
 }
 
 int rv_prof_enable(rv_index *h, int on) {      /* 0 off; 1 every class; otherwise bit k+1 selects class k */

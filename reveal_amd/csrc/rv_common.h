@@ -119,7 +119,10 @@ void rv_set_error(const char *fmt, ...);
     X(many_kchain_big, "RV_MANY_KCHAIN_BIG", 1) \
     X(kchain_big_min, "RV_KCHAIN_BIG_MIN", 512) \
     X(blocks_host, "RV_BLOCKS_HOST", 0) \
-    X(blocks_host_below, "RV_BLOCKS_HOST_BELOW", 4096)
+    X(blocks_host_below, "RV_BLOCKS_HOST_BELOW", 4096) \
+    X(glocal_host, "RV_GLOCAL_HOST", 0) \
+    X(glocal_host_below, "RV_GLOCAL_HOST_BELOW", (int64_t)1 << 31) \
+    X(glocal_edge_budget, "RV_GLOCAL_EDGE_BUDGET", 1 << 25)
 struct RvOptions {
 #define RV_X_(f, name, def) int64_t f = def;
     RV_OPTION_LIST(RV_X_)
@@ -387,6 +390,7 @@ struct Workspace {
     DBuf rs_digits;        // radix sort: the next pass' digit of every key, a byte each
     DBuf misc[20];
     DBuf blk[15];          // getblocks (rv_blocks.hip): records, ids, keys, sums and the block arrays
+    DBuf glc[3];           // the glocal chain (rv_glocal.hip): the arena of a call, a tile's edges, the tables that stay for every pass
     DBuf sa[32];           // SA-build scratch, kept between construct() calls
     HBuf hpin;             // pinned landing zone of rv_read_back
     hipEvent_t ev_rb = nullptr;
@@ -409,6 +413,7 @@ struct Workspace {
         rs_hist.release(); rs_digits.release();
         for (auto &b : misc) b.release();
         for (auto &b : blk) b.release();
+        for (auto &b : glc) b.release();
         for (auto &b : sa) b.release();
     }
 };
