@@ -31,7 +31,7 @@ struct RvLeafArgs {
 int rv_leaf_launch(Workspace &ws, const RvLeafArgs &a, int nroots);
 
 // k_leaf_chain (rv_leaf_chain.hip): the same kernel with the reference's default picker (schemes.graphmumpicker, rv_pick_chain for two samples) as its
-// pick stage, for roots that are whole jobs of rv_many.  What the caller must have checked (rv_many.hip many_chain_admits): trim on, minl > 0, no seeds,
+// pick stage, for roots that are whole jobs of rv_many.  What the caller must have checked (rv_many.hip many_class_admits, the RV_MANY_CHAIN row): trim on, minl > 0, no seeds,
 // a --maxmums that cannot bite, weights within RV_LEAF_CHAIN_WMAX.  a.trace must be 0.
 #define RV_LEAF_CHAIN_WMAX 65536
 struct RvLeafChainArgs {

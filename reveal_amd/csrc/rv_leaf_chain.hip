@@ -6,7 +6,7 @@
 // wavefront that owns the sub-index, so a job's whole recursion stays in one workgroup as it does with the built-in picker.  Frame stack, split,
 // bubble_sort and anchor staging are k_leaf's (rv_leaf_stages.h: leaf_run).  What is here: collect, where the lists live, what happens to a pick.
 //
-// What the caller guarantees (rv_many.hip many_chain_admits), and what follows from it:
+// What the caller guarantees (rv_many.hip many_class_admits, the RV_MANY_CHAIN row of many_classes), and what follows from it:
 //   trim on, minl > 0          no p-value cut (pow / exp / log stay on the host)
 //   no seed can arise          the "precomputed" branch of the picker is never needed: a child starts from its scan like the root
 //   --maxmums cannot bite      two MUMs never start at the same position of either sequence: a sub-index holds at most min(la, lb) of them

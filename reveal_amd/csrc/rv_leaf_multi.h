@@ -32,8 +32,8 @@ int rv_leaf_multi_launch(hipStream_t q, const RvLeafMultiArgs &a, int njobs, int
 
 // k_leaf_multi_chain (rv_leaf_multi_chain.hip): the same jobs -- 3 .. RV_MANY_KMAX samples in the narrow form, up to RV_MANY_WIDE_KMAX in the wide one, at
 // most RV_LEAF_N ranks -- with the reference's default picker (schemes.graphmumpicker; rv_pick_chain for any number of samples) as the pick stage, for
-// rv_many's RV_MANY_CHAIN_MULTI and RV_MANY_CHAIN_WIDE rounds.  What the caller must have checked (rv_many.hip many_chain_multi_admits,
-// many_chain_wide_admits): trim on, minl > 0, no seeds, a --maxmums that cannot bite, weights within RV_LEAF_MCHAIN_WMAX.
+// rv_many's RV_MANY_CHAIN_MULTI and RV_MANY_CHAIN_WIDE rounds.  What the caller must have checked (rv_many.hip many_class_admits, the
+// two rows of many_classes): trim on, minl > 0, no seeds, a --maxmums that cannot bite, weights within RV_LEAF_MCHAIN_WMAX.
 #define RV_LEAF_MCHAIN_WMAX 1024       // rv_leaf_multi_chain.hip derives it for both forms: scores of up to 16 / 64 paths in 32 bits
 struct RvLeafMultiChainArgs {
     int32_t wscore, wpen;                                    // 0 .. RV_LEAF_MCHAIN_WMAX

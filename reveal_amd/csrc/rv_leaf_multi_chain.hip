@@ -26,7 +26,7 @@
 //   1   trim_overlap raises in the reference                     2   the chain finds no predecessor / a broken back-pointer chain
 //   8   another match of the list has the split's offsets member by member: rv_pick_chain's `mapping` would hand out that one
 //   16  rv_many's test hook                                     32  the frame stack is full
-// What the caller guarantees (rv_many.hip many_chain_multi_admits, many_chain_wide_admits): trim on, minl > 0, no seed possible, a --maxmums of at least the job's ranks (a
+// What the caller guarantees (rv_many.hip many_class_admits, the RV_MANY_CHAIN_MULTI and RV_MANY_CHAIN_WIDE rows of many_classes): trim on, minl > 0, no seed possible, a --maxmums of at least the job's ranks (a
 // sub-index has fewer candidates than ranks), gap model 0 .. 2, and
 //   0 <= wscore, wpen <= RV_LEAF_MCHAIN_WMAX = 2^10: scores in 32 bits (rv_chain_stage.h).  A job has at most 2^11 ranks.  The lengths of a chain are disjoint on every
 //   path: they add up to at most 2^11, and n (n - 1) / 2 <= 120 < 2^7, so the gains of a chain add up to at most wscore * 2^18.  A gap cost is at most

@@ -55,32 +55,32 @@
 // rv_many_set_picker(m, 1, args): the reference's default picker (schemes.graphmumpicker; rv_pick_chain, rv_chain.hip) instead of the built-in one -- what
 // `reveal refine` aligns its bubbles with.  Every shared class above finishes with built-in-picker kernels, so under kind 1 none of them takes a job,
 // whatever its switch says: the jobs run the ordinary way with rv_set_picker(h, 1, args) on the internal handle.  RV_MANY_CHAIN (off by default): the
-// pair jobs many_chain_admits names share their launches all the same -- layout, index build and frontier of the small pair jobs, and ONE launch of
+// pair jobs of its row of many_classes (many_class_admits) share their launches all the same -- layout, index build and frontier of the small pair jobs, and ONE launch of
 // k_leaf_chain (rv_leaf_chain.hip), the leaf kernel with the picker's decision for two samples as its pick stage.  A job the kernel flags (where the
 // reference's own trim_overlap raises) is dropped from the round's results and runs the ordinary way.  The results do not depend on the switch.
 // RV_MANY_CHAIN_MULTI (off by default, independent of RV_MANY_CHAIN and RV_MANY_MULTI; it means something under kind 1 only): the jobs of 3 .. RV_MANY_KMAX
-// sequences many_chain_multi_admits names share their launches too, in rounds of their own -- layout and index build of RV_MANY_MULTI (many_round_multi) and
+// sequences of its row of many_classes share their launches too, in rounds of their own -- layout and index build of RV_MANY_MULTI (many_round_multi) and
 // ONE launch of k_leaf_multi_chain (rv_leaf_multi_chain.hip), the multi-sample leaf kernel with the whole picker as its pick stage: matches on sample
 // subsets, `segment`, trim and chain over k paths, a three-way split with a `rest` child.  Flags as for k_leaf_chain, per job.
 // RV_MANY_CHAIN_WIDE (off by default, independent of every other switch; it means something under kind 1 only): the jobs of 17 .. RV_MANY_WIDE_KMAX = 64
-// sequences many_chain_wide_admits names share their launches too, in rounds of their own -- layout and index build of the small RV_MANY_WIDE rounds
+// sequences of its row of many_classes share their launches too, in rounds of their own -- layout and index build of the small RV_MANY_WIDE rounds
 // (many_round_multi with kmax = 64) and ONE launch of the 64-sample form of k_leaf_multi_chain.  Flags and test hooks as for RV_MANY_CHAIN_MULTI.  Under a
 // picker the jobs of 17 .. 64 sequences above RV_LEAF_N ranks are RV_MANY_CHAIN_WIDE_LARGE's (below); every job of more than 64 sequences stays ordinary.
-// RV_MANY_CHAIN_LARGE (off by default, independent of every other switch; it means something under kind 1 only): the pair jobs many_chain_large_admits names
+// RV_MANY_CHAIN_LARGE (off by default, independent of every other switch; it means something under kind 1 only): the pair jobs of its row of many_classes
 // -- more than RV_LEAF_N and at most min(RV_MANY_LARGE_MAX, 2^17) ranks -- share their launches too, in rounds of their own, from RV_MANY_CHAIN_LARGE_MIN such
 // jobs in a call on: layout, segmented index build and frontier of the RV_MANY_LARGE rounds (many_round with `large` and `redo`), and the level pipeline under
 // the chain route -- every sub-index above RV_LEAF_N ranks gets its pick from k_pick_chain (rv_pick_chain.hip: the picker's decision for two samples, a
 // wavefront per sub-index, in place of the longest-match kernel; k_decide and the early split as they are), the others drop into k_leaf_chain as they shrink.
 // The flag words are the jobs': a flag set by any launch of any level drops all of the job's anchors, leaves its text untaken and sends it to the ordinary path.
 // RV_MANY_CHAIN_LARGE_MULTI (off by default, independent of every other switch; it means something under kind 1 only): the jobs of 3 .. RV_MANY_KMAX sequences
-// many_chain_large_multi_admits names -- more than RV_LEAF_N and at most min(RV_MANY_LARGE_MAX, 2^17) ranks -- share their launches too, in rounds of their own,
+// of its row of many_classes -- more than RV_LEAF_N and at most min(RV_MANY_LARGE_MAX, 2^17) ranks -- share their launches too, in rounds of their own,
 // from RV_MANY_CHAIN_LARGE_MULTI_MIN such jobs in a call on: sample-major layout, index build and frontier of the RV_MANY_LARGE_MULTI rounds
 // (many_round_large_multi with `redo`), and the multi-sample level pipeline under its chain route (rv_multi_chain_route) -- every level's scan unfiltered, every
 // sub-index picked by k_pick_multi_chain (rv_pick_multi_chain.hip: the picker's decision for up to 16 samples, a wavefront per sub-index) in place of
 // k_multi_pick1 / k_multi_pick2, the early split off; a pick of a sample subset leaves a `rest` child.  There is no leaf kernel for multi-sample sub-indices of
 // a handle: sub-indices of every size are picked this way.  Flag words per job as above.
 // RV_MANY_CHAIN_WIDE_LARGE (off by default, independent of every other switch; it means something under kind 1 only): the jobs of 17 .. RV_MANY_WIDE_KMAX = 64
-// sequences many_chain_wide_large_admits names -- more than RV_LEAF_N and at most min(RV_MANY_LARGE_MAX, 2^17) ranks -- share their launches too, in rounds of
+// sequences of its row of many_classes -- more than RV_LEAF_N and at most min(RV_MANY_LARGE_MAX, 2^17) ranks -- share their launches too, in rounds of
 // their own, from RV_MANY_CHAIN_WIDE_LARGE_MIN such jobs in a call on: the rounds of RV_MANY_CHAIN_LARGE_MULTI with kmax = RV_MANY_WIDE_KMAX
 // (many_round_large_multi with `redo`), every sub-index picked by the 64-sample form of k_pick_multi_chain.  That form holds 256 candidates a sub-index, not
 // 512, and its weight bound is 128: a sub-index with more flags its job (32), which finishes on the ordinary path.  Jobs of more than 64 sequences stay ordinary.
@@ -349,97 +349,100 @@ int many_handle(rv_many *m, rv_index **h) {
     return 0;
 }
 
-// The pair jobs k_leaf_chain finishes under picker kind 1 (RV_MANY_CHAIN): the rule, stated once (many.takes_shared_launch(.., picker=, chain=True) mirrors
-// it).  Everything the kernel leaves out has to be impossible for the job: no p-value cut (minl > 0), no untrimmed lists, no seeds for the children
-// (--seedsize above the longer sequence: no match is that long), no --maxmums cut (two MUMs never start at the same position of either sequence, so a
-// sub-index never holds more than min(la, lb)), weights that keep the scores in 32 bits (rv_leaf_chain.hip derives the bound).
-bool many_chain_admits(const rv_many *m, const ManyJob &jb, int minl) {
-    if (m->picker != 1 || !m->chain) return false;
-    if (jb.k != 2 || !jb.clean || jb.ranks > RV_LEAF_N) return false;
-    const rv_picker_args &a = m->pargs;
-    const int64_t la = m->lens[jb.seq0], lb = m->lens[jb.seq0 + 1];
-    if (!a.trim || minl <= 0) return false;
-    if (a.wscore < 0 || a.wpen < 0 || a.wscore > RV_LEAF_CHAIN_WMAX || a.wpen > RV_LEAF_CHAIN_WMAX) return false;
-    if (a.gcmodel < 0 || a.gcmodel > 2) return false;
-    if (a.seedsize > 0 && a.seedsize <= std::max(la, lb)) return false;
-    if (a.maxmums > 0 && a.maxmums < std::min(la, lb)) return false;
-    return true;
-}
-
-// The pair jobs above RV_LEAF_N ranks the level pipeline finishes under picker kind 1 (RV_MANY_CHAIN_LARGE), its picks made by k_pick_chain and k_leaf_chain:
-// the rule, stated once (many.takes_shared_launch(.., picker=, chain_large=True) mirrors it).  It is many_chain_admits' with
-//   RV_LEAF_N < ranks <= min(RV_MANY_LARGE_MAX, 2^17)      positions and lengths of a sub-index in 17 bits, whatever RV_MANY_LARGE_MAX says
-//   weights 0 .. RV_LEAF_MCHAIN_WMAX = 1024               scores in 32 bits at 2^17 ranks (rv_pick_chain.hip derives the bound)
-//   seedsize <= 0 or above the longer sequence, maxmums <= 0 or at least the shorter one: as there
-// rem.align's defaults (10 000 / 10 000) admit every bubble `reveal refine` produces (alleles below 10 000 bases) and nothing with an allele of 10 000 or more.
+// The classes of jobs that share launches, in the order in which many_run runs their rounds (the order of `info`, of `rest` and of the launches).  The
+// domains of the rows are disjoint in (picker kind, k, ranks): a job matches at most one.  many_class_admits states the rule, rv_many_option takes the
+// names of the switches and thresholds from here, and many.CLASSES (many.takes_shared_launch) mirrors the table row by row.
+//   picker        the picker kind the class belongs to: every built-in class finishes with built-in-picker kernels, so under kind 1 none of them
+//                 takes a job, whatever its switch says, and the kind-1 classes mean nothing without a picker
+//   kmin .. kmax  sequences of a job; kmax is the sample bound of the round routine's kernels as well
+//   large         false: ranks <= RV_LEAF_N.  true: RV_LEAF_N < ranks <= RV_MANY_LARGE_MAX, and the job has to fit a round (ranks <= lim: one that does not
+//                 goes the ordinary way); under kind 1 also ranks <= RV_PICK_CHAIN_RANKS = 2^17 -- positions and lengths of a sub-index in 17 bits,
+//                 whatever RV_MANY_LARGE_MAX says
+//   sw, min       the switch (none: always on) and the threshold: fewer admitted jobs in a call stay ordinary (none: one job is enough).  Every class is
+//                 counted on its own against a threshold of its own: what a call does with the jobs of one class does not depend on the others
+//   wmax, by_ranks   kind 1 only: the weight cap, and whether `maxmums` is compared with the job's ranks or (pairs) with the shorter sequence
+//   round         the routine that runs the class, with the row's `large` / kmax; a kind-1 round passes `rest` as its `redo`
+enum ManyRoundKind { MANY_PAIRS, MANY_CONTIGUOUS, MANY_SAMPLE_MAJOR };      // many_round, many_round_multi, many_round_large_multi
+struct ManyClass {
+    int picker, kmin, kmax;
+    bool large;
+    const char *sw_name; int64_t rv_many::*sw;
+    const char *min_name; int64_t rv_many::*min;
+    int wmax; bool by_ranks;
+    ManyRoundKind round;
+};
 static_assert(RV_PICK_CHAIN_WMAX == RV_LEAF_MCHAIN_WMAX && RV_PICK_CHAIN_WMAX <= RV_LEAF_CHAIN_WMAX, "one weight bound for the class");
-bool many_chain_large_admits(const rv_many *m, const ManyJob &jb, int minl) {
-    if (m->picker != 1 || !m->chain_large) return false;
-    if (jb.k != 2 || !jb.clean || jb.ranks <= RV_LEAF_N || jb.ranks > std::min<int64_t>(m->large_max, RV_PICK_CHAIN_RANKS)) return false;
-    const rv_picker_args &a = m->pargs;
-    const int64_t la = m->lens[jb.seq0], lb = m->lens[jb.seq0 + 1];
-    if (!a.trim || minl <= 0) return false;
-    if (a.wscore < 0 || a.wpen < 0 || a.wscore > RV_LEAF_MCHAIN_WMAX || a.wpen > RV_LEAF_MCHAIN_WMAX) return false;
-    if (a.gcmodel < 0 || a.gcmodel > 2) return false;
-    if (a.seedsize > 0 && a.seedsize <= std::max(la, lb)) return false;
-    if (a.maxmums > 0 && a.maxmums < std::min(la, lb)) return false;
-    return true;
-}
-
-// The jobs of several sequences above RV_LEAF_N ranks the multi-sample level pipeline finishes under picker kind 1, its picks made by k_pick_multi_chain:
-// the rule, stated once for both forms of the kernel -- 3 .. RV_MANY_KMAX sequences with RV_MANY_CHAIN_LARGE_MULTI, RV_MANY_KMAX + 1 .. RV_MANY_WIDE_KMAX with
-// RV_MANY_CHAIN_WIDE_LARGE (many.takes_shared_launch(.., picker=, chain_large_multi=True / chain_wide_large=True) mirrors it).  It is many_chain_k_admits' with
-//   RV_LEAF_N < ranks <= min(RV_MANY_LARGE_MAX, 2^17)      positions and lengths of a sub-index in 17 bits, whatever RV_MANY_LARGE_MAX says
-//   weights 0 .. wmax                                     scores in 32 bits at 2^17 ranks: RV_PICK_MCHAIN_WMAX = 512 over 120 pairs (1024 does not hold),
-//                                                         RV_PICK_WCHAIN_WMAX = 128 over 2016 pairs (256 does not hold); rv_pick_multi_chain.hip derives both
-//   seedsize <= 0 or above the longest sequence, maxmums <= 0 or at least the job's ranks: as there
-// rem.align's default maxmums of 10 000 therefore admits jobs of up to 10 000 ranks only (and its seedsize no sequence of 10 000 bases or more).
-bool many_chain_large_k_admits(const rv_many *m, const ManyJob &jb, int minl, int kmin, int kmax, int wmax, int64_t on) {
-    if (m->picker != 1 || !on) return false;
-    if (jb.k < kmin || jb.k > kmax || !jb.clean || jb.ranks <= RV_LEAF_N || jb.ranks > std::min<int64_t>(m->large_max, RV_PICK_CHAIN_RANKS)) return false;
-    const rv_picker_args &a = m->pargs;
-    if (!a.trim || minl <= 0) return false;
-    if (a.wscore < 0 || a.wpen < 0 || a.wscore > wmax || a.wpen > wmax) return false;
-    if (a.gcmodel < 0 || a.gcmodel > 2) return false;
-    int64_t longest = 0;
-    for (int q = 0; q < jb.k; q++) longest = std::max(longest, m->lens[jb.seq0 + (size_t)q]);
-    if (a.seedsize > 0 && a.seedsize <= longest) return false;
-    if (a.maxmums > 0 && a.maxmums < jb.ranks) return false;
-    return true;
-}
 static_assert(RV_PICK_MCHAIN_KMAX == RV_MANY_KMAX && RV_PICK_WCHAIN_KMAX == RV_MANY_WIDE_KMAX, "the two forms of k_pick_multi_chain take the two classes");
-bool many_chain_large_multi_admits(const rv_many *m, const ManyJob &jb, int minl) {
-    return many_chain_large_k_admits(m, jb, minl, 3, RV_MANY_KMAX, RV_PICK_MCHAIN_WMAX, m->chain_large_multi);
-}
-bool many_chain_wide_large_admits(const rv_many *m, const ManyJob &jb, int minl) {
-    return many_chain_large_k_admits(m, jb, minl, RV_MANY_KMAX + 1, RV_MANY_WIDE_KMAX, RV_PICK_WCHAIN_WMAX, m->chain_wide_large);
-}
+static const ManyClass many_classes[] = {
+    // the small pair jobs: no switch
+    {0, 2, 2, false, nullptr, nullptr, nullptr, nullptr, 0, false, MANY_PAIRS},
+    // RV_MANY_CHAIN: the pair jobs k_leaf_chain finishes.  Everything the kernel leaves out has to be impossible for the job: no p-value cut (minl > 0), no
+    // untrimmed lists, no seeds for the children (--seedsize above the longer sequence: no match is that long), no --maxmums cut (two MUMs never start at the
+    // same position of either sequence, so a sub-index never holds more than min(la, lb)), weights that keep the scores in 32 bits (rv_leaf_chain.hip derives
+    // the bound)
+    {1, 2, 2, false, "RV_MANY_CHAIN", &rv_many::chain, nullptr, nullptr, RV_LEAF_CHAIN_WMAX, false, MANY_PAIRS},
+    // RV_MANY_CHAIN_MULTI, RV_MANY_CHAIN_WIDE: the jobs of several sequences the two forms of k_leaf_multi_chain finish.  As above, everything the kernel
+    // leaves out has to be impossible for the job; none of the reasons depends on the number of sequences:
+    //   trim on, minl > 0, gap model 0 .. 2     no p-value cut, no untrimmed lists
+    //   weights 0 .. RV_LEAF_MCHAIN_WMAX        scores of up to 16 / 64 paths in 32 bits (rv_leaf_multi_chain.hip derives the bound for both forms)
+    //   seedsize <= 0 or above the longest sequence   no match is that long: no seeds for the children
+    //   maxmums <= 0 or >= the job's ranks      the cut is made on the matches of ONE sub-index, every one of them an inner node of the LCP-interval tree over the
+    //                                           sub-index' ranks: a tree over len leaves has fewer than len inner nodes, and len <= the job's ranks <= 2048, so
+    //                                           rem.align's default of 10 000 passes whatever the job
+    {1, 3, RV_MANY_KMAX, false, "RV_MANY_CHAIN_MULTI", &rv_many::chain_multi, nullptr, nullptr, RV_LEAF_MCHAIN_WMAX, true, MANY_CONTIGUOUS},
+    {1, RV_MANY_KMAX + 1, RV_MANY_WIDE_KMAX, false, "RV_MANY_CHAIN_WIDE", &rv_many::chain_wide, nullptr, nullptr, RV_LEAF_MCHAIN_WMAX, true, MANY_CONTIGUOUS},
+    // RV_MANY_CHAIN_LARGE: the pair jobs above RV_LEAF_N ranks the level pipeline finishes, its picks made by k_pick_chain and k_leaf_chain.  RV_MANY_CHAIN's rule with
+    //   weights 0 .. RV_PICK_CHAIN_WMAX = 1024               scores in 32 bits at 2^17 ranks (rv_pick_chain.hip derives the bound)
+    //   seedsize <= 0 or above the longer sequence, maxmums <= 0 or at least the shorter one: as there
+    // rem.align's defaults (10 000 / 10 000) admit every bubble `reveal refine` produces (alleles below 10 000 bases) and nothing with an allele of 10 000 or more.
+    {1, 2, 2, true, "RV_MANY_CHAIN_LARGE", &rv_many::chain_large, "RV_MANY_CHAIN_LARGE_MIN", &rv_many::chain_large_min, RV_PICK_CHAIN_WMAX, false, MANY_PAIRS},
+    // RV_MANY_CHAIN_LARGE_MULTI, RV_MANY_CHAIN_WIDE_LARGE: the jobs of several sequences above RV_LEAF_N ranks the multi-sample level pipeline finishes, its picks
+    // made by the two forms of k_pick_multi_chain.  RV_MANY_CHAIN_MULTI's rule with
+    //   weights 0 .. wmax                                     scores in 32 bits at 2^17 ranks: RV_PICK_MCHAIN_WMAX = 512 over 120 pairs (1024 does not hold),
+    //                                                         RV_PICK_WCHAIN_WMAX = 128 over 2016 pairs (256 does not hold); rv_pick_multi_chain.hip derives both
+    //   seedsize <= 0 or above the longest sequence, maxmums <= 0 or at least the job's ranks: as there
+    // rem.align's default maxmums of 10 000 therefore admits jobs of up to 10 000 ranks only (and its seedsize no sequence of 10 000 bases or more).
+    {1, 3, RV_MANY_KMAX, true, "RV_MANY_CHAIN_LARGE_MULTI", &rv_many::chain_large_multi, "RV_MANY_CHAIN_LARGE_MULTI_MIN", &rv_many::chain_large_multi_min, RV_PICK_MCHAIN_WMAX, true, MANY_SAMPLE_MAJOR},
+    {1, RV_MANY_KMAX + 1, RV_MANY_WIDE_KMAX, true, "RV_MANY_CHAIN_WIDE_LARGE", &rv_many::chain_wide_large, "RV_MANY_CHAIN_WIDE_LARGE_MIN", &rv_many::chain_wide_large_min, RV_PICK_WCHAIN_WMAX, true, MANY_SAMPLE_MAJOR},
+    // the built-in picker's classes behind the small pairs: pairs above RV_LEAF_N ranks, 3 .. 16 sequences below and above, 17 .. 64 sequences (one switch, RV_MANY_WIDE, for both sizes)
+    {0, 2, 2, true, "RV_MANY_LARGE", &rv_many::large, "RV_MANY_LARGE_MIN", &rv_many::large_min, 0, false, MANY_PAIRS},
+    {0, 3, RV_MANY_KMAX, false, "RV_MANY_MULTI", &rv_many::multi, nullptr, nullptr, 0, false, MANY_CONTIGUOUS},
+    {0, 3, RV_MANY_KMAX, true, "RV_MANY_LARGE_MULTI", &rv_many::large_multi, "RV_MANY_LARGE_MULTI_MIN", &rv_many::large_multi_min, 0, false, MANY_SAMPLE_MAJOR},
+    {0, RV_MANY_KMAX + 1, RV_MANY_WIDE_KMAX, false, "RV_MANY_WIDE", &rv_many::wide, nullptr, nullptr, 0, false, MANY_CONTIGUOUS},
+    {0, RV_MANY_KMAX + 1, RV_MANY_WIDE_KMAX, true, "RV_MANY_WIDE", &rv_many::wide, "RV_MANY_WIDE_LARGE_MIN", &rv_many::wide_large_min, 0, false, MANY_SAMPLE_MAJOR},
+};
+constexpr int MANY_NCLASS = (int)(sizeof many_classes / sizeof many_classes[0]);
 
-// The jobs of several sequences k_leaf_multi_chain finishes under picker kind 1: the rule, stated once for both forms of the kernel -- 3 .. RV_MANY_KMAX
-// sequences with RV_MANY_CHAIN_MULTI, RV_MANY_KMAX + 1 .. RV_MANY_WIDE_KMAX with RV_MANY_CHAIN_WIDE (many.takes_shared_launch(.., picker=, chain_multi=True /
-// chain_wide=True) mirrors it).  As above, everything the kernel leaves out has to be impossible for the job; none of the reasons depends on the number of
-// sequences:
-//   trim on, minl > 0, gap model 0 .. 2     no p-value cut, no untrimmed lists
-//   weights 0 .. RV_LEAF_MCHAIN_WMAX        scores of up to 16 / 64 paths in 32 bits (rv_leaf_multi_chain.hip derives the bound for both forms)
-//   seedsize <= 0 or above the longest sequence   no match is that long: no seeds for the children
-//   maxmums <= 0 or >= the job's ranks      the cut is made on the matches of ONE sub-index, every one of them an inner node of the LCP-interval tree over the
-//                                           sub-index' ranks: a tree over len leaves has fewer than len inner nodes, and len <= the job's ranks <= 2048, so
-//                                           rem.align's default of 10 000 passes whatever the job
-bool many_chain_k_admits(const rv_many *m, const ManyJob &jb, int minl, int kmin, int kmax, int64_t on) {
-    if (m->picker != 1 || !on) return false;
-    if (jb.k < kmin || jb.k > kmax || !jb.clean || jb.ranks > RV_LEAF_N) return false;
+// whether job `jb` belongs to class `c` (lim: the round limit of the run) -- the rule of every class, stated once; many.takes_shared_launch mirrors it
+bool many_class_admits(const rv_many *m, const ManyClass &c, const ManyJob &jb, int minl, int64_t lim) {
+    if (m->picker != c.picker || (c.sw && !(m->*c.sw))) return false;
+    if (jb.k < c.kmin || jb.k > c.kmax || !jb.clean) return false;
+    if (!c.large) { if (jb.ranks > RV_LEAF_N) return false; }      // (a small job always fits a round: lim is not asked)
+    else if (jb.ranks <= RV_LEAF_N || jb.ranks > m->large_max || jb.ranks > lim || (c.picker == 1 && jb.ranks > RV_PICK_CHAIN_RANKS)) return false;
+    if (c.picker != 1) return true;
     const rv_picker_args &a = m->pargs;
-    int64_t longest = 0;
-    for (int q = 0; q < jb.k; q++) longest = std::max(longest, m->lens[jb.seq0 + (size_t)q]);
     if (!a.trim || minl <= 0) return false;
-    if (a.wscore < 0 || a.wpen < 0 || a.wscore > RV_LEAF_MCHAIN_WMAX || a.wpen > RV_LEAF_MCHAIN_WMAX) return false;
+    if (a.wscore < 0 || a.wpen < 0 || a.wscore > c.wmax || a.wpen > c.wmax) return false;
     if (a.gcmodel < 0 || a.gcmodel > 2) return false;
+    int64_t longest = 0, shortest = INT64_MAX;
+    for (int q = 0; q < jb.k; q++) { const int64_t len = m->lens[jb.seq0 + (size_t)q]; longest = std::max(longest, len); shortest = std::min(shortest, len); }
     if (a.seedsize > 0 && a.seedsize <= longest) return false;
-    if (a.maxmums > 0 && a.maxmums < jb.ranks) return false;
+    if (a.maxmums > 0 && a.maxmums < (c.by_ranks ? jb.ranks : shortest)) return false;
     return true;
 }
-bool many_chain_multi_admits(const rv_many *m, const ManyJob &jb, int minl) { return many_chain_k_admits(m, jb, minl, 3, RV_MANY_KMAX, m->chain_multi); }
-bool many_chain_wide_admits(const rv_many *m, const ManyJob &jb, int minl) { return many_chain_k_admits(m, jb, minl, RV_MANY_KMAX + 1, RV_MANY_WIDE_KMAX, m->chain_wide); }
+
+// an order of jobs -> rounds: ascending size (ties as given), then as many jobs a round as stay within lim ranks, one at least; round(lo, hi) runs order[lo .. hi)
+template <class Round>
+int many_rounds(const rv_many *m, std::vector<int> &order, int64_t lim, Round round) {
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return m->jobs[(size_t)a].ranks < m->jobs[(size_t)b].ranks; });
+    for (size_t lo = 0; lo < order.size();) {
+        size_t hi = lo; int64_t sum = 0;
+        while (hi < order.size() && (hi == lo || sum + m->jobs[(size_t)order[hi]].ranks <= lim)) sum += m->jobs[(size_t)order[hi++]].ranks;
+        RV_TRY(round(lo, hi));
+        lo = hi;
+    }
+    return 0;
+}
 
 // anchors of the handle's last run -> records of `job`, or (job < 0) of the job whose first sequence holds the first member
 int many_collect(rv_many *m, rv_index *h, int job, const std::vector<int> &order, const std::vector<int64_t> &abeg, const std::vector<int64_t> &bbeg) {
@@ -1034,139 +1037,32 @@ int many_run(rv_many *m, int minl, int minn, rv_align_stats *total) {
     if (total) memset(total, 0, sizeof *total);
     const int nj = (int)m->jobs.size();
     m->info[0] = nj;
-    std::vector<int> order, morder, lorder, lmorder, rest;
     // rounds: a round's text stays below the 32-bit library's position limit (and a bound on the device memory of a round)
     const int64_t lim = std::max<int64_t>(std::min<int64_t>(m->round_max, (int64_t)INT_MAX - 4096), 1);
-    // (a large job has to fit a round: one that does not goes the ordinary way)
-    const auto is_large = [&](const ManyJob &jb) { return m->large && jb.k == 2 && jb.clean && jb.ranks > RV_LEAF_N && jb.ranks <= m->large_max && jb.ranks <= lim; };
-    int64_t nlarge = 0;
-    for (const ManyJob &jb : m->jobs) nlarge += is_large(jb) ? 1 : 0;
-    const bool take_large = nlarge > 0 && nlarge >= m->large_min;
-    // (the jobs of three and more sequences are counted on their own, against a threshold of their own: what a call does with its pair jobs does not depend on them)
-    const auto is_large_multi = [&](const ManyJob &jb) { return m->large_multi && jb.k >= 3 && jb.k <= RV_MANY_KMAX && jb.clean && jb.ranks > RV_LEAF_N && jb.ranks <= m->large_max && jb.ranks <= lim; };
-    int64_t nlmulti = 0;
-    for (const ManyJob &jb : m->jobs) nlmulti += is_large_multi(jb) ? 1 : 0;
-    const bool take_large_multi = nlmulti > 0 && nlmulti >= m->large_multi_min;
-    // (the jobs of 17 .. 64 sequences: classes of their own, rounds of their own -- what a call does with its other jobs does not depend on them)
-    const auto is_wide = [&](const ManyJob &jb) { return m->wide && jb.k > RV_MANY_KMAX && jb.k <= RV_MANY_WIDE_KMAX && jb.clean; };
-    const auto is_wide_large = [&](const ManyJob &jb) { return is_wide(jb) && jb.ranks > RV_LEAF_N && jb.ranks <= m->large_max && jb.ranks <= lim; };
-    int64_t nwlarge = 0;
-    for (const ManyJob &jb : m->jobs) nwlarge += is_wide_large(jb) ? 1 : 0;
-    const bool take_wide_large = nwlarge > 0 && nwlarge >= m->wide_large_min;
-    std::vector<int> worder, wlorder, cmorder, cworder, clorder;
-    // (picker kind 1, the pair jobs above RV_LEAF_N ranks: counted on their own against a threshold of their own)
-    const auto is_chain_large = [&](const ManyJob &jb) { return many_chain_large_admits(m, jb, minl) && jb.ranks <= lim; };
-    int64_t nclarge = 0;
-    for (const ManyJob &jb : m->jobs) nclarge += is_chain_large(jb) ? 1 : 0;
-    const bool take_chain_large = nclarge > 0 && nclarge >= m->chain_large_min;
-    // (... and the jobs of 3 .. 16 sequences above RV_LEAF_N ranks: the same, RV_MANY_CHAIN_LARGE_MULTI_MIN)
-    const auto is_chain_large_multi = [&](const ManyJob &jb) { return many_chain_large_multi_admits(m, jb, minl) && jb.ranks <= lim; };
-    int64_t nclmulti = 0;
-    for (const ManyJob &jb : m->jobs) nclmulti += is_chain_large_multi(jb) ? 1 : 0;
-    const bool take_chain_large_multi = nclmulti > 0 && nclmulti >= m->chain_large_multi_min;
-    // (... and the jobs of 17 .. 64 sequences above RV_LEAF_N ranks: the same, RV_MANY_CHAIN_WIDE_LARGE_MIN)
-    const auto is_chain_wide_large = [&](const ManyJob &jb) { return many_chain_wide_large_admits(m, jb, minl) && jb.ranks <= lim; };
-    int64_t ncwlarge = 0;
-    for (const ManyJob &jb : m->jobs) ncwlarge += is_chain_wide_large(jb) ? 1 : 0;
-    const bool take_chain_wide_large = ncwlarge > 0 && ncwlarge >= m->chain_wide_large_min;
-    std::vector<int> clmorder, cwlorder;
-    const bool chain = m->picker == 1;      // the shared classes finish with built-in-picker kernels: under kind 1 only many_chain_admits',
-                                            // many_chain_multi_admits' and many_chain_wide_admits' jobs share launches
+    // every job's class (MANY_NCLASS: none), the classes with fewer jobs than their threshold dropped
+    std::vector<int> cls((size_t)nj, MANY_NCLASS);
+    int64_t count[MANY_NCLASS + 1] = {};
     for (int j = 0; j < nj; j++) {
-        ManyJob &jb = m->jobs[(size_t)j];
-        jb.arr_off = -1;
-        if (chain) { if (many_chain_admits(m, jb, minl)) order.push_back(j); else if (take_chain_large && is_chain_large(jb)) clorder.push_back(j);
-                     else if (many_chain_multi_admits(m, jb, minl)) cmorder.push_back(j);
-                     else if (take_chain_large_multi && is_chain_large_multi(jb)) clmorder.push_back(j);
-                     else if (many_chain_wide_admits(m, jb, minl)) cworder.push_back(j);
-                     else if (take_chain_wide_large && is_chain_wide_large(jb)) cwlorder.push_back(j); else rest.push_back(j); }
-        else if (jb.k == 2 && jb.ranks <= RV_LEAF_N && jb.clean) order.push_back(j);
-        else if (take_large && is_large(jb)) lorder.push_back(j);
-        else if (take_large_multi && is_large_multi(jb)) lmorder.push_back(j);
-        else if (m->multi && jb.k >= 3 && jb.k <= RV_MANY_KMAX && jb.ranks <= RV_LEAF_N && jb.clean) morder.push_back(j);
-        else if (is_wide(jb) && jb.ranks <= RV_LEAF_N) worder.push_back(j);
-        else if (take_wide_large && is_wide_large(jb)) wlorder.push_back(j);
-        else rest.push_back(j);
+        for (int c = 0; c < MANY_NCLASS && cls[(size_t)j] == MANY_NCLASS; c++) if (many_class_admits(m, many_classes[c], m->jobs[(size_t)j], minl, lim)) cls[(size_t)j] = c;
+        count[cls[(size_t)j]]++;
     }
-    const auto by_size = [&](int a, int b) { return m->jobs[(size_t)a].ranks < m->jobs[(size_t)b].ranks; };
-    std::stable_sort(order.begin(), order.end(), by_size);
-    std::stable_sort(morder.begin(), morder.end(), by_size);
-    std::stable_sort(lorder.begin(), lorder.end(), by_size);
-    std::stable_sort(lmorder.begin(), lmorder.end(), by_size);
-    std::stable_sort(worder.begin(), worder.end(), by_size);
-    std::stable_sort(wlorder.begin(), wlorder.end(), by_size);
-    std::stable_sort(cmorder.begin(), cmorder.end(), by_size);
-    std::stable_sort(cworder.begin(), cworder.end(), by_size);
-    std::stable_sort(clorder.begin(), clorder.end(), by_size);
-    std::stable_sort(clmorder.begin(), clmorder.end(), by_size);
-    std::stable_sort(cwlorder.begin(), cwlorder.end(), by_size);
-    for (size_t lo = 0; lo < order.size();) {
-        size_t hi = lo; int64_t sum = 0;
-        while (hi < order.size() && (hi == lo || sum + m->jobs[(size_t)order[hi]].ranks <= lim)) sum += m->jobs[(size_t)order[hi++]].ranks;
-        RV_TRY(many_round(m, order, lo, hi, minl, minn, total, false, chain ? &rest : nullptr));
-        lo = hi;
+    bool take[MANY_NCLASS + 1] = {};
+    for (int c = 0; c < MANY_NCLASS; c++) take[c] = count[c] > 0 && (!many_classes[c].min || count[c] >= m->*many_classes[c].min);
+    std::vector<int> orders[MANY_NCLASS], rest;
+    for (int j = 0; j < nj; j++) {
+        m->jobs[(size_t)j].arr_off = -1;
+        (take[cls[(size_t)j]] ? orders[cls[(size_t)j]] : rest).push_back(j);
     }
-    for (size_t lo = 0; lo < cmorder.size();) {     // picker kind 1, the jobs of 3 .. 16 sequences (RV_MANY_CHAIN_MULTI): rounds of their own
-        size_t hi = lo; int64_t sum = 0;
-        while (hi < cmorder.size() && (hi == lo || sum + m->jobs[(size_t)cmorder[hi]].ranks <= lim)) sum += m->jobs[(size_t)cmorder[hi++]].ranks;
-        RV_TRY(many_round_multi(m, cmorder, lo, hi, minl, minn, total, RV_MANY_KMAX, &rest));
-        lo = hi;
+    for (int c = 0; c < MANY_NCLASS; c++) {
+        const ManyClass &C = many_classes[c];
+        std::vector<int> &ord = orders[c], *redo = C.picker == 1 ? &rest : nullptr;      // (a kind-1 round gives the jobs its kernels flag back)
+        RV_TRY(many_rounds(m, ord, lim, [&](size_t lo, size_t hi) {
+            return C.round == MANY_PAIRS ? many_round(m, ord, lo, hi, minl, minn, total, C.large, redo)
+                 : C.round == MANY_CONTIGUOUS ? many_round_multi(m, ord, lo, hi, minl, minn, total, C.kmax, redo)
+                 : many_round_large_multi(m, ord, lo, hi, minl, minn, total, C.kmax, redo);
+        }));
     }
-    for (size_t lo = 0; lo < cworder.size();) {     // picker kind 1, the jobs of 17 .. 64 sequences (RV_MANY_CHAIN_WIDE): rounds of their own
-        size_t hi = lo; int64_t sum = 0;
-        while (hi < cworder.size() && (hi == lo || sum + m->jobs[(size_t)cworder[hi]].ranks <= lim)) sum += m->jobs[(size_t)cworder[hi++]].ranks;
-        RV_TRY(many_round_multi(m, cworder, lo, hi, minl, minn, total, RV_MANY_WIDE_KMAX, &rest));
-        lo = hi;
-    }
-    for (size_t lo = 0; lo < clorder.size();) {     // picker kind 1, the pair jobs above RV_LEAF_N ranks (RV_MANY_CHAIN_LARGE): rounds of their own
-        size_t hi = lo; int64_t sum = 0;
-        while (hi < clorder.size() && (hi == lo || sum + m->jobs[(size_t)clorder[hi]].ranks <= lim)) sum += m->jobs[(size_t)clorder[hi++]].ranks;
-        RV_TRY(many_round(m, clorder, lo, hi, minl, minn, total, true, &rest));
-        lo = hi;
-    }
-    for (size_t lo = 0; lo < clmorder.size();) {    // picker kind 1, the jobs of 3 .. 16 sequences above RV_LEAF_N ranks (RV_MANY_CHAIN_LARGE_MULTI): rounds of their own
-        size_t hi = lo; int64_t sum = 0;
-        while (hi < clmorder.size() && (hi == lo || sum + m->jobs[(size_t)clmorder[hi]].ranks <= lim)) sum += m->jobs[(size_t)clmorder[hi++]].ranks;
-        RV_TRY(many_round_large_multi(m, clmorder, lo, hi, minl, minn, total, RV_MANY_KMAX, &rest));
-        lo = hi;
-    }
-    for (size_t lo = 0; lo < cwlorder.size();) {    // picker kind 1, the jobs of 17 .. 64 sequences above RV_LEAF_N ranks (RV_MANY_CHAIN_WIDE_LARGE): rounds of their own
-        size_t hi = lo; int64_t sum = 0;
-        while (hi < cwlorder.size() && (hi == lo || sum + m->jobs[(size_t)cwlorder[hi]].ranks <= lim)) sum += m->jobs[(size_t)cwlorder[hi++]].ranks;
-        RV_TRY(many_round_large_multi(m, cwlorder, lo, hi, minl, minn, total, RV_MANY_WIDE_KMAX, &rest));
-        lo = hi;
-    }
-    if (chain) std::sort(rest.begin(), rest.end());
-    for (size_t lo = 0; lo < lorder.size();) {      // the pair jobs above RV_LEAF_N ranks: rounds of their own
-        size_t hi = lo; int64_t sum = 0;
-        while (hi < lorder.size() && (hi == lo || sum + m->jobs[(size_t)lorder[hi]].ranks <= lim)) sum += m->jobs[(size_t)lorder[hi++]].ranks;
-        RV_TRY(many_round(m, lorder, lo, hi, minl, minn, total, true));
-        lo = hi;
-    }
-    for (size_t lo = 0; lo < morder.size();) {      // the jobs of three and more sequences: rounds of their own
-        size_t hi = lo; int64_t sum = 0;
-        while (hi < morder.size() && (hi == lo || sum + m->jobs[(size_t)morder[hi]].ranks <= lim)) sum += m->jobs[(size_t)morder[hi++]].ranks;
-        RV_TRY(many_round_multi(m, morder, lo, hi, minl, minn, total, RV_MANY_KMAX));
-        lo = hi;
-    }
-    for (size_t lo = 0; lo < lmorder.size();) {     // the jobs of three and more sequences above RV_LEAF_N ranks: rounds of their own
-        size_t hi = lo; int64_t sum = 0;
-        while (hi < lmorder.size() && (hi == lo || sum + m->jobs[(size_t)lmorder[hi]].ranks <= lim)) sum += m->jobs[(size_t)lmorder[hi++]].ranks;
-        RV_TRY(many_round_large_multi(m, lmorder, lo, hi, minl, minn, total, RV_MANY_KMAX));
-        lo = hi;
-    }
-    for (size_t lo = 0; lo < worder.size();) {      // the jobs of 17 .. 64 sequences (RV_MANY_WIDE): rounds of their own, the wide form of the leaf kernel
-        size_t hi = lo; int64_t sum = 0;
-        while (hi < worder.size() && (hi == lo || sum + m->jobs[(size_t)worder[hi]].ranks <= lim)) sum += m->jobs[(size_t)worder[hi++]].ranks;
-        RV_TRY(many_round_multi(m, worder, lo, hi, minl, minn, total, RV_MANY_WIDE_KMAX));
-        lo = hi;
-    }
-    for (size_t lo = 0; lo < wlorder.size();) {     // ... above RV_LEAF_N ranks: sample-major rounds of their own
-        size_t hi = lo; int64_t sum = 0;
-        while (hi < wlorder.size() && (hi == lo || sum + m->jobs[(size_t)wlorder[hi]].ranks <= lim)) sum += m->jobs[(size_t)wlorder[hi++]].ranks;
-        RV_TRY(many_round_large_multi(m, wlorder, lo, hi, minl, minn, total, RV_MANY_WIDE_KMAX));
-        lo = hi;
-    }
+    if (m->picker == 1) std::sort(rest.begin(), rest.end());      // (flagged jobs came back behind the others; the built-in classes never add to `rest`)
     for (int j : rest) RV_TRY(many_ordinary(m, j, minl, minn, total));
     // the anchors job by job
     m->an_first.assign((size_t)nj + 1, 0);
@@ -1618,13 +1514,7 @@ int many_scan(rv_many *m, int minl, int minn, int kind, const RvKchainArgs *kc =
     // the small rounds, then the large ones (a job above RV_LEAF_N ranks holds more than 2^11 of a round's at most 2^26 ranks: fewer than the build's 2^20 jobs)
     for (int large = 0; large < 2; large++) {
         std::vector<int> &ord = large ? lorder : order;
-        std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return m->jobs[(size_t)a].ranks < m->jobs[(size_t)b].ranks; });
-        for (size_t lo = 0; lo < ord.size();) {
-            size_t hi = lo; int64_t sum = 0;
-            while (hi < ord.size() && (hi == lo || sum + m->jobs[(size_t)ord[hi]].ranks <= lim)) sum += m->jobs[(size_t)ord[hi++]].ranks;
-            RV_TRY(many_round_scan(m, ord, lo, hi, minl, minn, kind, large != 0));
-            lo = hi;
-        }
+        RV_TRY(many_rounds(m, ord, lim, [&](size_t lo, size_t hi) { return many_round_scan(m, ord, lo, hi, minl, minn, kind, large != 0); }));
     }
     for (int j : rest) RV_TRY(many_scan_ordinary(m, j, minl, minn, kind));
     if (kc) {
@@ -1674,6 +1564,28 @@ int many_scan(rv_many *m, int minl, int minn, int kind, const RvKchainArgs *kc =
     return 0;
 }
 
+// rv_many_option: the options that are no class switch or threshold (those are many_classes') -- lo: the least value taken; boolean: any value but 0 is 1
+struct ManyOption { const char *name; int64_t rv_many::*field; int64_t lo; bool boolean; };
+const ManyOption many_options[] = {
+    {"RV_MANY_KEEP", &rv_many::keep, INT64_MIN, false},
+    {"RV_MANY_ROUND", &rv_many::round_max, 1, false},
+    {"RV_MANY_STAGE", &rv_many::stage, 0, false},
+    {"RV_MANY_WAVE_MAX", &rv_many::wave_max, 0, false},
+    {"RV_MANY_LARGE_MAX", &rv_many::large_max, 0, false},
+    {"RV_MANY_CHAIN_FLAG", &rv_many::chain_flag, 0, false},
+    {"RV_MANY_SCAN_ORDINARY", &rv_many::scan_ordinary, 0, true},
+    {"RV_MANY_SCAN_LARGE", &rv_many::scan_large, 0, true},
+    {"RV_MANY_SCAN_LARGE_MIN", &rv_many::scan_large_min, 0, false},
+};
+int many_set_option(rv_many *m, const char *name, int64_t rv_many::*field, int64_t lo, bool boolean, int64_t value) {
+    if (value < lo && !boolean) {
+        if (lo == 0) rv_set_error("%s: negative", name); else rv_set_error("%s: at least %lld", name, (long long)lo);
+        return -1;
+    }
+    m->*field = boolean ? (int64_t)(value != 0) : value;
+    return 0;
+}
+
 }  // namespace
 
 #define MANY_GUARD(body, fail)                                                                                   \
@@ -1705,31 +1617,11 @@ void rv_many_free(rv_many *m) {
 
 int rv_many_option(rv_many *m, const char *name, int64_t value) {
     if (!m || !name) { rv_set_error("rv_many_option: null argument"); return -1; }
-    if (strcmp(name, "RV_MANY_KEEP") == 0) { m->keep = value; return 0; }
-    if (strcmp(name, "RV_MANY_SCAN_ORDINARY") == 0) { m->scan_ordinary = value != 0; return 0; }
-    if (strcmp(name, "RV_MANY_SCAN_LARGE") == 0) { m->scan_large = value != 0; return 0; }
-    if (strcmp(name, "RV_MANY_SCAN_LARGE_MIN") == 0) { if (value < 0) { rv_set_error("RV_MANY_SCAN_LARGE_MIN: negative"); return -1; } m->scan_large_min = value; return 0; }
-    if (strcmp(name, "RV_MANY_ROUND") == 0) { if (value < 1) { rv_set_error("RV_MANY_ROUND: at least 1"); return -1; } m->round_max = value; return 0; }
-    if (strcmp(name, "RV_MANY_MULTI") == 0) { m->multi = value != 0; return 0; }
-    if (strcmp(name, "RV_MANY_LARGE") == 0) { m->large = value != 0; return 0; }
-    if (strcmp(name, "RV_MANY_LARGE_MULTI") == 0) { m->large_multi = value != 0; return 0; }
-    if (strcmp(name, "RV_MANY_LARGE_MULTI_MIN") == 0) { if (value < 0) { rv_set_error("RV_MANY_LARGE_MULTI_MIN: negative"); return -1; } m->large_multi_min = value; return 0; }
-    if (strcmp(name, "RV_MANY_WIDE") == 0) { m->wide = value != 0; return 0; }
-    if (strcmp(name, "RV_MANY_CHAIN") == 0) { m->chain = value != 0; return 0; }
-    if (strcmp(name, "RV_MANY_CHAIN_MULTI") == 0) { m->chain_multi = value != 0; return 0; }
-    if (strcmp(name, "RV_MANY_CHAIN_WIDE") == 0) { m->chain_wide = value != 0; return 0; }
-    if (strcmp(name, "RV_MANY_CHAIN_LARGE") == 0) { m->chain_large = value != 0; return 0; }
-    if (strcmp(name, "RV_MANY_CHAIN_LARGE_MULTI") == 0) { m->chain_large_multi = value != 0; return 0; }
-    if (strcmp(name, "RV_MANY_CHAIN_LARGE_MULTI_MIN") == 0) { if (value < 0) { rv_set_error("RV_MANY_CHAIN_LARGE_MULTI_MIN: negative"); return -1; } m->chain_large_multi_min = value; return 0; }
-    if (strcmp(name, "RV_MANY_CHAIN_WIDE_LARGE") == 0) { m->chain_wide_large = value != 0; return 0; }
-    if (strcmp(name, "RV_MANY_CHAIN_WIDE_LARGE_MIN") == 0) { if (value < 0) { rv_set_error("RV_MANY_CHAIN_WIDE_LARGE_MIN: negative"); return -1; } m->chain_wide_large_min = value; return 0; }
-    if (strcmp(name, "RV_MANY_CHAIN_LARGE_MIN") == 0) { if (value < 0) { rv_set_error("RV_MANY_CHAIN_LARGE_MIN: negative"); return -1; } m->chain_large_min = value; return 0; }
-    if (strcmp(name, "RV_MANY_CHAIN_FLAG") == 0) { if (value < 0) { rv_set_error("RV_MANY_CHAIN_FLAG: negative"); return -1; } m->chain_flag = value; return 0; }
-    if (strcmp(name, "RV_MANY_WIDE_LARGE_MIN") == 0) { if (value < 0) { rv_set_error("RV_MANY_WIDE_LARGE_MIN: negative"); return -1; } m->wide_large_min = value; return 0; }
-    if (strcmp(name, "RV_MANY_LARGE_MAX") == 0) { if (value < 0) { rv_set_error("RV_MANY_LARGE_MAX: negative"); return -1; } m->large_max = value; return 0; }
-    if (strcmp(name, "RV_MANY_LARGE_MIN") == 0) { if (value < 0) { rv_set_error("RV_MANY_LARGE_MIN: negative"); return -1; } m->large_min = value; return 0; }
-    if (strcmp(name, "RV_MANY_STAGE") == 0) { if (value < 0) { rv_set_error("RV_MANY_STAGE: negative"); return -1; } m->stage = value; return 0; }
-    if (strcmp(name, "RV_MANY_WAVE_MAX") == 0) { if (value < 0) { rv_set_error("RV_MANY_WAVE_MAX: negative"); return -1; } m->wave_max = value; return 0; }
+    for (const ManyClass &c : many_classes) {
+        if (c.sw_name && strcmp(name, c.sw_name) == 0) return many_set_option(m, name, c.sw, 0, true, value);
+        if (c.min_name && strcmp(name, c.min_name) == 0) return many_set_option(m, name, c.min, 0, false, value);
+    }
+    for (const ManyOption &o : many_options) if (strcmp(name, o.name) == 0) return many_set_option(m, name, o.field, o.lo, o.boolean, value);
     RvOptions probe;
     if (!probe.find(name)) { rv_set_error("rv_many_option: unknown option %s", name); return -1; }
     MANY_GUARD(

@@ -9,7 +9,7 @@
 // split and the host's bookkeeping stay as they are: to them a pick is a pick.
 // Sub-indices whose flag byte says "finished elsewhere" (bit 0: the leaf kernel takes them) are left alone.
 //
-// What the caller guarantees (rv_many.hip many_chain_large_admits) is what k_leaf_chain asks for, with other bounds:
+// What the caller guarantees (rv_many.hip many_class_admits, the RV_MANY_CHAIN_LARGE row of many_classes) is what k_leaf_chain asks for, with other bounds:
 //   trim on, minl > 0, no seed possible, a --maxmums that cannot bite, gap model 0 .. 2
 //   a job of at most 2^17 ranks          a sub-index' intervals are pieces of its job's two sequences: lengths and positions relative to the interval begins
 //                                        lie in [0, 2^17) -- 17 bits each (the kernel flags a job whose interval is longer instead of packing garbage)

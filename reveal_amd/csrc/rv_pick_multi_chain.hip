@@ -17,7 +17,7 @@
 // The members of a record are SA[ub - n + 1 .. ub]; the scan's member lists are not read (the scan is run with a member capacity of 0).  The sample of
 // a member is the one of the sub-index' intervals (one per sample: nodes[2 W s ..]) that holds it.
 //
-// What the caller guarantees (rv_many.hip many_chain_large_multi_admits) is what k_leaf_multi_chain<16> asks for, with other bounds:
+// What the caller guarantees (rv_many.hip many_class_admits, the RV_MANY_CHAIN_LARGE_MULTI row of many_classes) is what k_leaf_multi_chain<16> asks for, with other bounds:
 //   trim on, minl > 0, no seed possible, a --maxmums of at least the job's ranks, gap model 0 .. 2, at most KM = 16 samples
 //   a job of at most 2^17 ranks          a sub-index' intervals are pieces of its job's sequences: lengths and positions relative to the interval begins
 //                                        lie in [0, 2^17) -- 17 bits each (the kernel flags a job whose interval is longer instead of packing garbage)

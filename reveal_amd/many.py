@@ -175,56 +175,53 @@ def picker_struct(args):
                                  1 if args.trim else 0, float(args.pcutoff))
 
 
+# csrc/rv_many.hip many_classes row by row, in its order: (under a picker, k from, k to, above LEAF_RANKS, switch -- the keyword of takes_shared_launch and
+# align_many, None: no switch --, weight cap, maxmums against the job's ranks and not the shortest sequence); the last two mean something under a picker only
+CLASSES = (
+    (False, 2, 2, False, None, None, False),
+    (True, 2, 2, False, "chain", CHAIN_WMAX, False),
+    (True, 3, MULTI_KMAX, False, "chain_multi", CHAIN_MULTI_WMAX, True),
+    (True, MULTI_KMAX + 1, WIDE_KMAX, False, "chain_wide", CHAIN_MULTI_WMAX, True),
+    (True, 2, 2, True, "chain_large", CHAIN_MULTI_WMAX, False),
+    (True, 3, MULTI_KMAX, True, "chain_large_multi", CHAIN_LARGE_MULTI_WMAX, True),
+    (True, MULTI_KMAX + 1, WIDE_KMAX, True, "chain_wide_large", CHAIN_WIDE_LARGE_WMAX, True),
+    (False, 2, 2, True, "large", None, False),
+    (False, 3, MULTI_KMAX, False, "multi", None, False),
+    (False, 3, MULTI_KMAX, True, "large_multi", None, False),
+    (False, MULTI_KMAX + 1, WIDE_KMAX, False, "wide", None, False),
+    (False, MULTI_KMAX + 1, WIDE_KMAX, True, "wide", None, False),
+)
+SWITCHES = dict(chain="RV_MANY_CHAIN", chain_multi="RV_MANY_CHAIN_MULTI", chain_wide="RV_MANY_CHAIN_WIDE", chain_large="RV_MANY_CHAIN_LARGE",
+                chain_large_multi="RV_MANY_CHAIN_LARGE_MULTI", chain_wide_large="RV_MANY_CHAIN_WIDE_LARGE", multi="RV_MANY_MULTI", large="RV_MANY_LARGE",
+                large_multi="RV_MANY_LARGE_MULTI", wide="RV_MANY_WIDE")
+
+
 def takes_shared_launch(seqs, multi=False, large=False, large_max=LARGE_MAX, large_multi=False, wide=False, picker=None, chain=False, minlength=20,
                         chain_multi=False, chain_wide=False, chain_large=False, chain_large_multi=False, chain_wide_large=False):
-    """whether the library builds and finishes this job in the shared launches; multi: with RV_MANY_MULTI on; large: with RV_MANY_LARGE
-    on and RV_MANY_LARGE_MAX = large_max (in a call with at least RV_MANY_LARGE_MIN such jobs, and with rounds that hold the job);
-    large_multi: with RV_MANY_LARGE_MULTI on (in a call with at least RV_MANY_LARGE_MULTI_MIN such jobs, and with rounds that hold the job);
-    wide: with RV_MANY_WIDE on -- jobs of 17 .. 64 sequences, above 2048 ranks in a call with at least RV_MANY_WIDE_LARGE_MIN such jobs;
-    picker: a schemes.PickerArgs -- with the reference's default picker set (the other switches then mean nothing); chain: with RV_MANY_CHAIN on;
-    minlength: of the run (csrc/rv_many.hip many_chain_admits); chain_multi: with RV_MANY_CHAIN_MULTI on -- under a picker, the jobs of 3 .. 16
-    sequences (csrc/rv_many.hip many_chain_multi_admits); chain_wide: with RV_MANY_CHAIN_WIDE on -- under a picker, the jobs of 17 .. 64 sequences
-    (csrc/rv_many.hip many_chain_wide_admits); chain_large: with RV_MANY_CHAIN_LARGE on -- under a picker, the pair jobs of 2049 .. min(large_max, 2^17)
-    ranks (csrc/rv_many.hip many_chain_large_admits), in a call with at least RV_MANY_CHAIN_LARGE_MIN such jobs and with rounds that hold the job;
-    chain_large_multi: with RV_MANY_CHAIN_LARGE_MULTI on -- under a picker, the jobs of 3 .. 16 sequences and 2049 .. min(large_max, 2^17) ranks
-    (csrc/rv_many.hip many_chain_large_multi_admits), in a call with at least RV_MANY_CHAIN_LARGE_MULTI_MIN such jobs and with rounds that hold the job;
-    chain_wide_large: with RV_MANY_CHAIN_WIDE_LARGE on -- under a picker, the jobs of 17 .. 64 sequences and 2049 .. min(large_max, 2^17) ranks
-    (csrc/rv_many.hip many_chain_wide_large_admits: the same rule with a weight bound of 128), in a call with at least RV_MANY_CHAIN_WIDE_LARGE_MIN such jobs
-    and with rounds that hold the job"""
+    """whether the library builds and finishes this job in the shared launches: whether it belongs to a row of CLASSES whose switch is on -- the rule
+    csrc/rv_many.hip many_class_admits states once for every row of its table many_classes.  multi, large, large_multi, wide, chain, chain_multi,
+    chain_wide, chain_large, chain_large_multi, chain_wide_large: with that row's switch (SWITCHES) on; large_max: RV_MANY_LARGE_MAX, the ranks of the
+    largest job of a row above 2048 ranks (under a picker min(large_max, 2^17)); picker: a schemes.PickerArgs -- with the reference's default picker set
+    (the rows of the built-in picker then take nothing, and the chain switches mean nothing without one); minlength: of the run.  Under a picker a row
+    takes a job when trim is on, minlength > 0, the weights are 0 .. the row's cap (65536, 1024, 512 or 128), no sequence reaches seedsize, and maxmums
+    is at least the shorter sequence (pairs) or the job's ranks.  The rows above 2048 ranks take their jobs in a call with at least RV_MANY_*_MIN of
+    them and with rounds that hold the job; this function does not know the call."""
     k = len(seqs)
-    ranks = sum(len(s) for s in seqs) + k
+    lens = [len(s) for s in seqs]
+    ranks = sum(lens) + k
     if any(b"\0" in s for s in seqs):
         return False
-    if picker is not None:
-        A = picker_struct(picker)
-        if ranks > LEAF_RANKS and 3 <= k <= WIDE_KMAX:
-            # (csrc/rv_many.hip many_chain_large_k_admits: one rule, the switch and the weight bound by the number of sequences)
-            on, wmax = (chain_large_multi, CHAIN_LARGE_MULTI_WMAX) if k <= MULTI_KMAX else (chain_wide_large, CHAIN_WIDE_LARGE_WMAX)
-            if not on or ranks > min(int(large_max), CHAIN_LARGE_RANKS):
-                return False
-            return bool(A.trim and int(minlength) > 0 and 0 <= A.wscore <= wmax and 0 <= A.wpen <= wmax
-                        and (A.seedsize <= 0 or A.seedsize > max(len(s) for s in seqs)) and (A.maxmums <= 0 or A.maxmums >= ranks))
-        if ranks > LEAF_RANKS:
-            if not chain_large or k != 2 or ranks > min(int(large_max), CHAIN_LARGE_RANKS):
-                return False
-            la, lb = len(seqs[0]), len(seqs[1])
-            return bool(A.trim and int(minlength) > 0 and 0 <= A.wscore <= CHAIN_MULTI_WMAX and 0 <= A.wpen <= CHAIN_MULTI_WMAX
-                        and (A.seedsize <= 0 or A.seedsize > max(la, lb)) and (A.maxmums <= 0 or A.maxmums >= min(la, lb)))
-        if 3 <= k <= MULTI_KMAX or (chain_wide and MULTI_KMAX < k <= WIDE_KMAX):
-            return bool((chain_multi if k <= MULTI_KMAX else chain_wide) and A.trim and int(minlength) > 0 and 0 <= A.wscore <= CHAIN_MULTI_WMAX and 0 <= A.wpen <= CHAIN_MULTI_WMAX
-                        and (A.seedsize <= 0 or A.seedsize > max(len(s) for s in seqs)) and (A.maxmums <= 0 or A.maxmums >= ranks))
-        if not chain or k != 2:
-            return False
-        la, lb = len(seqs[0]), len(seqs[1])
-        return bool(A.trim and int(minlength) > 0 and 0 <= A.wscore <= CHAIN_WMAX and 0 <= A.wpen <= CHAIN_WMAX
-                    and (A.seedsize <= 0 or A.seedsize > max(la, lb)) and (A.maxmums <= 0 or A.maxmums >= min(la, lb)))
-    if MULTI_KMAX < k <= WIDE_KMAX:
-        return bool(wide) and (ranks <= LEAF_RANKS or ranks <= large_max)
-    if not (2 <= k <= MULTI_KMAX):
-        return False
-    if ranks <= LEAF_RANKS:
-        return k == 2 or bool(multi)
-    return ranks <= large_max and bool(large if k == 2 else large_multi)
+    on = dict(multi=multi, large=large, large_multi=large_multi, wide=wide, chain=chain, chain_multi=chain_multi, chain_wide=chain_wide,
+              chain_large=chain_large, chain_large_multi=chain_large_multi, chain_wide_large=chain_wide_large)
+    A = picker_struct(picker) if picker is not None else None
+    for pk, kmin, kmax, above, switch, wmax, by_ranks in CLASSES:
+        if pk != (A is not None) or not kmin <= k <= kmax or above != (ranks > LEAF_RANKS) or not (switch is None or on[switch]):
+            continue
+        if above and ranks > (min(int(large_max), CHAIN_LARGE_RANKS) if pk else large_max):
+            continue
+        return not pk or bool(A.trim and int(minlength) > 0 and 0 <= A.wscore <= wmax and 0 <= A.wpen <= wmax
+                              and (A.seedsize <= 0 or A.seedsize > max(lens)) and (A.maxmums <= 0 or A.maxmums >= (ranks if by_ranks else min(lens))))
+    return False
 
 
 def takes_shared_scan(seqs, large=False, large_max=LARGE_MAX):
@@ -455,26 +452,11 @@ def align_many(jobs, minlength=20, minn=2, sa64=False, toupper=True, batch=None,
         picker_struct(picker)
     b = batch if batch is not None else Batch(sa64)
     b.set_picker(picker)
-    if chain is not None:
-        b.option("RV_MANY_CHAIN", 1 if chain else 0)
-    if chain_multi is not None:
-        b.option("RV_MANY_CHAIN_MULTI", 1 if chain_multi else 0)
-    if chain_wide is not None:
-        b.option("RV_MANY_CHAIN_WIDE", 1 if chain_wide else 0)
-    if chain_large is not None:
-        b.option("RV_MANY_CHAIN_LARGE", 1 if chain_large else 0)
-    if chain_large_multi is not None:
-        b.option("RV_MANY_CHAIN_LARGE_MULTI", 1 if chain_large_multi else 0)
-    if chain_wide_large is not None:
-        b.option("RV_MANY_CHAIN_WIDE_LARGE", 1 if chain_wide_large else 0)
-    if multi is not None:
-        b.option("RV_MANY_MULTI", 1 if multi else 0)
-    if large is not None:
-        b.option("RV_MANY_LARGE", 1 if large else 0)
-    if large_multi is not None:
-        b.option("RV_MANY_LARGE_MULTI", 1 if large_multi else 0)
-    if wide is not None:
-        b.option("RV_MANY_WIDE", 1 if wide else 0)
+    given = dict(chain=chain, chain_multi=chain_multi, chain_wide=chain_wide, chain_large=chain_large, chain_large_multi=chain_large_multi,
+                 chain_wide_large=chain_wide_large, multi=multi, large=large, large_multi=large_multi, wide=wide)
+    for key, name in SWITCHES.items():
+        if given[key] is not None:
+            b.option(name, 1 if given[key] else 0)
     b.clear()
     for seqs in prepared:
         b.add(seqs)

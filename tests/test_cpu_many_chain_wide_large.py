@@ -131,7 +131,7 @@ def test_the_fixture_tests_the_picker(jobs, golden):
 
 
 def test_what_the_shared_launches_take_under_the_switch():
-    """both sides of every bound of csrc/rv_many.hip many_chain_wide_large_admits"""
+    """both sides of every bound of the RV_MANY_CHAIN_WIDE_LARGE row of csrc/rv_many.hip many_classes"""
     rng = __import__("random").Random(7)
     a = mc.rnd(rng, 130)
     fam = [mc.mutate(rng, a, 0.01).encode() for _ in range(17)]                                          # 17 x 131 = 2227 ranks

@@ -179,12 +179,13 @@ def test_several_rounds(jobs, golden):
     check_golden(results, golden["default"], "three rounds")
 
 
-def test_mixed_batch_with_every_switch_on(jobs, golden):
-    """small pairs, large pairs, small and large jobs of 3 .. 16 sequences, small jobs of 17 .. 64, this class and a job of 65 sequences, with every
-    picker switch on: only the job of 65 sequences stays ordinary, info["shared"] is what takes_shared_launch says; a sample against the product's
-    rem.align per job, the rest against the golden files"""
-    kw = dict(minlength=20)
-    args = cw.picker_args(kw)
+PICKER_SWITCHES = dict(chain=True, chain_multi=True, chain_wide=True, chain_large=True, chain_large_multi=True, chain_wide_large=True)
+EVERY_SWITCH = dict(PICKER_SWITCHES, multi=True, large=True, large_multi=True, wide=True)
+
+
+def mixed_batch(jobs, golden):
+    """small pairs, large pairs, small and large jobs of 3 .. 16 sequences, small jobs of 17 .. 64, this class and a job of 65 sequences, shuffled
+    -> (batch, want, position of the job of 65 sequences): want[k] = the golden result of batch[k], None for the job of 65 sequences"""
     small = list(range(0, len(cc.jobs()), 20))
     large = list(range(20, len(cp.jobs()), 10))
     multi = list(range(0, len(cm.jobs()), 16))
@@ -200,13 +201,21 @@ def test_mixed_batch_with_every_switch_on(jobs, golden):
             [cl.load_golden()["default"][j] for j in lmulti] + [gx[j] for j in wide] + [golden["default"][j] for j in mine] + [None])
     order = list(range(len(batch)))
     random.Random(22).shuffle(order)
-    batch = [batch[k] for k in order]; want = [want[k] for k in order]
-    on = dict(chain=True, chain_multi=True, chain_wide=True, chain_large=True, chain_large_multi=True, chain_wide_large=True)
-    results, info = many.align_many(batch, minlength=20, picker=args, multi=True, large=True, large_multi=True, wide=True, **on)
+    return [batch[k] for k in order], [want[k] for k in order], order.index(len(batch) - 1)
+
+
+def test_mixed_batch_with_every_switch_on(jobs, golden):
+    """the jobs of mixed_batch with every picker switch on: only the job of 65 sequences stays ordinary, info["shared"] is what takes_shared_launch
+    says, every class runs one round; a sample against the product's rem.align per job, the rest against the golden files"""
+    kw = dict(minlength=20)
+    args = cw.picker_args(kw)
+    batch, want, at65 = mixed_batch(jobs, golden)
+    results, info = many.align_many(batch, minlength=20, picker=args, **EVERY_SWITCH)
     print("info", info)
-    takes = [many.takes_shared_launch(as_bytes(j), picker=args, minlength=20, **on) for j in batch]
-    assert sum(takes) == len(batch) - 1 and not takes[order.index(len(batch) - 1)]
+    takes = [many.takes_shared_launch(as_bytes(j), picker=args, minlength=20, **PICKER_SWITCHES) for j in batch]
+    assert sum(takes) == len(batch) - 1 and not takes[at65]
     assert info["shared"] == sum(takes) and info["ordinary"] == 1
+    assert info["rounds"] == 6 and info["launches"] == 1108      # a round per class that has jobs; the launches of this batch, as recorded before the class table
     sample = set(random.Random(23).sample(range(len(batch)), 4)) | {k for k, w in enumerate(want) if w is None}
     check_rem_align(batch, results, kw, sorted(sample))
     for k, w in enumerate(want):

@@ -204,13 +204,18 @@ def test_large_wide_jobs():
     assert info["shared"] == many.WIDE_LARGE_MIN and info["ordinary"] == 0
 
 
-def test_every_switch_on():
-    """one call with all four switches on: wide jobs on both sides of 2048 ranks among jobs of 3 .. 16 sequences above 2048 ranks, small ones and
-    pairs -- every class in rounds of its own, nothing ordinary but the job of 65 sequences"""
+def every_switch_jobs():
+    """wide jobs on both sides of 2048 ranks among jobs of 3 .. 16 sequences above 2048 ranks, small ones and pairs, and a job of 65 sequences, shuffled"""
     wide_large = [seqs for _, _, seqs in mw.large_jobs(2, seed=13)]
     jobs = wide_large + lm.sized_jobs(5, seed=18) + [seqs for _, seqs, _ in mw.corner_jobs()] + mm.small_jobs(4, seed=19)
     jobs += [list(p) for _, p in mc.class_jobs(1, seed=20)][:5] + [list(p) for p in mc.big_pairs(2, seed=21)]
     random.Random(5).shuffle(jobs)
+    return jobs
+
+
+def test_every_switch_on():
+    """one call with all four switches on: the jobs of every_switch_jobs -- every class in rounds of its own, nothing ordinary but the job of 65 sequences"""
+    jobs = every_switch_jobs()
     b = many.Batch(False)
     for name, v in (("RV_MANY_WIDE_LARGE_MIN", 1), ("RV_MANY_LARGE_MULTI_MIN", 1), ("RV_MANY_LARGE_MIN", 1)):
         b.option(name, v)
