@@ -92,6 +92,20 @@ int rv_upload(rv_index *h);
 /* the same copy once more, whether or not the text changed: what the text's way into HBM costs once the buffers exist (bench.py's
  * upload_ms; the first rv_upload of a handle also pays for its device allocations) */
 int rv_upload_again(rv_index *h);
+/* rv_construct(rc = 1) reverses and complements T[nsep[0], n) every time it is called (interface.c:168-175).  By default it does so on the text
+ * in device memory, in place (k_text_revcomp, csrc/rv_revcomp.hip): the text goes up once, as it stands, and the host's copy is brought up to date
+ * only when somebody reads or writes it (the T getter, rv_add_sequence, rv_clone, the cache file, a later upload).  Switch RV_RC_HOST = 1: the
+ * host loop and a second upload of the whole text (the A/B leg); a range shorter than RV_RC_HOST_BELOW bytes (default 0: never) takes that route
+ * by itself.  The results are the same bytes either way.
+ * rv_text_info: up to n values, returns how many were written (5 exist) or -1: [0] uploads -- host-to-device copies of the text over the handle's
+ * life, [1] upload_bytes, [2] rc_device -- 1 if the last rv_construct(rc = 1) reversed on the device, [3] host_stale -- how many
+ * reversals the host's copy owes (0, 1, or 2: a second device reversal cancels the first only where the range holds no U, u or 96, the bytes the rule
+ * does not map back), [4] rc_launches -- launches of the kernel.  Host counters only.
+ * rv_text_guard: the 64 bytes behind the text in device memory, which rv_upload zeroes and nothing writes (tests).
+ * rv_revcomp_bytes: the host rule on a caller's buffer of n bytes, in place; no device is asked for. */
+int rv_text_info(rv_index *h, int64_t *out, int n);
+int rv_text_guard(rv_index *h, void *out64);
+int rv_revcomp_bytes(char *buf, int64_t n);
 
 /* getters (interface.c:538-729).  which: */
 enum { RV_T = 0, RV_SA = 1, RV_SAI = 2, RV_LCP = 3, RV_SO = 4, RV_NSEP = 5, RV_NODES = 6 };
@@ -763,6 +777,10 @@ int rv_test_radix_sort(uint64_t *keys, uint32_t *vals, int64_t n, int bit_lo, in
  * 2 constant; flags: 1 = 10-bit digits, 2 = XCD-aware tile order, 4 = 16-bit wave counters, 8 = histograms from the keys (no digit bytes);
  * *bad = pairs out of order afterwards */
 int rv_test_radix_time(int64_t n, int bits, int dist, int flags, int iters, double *ms, int64_t *bad);
+/* k_text_revcomp on the range [lo, lo + len) of a text of pseudo-random ACGT, and a device-to-device copy of len bytes, `iters` times in turn after a
+ * warm-up, each between two HIP events of one stream and behind lo + len bytes of unrelated writes (the range is not served from the last-level cache):
+ * kernel_ms[iters], copy_ms[iters] (tools/time_rc.py) */
+int rv_test_revcomp_time(int64_t lo, int64_t len, int iters, double *kernel_ms, double *copy_ms);
 
 #ifdef __cplusplus
 }

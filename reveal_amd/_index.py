@@ -179,6 +179,21 @@ def make_index_type(sa64, error):
             if self._dll.rv_upload_again(self._h) != 0:
                 self._fail()
 
+        def text_info(self):
+            """the text's traffic and what construct(rc=1) left (rv_text_info): {uploads, upload_bytes, rc_device, host_stale, rc_launches}"""
+            out = (ctypes.c_int64 * len(_lib.TEXT_INFO))()
+            got = self._dll.rv_text_info(self._h, out, len(_lib.TEXT_INFO))
+            if got != len(_lib.TEXT_INFO):
+                raise error("rv_text_info: %d of %d fields" % (got, len(_lib.TEXT_INFO)))
+            return {name: int(out[k]) for k, name in enumerate(_lib.TEXT_INFO)}
+
+        def text_guard(self):
+            """the 64 bytes behind the text in device memory (rv_text_guard): zero while nothing wrote past the text"""
+            out = np.zeros(64, dtype=np.uint8)
+            if self._dll.rv_text_guard(self._h, out.ctypes.data) != 0:
+                self._fail()
+            return out
+
         def prof(self, enable=None, reset=False, only=None):
             """HIP-event kernel timing on the index' stream -> {kernel: (launches, ms, bytes)}
             only = names of the kernel classes to time (default: all; every timed span costs the stream two events)"""

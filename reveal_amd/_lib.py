@@ -27,6 +27,9 @@ SA_PATHS = ("tiny", "short_alphabet", "ends_with_sep", "g", "K", "bits", "fused_
             "diag_table_tried", "diag_table_kept", "heads_kernel", "text_round", "text_mode", "packed_text", "text_big", "far_ran", "nd_table",
             "doubling_rounds", "slow_class", "text_jump", "lcp_list_overflow", "defer_max", "defer_cap", "lcp_by_rank")
 
+# rv_text_info: the order of its fields (include/reveal_amd.h)
+TEXT_INFO = ("uploads", "upload_bytes", "rc_device", "host_stale", "rc_launches")
+
 c_i64p = ctypes.POINTER(ctypes.c_int64)
 V = ctypes.c_void_p
 
@@ -69,6 +72,9 @@ SYMBOLS = {
     "rv_construct": (_I, [V, _I, ctypes.c_char_p, ctypes.c_char_p, _I]),
     "rv_upload": (_I, [V]),
     "rv_upload_again": (_I, [V]),
+    "rv_text_info": (_I, [V, c_i64p, _I]),
+    "rv_text_guard": (_I, [V, V]),
+    "rv_revcomp_bytes": (_I, [V, _L]),
     "rv_get_array": (_L, [V, _I, V, _L]),
     "rv_getmums": (_L, [V, _I]),
     "rv_fetch_mums": (_I, [V, V, V, V, _L]),
@@ -207,6 +213,7 @@ SYMBOLS = {
     "rv_test_inclusive_max_u32": (_I, [V, V, _L]),
     "rv_test_radix_sort": (_I, [V, V, _L, _I, _I]),
     "rv_test_radix_time": (_I, [_L, _I, _I, _I, _I, ctypes.POINTER(_D), c_i64p]),
+    "rv_test_revcomp_time": (_I, [_L, _L, _I, ctypes.POINTER(_D), ctypes.POINTER(_D)]),
 }
 
 

@@ -2817,13 +2817,14 @@ static int sx_check_inside(const rv_subindex *x, const RvIntv *iv, int n, const 
 // only in the window in front of each cut, which is the same thing unless a LATER interval of the list begins less than
 // maxlcp in front of an earlier one with no separator in between (a suffix could then cross both cuts and the reference
 // would move it twice).  A match never does that (its members lie in different sequences); refuse the rest.
-static int sx_check_cut_order(const rv_index *h, const RvIntv *match, int nmatch) {
+static int sx_check_cut_order(rv_index *h, const RvIntv *match, int nmatch) {
+    const HostText &T = rv_host_text(h);
     for (int i = 0; i < nmatch; i++)
         for (int j = i + 1; j < nmatch; j++) {
             if (match[j].begin >= match[i].begin) continue;
             if (match[i].begin - match[j].begin >= (int64_t)h->maxlcp) continue;
             bool sep = false;
-            for (int64_t p = match[j].begin; p < match[i].begin && !sep; p++) sep = h->T[(size_t)p] == '$' || h->T[(size_t)p] == 'N';
+            for (int64_t p = match[j].begin; p < match[i].begin && !sep; p++) sep = T[(size_t)p] == '$' || T[(size_t)p] == 'N';
             if (!sep) { rv_set_error("matching intervals closer than the longest repeat must be listed in ascending order"); return -1; }
         }
     return 0;

@@ -79,7 +79,7 @@ rv_index *rv_new(int device) {
         delete h;
         return nullptr;
     }
-    h->T.push_back('\0');
+    h->host_text_.push_back('\0');
     h->ws.prof_ctx = &h->prof;
     h->ws.prof_begin_fn = [](void *c, hipStream_t st, int k, double b) { return ((RvProf *)c)->begin(st, k, b); };
     h->ws.prof_end_fn = [](void *c, hipStream_t st, int id) { ((RvProf *)c)->end(st, id); };
@@ -96,7 +96,7 @@ void rv_free(rv_index *h) {
     (void)rv_set_result_buffers(h, nullptr, 0, nullptr, 0, nullptr, 0);
     rv_align_free(h);
     h->prof.release();
-    h->dT.release(); h->dT0.release(); h->dSA.release(); h->dSAi.release(); h->dLCP.release(); h->dBWT.release(); h->dNsep.release();
+    h->dRcSeen.release(); h->dT.release(); h->dT0.release(); h->dSA.release(); h->dSAi.release(); h->dLCP.release(); h->dBWT.release(); h->dNsep.release();
     h->ws.release();
     h->hscan.release();
     for (auto &b : h->ps) b.release();
@@ -155,9 +155,10 @@ rv_index *rv_clone(rv_index *h) {
     if (rv_need_sai(h)) return nullptr;
     rv_index *c = rv_new(h->device);
     if (!c) return nullptr;
-    try { c->T = h->T; c->nsep = h->nsep; c->nodes = h->nodes; }
+    const HostText &src = rv_host_text(h);      // (after a device-side construct(rc=1): the reversed text, as the device holds it)
+    try { c->host_text_ = src; c->nsep = h->nsep; c->nodes = h->nodes; }
     catch (...) { rv_set_error("copy of the index: out of host memory"); rv_free(c); return nullptr; }
-    if (c->T.size() != h->T.size()) { rv_free(c); return nullptr; }      // (HostText::resize failed and said why)
+    if (c->host_text_.size() != src.size()) { rv_free(c); return nullptr; }      // (HostText::resize failed and said why)
     c->nsamples = h->nsamples; c->n = h->n; c->nT = h->nT; c->rc = h->rc;
     c->maxlcp = h->maxlcp; c->sa_stats = h->sa_stats; c->text_dirty = true;
     c->ws.opt = h->ws.opt;
@@ -201,9 +202,10 @@ int rv_add_sequence(rv_index *h, const char *seq, int64_t len, int64_t *begin, i
     // carries the sample side (rv_common.h) --, block by block so that the test reads what the copy just left in the cache; four threads
     // above 4 MB (250 Mbp: 60 ms -> 12 ms; a stream of inputs is assembled while the GPU works on the one before)
     const int64_t s = h->n;
-    if ((size_t)(h->n + len + 2) > h->T.cap) (void)hipSetDevice(h->device);      // (a large text is page-locked memory; 10^7 segments of a graph each find the room there)
-    if (h->T.resize((size_t)(h->n + len + 2)) != 0) return -1;
-    char *dst = h->T.data() + h->n;
+    HostText &T = rv_host_text(h);
+    if ((size_t)(h->n + len + 2) > T.cap) (void)hipSetDevice(h->device);      // (a large text is page-locked memory; 10^7 segments of a graph each find the room there)
+    if (T.resize((size_t)(h->n + len + 2)) != 0) return -1;
+    char *dst = T.data() + h->n;
     auto copy_check = [dst, seq](int64_t lo, int64_t hi) -> uint64_t {
         uint64_t acc = 0;
         const int64_t B = 32768;
@@ -236,13 +238,13 @@ int rv_add_sequence(rv_index *h, const char *seq, int64_t len, int64_t *begin, i
         acc = copy_check(0, len);
     }
     if (acc & 0x8080808080808080ull) {
-        (void)h->T.resize((size_t)h->n + 1);
-        h->T[(size_t)h->n] = '\0';
+        (void)T.resize((size_t)h->n + 1);
+        T[(size_t)h->n] = '\0';
         rv_set_error("addsequence: the sequence contains non-ASCII bytes");
         return -1;
     }
-    h->T[(size_t)(h->n + len)] = '$';
-    h->T[(size_t)(h->n + len + 1)] = '\0';
+    T[(size_t)(h->n + len)] = '$';
+    T[(size_t)(h->n + len + 1)] = '\0';
     h->n += len + 1;
     h->text_dirty = true;
     h->constructed = false; h->text_only = false;      /* SA / LCP / BWT in HBM are sized for the old text (the getters would read past them) */
@@ -266,9 +268,10 @@ int rv_add_sequences(rv_index *h, const char *text, int64_t total, const int64_t
         return -1;
     }
 #endif
-    if ((size_t)(h->n + total + 1) > h->T.cap) (void)hipSetDevice(h->device);
-    if (h->T.resize((size_t)(h->n + total + 1)) != 0) return -1;
-    char *dst = h->T.data() + h->n;
+    HostText &T = rv_host_text(h);
+    if ((size_t)(h->n + total + 1) > T.cap) (void)hipSetDevice(h->device);
+    if (T.resize((size_t)(h->n + total + 1)) != 0) return -1;
+    char *dst = T.data() + h->n;
     uint64_t acc = 0;
     {
         const int nt = total >= ((int64_t)4 << 20) ? 4 : 1;
@@ -288,8 +291,8 @@ int rv_add_sequences(rv_index *h, const char *text, int64_t total, const int64_t
         for (uint64_t a : part) acc |= a;
     }
     if (acc & 0x8080808080808080ull) {
-        (void)h->T.resize((size_t)h->n + 1);
-        h->T[(size_t)h->n] = '\0';
+        (void)T.resize((size_t)h->n + 1);
+        T[(size_t)h->n] = '\0';
         rv_set_error("addsequence: the sequence contains non-ASCII bytes");
         return -1;
     }
@@ -297,12 +300,12 @@ int rv_add_sequences(rv_index *h, const char *text, int64_t total, const int64_t
         h->nodes.reserve(h->nodes.size() + (size_t)count);
         int64_t at = h->n;
         for (int64_t k = 0; k < count; k++) {
-            if (dst[at - h->n + lens[k]] != '$') { rv_set_error("rv_add_sequences: no '$' behind sequence %lld", (long long)k); (void)h->T.resize((size_t)h->n + 1); h->T[(size_t)h->n] = '\0'; return -1; }
+            if (dst[at - h->n + lens[k]] != '$') { rv_set_error("rv_add_sequences: no '$' behind sequence %lld", (long long)k); (void)T.resize((size_t)h->n + 1); T[(size_t)h->n] = '\0'; return -1; }
             h->nodes.push_back(RvIntv{at, at + lens[k]});
             at += lens[k] + 1;
         }
     } catch (...) { rv_set_error("addsequence: out of host memory"); return -1; }
-    h->T[(size_t)(h->n + total)] = '\0';
+    T[(size_t)(h->n + total)] = '\0';
     h->n += total;
     h->text_dirty = true;
     h->constructed = false; h->text_only = false;
@@ -317,8 +320,9 @@ int rv_reset(rv_index *h) {
     RV_HIP(hipSetDevice(h->device));
     if (h->al) (void)rv_align_end(h);
     RV_HIP(hipStreamSynchronize(h->ws.stream));
-    if (h->T.resize(1) != 0) return -1;
-    h->T[0] = '\0';
+    h->host_stale = 0;      // (the text the reversals were owed to is gone)
+    if (h->host_text_.resize(1) != 0) return -1;
+    h->host_text_[0] = '\0';
     h->n = 0; h->nT = 0; h->nsamples = 0; h->rc = 0;
     h->nsep.clear(); h->nodes.clear();
     h->constructed = false; h->main_arrays_freed = false; h->sai_valid = false; h->text_only = false; h->text_dirty = true;
@@ -343,7 +347,7 @@ int rv_capacity_events(const rv_index *h, int64_t *out) {
 int rv_reserve_text(rv_index *h, int64_t bytes) {
     if (!h || bytes < 0) { rv_set_error("rv_reserve_text: bad argument"); return -1; }
     (void)hipSetDevice(h->device);
-    return h->T.reserve((size_t)bytes + 2);
+    return rv_host_text(h).reserve((size_t)bytes + 2);
 }
 
 int64_t rv_n(const rv_index *h) { return h->n; }
@@ -355,21 +359,30 @@ int rv_node_list(const rv_index *h, int64_t *begin_end) {
     return 0;
 }
 
-/* interface.c:136-158 */
-static char comp_of(char ch) {
-    static const char up[] = "TVGHEFCDIJMLKNOPQYSAABWXRZ";
-    const unsigned char c = (unsigned char)ch;
-    if (c >= 'A' && c <= 'Z') return up[c - 'A'];
-    if (c >= 'a' && c <= 'z') return (char)(up[c - 'a'] + 32);
-    if (c == 96) return 64;
-    return ch;
+/* interface.c:136-158 on a caller's buffer: the host rule of construct(rc=1) (rv_revcomp.h), no device is asked for */
+int rv_revcomp_bytes(char *buf, int64_t n) {
+    if (n < 0 || (n && !buf)) { rv_set_error("rv_revcomp_bytes: bad arguments"); return -1; }
+    rv_revcomp_host(buf, n);
+    return 0;
 }
-static void revcomp(char *T, int64_t n) {
-    for (int64_t i = 0; i < n >> 1; ++i) {
-        const char c0 = comp_of(T[i]), c1 = comp_of(T[n - 1 - i]);
-        T[i] = c1; T[n - 1 - i] = c0;
-    }
-    if (n & 1) T[n >> 1] = comp_of(T[n >> 1]);
+
+/* The text's traffic and the state construct(rc=1) left: out[0..n) = uploads, upload_bytes, rc_device, host_stale, rc_launches (the order of
+ * TEXT_INFO in reveal_amd/_lib.py).  Host counters only.  Returns the number of fields written. */
+int rv_text_info(rv_index *h, int64_t *out, int n) {
+    if (!h || !out || n < 0) { rv_set_error("rv_text_info: bad arguments"); return -1; }
+    const int64_t v[5] = {h->text_uploads, h->text_upload_bytes, h->rc_device, h->host_stale, h->rc_launches};
+    const int k = std::min(n, 5);
+    for (int i = 0; i < k; i++) out[i] = v[i];
+    return k;
+}
+
+/* The 64 bytes behind the text in device memory, which rv_upload zeroes and nothing may write (tests). */
+int rv_text_guard(rv_index *h, void *out64) {
+    if (!h || !out64 || !h->dT0.p || h->text_dirty) { rv_set_error("rv_text_guard: no text in device memory"); return -1; }
+    RV_HIP(hipSetDevice(h->device));
+    RV_HIP(hipStreamSynchronize(h->ws.stream));
+    RV_HIP(hipMemcpy(out64, h->dT0.as<uint8_t>() + h->n, 64, hipMemcpyDeviceToHost));
+    return 0;
 }
 
 static int read_raw(const char *path, void *dst, size_t bytes) {
@@ -396,13 +409,14 @@ int rv_upload(rv_index *h) {
     RV_HIP(hipSetDevice(h->device));
     if (!h->text_dirty) return 0;
     const int64_t n = h->n;
+    const HostText &T = rv_host_text(h);
     RV_TRY(h->dT0.reserve((size_t)n + 64));
     hipStream_t q = h->ws.stream;
     RV_HIP(hipMemsetAsync(h->dT0.p, 0, 64, q));
     RV_HIP(hipMemsetAsync(h->dT0.as<uint8_t>() + n, 0, 64, q));
     const size_t CH = (size_t)32 << 20;
-    if ((size_t)n < 2 * CH || h->T.pinned) {      // (a page-locked text: one copy by the DMA engine, no host thread touches it)
-        RV_HIP(hipMemcpyAsync(h->dT0.p, h->T.data(), (size_t)n, hipMemcpyHostToDevice, q));
+    if ((size_t)n < 2 * CH || T.pinned) {      // (a page-locked text: one copy by the DMA engine, no host thread touches it)
+        RV_HIP(hipMemcpyAsync(h->dT0.p, T.data(), (size_t)n, hipMemcpyHostToDevice, q));
     } else {
         // A large text through two pinned chunks: several host threads fill one while the other is on the wire.  (Straight from the
         // pageable vector the runtime stages it itself, single-threaded: 500 MB took 38-52 ms, 10-13 GB/s.)
@@ -421,9 +435,9 @@ int rv_upload(rv_index *h) {
             std::thread th[nt];
             for (int t = 1; t < nt; t++) {
                 const size_t lo = len / nt * t, hi = t + 1 == nt ? len : len / nt * (t + 1);
-                th[t] = std::thread([=]() { memcpy(dst + lo, h->T.data() + at + lo, hi - lo); });
+                th[t] = std::thread([=, &T]() { memcpy(dst + lo, T.data() + at + lo, hi - lo); });
             }
-            memcpy(dst, h->T.data() + at, len / nt);
+            memcpy(dst, T.data() + at, len / nt);
             for (int t = 1; t < nt; t++) th[t].join();
             RV_HIP(hipMemcpyAsync(h->dT0.as<char>() + at, dst, len, hipMemcpyHostToDevice, q));
             RV_HIP(hipEventRecord(ev[slot], q));
@@ -433,6 +447,7 @@ int rv_upload(rv_index *h) {
     }
     RV_HIP(hipStreamSynchronize(q));
     h->text_dirty = false;
+    h->text_uploads++; h->text_upload_bytes += n;
     return 0;
 }
 
@@ -445,11 +460,26 @@ int rv_upload_again(rv_index *h) {
 int rv_construct(rv_index *h, int rc, const char *safile, const char *lcpfile, int cache) {
     RV_HIP(hipSetDevice(h->device));
     memset(h->ws.cap_events, 0, sizeof h->ws.cap_events);
+    // rc = 1: T[nsep[0], n) reversed and complemented (interface.c:168-175), every time it is asked for.  On the device (the default): the text
+    // in device memory is brought up to date as it stands, k_text_revcomp turns the range there in place, and the host's copy is left owing
+    // the reversal (rv_host_text) -- nothing is uploaded a second time.  RV_RC_HOST, or a range below RV_RC_HOST_BELOW bytes: the host loop,
+    // then the whole text goes up again.
+    // Where a call fails: the host leg has turned the host text (and marked it dirty) before the checks below can refuse the call, as the
+    // reference has; the device leg turns nothing before they pass.  A failure behind the kernel -- an allocation, the build -- leaves the
+    // device text turned and host_stale saying so: both sides still describe one text, and the index is "not constructed" until a
+    // construct() succeeds.
+    bool rc_dev = false;
     if (rc == 1) {
         if (h->nsep.empty()) { rv_set_error("construct(rc=1) needs at least two samples"); return -1; }
         h->rc = 1;
-        revcomp(h->T.data() + h->nsep[0], h->n - h->nsep[0]);
-        h->text_dirty = true;
+        const int64_t len = h->n - h->nsep[0];
+        if (h->ws.opt.rc_host != 0 || len < std::max<int64_t>(h->ws.opt.rc_host_below, 0) || h->n == 0) {
+            rv_revcomp_host(rv_host_text(h).data() + h->nsep[0], len);
+            h->text_dirty = true;
+            h->rc_device = 0;
+        } else {
+            rc_dev = true;
+        }
     } else {
         h->rc = 0;
     }
@@ -458,7 +488,6 @@ int rv_construct(rv_index *h, int rc, const char *safile, const char *lcpfile, i
     // ranks, child sizes and scan records are carried as u32 inside the library (rv_scan.h, rv_split.h), whatever the width of
     // sa_t and however SA is obtained (built, or read from a file)
     if (n >= ((int64_t)1 << 32) - 2) { rv_set_error("index of %lld positions: this build carries ranks in 32 bits (n < 2^32 - 2)", (long long)n); return -1; }
-    if (cache == 1) RV_TRY(write_raw(".reveal.t", h->T.data(), (size_t)n));
     if (h->al) (void)rv_align_end(h);        /* a new construct ends any recursion in flight; its device scratch is kept */
     h->nT = n;
     hipStream_t q = h->ws.stream;
@@ -466,6 +495,26 @@ int rv_construct(rv_index *h, int rc, const char *safile, const char *lcpfile, i
     // is built from the pristine text -- the same bytes, the same padding
     if (h->dT_inflight) { RV_HIP(hipStreamWaitEvent(q, h->ev_text, 0)); h->dT_inflight = false; }      // (a copy nobody has waited for yet: before its buffers change)
     RV_TRY(rv_upload(h));
+    if (rc_dev) {
+        const int64_t lo = h->nsep[0], len = n - lo;
+        if (h->host_stale && (h->rc_lo != lo || h->rc_len != len)) (void)rv_host_text(h);      // (a debt for another range -- none of the ABI's paths leaves one -- is paid first)
+        if (!h->dRcSeen.p) { RV_TRY(h->dRcSeen.reserve(64)); RV_HIP(hipMemsetAsync(h->dRcSeen.p, 0, 64, q)); }
+        // the reversal the host will owe first: its kernel leaves its number (never 0) in dRcSeen if it meets U, u or 96 -- a second one then
+        // does not cancel it
+        const bool first = h->host_stale == 0;
+        if (first) h->rc_seen_mark = (u32)(h->rc_launches + 1) | 0x80000000u;
+        u32 got = 0;
+        if (h->host_stale == 1) RV_TRY(rv_read_back(h->ws, &got, h->dRcSeen.p, 4));
+        const bool odd = got == h->rc_seen_mark;
+        RV_TRY(rv_text_revcomp(h->ws, h->dT0.as<uint8_t>(), lo, len, first ? h->dRcSeen.as<u32>() : nullptr, h->rc_seen_mark));
+        h->rc_launches++;
+        h->rc_device = 1;
+        // device text = the host's reversed host_stale times.  R^3 = R on every text; R^2 = identity only without U, u and 96 in the range
+        if (h->host_stale == 0) { h->host_stale = 1; h->rc_lo = lo; h->rc_len = len; }
+        else if (h->host_stale == 1) h->host_stale = odd ? 2 : 0;
+        else h->host_stale = 1;
+    }
+    if (cache == 1) RV_TRY(write_raw(".reveal.t", rv_host_text(h).data(), (size_t)n));
     RV_TRY(h->dT.reserve((size_t)n + 64));
     h->dT_pending = true;
     RV_TRY(h->dSA.reserve((size_t)(n + 64) * sizeof(sa_t)));
@@ -540,12 +589,13 @@ int64_t rv_get_array(rv_index *h, int which, void *out, int64_t cap) {
     switch (which) {
     case RV_T:
         if (cap < n) { rv_set_error("buffer too small"); return -1; }
+        (void)rv_host_text(h);      // (whoever reads T finds the host's copy up to date behind the call, whichever side the bytes come from)
         if (h->constructed || h->text_only) {
             if (rv_ensure_working_text(h) != 0) return -1;
             if (hipStreamSynchronize(h->ws.stream) != hipSuccess) { rv_set_error("stream failed"); return -1; }
             if (hipMemcpy(out, h->dT.p, (size_t)n, hipMemcpyDeviceToHost) != hipSuccess) { rv_set_error("D2H failed"); return -1; }
         } else {
-            memcpy(out, h->T.data(), (size_t)n);
+            memcpy(out, rv_host_text(h).data(), (size_t)n);
         }
         return n;
     case RV_SA: case RV_SAI: case RV_LCP: {
@@ -1578,6 +1628,52 @@ int rv_test_radix_time(int64_t n, int bits, int dist, int flags, int iters, doub
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
     k0.release(); k1.release(); v0.release(); v1.release(); db.release();
+    test_ws_done(ws);
+    return r;
+}
+
+}  // extern "C"
+namespace {
+// 16 pseudo-random letters of ACGT per thread (a hash of the position)
+__global__ __launch_bounds__(256) void k_rc_fill(uint8_t *__restrict__ T, int64_t n16) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n16) return;
+    u64 x = (u64)i * 0x9E3779B97F4A7C15ull + 0x632BE59BD9B4E019ull;
+    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull; x ^= x >> 27; x *= 0x94D049BB133111EBull; x ^= x >> 31;
+    for (int k = 0; k < 16; k++) T[i * 16 + k] = (uint8_t)"ACGT"[(x >> (2 * k)) & 3];
+}
+}  // namespace
+extern "C" {
+/* k_text_revcomp on [lo, lo + len) of a text of pseudo-random ACGT and a device-to-device copy of as many bytes, `iters` times in turn after a
+ * warm-up, each between two events on one stream: kernel_ms[it], copy_ms[it] (tools/time_rc.py).  In front of every timed item lo + len bytes
+ * that neither touches are overwritten, so that a range smaller than the last-level cache is not served from it. */
+int rv_test_revcomp_time(int64_t lo, int64_t len, int iters, double *kernel_ms, double *copy_ms) {
+    if (lo < 0 || len < 1 || iters < 1 || !kernel_ms || !copy_ms) { rv_set_error("rv_test_revcomp_time: bad arguments"); return -1; }
+    Workspace ws;
+    RV_TRY(test_ws(ws));
+    DBuf text, other;
+    int r = 0;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    DBuf flush;
+    const int64_t n16 = ceil_div(lo + len, 16);
+    if (text.reserve((size_t)n16 * 16 + 64) || other.reserve((size_t)len + 64) || flush.reserve((size_t)(lo + len) + 64)) r = -1;
+    if (!r && (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess)) r = -1;
+    if (!r) { hipLaunchKernelGGL(k_rc_fill, dim3((unsigned)ceil_div(n16, 256)), dim3(256), 0, ws.stream, text.as<uint8_t>(), n16); if (hipGetLastError() != hipSuccess) r = -1; }
+    for (int it = -1; !r && it < iters; it++) {       // (it = -1: warm-up)
+        for (int what = 0; !r && what < 2; what++) {
+            if (hipMemsetAsync(flush.p, it & 1, (size_t)(lo + len), ws.stream) != hipSuccess) r = -1;
+            (void)hipEventRecord(e0, ws.stream);
+            if (what == 0) r = rv_text_revcomp(ws, text.as<uint8_t>(), lo, len);
+            else if (hipMemcpyAsync(other.p, text.as<uint8_t>() + lo, (size_t)len, hipMemcpyDeviceToDevice, ws.stream) != hipSuccess) r = -1;
+            (void)hipEventRecord(e1, ws.stream);
+            if (!r && hipEventSynchronize(e1) != hipSuccess) { rv_set_error("sync failed: %s", hipGetErrorString(hipGetLastError())); r = -1; }
+            float t = 0;
+            if (!r && it >= 0) { (void)hipEventElapsedTime(&t, e0, e1); (what ? copy_ms : kernel_ms)[it] = t; }
+        }
+    }
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    text.release(); other.release(); flush.release();
     test_ws_done(ws);
     return r;
 }

@@ -122,7 +122,9 @@ void rv_set_error(const char *fmt, ...);
     X(blocks_host_below, "RV_BLOCKS_HOST_BELOW", 4096) \
     X(glocal_host, "RV_GLOCAL_HOST", 0) \
     X(glocal_host_below, "RV_GLOCAL_HOST_BELOW", (int64_t)1 << 31) \
-    X(glocal_edge_budget, "RV_GLOCAL_EDGE_BUDGET", 1 << 25)
+    X(glocal_edge_budget, "RV_GLOCAL_EDGE_BUDGET", 1 << 25) \
+    X(rc_host, "RV_RC_HOST", 0) \
+    X(rc_host_below, "RV_RC_HOST_BELOW", 0)
 struct RvOptions {
 #define RV_X_(f, name, def) int64_t f = def;
     RV_OPTION_LIST(RV_X_)

@@ -4,6 +4,7 @@
 #include "rv_scan.h"
 #include "rv_blocks.h"
 #include "rv_glocal.h"
+#include "rv_revcomp.h"
 #include "../../include/reveal_amd.h"
 #include <utility>
 
@@ -122,7 +123,20 @@ struct rv_index {
     Workspace ws;
     RvProf prof;
     // ---- host text assembly (interface.c:18-95)
-    HostText T;                        // n chars + NUL
+    HostText host_text_;               // n chars + NUL.  Read and written through rv_host_text() alone (rv_new and rv_reset start it empty)
+    // construct(rc=1) has reversed [rc_lo, rc_lo + rc_len) of the text in device memory and left the host's copy as it was: the host owes
+    // host_stale (0, 1 or 2) reversals of that range to whoever reads or writes its text next (rv_host_text pays them, one host loop each).
+    // Reversing is its own inverse only where the range holds no U, u or 96 (rv_comp_of: U -> A -> T, 96 -> 64 -> 64), and three reversals
+    // always equal one.  So a second device reversal cancels the debt when the first one's kernel met none of those bytes (dRcSeen, read back
+    // then) and makes it 2 otherwise; a third brings 2 back to 1.
+    int host_stale = 0;
+    int64_t rc_lo = 0, rc_len = 0;
+    DBuf dRcSeen;                      // one word: holds rc_seen_mark iff the kernel of the reversal that took host_stale from 0 to 1 met U, u or 96
+    u32 rc_seen_mark = 0;
+    // rv_text_info: host-to-device copies of the text over the handle's life and their bytes, whether the last construct(rc=1) reversed on the
+    // device, launches of k_text_revcomp
+    int64_t text_uploads = 0, text_upload_bytes = 0, rc_launches = 0;
+    int rc_device = 0;
     std::vector<int64_t> nsep;
     std::vector<int64_t> nsep_dev;     // what dNsep holds
     std::vector<RvIntv> nodes;
@@ -163,6 +177,13 @@ struct rv_index {
         bool direct = false;           // the last run's leaf / cascade anchors are already in them (rv_fetch_anchors copies the rest)
     } rb;
 };
+
+// The host's text, up to date: pays the reversals device-side construct(rc=1) calls left owing.  Every reader and writer of the host text takes it
+// from here.
+inline HostText &rv_host_text(rv_index *h) {
+    for (; h->host_stale > 0; h->host_stale--) rv_revcomp_host(h->host_text_.data() + h->rc_lo, h->rc_len);
+    return h->host_text_;
+}
 
 // scan of SA/LCP[0..m) -> host records in rank order (rv_api.hip)
 // d_err (optional): device word copied into the scan header and returned through err_out (deferred error check of the previous commit)

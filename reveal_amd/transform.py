@@ -144,7 +144,8 @@ def synteny_blocks(reference, contigs, minlength=20, cluster=True, maxdist=30, m
     """transform.py:228-293: reference and contigs (FASTA paths, or lists of sequences) -> dict(blocks, ctg2range, sep, rlength, qlength, mums), what
     glocalchain is handed.  Sequences shorter than minctglength are skipped in both inputs (transform.py:241).  Sample 0 is the reference, sample 1 the
     contigs; blocks = the forward blocks (construct(rc=0), getblocks) followed by the reverse-complement ones (construct(rc=1), getblocks); mums =
-    (forward, reverse-complement) MUM counts; also refnames / ctgnames of the sequences kept."""
+    (forward, reverse-complement) MUM counts; also refnames / ctgnames of the sequences kept, and text = index.text_info() behind the second getblocks (by
+    default the text went up once: construct(rc=1) reverses it in device memory)."""
     from . import reveallib, reveallib64
     idx = (reveallib64 if sa64 else reveallib).index()
     ctg2range, names = [], ([], [])
@@ -161,11 +162,12 @@ def synteny_blocks(reference, contigs, minlength=20, cluster=True, maxdist=30, m
     fwd = idx.getblocks_arrays(minlength, cluster, maxdist, mincluster)
     idx.construct(rc=1)
     rc = idx.getblocks_arrays(minlength, cluster, maxdist, mincluster)
+    text = idx.text_info()
     sep, n = idx.nsep[0], idx.n
     keys = ("s1", "e1", "s2", "e2", "score", "refid", "ctgid")
     blocks = _tuples(0, [fwd[c] for c in keys]) + _tuples(1, [rc[c] for c in keys])
     return dict(blocks=blocks, ctg2range=ctg2range, sep=sep, rlength=sep, qlength=n - sep, mums=(fwd["info"]["mums"], rc["info"]["mums"]),
-                refnames=names[0], ctgnames=names[1])
+                refnames=names[0], ctgnames=names[1], text=text)
 
 
 # ---- glocalchain (transform.py:947-1180, useheap=False); the rule: include/reveal_amd.h, rv_glocal_filter ---------------------------------------------
