@@ -770,8 +770,11 @@ int rv_sa_tail(rv_index *h, int64_t *out);
 int rv_sa_paths(rv_index *h, int64_t *out, int count);
 
 /* ---- self-test hooks for the device primitives (tests/ only) ------------------ */
+/* the scans on host buffers of n items.  in == out: one device buffer scanned in place; otherwise from one device buffer into another */
 int rv_test_exclusive_sum_u32(const uint32_t *in, uint32_t *out, int64_t n);
 int rv_test_inclusive_max_u32(const uint32_t *in, uint32_t *out, int64_t n);
+int rv_test_exclusive_sum_u64(const uint64_t *in, uint64_t *out, int64_t n);
+int rv_test_inclusive_max_u64(const uint64_t *in, uint64_t *out, int64_t n);
 int rv_test_radix_sort(uint64_t *keys, uint32_t *vals, int64_t n, int bit_lo, int bit_hi);
 /* the same sort timed on device-made keys (HIP events on its stream): dist 0 uniform, 1 first keys of a DNA text (base-5 digits 1..4),
  * 2 constant; flags: 1 = 10-bit digits, 2 = XCD-aware tile order, 4 = 16-bit wave counters, 8 = histograms from the keys (no digit bytes);

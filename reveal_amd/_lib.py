@@ -211,6 +211,8 @@ SYMBOLS = {
     "rv_many_arrays": (_L, [V, _L, _I, V, _L]),
     "rv_test_exclusive_sum_u32": (_I, [V, V, _L]),
     "rv_test_inclusive_max_u32": (_I, [V, V, _L]),
+    "rv_test_exclusive_sum_u64": (_I, [V, V, _L]),
+    "rv_test_inclusive_max_u64": (_I, [V, V, _L]),
     "rv_test_radix_sort": (_I, [V, V, _L, _I, _I]),
     "rv_test_radix_time": (_I, [_L, _I, _I, _I, _I, ctypes.POINTER(_D), c_i64p]),
     "rv_test_revcomp_time": (_I, [_L, _L, _I, ctypes.POINTER(_D), ctypes.POINTER(_D)]),

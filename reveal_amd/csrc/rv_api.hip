@@ -1538,22 +1538,31 @@ static int test_ws(Workspace &ws) {
 }
 static void test_ws_done(Workspace &ws) { ws.release(); (void)hipStreamDestroy(ws.stream); }
 
-static int test_scan(const uint32_t *in, uint32_t *out, int64_t n, bool maxscan) {
+// width = bytes of an item (4 or 8).  in == out: ONE device buffer, scanned in place (as every caller in rv_glocal.hip and rv_blocks.hip scans)
+static int test_scan(const void *in, void *out, int64_t n, size_t width, bool maxscan) {
+    if (n < 0 || !in || !out) { rv_set_error("scan test: bad arguments"); return -1; }
     Workspace ws;
     RV_TRY(test_ws(ws));
+    const bool inplace = in == out;
     DBuf a, b;
     int r = 0;
-    if (a.reserve((size_t)n * 4 + 64) || b.reserve((size_t)n * 4 + 64)) r = -1;
-    if (!r && hipMemcpy(a.p, in, (size_t)n * 4, hipMemcpyHostToDevice) != hipSuccess) r = -1;
-    if (!r) r = maxscan ? rv_inclusive_max_u32(ws, a.as<u32>(), b.as<u32>(), n) : rv_exclusive_sum_u32(ws, a.as<u32>(), b.as<u32>(), n);
+    if (a.reserve((size_t)n * width + 64) || (!inplace && b.reserve((size_t)n * width + 64))) r = -1;
+    void *src = a.p, *dst = inplace ? a.p : b.p;
+    if (!r && hipMemcpy(src, in, (size_t)n * width, hipMemcpyHostToDevice) != hipSuccess) r = -1;
+    if (!r) {
+        if (width == 8) r = maxscan ? rv_inclusive_max_u64(ws, (const u64 *)src, (u64 *)dst, n) : rv_exclusive_sum_u64(ws, (const u64 *)src, (u64 *)dst, n);
+        else r = maxscan ? rv_inclusive_max_u32(ws, (const u32 *)src, (u32 *)dst, n) : rv_exclusive_sum_u32(ws, (const u32 *)src, (u32 *)dst, n);
+    }
     if (!r && hipStreamSynchronize(ws.stream) != hipSuccess) { rv_set_error("sync failed: %s", hipGetErrorString(hipGetLastError())); r = -1; }
-    if (!r && hipMemcpy(out, b.p, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess) r = -1;
+    if (!r && hipMemcpy(out, dst, (size_t)n * width, hipMemcpyDeviceToHost) != hipSuccess) r = -1;
     a.release(); b.release();
     test_ws_done(ws);
     return r;
 }
-int rv_test_exclusive_sum_u32(const uint32_t *in, uint32_t *out, int64_t n) { return test_scan(in, out, n, false); }
-int rv_test_inclusive_max_u32(const uint32_t *in, uint32_t *out, int64_t n) { return test_scan(in, out, n, true); }
+int rv_test_exclusive_sum_u32(const uint32_t *in, uint32_t *out, int64_t n) { return test_scan(in, out, n, 4, false); }
+int rv_test_inclusive_max_u32(const uint32_t *in, uint32_t *out, int64_t n) { return test_scan(in, out, n, 4, true); }
+int rv_test_exclusive_sum_u64(const uint64_t *in, uint64_t *out, int64_t n) { return test_scan(in, out, n, 8, false); }
+int rv_test_inclusive_max_u64(const uint64_t *in, uint64_t *out, int64_t n) { return test_scan(in, out, n, 8, true); }
 
 int rv_test_radix_sort(uint64_t *keys, uint32_t *vals, int64_t n, int bit_lo, int bit_hi) {
     Workspace ws;

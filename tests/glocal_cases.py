@@ -125,6 +125,110 @@ FILTERED = ("empty", "one", "cross", "long_span", "window_n2_bp10", "window_n3_b
             "passes_second_drops", "passes_four", "refuse_fraction", "refuse_huge")      # the cases that also run both loops
 
 
+# ---- the large cases: what the kernels of rv_glocal.hip do above one workgroup, above 192 edges a window and above the 2048 scores of the LDS ring.
+# Their records stand under "large" in the golden file; reach() states, per case and axis, the arithmetic that takes it to the line it is there for
+# (tests/test_cpu_glocal.py::test_large_reach asserts it on the CPU, the GPU tests assert the counts the library reports).
+WG = 256                 # threads of a per-entry kernel: gm = ceil((m + 2) / WG) workgroups
+SCAN_TILE = 2048         # items of a scan tile (rv_prims.hip)
+RING = 2048              # GLC_RING: the scores k_glc_chain keeps in LDS
+AHEAD = 192              # GLC_NR * 64: the edges of a window that k_glc_chain loads ahead; the rest is its tail loop
+NDUMMY = (2, 3)          # dummies per axis with RANGES and with LONG_RANGES: two reference sequences, three contigs
+LONG_RANGES = [(0, 49999), (50000, 54999), (55000, 104999), (105000, 108999), (109000, 112999)]      # room for a thousand blocks on one diagonal
+LONG_SEP = 54999
+RING_TILE_BUDGET = 500000                                # ring_2300 under this edge budget: six tiles, the last one begins behind entry RING
+PASSES_BIG = (1, 2300, 2)                                # (seed, blocks, lastn): tools/gen_glocal_golden.py asserts three passes and > WG survivors
+FAR = ((191, 0), (191, 1), (192, 0), (192, 1), (2047, 0), (2048, 0))      # (entries between a block and its best predecessor, the axis it is built on)
+COLLINEAR = (253, 254, 1021, 1022)
+
+
+def collinear_blocks(n):
+    """n blocks that do not overlap, on one diagonal of the first reference sequence and the first contig"""
+    rng = random.Random(n)
+    out = []
+    for k in range(n):
+        L = rng.randint(8, 30)
+        out.append((10 + 40 * k, 10 + 40 * k + L, 55010 + 40 * k, 55010 + 40 * k + L, 0, rng.randint(1, L), 0, 2))
+    return out
+
+
+def far_blocks(between, axis):
+    """A block B whose best predecessor lies `between` entries back in the sorted order of `axis`: 40 blocks A on a diagonal, then `between` blocks
+    whose other coordinate lies below every A and falls from one to the next (o = 0: reaching one of them, or leaving one for a block further up,
+    is a rearrangement), then B and ten more on the diagonal of A.  With eps = 0 the step A[39] -> B costs gapopen alone.  -> (blocks, index of
+    A[39], index of B)"""
+    lay = [(2 + 20 * i, 10, 30002 + 20 * i, 8 + i % 3) for i in range(40)]                      # (begin on the axis, length, begin on the other, score)
+    lay += [(1000 + 8 * t, 4, 25000 - 10 * t, 1 + t % 3) for t in range(between)]
+    p0 = 1000 + 8 * between + 20
+    lay += [(p0 + 20 * i, 10, 30000 + p0 + 20 * i, 9 + i % 2) for i in range(11)]
+    out = []
+    for p, L, s, sc in lay:
+        out.append((p, p + L, 55000 + s, 55000 + s + L, 0, sc, 0, 2) if axis == 0 else (s, s + L, 55000 + p, 55000 + p + L, 0, sc, 0, 2))
+    return out, 39, 40 + between
+
+
+def large_cases():
+    """name -> case, as cases(): the smallest lists that reach the lines named beside them"""
+    C = {}
+    # m + 2 = 254 .. 258 over the two axes: the second workgroup of every per-entry kernel and their guards k > m, k <= m + 1
+    for n in (250, 251, 252, 253):
+        C["entries_256_%d" % n] = _case(rand_blocks(random.Random(n), n))
+    # the longest path a list can have, m + 1 on axis 0 = 256, 257, 1024, 1025: every launch of k_glc_double is needed at a power of two
+    for n in COLLINEAR:
+        C["collinear_%d" % n] = _case(collinear_blocks(n), LONG_RANGES, LONG_SEP, _lambda=2, eps=0, gapopen=0, rearrangecost=60, alfa=1)
+    # the k-th entry looks back over exactly k entries: windows of 191, 192, 193, 256, 257 edges -- the tail loop of k_glc_chain behind AHEAD edges
+    # (every fifth block lies 20 off the line the others follow, and a block gains 16 .. 26 against 15 for a step along it: 206 of them are kept)
+    off = [20 if k % 5 == 2 else 0 for k in range(260)]
+    C["window_260"] = _case([(20 + 19 * k, 32 + 19 * k, 10020 + 15 * k + off[k], 10032 + 15 * k + off[k], 0, 16 + 7 * k % 11, 0, 2) for k in range(260)],
+                            lastn=1000, lastbp=10 ** 6)
+    # the same with 2300 random blocks: windows above RING edges (scores read from global memory), three scans over two scan tiles, ten workgroups;
+    # under RING_TILE_BUDGET a tile that begins behind entry RING (the ring's pre-load from klo - RING > 0)
+    C["ring_2300"] = _case(rand_blocks(random.Random(2300), 2300), lastn=3000, lastbp=10 ** 6)
+    # the best predecessor at a known distance: the last edge loaded ahead and the first of the tail loop, the last score in the ring and the first
+    # outside it
+    for between, axis in FAR:
+        C["far_%d_axis%d" % (between, axis)] = _case(far_blocks(between, axis)[0], LONG_RANGES, LONG_SEP, lastn=3000, lastbp=10 ** 6, rearrangecost=100,
+                                                      inversioncost=0, _lambda=5, eps=0, alfa=1, gapopen=1)
+    # several passes over a list of ten workgroups: compaction into a second pass of more than WG entries
+    seed, n, lastn = PASSES_BIG
+    C["passes_big"] = _case(rand_blocks(random.Random(seed), n), lastn=lastn, lastbp=20)
+    # the two-sort route (coordinates above 2^40) above one workgroup: the second sort's permutation gathered by three
+    base = 1 << 40
+    wr = [(0, base + 4999)] + [(base + s, base + e) for s, e in RANGES[1:]]
+    for o in (0, 1):
+        rng = random.Random(600 + o)
+        wb = [(s1, e1, s2, e2, oo if o else 0, sc << 20, r, c) for s1, e1, s2, e2, oo, sc, r, c in rand_blocks(rng, 600, [(base, base + 4999)] + wr[1:])]
+        C["wide_600_o%d" % o] = _case(wb, wr, base + SEP, rearrangecost=1024 * 60, inversioncost=1024, _lambda=1024, eps=1024, alfa=1024, gapopen=1024)
+    return C
+
+
+LARGE_FILTERED = ("entries_256_250", "entries_256_251", "entries_256_252", "entries_256_253", "passes_big", "wide_600_o0", "wide_600_o1")
+WHOLE_PREFIX = ("window_260", "ring_2300") + tuple("far_%d_axis%d" % f for f in FAR)      # the window of the k-th entry is the k entries in front of it
+LARGE_BUDGETS = {"window_260": (64, 1000), "ring_2300": (RING_TILE_BUDGET,)}              # the cases that also run under a low edge budget
+
+
+def entries(c, axis):
+    """m of a pass over the whole list: the blocks and the dummies of the axis"""
+    nd = sum(1 for s, _ in c["ctg2range"] if (s < c["rlength"]) == (axis == 0))
+    return len(c["blocks"]) + nd
+
+
+def whole_prefix_edges(m):
+    return m * (m + 1) // 2
+
+
+def doubling_launches(m):
+    """launches of k_glc_double: ceil(log2(m + 1)); after t of them the marks reach 2^t - 1 steps down the path from `end`"""
+    return (m).bit_length()
+
+
+def first_entry_of_tile(tile, budget):
+    """whole-prefix windows, eoff[k] = k (k - 1) / 2: the first entry whose first edge lies at or behind tile * budget"""
+    k = 1
+    while k * (k - 1) // 2 < tile * budget:
+        k += 1
+    return k
+
+
 def multi_blocks():
     """the block list of blocks_cases.multi_case() as the golden file of getblocks holds it (forward, then reverse complement) + its ranges"""
     T, nsep, nodes = assemble(blocks_cases.multi_inputs())

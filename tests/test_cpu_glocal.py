@@ -76,6 +76,101 @@ def test_expectations():
     assert GOLD["multi"]["n"] == len(C.multi_blocks()[0]) and len(GOLD["multi"]["chain"]) > 0
 
 
+# ---- the large cases (glocal_cases.large_cases): the golden records under "large" pinned here, without a GPU
+LARGE = C.large_cases()
+
+
+# (the Python rule takes seconds on 2000 entries with whole-prefix windows: the far_2047 / far_2048 lists run it on the axis they are built on)
+@pytest.mark.parametrize("name,axis", [(n, a) for n in LARGE for a in (0, 1) if not (n.startswith("far_20") and a == 1)])
+def test_large_python_matches_the_reference(name, axis):
+    c = LARGE[name]
+    got = transform.glocalchain_python(*args(c), axis=axis, **c["kw"])
+    assert C.matches(C.indices(c["blocks"], got), GOLD["large"][name]["axis%d" % axis])
+
+
+@pytest.mark.parametrize("sa64", [False, True])
+@pytest.mark.parametrize("axis", [0, 1])
+@pytest.mark.parametrize("name", list(LARGE))
+def test_large_native_matches_the_reference(name, axis, sa64):
+    c = LARGE[name]
+    got = transform.glocalchain_native(*args(c), axis=axis, sa64=sa64, **c["kw"])
+    assert C.matches(C.indices(c["blocks"], got), GOLD["large"][name]["axis%d" % axis])
+
+
+@pytest.mark.parametrize("route", ["python", "host"])
+@pytest.mark.parametrize("name", C.LARGE_FILTERED)
+def test_large_filter_matches_the_reference_loops(name, route):
+    c = LARGE[name]
+    want = GOLD["large"][name]["filter"]
+    got, info = transform.glocal_filter(*args(c), route=route, **c["kw"])
+    assert C.matches(C.indices(c["blocks"], got), want["chain"])
+    assert list(info["passes"]) == want["passes"] and info["after"] == want["after"] and info["route"] == route
+
+
+def test_large_reach():
+    """the arithmetic that takes each large case to the line of rv_glocal.hip it is there for"""
+    g = GOLD["large"]
+    assert set(g) == set(LARGE) and all(g[n]["n"] == len(LARGE[n]["blocks"]) for n in LARGE)
+    assert set(C.LARGE_FILTERED) <= set(LARGE) and set(C.WHOLE_PREFIX) <= set(LARGE) and set(C.LARGE_BUDGETS) <= set(C.WHOLE_PREFIX)
+    for c in LARGE.values():
+        assert tuple(C.entries(c, a) - len(c["blocks"]) for a in (0, 1)) == C.NDUMMY
+    # entries_256_*: m + 2 slots, the grid of every per-entry kernel, from two below 256 to two above it: one workgroup and two, with
+    # k = m and k = m + 1 (what the guards k > m and k <= m + 1 tell apart) on either side of the workgroup border
+    slots = sorted({C.entries(LARGE["entries_256_%d" % n], a) + 2 for n in (250, 251, 252, 253) for a in (0, 1)})
+    assert slots == [254, 255, 256, 257, 258]
+    assert {-(-s // C.WG) for s in slots} == {1, 2}
+    # collinear_n: the path from `end` runs through all n blocks (the generator asserts it on the reference's chain; here the record is that chain),
+    # so it is at least n steps long: at m + 1 = 256 and 1024 the last launch of k_glc_double is needed (2^(t-1) - 1 steps do not reach the first
+    # block), at 257 and 1025 the count has just grown by one
+    want = {253: (256, 8), 254: (257, 9), 1021: (1024, 10), 1022: (1025, 11)}
+    for n in C.COLLINEAR:
+        c, rec = LARGE["collinear_%d" % n], g["collinear_%d" % n]
+        assert C.matches(list(range(n)), rec["axis0"])
+        m = C.entries(c, 0)
+        t = C.doubling_launches(m)
+        assert (m + 1, t) == want[n] and 2 ** (t - 1) < m + 1 <= 2 ** t
+        if (m + 1) & m == 0:
+            assert 2 ** (t - 1) - 1 < n
+        assert -(-(m + 2) // C.WG) >= 2
+    # whole-prefix windows: no entry lies more than lastbp in front of another and lastn is above the list, so the walk back never ends early:
+    # the k-th entry has k edges, the pass m (m + 1) / 2
+    for name in C.WHOLE_PREFIX:
+        c = LARGE[name]
+        lo = min(min(b[0], b[2]) for b in c["blocks"])
+        hi = max(e for _, e in c["ctg2range"])
+        assert hi - lo <= c["kw"]["lastbp"] and c["kw"]["lastn"] > max(C.entries(c, 0), C.entries(c, 1))
+    for axis in (0, 1):
+        m = C.entries(LARGE["window_260"], axis)
+        assert m >= 257 > C.AHEAD + 64 and m + 2 > C.WG                       # windows of 191, 192, 193, 256 and 257 edges: 1 .. m are all there
+        for budget in C.LARGE_BUDGETS["window_260"]:
+            assert C.whole_prefix_edges(m) // budget + 1 >= 30                # tiles of a few windows each: the long ones reach over their borders
+        m = C.entries(LARGE["ring_2300"], axis)
+        assert m > C.RING + C.AHEAD and m + 2 > C.SCAN_TILE                   # windows above the ring, every scan of the pass over two scan tiles
+        assert -(-(m + 2) // C.WG) == (9, 10)[axis]                           # m + 2 = 2304 = 9 * 256 on axis 0, one more entry and workgroup on axis 1
+        assert C.whole_prefix_edges(m) < 1 << 25                              # one tile at the default budget
+        tiles = C.whole_prefix_edges(m) // C.RING_TILE_BUDGET + 1
+        assert tiles == 6
+        klo = C.first_entry_of_tile(tiles - 1, C.RING_TILE_BUDGET)
+        assert C.RING < klo <= m and klo in (2237, 2238)                      # the last tile begins behind entry RING: its pre-load starts at klo - RING > 0
+    # far_*: the best predecessor of block B (the generator asserts that the reference's chain reaches B from A[39]) lies `between` entries in front
+    # of it in the sorted order, that is edge number `between` of its window: 191 = the last edge loaded ahead, 192 = the first of the tail loop,
+    # 2047 = the oldest score in the ring, 2048 = the first one read from global memory
+    assert {b for b, _ in C.FAR} == {C.AHEAD - 1, C.AHEAD, C.RING - 1, C.RING}
+    for between, axis in C.FAR:
+        blocks, a, b = C.far_blocks(between, axis)
+        order = sorted(range(len(blocks)), key=lambda i: (blocks[i][2 * axis], -blocks[i][5]))
+        assert order.index(b) - 1 - order.index(a) == between
+    # passes_big: three passes on one axis, and the second pass' list is spread over several workgroups
+    f = g["passes_big"]["filter"]
+    assert max(f["passes"]) >= 3 and f["after"][0] > C.WG and g["passes_big"]["n"] + 2 > C.SCAN_TILE
+    # wide_600: 2^40 coordinates and scores of more than 24 bits leave no room for one 64-bit key, and three workgroups gather the permutation
+    for o in (0, 1):
+        c = LARGE["wide_600_o%d" % o]
+        mc, ms = max(e for _, e in c["ctg2range"]), max(b[5] for b in c["blocks"])
+        assert mc.bit_length() + ms.bit_length() > 64 and -(-(C.entries(c, 0) + 2) // C.WG) == 3
+        assert g["wide_600_o%d" % o]["score0"] > 1 << 32
+
+
 def test_multi_case_filter():
     """the end-to-end list of synteny_chain (the golden blocks of blocks_cases.multi_case) through both CPU routes"""
     blocks, nodes, rlength, qlength = C.multi_blocks()

@@ -1,6 +1,7 @@
 """The glocal chain of `reveal transform` on the GPU (rv_glocal.hip): transform.glocalchain_device, glocal_filter and synteny_chain against
 tests/golden/glocal.json (the reference's own glocalchain, tools/gen_glocal_golden.py), against the RV_GLOCAL_HOST leg, and as shipped beside the
-kernels forced (RV_GLOCAL_HOST_BELOW = 0; the shipped threshold lies above every list, so the default route is the host rule), in both libraries."""
+kernels forced (RV_GLOCAL_HOST_BELOW = 0; the shipped threshold lies above every list, so the default route is the host rule), in both libraries.
+Section 3b runs the large cases: lists of 250 .. 2300 blocks, the sizes at which the kernels take their other paths."""
 import functools
 
 import pytest
@@ -111,6 +112,82 @@ def test_tiles(budget, sa64):
         assert info["tiles"] >= 4 and info["tiles"] == info["edges"] // budget + 1          # several tiles, windows crossing their borders
     got, info = t.glocal_filter(*args(c), sa64=sa64, index=idx, **c["kw"])
     assert C.matches(C.indices(c["blocks"], got), GOLD["cases"]["lastn100_150"]["filter"]["chain"]) and info["tiles_max"] >= 4
+
+
+# ---- 3b. the large cases (glocal_cases.large_cases): more than one workgroup, windows above 192 edges, lists above the 2048 scores of the LDS ring
+LARGE = C.large_cases()
+
+
+@functools.lru_cache(maxsize=None)
+def large_lender(sa64, leg, budget=None):
+    """a handle per library, leg and edge budget (None: the shipped 2^25)"""
+    idx = mod(sa64).index()
+    if leg == "kernels":
+        idx.set_option("RV_GLOCAL_HOST_BELOW", 0)
+    elif leg == "host":
+        idx.set_option("RV_GLOCAL_HOST", 1)
+    else:
+        assert idx.get_option("RV_GLOCAL_HOST") == 0 and idx.get_option("RV_GLOCAL_HOST_BELOW") > 2400
+    if budget is None:
+        assert idx.get_option("RV_GLOCAL_EDGE_BUDGET") == 1 << 25
+    else:
+        idx.set_option("RV_GLOCAL_EDGE_BUDGET", budget)
+    return idx
+
+
+@pytest.mark.parametrize("sa64", [False, True])
+@pytest.mark.parametrize("axis", [0, 1])
+@pytest.mark.parametrize("name", list(LARGE))
+def test_large_one_pass(name, axis, sa64):
+    """one pass of the kernels against the reference's record, the host leg and the shipped default; the counts the library reports say that the
+    case got where glocal_cases.large_cases sends it (the arithmetic behind them: test_cpu_glocal.py::test_large_reach)"""
+    t = transform()
+    c = LARGE[name]
+    want = GOLD["large"][name]["axis%d" % axis]
+    m = C.entries(c, axis)
+    got, info = t.glocalchain_device(*args(c), axis=axis, sa64=sa64, index=large_lender(sa64, "kernels"), info=True, **c["kw"])
+    assert C.matches(C.indices(c["blocks"], got), want)
+    assert info["route"] == "device"
+    host, hinfo = t.glocalchain_device(*args(c), axis=axis, sa64=sa64, index=large_lender(sa64, "host"), info=True, **c["kw"])
+    dflt, dinfo = t.glocalchain_device(*args(c), axis=axis, sa64=sa64, index=large_lender(sa64, "default"), info=True, **c["kw"])
+    assert got == host == dflt and hinfo["route"] == dinfo["route"] == "host"
+    assert info["passes"] == hinfo["passes"] == ((1, 0) if axis == 0 else (0, 1)) and info["after"] == hinfo["after"] == [len(got)]
+    assert info["tiles"] == 1 and info["chain_blocks"] == m
+    assert info["sort_keys"] == (2 if name.startswith("wide") else 1)
+    if name in C.WHOLE_PREFIX:
+        assert info["edges"] == C.whole_prefix_edges(m)                       # the k-th entry has k edges: every window length 1 .. m is there
+    else:
+        assert m <= info["edges"] <= C.whole_prefix_edges(m)
+    if name.startswith("collinear") and axis == 0:
+        assert len(got) == len(c["blocks"])                                   # the longest path a list of this length can have
+    for budget in C.LARGE_BUDGETS.get(name, ()):
+        low, linfo = t.glocalchain_device(*args(c), axis=axis, sa64=sa64, index=large_lender(sa64, "kernels", budget), info=True, **c["kw"])
+        assert low == got and linfo["route"] == "device"
+        assert linfo["edges"] == info["edges"] and linfo["tiles"] == linfo["edges"] // budget + 1 > 1
+        if name == "ring_2300":
+            assert linfo["tiles"] == 6 and C.first_entry_of_tile(5, budget) > C.RING      # the last tile's pre-load starts behind entry 0
+
+
+@pytest.mark.parametrize("sa64", [False, True])
+@pytest.mark.parametrize("name", C.LARGE_FILTERED)
+def test_large_filter(name, sa64):
+    """both loops: the survivors of a pass compacted into the next pass' list, over more than one workgroup"""
+    t = transform()
+    c = LARGE[name]
+    want = GOLD["large"][name]["filter"]
+    got, info = t.glocal_filter(*args(c), sa64=sa64, index=large_lender(sa64, "kernels"), **c["kw"])
+    assert C.matches(C.indices(c["blocks"], got), want["chain"])
+    host, hinfo = t.glocal_filter(*args(c), sa64=sa64, index=large_lender(sa64, "host"), **c["kw"])
+    dflt, dinfo = t.glocal_filter(*args(c), sa64=sa64, index=large_lender(sa64, "default"), **c["kw"])
+    assert got == host == dflt
+    assert info["route"] == "device" and hinfo["route"] == dinfo["route"] == "host"
+    assert list(info["passes"]) == want["passes"] and info["after"] == want["after"]
+    assert info["passes"] == hinfo["passes"] and info["after"] == hinfo["after"]
+    assert info["tiles"] == sum(info["passes"]) and info["tiles_max"] == 1
+    assert info["bytes_down"] == 28 * info["tiles"] + 4 * len(got)
+    assert info["sort_keys"] == (2 if name.startswith("wide") else 1)
+    if name == "passes_big":
+        assert max(info["passes"]) >= 3 and info["after"][0] > C.WG            # a second pass of more than one workgroup
 
 
 # ---- 4. what the library's arithmetic refuses

@@ -8,7 +8,7 @@ tree: glocalchain compares None with integers (`pblock[c2] >= block[c2]` on a du
 everything -- and Python 3 refuses.  Every <, <=, >, >= of the two functions goes through a helper with Python 2's ordering; the result there is always
 and-ed with `prefid != None`, so the outcome is the reference's.
 
-Per case of tests/glocal_cases.py: one pass on either axis (the chain as indices of the kept input blocks, the end score from the function's own log
+Per case of tests/glocal_cases.py (cases() under "cases", large_cases() under "large"): one pass on either axis (the chain as indices of the kept input blocks, the end score from the function's own log
 line) and, for the cases named there, the two loops of transform.py:307-356.  An empty list is written as the library defines it (an empty chain).
 
     python tools/gen_glocal_golden.py      # rewrites tests/golden/glocal.json
@@ -124,6 +124,31 @@ def main():
     for name in ("window_n1_bp0", "window_n2_bp10", "window_n8_bp100", "lastn100_150", "ties", "long_span"):
         assert 0 < len(g[name]["axis0"]) < g[name]["n"] and 0 < len(g[name]["axis1"]) < g[name]["n"], name
     assert g["window_n1_bp0"]["axis0"] != g["window_n8_bp100"]["axis0"], "the window does not matter at 70 blocks"
+    # the large cases: the same per case, under "large"
+    out["large"] = {}
+    large = C.large_cases()
+    for name, c in large.items():
+        rec = {"n": len(c["blocks"])}
+        for axis in (0, 1):
+            chain, score = one_pass(fn, c["blocks"], c, axis)
+            idx = C.indices(c["blocks"], chain)
+            if name.startswith("collinear"):
+                assert axis == 1 or idx == list(range(rec["n"])), "%s: the chain on axis 0 is not the whole list" % name
+            if name.startswith("far_") and name.endswith("axis%d" % axis):
+                between = int(name.split("_")[1])
+                _, a, b = C.far_blocks(between, axis)
+                assert idx[idx.index(b) - 1] == a, "%s: the block behind the gap is not reached from the last one in front of it" % name
+            rec["axis%d" % axis] = C.chain_record(idx)
+            rec["score%d" % axis] = score
+        if name in C.LARGE_FILTERED:
+            chain, passes, after = loops(fn, c["blocks"], c)
+            rec["filter"] = dict(chain=C.chain_record(C.indices(c["blocks"], chain)), passes=passes, after=after)
+        out["large"][name] = rec
+    gl = out["large"]
+    f = gl["passes_big"]["filter"]
+    assert max(f["passes"]) >= 3 and f["after"][0] > C.WG, "passes_big: fewer than three passes on either axis, or a second pass of one workgroup: %s" % f
+    for o in (0, 1):
+        assert gl["wide_600_o%d" % o]["score0"] > 1 << 32 and gl["wide_600_o%d" % o]["score1"] > 1 << 32, "wide_600: the end score stays inside 32 bits"
     # end to end: the loops on the blocks of blocks_cases.multi_case() with the command line's weights
     blocks, nodes, rlength, qlength = C.multi_blocks()
     c = dict(blocks=blocks, ctg2range=nodes, rlength=rlength, qlength=qlength)
@@ -132,9 +157,13 @@ def main():
     path = os.path.join(ROOT, "tests", "golden", "glocal.json")
     with open(path, "w") as f:
         rows = ",\n".join("%s: %s" % (json.dumps(k), json.dumps(v, sort_keys=True, separators=(",", ":"))) for k, v in sorted(out["cases"].items()))      # a case per line
-        f.write('{"cases": {\n%s\n},\n"multi": %s}\n' % (rows, json.dumps(out["multi"], sort_keys=True, separators=(",", ":"))))
+        lrows = ",\n".join("%s: %s" % (json.dumps(k), json.dumps(v, sort_keys=True, separators=(",", ":"))) for k, v in sorted(out["large"].items()))
+        f.write('{"cases": {\n%s\n},\n"large": {\n%s\n},\n"multi": %s}\n' % (rows, lrows, json.dumps(out["multi"], sort_keys=True, separators=(",", ":"))))
     for name in ("passes_second_drops", "passes_four", "lastn100_150", "wide_o1"):
         print(name, g[name]["n"], "blocks ->", len(g[name]["axis0"]), "/", len(g[name]["axis1"]), "filter", g[name]["filter"]["passes"], g[name]["filter"]["after"])
+    for name, rec in sorted(gl.items()):
+        print(name, rec["n"], "blocks ->", [rec[a]["count"] if isinstance(rec[a], dict) else len(rec[a]) for a in ("axis0", "axis1")],
+              "filter %s %s" % (rec["filter"]["passes"], rec["filter"]["after"]) if "filter" in rec else "")
     print("multi:", out["multi"])
     print("wrote %s (%d bytes)" % (path, os.path.getsize(path)))
 
