@@ -211,6 +211,56 @@ int64_t rv_glocal_filter(rv_index *h, int64_t n, const int64_t *s1, const int64_
                          int64_t *info, int ninfo);
 int rv_fetch_glocal(rv_index *h, int32_t *idx, int64_t cap);
 
+/* merge_consecutive: the third stage of `reveal transform` (transform.py:376-377, :713-746) on a block list in columns (s1, e1, s2, e2, o, score, refid,
+ * ctgid), n rows.  THE LIST = the rows sel[0 .. nsel) names, in that order (int32 row numbers, duplicates allowed: what rv_fetch_glocal returns); sel = NULL:
+ * every row, in row order.
+ *   fewer than two blocks: the list as it is.
+ *   R         the list stably sorted by s1: ties keep the list's order.
+ *   qinv[i]   the rank of R[i] in the stable sort of R by s2.
+ *   join      for i >= 1, R[i] joins R[i-1] iff their ctgid are equal (refid is NOT compared) and either both have o = 0 and qinv[i] = qinv[i-1] + 1, or both
+ *             have o = 1 and qinv[i] = qinv[i-1] - 1.
+ *   block     a maximal run with head h and tail t becomes (s1_h, e1_t, o_h = 0 ? s2_h : s2_t, o_h = 0 ? e2_t : e2_h, o_h, sum of the scores, refid_h, ctgid_h).
+ *   order     the runs in the order of R.
+ * The input is validated: 0 <= every coordinate < 2^61, o in {0, 1}, score >= 0 with the list's total below 2^62, sel inside 0 .. n.
+ * rv_merge_host: the rule in host C++, no device is asked for; the result goes into the eight arrays (`cap` rows each; the list's length always suffices).
+ * rv_merge_blocks: the kernels (rv_merge.hip): the columns and sel are uploaded, both sorts go over the bits the largest s1 / s2 of the list needs, and the
+ * row count and the merged rows are all that is copied back; they wait for rv_fetch_merge.  The handle lends stream and workspace and need not be
+ * constructed.  Both return the number of merged rows.  info (ninfo >= 9 words, or NULL): [0] route (0 kernels, 1 host rule), [1] rows in (the list's
+ * length), [2] rows out, [3] / [4] bytes copied to / from the device, [5] / [6] key bits of the sort by s1 / by s2, [7] kernels launched by rv_merge.hip itself
+ * (each sort adds its passes, each sum its levels), [8] nanoseconds between events round all of them; [3 ..] are 0 for the host rule.
+ * Switches: RV_MERGE_HOST = 1 runs the host rule inside rv_merge_blocks (the A/B leg); a list of fewer than RV_MERGE_HOST_BELOW blocks takes it by itself
+ * (default 8192: the smallest length measured from which the kernels beat the host rule by more than both spreads; 0: never). */
+int64_t rv_merge_host(int64_t n, const int64_t *s1, const int64_t *e1, const int64_t *s2, const int64_t *e2, const int32_t *o, const int64_t *score, const int32_t *refid,
+                      const int32_t *ctgid, int64_t nsel, const int32_t *sel, int64_t *info, int ninfo, int64_t *os1, int64_t *oe1, int64_t *os2, int64_t *oe2, int32_t *oo,
+                      int64_t *oscore, int32_t *orefid, int32_t *octgid, int64_t cap);
+int64_t rv_merge_blocks(rv_index *h, int64_t n, const int64_t *s1, const int64_t *e1, const int64_t *s2, const int64_t *e2, const int32_t *o, const int64_t *score,
+                        const int32_t *refid, const int32_t *ctgid, int64_t nsel, const int32_t *sel, int64_t *info, int ninfo);
+int rv_fetch_merge(rv_index *h, int64_t *s1, int64_t *e1, int64_t *s2, int64_t *e2, int32_t *o, int64_t *score, int32_t *refid, int32_t *ctgid, int64_t cap);
+
+/* chainscore and optimise (transform.py:801-935) on the few blocks merge_consecutive leaves: host C++, 64-bit integers, no device is asked for.
+ * rs[i] / re[i] = ctg2range; params = {rearrangecost, inversioncost, lambda, eps, alfa, gapopen, (two words not read)}: non-negative integers inside
+ * rv_glocal_admit's bound for this list, anything else is an error (reveal_amd.transform.chainscore_python has Python's arithmetic).
+ * CHAINSCORE.  An empty chain: weight 0, cost = gapcost((0, 0, rlength, rlength, o = 0), (rlength, rlength, rlength + qlength, rlength + qlength, o = 0)), one
+ * edge.  Otherwise C = the list stably sorted by s1, q = the ranks of C in its stable sort by s2, o0 = the orientation of C[0];
+ *   start = (0, 0, x, x, o0), x = begin of C[0]'s contig for o0 = 0, its '$' for o0 = 1;  end = (rlength, rlength, y, y, o0), y = '$' of the last block's contig
+ *   for o0 = 0, its begin for o0 = 1;  weight = alfa * sum of the scores;  edges: gapcost(start, C[0]), one per neighbouring pair (p, b) of C, gapcost(last, end):
+ *     same refid and same ctgid: gapcost(p, b) where |q_p - q_b| = 1, else gapopen + rearrangecost;
+ *     otherwise: with pq = the block in front of b in the query order for o_b = 0, behind it for o_b = 1, and nq = the block behind p for o_p = 0, in front
+ *     of it for o_p = 1 (none at either end of the order): gapopen + rearrangecost where pq lies in b's contig or nq in p's; else the edge costs gapopen,
+ *     which enters the edge costs and NOT the cost (the reference's own arithmetic).
+ *   cost = the sum of the other edges.  gapcost is the one of rv_glocal_* with axis 0.  A block that begins behind rlength is an error.
+ * -> n + 1 edge costs (cap >= n + 1), weight_cost = {weight, cost}.
+ * OPTIMISE, one sweep.  best = weight - cost of the list.  The candidates in ascending score, ties in list order; a chain without a candidate holds the
+ * other blocks in that same order (it decides between equal s1).  A candidate whose chain scores not lower than best is dropped for good and best becomes
+ * that score.  -> the rows kept, in reference order (idx, cap >= n), weight_cost of that chain.  The two orders are made once and a candidate is skipped
+ * in them, where the reference sorts twice per candidate. */
+int64_t rv_chainscore_host(int64_t n, const int64_t *s1, const int64_t *e1, const int64_t *s2, const int64_t *e2, const int32_t *o, const int64_t *score, const int32_t *refid,
+                           const int32_t *ctgid, int64_t nseq, const int64_t *rs, const int64_t *re, int64_t rlength, int64_t qlength, const int64_t *params,
+                           int64_t weight_cost[2], int64_t *edgecosts, int64_t cap);
+int64_t rv_optimise_host(int64_t n, const int64_t *s1, const int64_t *e1, const int64_t *s2, const int64_t *e2, const int32_t *o, const int64_t *score, const int32_t *refid,
+                         const int32_t *ctgid, int64_t nseq, const int64_t *rs, const int64_t *re, int64_t rlength, int64_t qlength, const int64_t *params,
+                         int64_t weight_cost[2], int32_t *idx, int64_t cap);
+
 /* ---- the recursion: align() / aligner() (interface.c:293-415, reveal.c:731-1338)
  *
  * The reference pops one sub-index at a time (LIFO) and calls back into

@@ -89,6 +89,11 @@ SYMBOLS = {
     "rv_glocal_blocks": (_L, [V, _L, V, V, V, V, V, V, V, V, _L, V, V, _L, V, _I, V, _I]),
     "rv_glocal_filter": (_L, [V, _L, V, V, V, V, V, V, V, V, _L, V, V, _L, V, _I, V, _I]),
     "rv_fetch_glocal": (_I, [V, V, _L]),
+    "rv_merge_host": (_L, [_L, V, V, V, V, V, V, V, V, _L, V, V, _I, V, V, V, V, V, V, V, V, _L]),
+    "rv_merge_blocks": (_L, [V, _L, V, V, V, V, V, V, V, V, _L, V, V, _I]),
+    "rv_fetch_merge": (_I, [V, V, V, V, V, V, V, V, V, _L]),
+    "rv_chainscore_host": (_L, [_L, V, V, V, V, V, V, V, V, _L, V, V, _L, _L, V, V, V, _L]),
+    "rv_optimise_host": (_L, [_L, V, V, V, V, V, V, V, V, _L, V, V, _L, _L, V, V, V, _L]),
     "rv_align_begin": (_I, [V, _I, _I]),
     "rv_frontier_size": (_I, [V]),
     "rv_frontier_scan": (_I, [V]),

@@ -3,6 +3,7 @@
 // The recursion lives in rv_align.hip.
 #include "rv_index.h"
 #include "rv_cascade.h"
+#include "rv_tail.h"
 #include <limits>
 #include <stdarg.h>
 #include <stdio.h>
@@ -329,7 +330,7 @@ int rv_reset(rv_index *h) {
     h->maxlcp = 0;
     h->m_l.clear(); h->m_a.clear(); h->m_b.clear();
     h->mm_l.clear(); h->mm_n.clear(); h->mm_off.clear(); h->mm_pos.clear(); h->mm_so.clear();
-    h->blk.clear(); h->glc.clear();
+    h->blk.clear(); h->glc.clear(); h->mrg.clear();
     memset(h->ws.cap_events, 0, sizeof h->ws.cap_events);
     return 0;
 }
@@ -1320,6 +1321,102 @@ int rv_fetch_glocal(rv_index *h, int32_t *idx, int64_t cap) {
     if (cap < (int64_t)k || (k && !idx)) { rv_set_error("buffer too small"); return -1; }
     if (k) memcpy(idx, h->glc.idx.data(), k * 4);
     return 0;
+}
+
+/* ---- merge_consecutive of `reveal transform` (transform.py:713-746) on a block list in columns: rv_merge.hip.  The rule is stated in include/reveal_amd.h. */
+static void mrg_args(RvMrgIn &in, int64_t n, const int64_t *s1, const int64_t *e1, const int64_t *s2, const int64_t *e2, const int32_t *o, const int64_t *score,
+                     const int32_t *refid, const int32_t *ctgid, int64_t nsel, const int32_t *sel) {
+    in.n = n; in.s1 = s1; in.e1 = e1; in.s2 = s2; in.e2 = e2; in.o = o; in.score = score; in.refid = refid; in.ctgid = ctgid;
+    in.sel = sel; in.m = sel ? nsel : n;
+}
+static void mrg_host_info(int64_t *info, int ninfo, const RvMrgIn &in, const RvMrgOut &out) {
+    if (!info) return;
+    for (int k = 0; k < ninfo && k < RV_MRG_INFO; k++) info[k] = 0;
+    info[RV_MRG_ROUTE] = 1; info[RV_MRG_ROWS_IN] = in.m; info[RV_MRG_ROWS_OUT] = (int64_t)out.size();
+}
+static int mrg_copy_out(const RvMrgOut &out, int64_t *s1, int64_t *e1, int64_t *s2, int64_t *e2, int32_t *o, int64_t *score, int32_t *refid, int32_t *ctgid, int64_t cap) {
+    const size_t k = out.size();
+    if (cap < (int64_t)k || (k && (!s1 || !e1 || !s2 || !e2 || !o || !score || !refid || !ctgid))) { rv_set_error("buffer too small"); return -1; }
+    if (!k) return 0;
+    memcpy(s1, out.s1.data(), k * 8); memcpy(e1, out.e1.data(), k * 8); memcpy(s2, out.s2.data(), k * 8); memcpy(e2, out.e2.data(), k * 8);
+    memcpy(o, out.o.data(), k * 4); memcpy(score, out.score.data(), k * 8); memcpy(refid, out.refid.data(), k * 4); memcpy(ctgid, out.ctgid.data(), k * 4);
+    return 0;
+}
+
+int64_t rv_merge_host(int64_t n, const int64_t *s1, const int64_t *e1, const int64_t *s2, const int64_t *e2, const int32_t *o, const int64_t *score, const int32_t *refid,
+                      const int32_t *ctgid, int64_t nsel, const int32_t *sel, int64_t *info, int ninfo, int64_t *os1, int64_t *oe1, int64_t *os2, int64_t *oe2, int32_t *oo,
+                      int64_t *oscore, int32_t *orefid, int32_t *octgid, int64_t cap) {
+    if (info && ninfo < RV_MRG_INFO) { rv_set_error("rv_merge_host: info takes %d words", (int)RV_MRG_INFO); return -1; }
+    RvMrgIn in; RvMrgOut out;
+    mrg_args(in, n, s1, e1, s2, e2, o, score, refid, ctgid, nsel, sel);
+    if (rv_merge_validate(in, nullptr, nullptr) != 0 || rv_merge_rule_host(in, out) != 0) return -1;
+    if (mrg_copy_out(out, os1, oe1, os2, oe2, oo, oscore, orefid, octgid, cap) != 0) return -1;
+    mrg_host_info(info, ninfo, in, out);
+    return (int64_t)out.size();
+}
+
+/* the kernels, or -- by RV_MERGE_HOST, and for a list of fewer than RV_MERGE_HOST_BELOW blocks -- the host rule: -> h->mrg, which waits for rv_fetch_merge */
+int64_t rv_merge_blocks(rv_index *h, int64_t n, const int64_t *s1, const int64_t *e1, const int64_t *s2, const int64_t *e2, const int32_t *o, const int64_t *score,
+                        const int32_t *refid, const int32_t *ctgid, int64_t nsel, const int32_t *sel, int64_t *info, int ninfo) {
+    if (!h) { rv_set_error("rv_merge_blocks: null handle"); return -1; }
+    if (info && ninfo < RV_MRG_INFO) { rv_set_error("rv_merge_blocks: info takes %d words", (int)RV_MRG_INFO); return -1; }
+    h->mrg.clear();
+    RvMrgIn in;
+    mrg_args(in, n, s1, e1, s2, e2, o, score, refid, ctgid, nsel, sel);
+    int64_t max1 = 0, max2 = 0;
+    if (rv_merge_validate(in, &max1, &max2) != 0) return -1;
+    const bool host = h->ws.opt.merge_host != 0 || in.m < 2 || in.m < std::max<int64_t>(h->ws.opt.merge_host_below, 0);
+    int r;
+    if (host) {
+        r = rv_merge_rule_host(in, h->mrg);
+        if (r == 0) mrg_host_info(info, ninfo, in, h->mrg);
+    } else {
+        (void)hipSetDevice(h->device);
+        r = rv_merge_device(h->ws, in, max1, max2, info, h->mrg);
+    }
+    if (r != 0) { h->mrg.clear(); return -1; }
+    return (int64_t)h->mrg.size();
+}
+
+int rv_fetch_merge(rv_index *h, int64_t *s1, int64_t *e1, int64_t *s2, int64_t *e2, int32_t *o, int64_t *score, int32_t *refid, int32_t *ctgid, int64_t cap) {
+    if (!h) { rv_set_error("rv_fetch_merge: null handle"); return -1; }
+    return mrg_copy_out(h->mrg, s1, e1, s2, e2, o, score, refid, ctgid, cap);
+}
+
+/* ---- chainscore and one sweep of optimise (transform.py:801-935) in host C++: rv_tail.hip.  params as for rv_glocal_*; lastn and lastbp are not read. */
+static void tail_args(RvTailIn &in, RvGlcParams &w, int64_t n, const int64_t *s1, const int64_t *e1, const int64_t *s2, const int64_t *e2, const int32_t *o, const int64_t *score,
+                      const int32_t *refid, const int32_t *ctgid, int64_t nseq, const int64_t *rs, const int64_t *re, int64_t rlength, int64_t qlength, const int64_t *p) {
+    in.n = n; in.s1 = s1; in.e1 = e1; in.s2 = s2; in.e2 = e2; in.o = o; in.score = score; in.refid = refid; in.ctgid = ctgid;
+    in.nseq = nseq; in.rs = rs; in.re = re; in.rlength = rlength; in.qlength = qlength;
+    w.rearr = p[0]; w.inv = p[1]; w.lambda = p[2]; w.eps = p[3]; w.alfa = p[4]; w.gapopen = p[5]; w.lastn = 0; w.lastbp = 0;
+}
+
+int64_t rv_chainscore_host(int64_t n, const int64_t *s1, const int64_t *e1, const int64_t *s2, const int64_t *e2, const int32_t *o, const int64_t *score, const int32_t *refid,
+                           const int32_t *ctgid, int64_t nseq, const int64_t *rs, const int64_t *re, int64_t rlength, int64_t qlength, const int64_t *params,
+                           int64_t weight_cost[2], int64_t *edgecosts, int64_t cap) {
+    if (!params || !weight_cost) { rv_set_error("rv_chainscore_host: bad arguments"); return -1; }
+    RvTailIn in; RvGlcParams w;
+    tail_args(in, w, n, s1, e1, s2, e2, o, score, refid, ctgid, nseq, rs, re, rlength, qlength, params);
+    if (rv_tail_validate(in, w) != 0) return -1;
+    std::vector<int64_t> edges;
+    if (rv_chainscore_rule_host(in, w, &weight_cost[0], &weight_cost[1], &edges) != 0) return -1;
+    if (cap < (int64_t)edges.size() || !edgecosts) { rv_set_error("buffer too small"); return -1; }
+    memcpy(edgecosts, edges.data(), edges.size() * 8);
+    return (int64_t)edges.size();
+}
+
+int64_t rv_optimise_host(int64_t n, const int64_t *s1, const int64_t *e1, const int64_t *s2, const int64_t *e2, const int32_t *o, const int64_t *score, const int32_t *refid,
+                         const int32_t *ctgid, int64_t nseq, const int64_t *rs, const int64_t *re, int64_t rlength, int64_t qlength, const int64_t *params,
+                         int64_t weight_cost[2], int32_t *idx, int64_t cap) {
+    if (!params || !weight_cost) { rv_set_error("rv_optimise_host: bad arguments"); return -1; }
+    RvTailIn in; RvGlcParams w;
+    tail_args(in, w, n, s1, e1, s2, e2, o, score, refid, ctgid, nseq, rs, re, rlength, qlength, params);
+    if (rv_tail_validate(in, w) != 0) return -1;
+    std::vector<int32_t> kept;
+    if (rv_optimise_rule_host(in, w, &weight_cost[0], &weight_cost[1], kept) != 0) return -1;
+    if (cap < (int64_t)kept.size() || (!idx && !kept.empty())) { rv_set_error("buffer too small"); return -1; }
+    if (!kept.empty()) memcpy(idx, kept.data(), kept.size() * 4);
+    return (int64_t)kept.size();
 }
 
 int rv_prof_enable(rv_index *h, int on) {      /* 0 off; 1 every class; otherwise bit k+1 selects class k */

@@ -124,7 +124,9 @@ void rv_set_error(const char *fmt, ...);
     X(glocal_host_below, "RV_GLOCAL_HOST_BELOW", (int64_t)1 << 31) \
     X(glocal_edge_budget, "RV_GLOCAL_EDGE_BUDGET", 1 << 25) \
     X(rc_host, "RV_RC_HOST", 0) \
-    X(rc_host_below, "RV_RC_HOST_BELOW", 0)
+    X(rc_host_below, "RV_RC_HOST_BELOW", 0) \
+    X(merge_host, "RV_MERGE_HOST", 0) \
+    X(merge_host_below, "RV_MERGE_HOST_BELOW", 8192)
 struct RvOptions {
 #define RV_X_(f, name, def) int64_t f = def;
     RV_OPTION_LIST(RV_X_)
@@ -393,6 +395,7 @@ struct Workspace {
     DBuf misc[20];
     DBuf blk[15];          // getblocks (rv_blocks.hip): records, ids, keys, sums and the block arrays
     DBuf glc[3];           // the glocal chain (rv_glocal.hip): the arena of a call, a tile's edges, the tables that stay for every pass
+    DBuf mrg[10];          // merge_consecutive (rv_merge.hip): the uploaded and the gathered columns, keys, permutations, sums, the merged rows
     DBuf sa[32];           // SA-build scratch, kept between construct() calls
     HBuf hpin;             // pinned landing zone of rv_read_back
     hipEvent_t ev_rb = nullptr;
@@ -416,6 +419,7 @@ struct Workspace {
         for (auto &b : misc) b.release();
         for (auto &b : blk) b.release();
         for (auto &b : glc) b.release();
+        for (auto &b : mrg) b.release();
         for (auto &b : sa) b.release();
     }
 };

@@ -4,6 +4,7 @@
 #include "rv_scan.h"
 #include "rv_blocks.h"
 #include "rv_glocal.h"
+#include "rv_merge.h"
 #include "rv_revcomp.h"
 #include "../../include/reveal_amd.h"
 #include <utility>
@@ -166,6 +167,7 @@ struct rv_index {
     std::vector<u32> mm_l; std::vector<int32_t> mm_n; std::vector<int64_t> mm_off, mm_pos; std::vector<uint16_t> mm_so;
     RvBlkOut blk;                      // rv_getblocks / rv_blocks_records -> rv_fetch_blocks
     RvGlcOut glc;                      // rv_glocal_blocks / rv_glocal_filter -> rv_fetch_glocal
+    RvMrgOut mrg;                      // rv_merge_blocks -> rv_fetch_merge
     // ---- recursion state (rv_align.hip)
     struct Align *al = nullptr;
     struct RvBatchGroup *batch = nullptr;      // rv_batch_run: the group this handle's job meets in the middle of its anchor cascade (rv_cascade_multi.hip)

@@ -19,9 +19,21 @@ weights (2.0 counts as 2) whose largest possible score stays inside 62 bits (rv_
 Python's own arithmetic.  Departures: every list entry is a block of its own (the reference's dictionary merges equal tuples), an empty list gives
 an empty chain.
 
-Not done here: merge_consecutive, remove_overlap_*, optimise / chainscore, extendblocks, the bed file and the breakpoint graph (host work on the few
-blocks that survive); useheap; non-integral weights outside Python; the getblocks output kept in device memory across construct(rc=1); --cutn, a
-reverse complement made on the device, a form for many inputs at once.
+The third stage and the chain's tail (transform.py:376-435, 528-530, 713-935, 1334-1485): merge_consecutive, overlap removal, the optimise loop,
+chainscore, extendblocks.
+
+    synteny_layout(reference, contigs)      everything above and below in one call, the block list in columns until merge_consecutive has made it small
+    merge_consecutive_python / merge_consecutive_native / merge_consecutive_device, merge_arrays      the merge: plain Python, host C++ (rv_merge_host), the
+                                            kernels (rv_merge_blocks); merge_arrays takes columns and the filter's chain as `sel`
+    chain_tail(chain, ...)                  what follows glocal_filter, on tuples -> the chain the bed file reads, its weight, cost and edge costs, the extended list
+    remove_overlap_python, chainscore_python / chainscore_native, optimise_python / optimise_native, optimise_loop, extendblocks_python      its stages
+
+The merge rule and the rules of chainscore and optimise are stated in include/reveal_amd.h (rv_merge_blocks, rv_chainscore_host).  Where the reference
+raises (the pop loop of remove_overlap_* emptying its list, an assert), transform.error is raised.  None of these functions changes its argument (the
+reference's sort and rebuild theirs in place).
+
+Not done here: the bed file and the breakpoint graph; useheap; non-integral weights outside Python; the chain handed from the filter to the merge in
+device memory (it crosses as `sel`); the getblocks output kept in device memory across construct(rc=1); --cutn; a form for many inputs at once.
 """
 from bisect import bisect_left
 
@@ -31,7 +43,9 @@ from . import _lib
 from .reveallib import error
 
 __all__ = ["blocks_python", "blocks_native", "blocks_device", "synteny_blocks", "glocalchain_python", "glocalchain_native", "glocalchain_device",
-           "glocal_filter", "glocal_arrays", "glocal_admit", "synteny_chain", "error"]
+           "glocal_filter", "glocal_arrays", "glocal_admit", "synteny_chain", "merge_consecutive_python", "merge_consecutive_native",
+           "merge_consecutive_device", "merge_arrays", "remove_overlap_python", "chainscore_python", "chainscore_native", "optimise_python", "optimise_native",
+           "optimise_loop", "extendblocks_python", "chain_tail", "synteny_layout", "error"]
 
 
 def _records(mums):
@@ -451,4 +465,422 @@ def synteny_chain(reference, contigs, minlength=20, cluster=True, maxdist=30, mi
     chain, info = glocal_filter(r["blocks"], r["rlength"], r["qlength"], r["ctg2range"], rearrangecost, inversioncost, lastn, lastbp, _lambda, eps, alfa,
                                 gapopen, sa64=sa64)
     r.update(chain=chain, info=info)
+    return r
+
+
+# ---- merge_consecutive (transform.py:713-746); the rule: include/reveal_amd.h, rv_merge_blocks ---------------------------------------------------------
+_MERGE_INFO = 9
+
+
+def merge_consecutive_python(blocks):
+    """the reference's merge_consecutive restated without its running head: neighbours of the reference order that are neighbours of the query order
+    too, in the direction of their orientation and on one contig, fold into one block -> a new list in reference order; `blocks` is left as it is"""
+    m = len(blocks)
+    if m < 2:
+        return list(blocks)
+    R = sorted(blocks, key=lambda b: b[0])                                      # stable: ties keep the caller's order
+    qinv = [0] * m
+    for rank, i in enumerate(sorted(range(m), key=lambda i: R[i][2])):
+        qinv[i] = rank
+    out = []
+    head, score = 0, R[0][5]
+    for i in range(1, m + 1):
+        if i < m:
+            p, b = R[i - 1], R[i]
+            if b[7] == p[7] and ((b[4] == p[4] == 0 and qinv[i] == qinv[i - 1] + 1) or (b[4] == p[4] == 1 and qinv[i] == qinv[i - 1] - 1)):
+                score += b[5]
+                continue
+        h, t = R[head], R[i - 1]
+        out.append((h[0], t[1], h[2], t[3], h[4], score, h[6], h[7]) if h[4] == 0 else (h[0], t[1], t[2], h[3], h[4], score, h[6], h[7]))
+        if i < m:
+            head, score = i, R[i][5]
+    return out
+
+
+def _columns(blocks, what):
+    n = len(blocks)
+    try:
+        return {k: np.fromiter((int(b[c]) for b in blocks), dtype=dt, count=n) for c, (k, dt) in enumerate(_COLS)}
+    except OverflowError:
+        raise error("%s: a block outside the library's integers" % what)
+
+
+def _rows(cols):
+    return list(zip(*[np.asarray(cols[k]).tolist() for k, _ in _COLS]))
+
+
+def _merge_info(info):
+    return dict(route="host" if info[0] else "device", rows_in=int(info[1]), rows_out=int(info[2]), bytes_up=int(info[3]), bytes_down=int(info[4]),
+                key_bits=(int(info[5]), int(info[6])), launches=int(info[7]), kernel_ms=info[8] / 1e6)
+
+
+def merge_arrays(cols, sel=None, sa64=False, index=None, host=False):
+    """the library's merge on columns: cols = dict of equally long arrays s1, e1, s2, e2, o, score, refid, ctgid; sel = the rows that make the list, in
+    list order (int32 row numbers, duplicates allowed: the idx glocal_arrays returns), None = every row.  host: rv_merge_host, no device is asked for;
+    otherwise rv_merge_blocks through `index` (or a fresh handle), whose switches choose the route.  -> (the merged list as a dict of columns, info)"""
+    if not host and index is None:
+        from . import reveallib, reveallib64
+        index = (reveallib64 if sa64 else reveallib).index()
+    lib = _lib.get(sa64) if host else index._lib
+    arr = [np.ascontiguousarray(cols[k], dtype=dt) for k, dt in _COLS]
+    n = len(arr[0])
+    if any(a.ndim != 1 or len(a) != n for a in arr):
+        raise error("merge: columns of different lengths")
+    if sel is None:
+        m, psel = n, None
+    else:
+        s = np.asarray(sel)
+        if s.ndim != 1 or (len(s) and s.dtype.kind not in "iu"):
+            raise error("merge: sel is a list of row numbers")
+        if len(s) and (int(s.min()) < 0 or int(s.max()) >= n):
+            raise error("merge: sel names a row outside 0 .. %d" % n)
+        m = len(s)
+        s = np.ascontiguousarray(s, dtype=np.int32) if m else np.zeros(1, dtype=np.int32)       # (an empty sel is still a sel: a pointer, not NULL)
+        psel = s.ctypes.data
+    info = np.zeros(_MERGE_INFO, dtype=np.int64)
+    out = [np.zeros(max(m, 1), dtype=dt) for _, dt in _COLS]
+    head = (n, *[c.ctypes.data for c in arr], m, psel, info.ctypes.data, len(info))
+    if host:
+        k = lib.dll.rv_merge_host(*head, *[c.ctypes.data for c in out], max(m, 1))
+    else:
+        k = lib.dll.rv_merge_blocks(index._h, *head)
+        if k >= 0 and lib.dll.rv_fetch_merge(index._h, *[c.ctypes.data for c in out], max(m, 1)) != 0:
+            k = -1
+    if k < 0:
+        raise error(lib.err())
+    return {name: c[:k] for (name, _), c in zip(_COLS, out)}, _merge_info(info)
+
+
+def merge_consecutive_native(blocks, sa64=False):
+    """the same through the library's host C++ (rv_merge_host): no device is asked for"""
+    return _rows(merge_arrays(_columns(blocks, "merge"), None, sa64, None, True)[0])
+
+
+def merge_consecutive_device(blocks, sa64=False, index=None, info=False):
+    """the same through rv_merge_blocks: the kernels, or the host rule where the handle's switches say so (RV_MERGE_HOST, RV_MERGE_HOST_BELOW).
+    index: a handle that lends its stream, workspace and switches; without one a fresh index object is made.  info=True: -> (list, info)"""
+    cols, i = merge_arrays(_columns(blocks, "merge"), None, sa64, index, False)
+    return (_rows(cols), i) if info else _rows(cols)
+
+
+# ---- the chain's tail (transform.py:376-435, 528-530): overlap removal, chainscore, optimise, extendblocks -------------------------------------------
+def _trim(b, overlap, coord, front):
+    """block b with `overlap` taken off its front (front=True) or its end on the axis of `coord`, the other axis following the orientation"""
+    s1, e1, s2, e2, o, score, refid, ctgid = b
+    left = score - overlap if overlap < score else 0
+    if front:
+        if o == 0:
+            return (s1 + overlap, e1, s2 + overlap, e2, o, left, refid, ctgid)
+        return (s1 + overlap, e1, s2, e2 - overlap, o, left, refid, ctgid) if coord == 0 else (s1, e1 - overlap, s2 + overlap, e2, o, left, refid, ctgid)
+    if o == 0:
+        return (s1, e1 - overlap, s2, e2 - overlap, o, left, refid, ctgid)
+    return (s1, e1 - overlap, s2 + overlap, e2, o, left, refid, ctgid) if coord == 0 else (s1 + overlap, e1, s2, e2 - overlap, o, left, refid, ctgid)
+
+
+def remove_overlap_python(blocks, greedy=False):
+    """remove_overlap_conservative_blocks (transform.py:1334-1400) or, greedy=True, remove_overlap_greedy_blocks (:1402-1485): on the reference axis and
+    then on the query axis, contained blocks leave and an overlap of two neighbours is taken off one of them -> a new list.  Where the reference
+    raises (its pop loop empties the list: IndexError; one of its asserts), this raises transform.error."""
+    anchors = [tuple(b) for b in blocks]
+    for coord in (0, 2):
+        if len(anchors) <= 1:
+            return anchors
+        anchors.sort(key=lambda m: (m[coord], (m[coord + 1] - m[coord]) * -1))
+        kept = [anchors[0]]
+        last = anchors[0]
+        for a in anchors[1:]:
+            if a[coord] < last[coord + 1] and a[coord + 1] <= last[coord + 1]:        # contained
+                continue
+            kept.append(a)
+            last = a
+        anchors = kept
+        out = [anchors[0]]
+        for a in anchors[1:]:
+            score = a[5]
+            prev = out[-1]
+            pl, pscore = prev[1] - prev[0], prev[5]
+            overlap = prev[coord + 1] - a[coord]
+            if overlap > 0:
+                if not greedy or pscore > score:                                     # the block itself gives the overlap up
+                    if score <= overlap:
+                        continue
+                    a = _trim(a, overlap, coord, True)
+                    if greedy:
+                        out.append(a)
+                        continue
+                    if not a[coord + 1] > prev[coord + 1]:
+                        raise error("remove_overlap: a trimmed block ends inside the one in front of it")
+                while pl <= overlap or pscore <= overlap:
+                    out.pop()
+                    if not out:
+                        raise error("remove_overlap: no block left in front of an overlap")
+                    prev = out[-1]
+                    pscore = prev[5]
+                    overlap = prev[coord + 1] - a[coord]
+                    if overlap < 0:
+                        break
+                    pl = prev[1] - prev[0]
+                if overlap > 0:
+                    if greedy and not (pl > overlap and pscore > overlap):
+                        raise error("remove_overlap: an overlap as long as the block in front of it")
+                    if pscore - overlap < 0:
+                        raise error("remove_overlap: an overlap above the score of the block in front of it")
+                    out[-1] = _trim(prev, overlap, coord, False)
+            out.append(a)
+        anchors = out
+    return anchors
+
+
+def _orders(chain):
+    """the chain stably sorted by s1, its query order (positions into the sorted chain) and the inverse of that"""
+    C = sorted(chain, key=lambda s: s[0])
+    qryorder = sorted(range(len(C)), key=lambda i: C[i][2])
+    inv = [0] * len(C)
+    for rank, i in enumerate(qryorder):
+        inv[i] = rank
+    return C, qryorder, inv
+
+
+def chainscore_python(chain, rlength, qlength, ctg2range, rearrangecost=1000, inversioncost=1, _lambda=5, eps=1, alfa=1, gapopen=10):
+    """the reference's chainscore (transform.py:836-935) -> (weight, cost, edgecosts); `chain` is left as it is (the reference sorts it in place).  A
+    plain step from one contig to the next costs gapopen in edgecosts and nothing in cost, as in the reference."""
+    w = dict(rearrangecost=rearrangecost, inversioncost=inversioncost, _lambda=_lambda, eps=eps, gapopen=gapopen)
+    if len(chain) == 0:
+        cost = _gapcost((0, 0, rlength, rlength, 0), (rlength, rlength, rlength + qlength, rlength + qlength, 0), w, 0, 2)
+        return 0, cost, [cost]
+    C, qryorder, inv = _orders(chain)
+    o0 = C[0][4]
+    fs, fe = ctg2range[C[0][7]]
+    ls, le = ctg2range[C[-1][7]]
+    start = (0, 0, fs, fs, o0) if o0 == 0 else (0, 0, fe, fe, o0)
+    end = (rlength, rlength, le, le, o0) if o0 == 0 else (rlength, rlength, ls, ls, o0)
+    if C[-1][0] > rlength:
+        raise error("chainscore: a block begins behind rlength")
+    cost = _gapcost(start, C[0], w, 0, 2)
+    edgecosts = [cost]
+    weight = alfa * C[0][5]
+    n = len(C)
+    for ri in range(1, n):
+        p, b = C[ri - 1], C[ri]
+        weight += alfa * b[5]
+        pqi, qi = inv[ri - 1], inv[ri]
+        if p[7] == b[7] and p[6] == b[6]:
+            gc = _gapcost(p, b, w, 0, 2) if (pqi == qi - 1 or pqi == qi + 1) else gapopen + rearrangecost
+            cost += gc
+            edgecosts.append(gc)
+            continue
+        if b[4] == 0:
+            pq_ctg = C[qryorder[qi - 1]][7] if qi > 0 else "start"
+        else:
+            pq_ctg = C[qryorder[qi + 1]][7] if qi < n - 1 else "end"
+        if p[4] == 0:
+            nq_ctg = C[qryorder[pqi + 1]][7] if pqi < n - 1 else "end"
+        else:
+            nq_ctg = C[qryorder[pqi - 1]][7] if pqi > 0 else "start"
+        if pq_ctg == b[7] or nq_ctg == p[7]:
+            cost += gapopen + rearrangecost
+            edgecosts.append(gapopen + rearrangecost)
+        else:
+            edgecosts.append(gapopen)
+    endcost = _gapcost(C[-1], end, w, 0, 2)
+    cost += endcost
+    edgecosts.append(endcost)
+    return weight, cost, edgecosts
+
+
+def optimise_python(blocks, rlength, qlength, ctg2range, rearrangecost=1000, inversioncost=1, _lambda=5, eps=1, alfa=1, gapopen=10):
+    """one sweep of the reference's optimise (transform.py:801-834): the candidates in ascending score (ties in incoming order); a candidate whose
+    chain scores not lower without it is dropped for good -> (chain in reference order, weight, cost, edgecosts); `blocks` is left as it is"""
+    kw = dict(rearrangecost=rearrangecost, inversioncost=inversioncost, _lambda=_lambda, eps=eps, alfa=alfa, gapopen=gapopen)
+    org = sorted(blocks, key=lambda c: c[5])
+    best = sorted(blocks, key=lambda s: s[0])
+    bw, bc, be = chainscore_python(best, rlength, qlength, ctg2range, **kw)
+    stack = []
+    for i in range(len(org)):
+        tmp = stack + org[i + 1:]
+        w, c, e = chainscore_python(tmp, rlength, qlength, ctg2range, **kw)
+        if w - c < bw - bc:
+            stack.append(org[i])
+        else:
+            best, bw, bc, be = sorted(tmp, key=lambda s: s[0]), w, c, e
+    return best, bw, bc, be
+
+
+def _tail_admit(blocks, rlength, qlength, ctg2range, kw):
+    """the weights as ints where the library's 64-bit arithmetic takes them on this list, else None"""
+    w = _integral(dict(kw, lastn=0, lastbp=0))
+    if w is None or any(v < 0 or v >= 1 << 62 for v in w.values()):
+        return None
+    try:
+        vals = [int(rlength) + int(qlength)] + [int(x) for r in ctg2range for x in r] + [int(x) for b in blocks for x in b[:4]]
+        maxs = sum(int(b[5]) for b in blocks)                                      # (what merge_consecutive can make of them)
+    except (TypeError, ValueError):
+        return None
+    if min(vals) < 0 or max(vals) >= 1 << 61 or maxs >= 1 << 61 or any(int(b[5]) < 0 for b in blocks):
+        return None
+    par = np.array([w[k] for k in _W + ("lastn", "lastbp")], dtype=np.int64)
+    if _lib.get(False).dll.rv_glocal_admit(len(blocks), len(ctg2range), max(vals), maxs, par.ctypes.data) != 1:
+        return None
+    return w
+
+
+def _tail_call(fn, blocks, rlength, qlength, ctg2range, w, sa64):
+    lib = _lib.get(sa64)
+    cols = _columns(blocks, "chainscore")
+    arr = [cols[k] for k, _ in _COLS]
+    rs = np.ascontiguousarray(np.array([int(s) for s, _ in ctg2range], dtype=np.int64))
+    re = np.ascontiguousarray(np.array([int(e) for _, e in ctg2range], dtype=np.int64))
+    par = np.array([w[k] for k in _W] + [0, 0], dtype=np.int64)
+    wc = np.zeros(2, dtype=np.int64)
+    n = len(blocks)
+    res = np.zeros(n + 1, dtype=np.int64 if fn == "rv_chainscore_host" else np.int32)
+    k = getattr(lib.dll, fn)(n, *[c.ctypes.data for c in arr], len(rs), rs.ctypes.data, re.ctypes.data, int(rlength), int(qlength), par.ctypes.data, wc.ctypes.data,
+                             res.ctypes.data, n + 1)
+    if k < 0:
+        raise error(lib.err())
+    return int(wc[0]), int(wc[1]), res[:k].tolist()
+
+
+def chainscore_native(chain, rlength, qlength, ctg2range, rearrangecost=1000, inversioncost=1, _lambda=5, eps=1, alfa=1, gapopen=10, sa64=False):
+    """chainscore through the library's host C++ (rv_chainscore_host); integral weights inside rv_glocal_admit's bound, anything else raises"""
+    kw = dict(rearrangecost=rearrangecost, inversioncost=inversioncost, _lambda=_lambda, eps=eps, alfa=alfa, gapopen=gapopen)
+    w = _tail_admit(chain, rlength, qlength, ctg2range, kw)
+    if w is None:
+        raise error("chainscore: these weights are outside the library's integer arithmetic")
+    return _tail_call("rv_chainscore_host", chain, rlength, qlength, ctg2range, w, sa64)
+
+
+def optimise_native(blocks, rlength, qlength, ctg2range, rearrangecost=1000, inversioncost=1, _lambda=5, eps=1, alfa=1, gapopen=10, sa64=False):
+    """one sweep through the library's host C++ (rv_optimise_host: both orders made once, a candidate skipped in them) -> as optimise_python"""
+    kw = dict(rearrangecost=rearrangecost, inversioncost=inversioncost, _lambda=_lambda, eps=eps, alfa=alfa, gapopen=gapopen)
+    w = _tail_admit(blocks, rlength, qlength, ctg2range, kw)
+    if w is None:
+        raise error("optimise: these weights are outside the library's integer arithmetic")
+    bw, bc, idx = _tail_call("rv_optimise_host", blocks, rlength, qlength, ctg2range, w, sa64)
+    best = [tuple(blocks[i]) for i in idx]
+    return best, bw, bc, _tail_call("rv_chainscore_host", best, rlength, qlength, ctg2range, w, sa64)[2]
+
+
+def optimise_loop(blocks, rlength, qlength, ctg2range, rearrangecost=1000, inversioncost=1, _lambda=5, eps=1, alfa=1, gapopen=10, route="python", sa64=False):
+    """the loop of transform.py:404-433: sweeps until one does not raise the score, merge_consecutive behind every accepted one
+    -> (blocks, weight, cost, edgecosts, accepted sweeps).  route: "python" or "host" (the library's host C++)."""
+    kw = dict(rearrangecost=rearrangecost, inversioncost=inversioncost, _lambda=_lambda, eps=eps, alfa=alfa, gapopen=gapopen)
+    score_fn, sweep_fn, merge_fn = (chainscore_python, optimise_python, merge_consecutive_python) if route == "python" else (
+        lambda *a, **k: chainscore_native(*a, sa64=sa64, **k), lambda *a, **k: optimise_native(*a, sa64=sa64, **k), lambda b: merge_consecutive_native(b, sa64))
+    blocks = sorted(blocks, key=lambda s: s[0])
+    weight, cost, edgecosts = score_fn(blocks, rlength, qlength, ctg2range, **kw)
+    score, sweeps = weight - cost, 0
+    while True:
+        t, tw, tc, te = sweep_fn(blocks, rlength, qlength, ctg2range, **kw)
+        if tw - tc <= score:
+            break
+        score, weight, cost, edgecosts = tw - tc, tw, tc, te
+        blocks = merge_fn(t)
+        sweeps += 1
+    return blocks, weight, cost, edgecosts, sweeps
+
+
+def extendblocks_python(blocks, ctg2range):
+    """the reference's extendblocks (transform.py:748-799): every block grows to the end of its neighbour in front and half-way (floor) to the one
+    behind it, or to the ends of its sequence, on the reference axis and then on the query axis -> a new list in query order, as the reference
+    leaves it.  A block that ends up empty raises transform.error (the reference's assert)."""
+    B = sorted((tuple(b) for b in blocks), key=lambda s: s[0])
+    for axis, (c, ident) in enumerate(((0, 6), (2, 7))):
+        if axis == 1:
+            B.sort(key=lambda s: s[2])
+        n = len(B)
+        for i in range(n):
+            blk = list(B[i])
+            seq = blk[ident]
+            s, e = blk[c], blk[c + 1]
+            s = B[i - 1][c + 1] if i > 0 and B[i - 1][ident] == seq else ctg2range[seq][0]          # (B[i-1] has been extended already)
+            if i < n - 1 and B[i + 1][ident] == seq:
+                e += (B[i + 1][c] - e) // 2
+            else:
+                e = ctg2range[seq][1]
+            if not s < e:
+                raise error("extendblocks: an empty block on the %s axis" % ("reference" if axis == 0 else "query"))
+            blk[c], blk[c + 1] = s, e
+            B[i] = tuple(blk)
+    return B
+
+
+def chain_tail(chain, rlength, qlength, ctg2range, greedy=False, minchainsum=50, optimise=True, rearrangecost=10000, inversioncost=5, _lambda=3, eps=2, alfa=2,
+               gapopen=1, route=None, sa64=False, merged=False):
+    """transform.py:376-435 and 528-530 on the chain glocal_filter leaves: merge_consecutive, overlap removal (conservative, or greedy), blocks below
+    minchainsum dropped, merge_consecutive, the optimise loop where more than one block is left, merge_consecutive, chainscore, extendblocks.  The
+    weights default to the command line's.  route: None = the library's host C++ where rv_glocal_admit takes the weights on this list and Python's
+    arithmetic where not, "host" / "python" ask for one of them.  merged=True: `chain` has been through the first merge_consecutive already.
+    -> dict(blocks = the chain in reference order before extension (what the bed file reads), weight, cost, edgecosts, extended = the list of
+    extendblocks, info = dict(route, sweeps, stages = the list behind every stage))"""
+    kw = dict(rearrangecost=rearrangecost, inversioncost=inversioncost, _lambda=_lambda, eps=eps, alfa=alfa, gapopen=gapopen)
+    if route not in (None, "host", "python"):
+        raise error("chain_tail: unknown route")
+    if any(kw[k] < 0 for k in _W):
+        raise error("chain_tail: negative weight")
+    chain = [tuple(b) for b in chain]
+    stages = {}
+
+    def admitted(blocks):
+        return route != "python" and _tail_admit(blocks, rlength, qlength, ctg2range, kw) is not None
+
+    native = admitted(chain)
+    if route == "host" and not native:
+        raise error("chain_tail: these weights are outside the library's integer arithmetic")
+    merge = (lambda b: merge_consecutive_native(b, sa64)) if native else merge_consecutive_python
+    cur = chain if merged else merge(chain)
+    stages["merged"] = list(cur)
+    cur = remove_overlap_python(cur, greedy)
+    stages["overlap"] = list(cur)
+    cur = [b for b in cur if b[5] >= minchainsum]
+    stages["filtered"] = list(cur)
+    cur = merge(cur)
+    stages["merged2"] = list(cur)
+    sweeps = 0
+    if optimise and len(cur) > 1:
+        cur, _, _, _, sweeps = optimise_loop(cur, rlength, qlength, ctg2range, route="host" if native else "python", sa64=sa64, **kw)
+        stages["optimised"] = list(cur)
+    cur = merge(cur)
+    weight, cost, edgecosts = (chainscore_native(cur, rlength, qlength, ctg2range, sa64=sa64, **kw) if native else
+                               chainscore_python(cur, rlength, qlength, ctg2range, **kw))
+    cur = sorted(cur, key=lambda s: s[0])
+    return dict(blocks=cur, weight=weight, cost=cost, edgecosts=edgecosts, extended=extendblocks_python(cur, ctg2range),
+                info=dict(route="host" if native else "python", sweeps=sweeps, stages=stages))
+
+
+def synteny_layout(reference, contigs, minlength=20, cluster=True, maxdist=30, mincluster=50, minctglength=10000, rearrangecost=10000, inversioncost=5,
+                   lastn=50, lastbp=20000, _lambda=3, eps=2, alfa=2, gapopen=1, greedy=False, minchainsum=50, optimise=True, sa64=False):
+    """reference and contigs -> the layout `reveal transform` writes its bed file and builds its breakpoint graph from: synteny_chain's stages and
+    chain_tail in one call, the block list staying in columns from getblocks through the glocal filter until merge_consecutive (rv_merge_blocks, the
+    filter's chain as `sel`) has made it small; only the merged rows become tuples.  -> chain_tail's dict plus ctg2range, sep, rlength, qlength,
+    refnames, ctgnames, mums, and info with `glocal` and `merge` (the two calls' own info) and `blocks` (the rows in front of the filter)"""
+    from . import reveallib, reveallib64
+    idx = (reveallib64 if sa64 else reveallib).index()
+    ctg2range, names = [], ([], [])
+    for k, src in enumerate((reference, contigs)):
+        idx.addsample("reference" if k == 0 else "contigs")
+        for name, seq in _sequences(src):
+            if len(seq) < minctglength:
+                continue
+            ctg2range.append(idx.addsequence(seq))
+            names[k].append(name)
+    if not names[0] or not names[1]:
+        raise error("synteny_layout: no sequence of at least minctglength in %s" % ("the reference" if not names[0] else "the contigs"))
+    idx.construct(rc=0)
+    fwd = idx.getblocks_arrays(minlength, cluster, maxdist, mincluster)
+    idx.construct(rc=1)
+    rc = idx.getblocks_arrays(minlength, cluster, maxdist, mincluster)
+    sep, n = idx.nsep[0], idx.n
+    cols = {k: np.concatenate([np.asarray(fwd[k], dtype=dt), np.asarray(rc[k], dtype=dt)]) for k, dt in _COLS if k != "o"}
+    cols["o"] = np.concatenate([np.zeros(len(fwd["s1"]), dtype=np.int32), np.ones(len(rc["s1"]), dtype=np.int32)])
+    rlength, qlength = sep, n - sep
+    kw = dict(rearrangecost=rearrangecost, inversioncost=inversioncost, lastn=lastn, lastbp=lastbp, _lambda=_lambda, eps=eps, alfa=alfa, gapopen=gapopen)
+    if _integral(kw) is None:
+        raise error("synteny_layout: the column pipeline takes integral weights (synteny_chain + chain_tail take any)")
+    sel, ginfo = glocal_arrays(cols, rlength, ctg2range, (0, 1), True, sa64, idx, False, **kw)
+    mcols, minfo = merge_arrays(cols, sel, sa64, idx, False)
+    tail = {k: kw[k] for k in _W}
+    r = chain_tail(_rows(mcols), rlength, qlength, ctg2range, greedy, minchainsum, optimise, sa64=sa64, merged=True, **tail)
+    r["info"].update(glocal=ginfo, merge=minfo, blocks=len(cols["s1"]))
+    r.update(ctg2range=ctg2range, sep=sep, rlength=rlength, qlength=qlength, refnames=names[0], ctgnames=names[1], mums=(fwd["info"]["mums"], rc["info"]["mums"]))
     return r
